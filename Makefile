@@ -7,7 +7,7 @@ test:             ## CPU suite: oracle vs golden vectors, C ABI, host logic, glo
 test-gpu:         ## parity of every HIP operator and of the whole step (needs an MI355X)
 	python -m pytest tests -q -m gpu
 bench:            ## one JSON line: point-clouds/s, roofline of the dominant kernel, CPU baseline
-	python bench.py
+	python bench.py --full
 profile:          ## rocprofv3 kernel trace + HBM traffic counters -> gpurun_out/prof_<tag>/
 	bash tools/profile_roofline.sh local
 clean:

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """bench.py -- detector fwd+bwd throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model ball|som] [--pairs 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model ball|som] [--pairs 8] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,10 +14,18 @@ MI355X"): 8 pairs -> 16 clouds per GPU, Cs=4, node_knn_k_1=16; the K=64 model is
 RPN_Detector_Ball.  Weak scaling: every rank owns 8 pairs.  Synthetic "slab" clouds, seeds
 1234+rank; random-init weights (seeded, identical on every rank).
 
-Rank 0 prints ONE JSON line; `roofline` is for the kernel with the largest share of the timed
-region (HIP events on the launch stream, usip_amd/prof.py), `kernels` lists the others, and
-`cpu_baseline` is the oracle's PyTorch-CPU restatement of the same step timed on this box's
-host cores on a bounded sample (1 pair).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps (every one of
+them a plain step: no per-kernel events) and prints the headline keys (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  --full adds everything else, as
+before: `roofline` for the kernel with the largest share of the timed region (HIP events on
+the launch stream, usip_amd/prof.py), `kernels` for the others plus the stand-alone legs,
+`fp32_mfma_only`, `cpu_baseline` (the oracle's PyTorch-CPU restatement of the same step timed
+on the host cores on a bounded sample, 1 pair) with its `parity_check`, and for N > 1 the
+single-GPU probe and the all-reduce timings.
+
+--dump-outputs DIR writes what the last timed step computed (the step's outputs and losses,
+the parameters and buffers it left behind) as DIR/<name>.npy, float32 / float64: inputs and
+weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -93,7 +102,52 @@ def parse():
                          "(dist-in ball_query, index_max), which runs after the timed region at N=1")
     ap.add_argument("--only-kernels", action="store_true",
                     help="run ONLY that leg and print its rows (what tools/profile_roofline.sh puts under rocprofv3)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel timing and roofline, the stand-alone kernel leg, the fp32 leg, "
+                         "the CPU baseline with its parity check, and (N > 1) the single-GPU probe and all-reduce timings; "
+                         "the --no-* options above switch single parts of it off.  Off by default: a plain run only sets "
+                         "up, warms up, times the steps and prints the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32 / float64)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = args.no_n1_probe = True
+        args.no_fp32_leg = args.no_kernel_leg = True
+    return args
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMENTS = 1 << 21          # larger arrays are written as a fixed, seeded sample of this many entries
+
+
+def dump_outputs(out_dir, st):
+    """What the last step computed, as a caller of the step receives it: every tensor of `st.last` (outputs and losses),
+    and the parameters and floating-point buffers (BatchNorm statistics) the step left in the module, each flattened
+    in state_dict order.  Integer / boolean tensors are written as float64 (exact), everything else keeps float32 /
+    float64.  An array above DUMP_MAX_ELEMENTS entries is replaced by its entries at fixed, seeded positions."""
+    import numpy as np
+    arrays = {}
+    for k, v in st.last.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach()
+    sd = st.module.state_dict(keep_vars=True)
+    names = {id(p) for p in st.module.parameters()}
+    arrays["parameters"] = torch.cat([v.detach().reshape(-1) for v in sd.values() if id(v) in names])
+    bufs = [v.detach().reshape(-1) for v in sd.values() if id(v) not in names and v.is_floating_point()]
+    if bufs:
+        arrays["buffers"] = torch.cat(bufs)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+        if a.size > DUMP_MAX_ELEMENTS:
+            pick = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_BUDGET_BYTES, "bench.py --dump-outputs: %d bytes" % total
+    return sorted(arrays)
 
 
 def load_traffic_db(precision):
@@ -451,6 +505,8 @@ def main():
 
     opt = DetectorOptions(surface_normal_len=4, node_knn_k_1=16)
     torch.manual_seed(0)                                   # identical replicas, no broadcast needed
+    import numpy as np
+    np.random.seed(1234 + rank)                            # the descriptor's per-step point permutation: same every run
     if args.model == "descriptor":
         # BASELINE configs[4]: N=16384, 256 keypoints, 4 (anchor, positive) pairs per GPU; keypoints are cloud
         # points, sigmas U(0.1, 3), in-batch negatives = the next pair's anchor
@@ -509,7 +565,7 @@ def main():
         st.step(batch)
     torch.cuda.synchronize()
     barrier()
-    if world > 1 and not getattr(st, "allreduce_in_graph", False):
+    if args.full and world > 1 and not getattr(st, "allreduce_in_graph", False):
         st.allreduce_events = []                           # two HIP events around every gradient all-reduce
     # Per-kernel HIP events cost ~3 us of stream bubble each (~0.7 ms per step for ~220 of them): they are
     # recorded on every 4th step (1-GPU eager runs) or on one middle step only (graph replay, multi-GPU), which keeps the headline
@@ -523,11 +579,12 @@ def main():
     timed_steps_sampled = 0
     if not args.no_kernel_timing:
         prof.reset()
-    # one HIP event per step boundary (median and p10/p90 of the step time); 3 us each
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # --full: one HIP event per step boundary (median and p10/p90 of the step time); 3 us each
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    marks[0].record()
+    if marks:
+        marks[0].record()
     for i in range(args.steps):
         # graph replay: instrument the MIDDLE step -- the host is then a few replays ahead of the GPU, so the ~8 ms it
         # needs to launch an eager step never leave the GPU waiting (at step 0 they do: the queue starts empty)
@@ -540,11 +597,14 @@ def main():
             st.step(batch, eager=sampled)
         else:
             st.step(batch)
-        marks[i + 1].record()
+        if marks:
+            marks[i + 1].record()
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
     prof.enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st)                # before anything below runs another step
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -643,7 +703,8 @@ def main():
                                  "p90": max(c["allreduce_us_p90"] or 0.0 for c in census),
                                  "calls_timed_per_rank": min(c["allreduce_calls"] for c in census),
                                  "how": "HIP events on the launch stream around all_reduce(SUM) + 1/world scale, every "
-                                        "step of the timed region, max over ranks of each rank's percentile"},
+                                        "step of the timed region, max over ranks of each rank's percentile"}
+                                if args.full else None,
                 "step_ms_per_rank": [round(c["step_ms_wall"], 4) for c in census],
                 "loss_per_rank": [c["loss"] for c in census],
                 "param_checksum_per_rank": [c["param_checksum"] for c in census],
@@ -662,7 +723,7 @@ def main():
                                            % (world, d["distinct_devices"], d["replicas_identical"]),
                                   "distributed": d, "ranks_seen": out["ranks_seen"]}), flush=True)
                 sys.exit(3)
-        raw_steps = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+        raw_steps = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)] if marks else []
         per_step = sorted(raw_steps)
         if per_step:
             pick = lambda q: per_step[min(len(per_step) - 1, int(q * len(per_step)))]
@@ -825,7 +886,10 @@ def main():
                                    "after the timed region (see their note)").lstrip("; ")
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], out["parity_check"] = cpu_baseline(args, args.model, dev)
-        emit(out, world)
+        if args.full:
+            emit(out, world)
+        else:
+            print(compact_line(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

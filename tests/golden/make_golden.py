@@ -701,8 +701,36 @@ def gen_pre_post(networks):
     save("pre_post_cases.npz", **out)
 
 
+def gen_self_contained(ref_im, networks):
+    """What the tests that otherwise need the reference checkout at run time compare against: the reference's index_max
+    on the two random cases of tests/test_oracle.py, and the state_dict keys and shapes of its four detector classes
+    under the options of tests/test_reference_compat.py."""
+    import json
+    rng = np.random.default_rng(7)
+    cases = {}
+    for tag, (B, C, N, K) in (("small", (2, 5, 777, 19)), ("wide", (1, 16, 4096, 64))):
+        d = rng.normal(0, 1, (B, C, N)).astype(np.float32)
+        i = rng.integers(0, K, (B, N)).astype(np.int32)
+        cases[tag + "_data"], cases[tag + "_index"], cases[tag + "_K"] = d, i, np.int32(K)
+        cases[tag + "_out"] = ref_im.forward_cpu(torch.from_numpy(d), torch.from_numpy(i), K).numpy()
+    save("index_max_live_cases.npz", **cases)
+    opt = Opt()
+    opt.surface_normal_len, opt.activation, opt.normalization = 4, "relu", "batch"
+    opt.bn_momentum, opt.bn_momentum_decay_step, opt.bn_momentum_decay = 0.1, None, 0.6
+    opt.k, opt.node_knn_k_1, opt.loss_sigma_lower_bound = 1, 16, 1e-3
+    shapes = {cls: {k: list(v.shape) for k, v in getattr(networks, cls)(opt).state_dict().items()}
+              for cls in ("RPN_Detector", "RPN_DetectorLite", "RPN_Detector_Ball", "RPN_Detector_KNN")}
+    path = os.path.join(HERE, "reference_state_dicts.json")
+    with open(path, "w") as f:
+        json.dump(shapes, f, indent=0)
+    print("%-34s %8.1f KB" % (os.path.basename(path), os.path.getsize(path) / 1024))
+
+
 if __name__ == "__main__":
     ref_im, networks, losses, layers, som = import_reference()
+    if "--only-self-contained" in sys.argv:
+        gen_self_contained(ref_im, networks)
+        sys.exit(0)
     if "--only-ball-ancestor" in sys.argv:
         gen_ball_query_ancestor()
         sys.exit(0)
@@ -739,3 +767,4 @@ if __name__ == "__main__":
     gen_detectors_options(networks, losses, som)
     gen_descriptor(networks, losses)
     gen_pre_post(networks)
+    gen_self_contained(ref_im, networks)

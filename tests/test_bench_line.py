@@ -99,3 +99,37 @@ def test_emit_prints_the_compact_line_last_and_writes_the_full_record(tmp_path, 
     assert json.loads(out[0])["kernels_total"] == len(rec["kernels"])
     full = json.load(open(tmp_path / "bench_full_n1.json"))
     assert len(full["kernels"]) == len(rec["kernels"])
+
+
+def test_dump_outputs_writes_what_the_step_left_as_float_arrays(tmp_path):
+    """--dump-outputs: every tensor of the step's `last`, the parameters and the floating-point buffers, as float32 /
+    float64 .npy files (integers exactly as float64); an array above the cap is a fixed, seeded sample."""
+    import types
+
+    import numpy as np
+    import torch
+    mod = torch.nn.Sequential(torch.nn.Conv1d(3, 4, 1), torch.nn.BatchNorm1d(4))
+    big = torch.arange(bench.DUMP_MAX_ELEMENTS + 10, dtype=torch.float32)
+    st = types.SimpleNamespace(module=mod, last=dict(loss=torch.tensor(0.5), idx=torch.arange(7, dtype=torch.int32),
+                                                     big=big))
+    names = bench.dump_outputs(str(tmp_path / "a"), st)
+    assert names == ["big", "buffers", "idx", "loss", "parameters"]
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["idx"].dtype == np.float64 and np.array_equal(got["idx"], np.arange(7))
+    assert got["parameters"].size == sum(p.numel() for p in mod.parameters())
+    assert got["buffers"].size == 8 and got["big"].size == bench.DUMP_MAX_ELEMENTS
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_BUDGET_BYTES
+    bench.dump_outputs(str(tmp_path / "b"), st)
+    assert np.array_equal(np.load(tmp_path / "b" / "big.npy"), got["big"])
+
+
+def test_plain_run_switches_the_extra_legs_off(monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7"])
+    a = bench.parse()
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_kernel_timing and a.no_n1_probe and a.no_fp32_leg and a.no_kernel_leg
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+    assert not (a.no_cpu_baseline or a.no_kernel_timing or a.no_n1_probe or a.no_fp32_leg or a.no_kernel_leg)

@@ -181,7 +181,7 @@ def test_bench_eight_ranks_gloo_one_gpu(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1", "--pairs", "1",
-           "--points", "2048", "--nodes", "64", "--no-cpu-baseline", "--no-fp32-leg"]
+           "--points", "2048", "--nodes", "64", "--full", "--no-cpu-baseline", "--no-fp32-leg"]
     res = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     text = res.stdout.decode()

@@ -1223,7 +1223,7 @@ def test_bench_gpus_2_spawns_its_own_ranks(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--pairs", "2",
-           "--points", "4096", "--nodes", "128", "--no-cpu-baseline", "--no-kernel-timing"]
+           "--points", "4096", "--nodes", "128", "--full", "--no-cpu-baseline", "--no-kernel-timing"]
     res = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     line, out = _bench_line_and_record(res, tmp_path, 2)
@@ -1266,8 +1266,8 @@ def test_bench_two_ranks_graph_replay_on_one_gpu(tmp_path):
                USIP_BENCH_OUT=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "2", "--pairs", "2", "--points", "4096", "--nodes", "128", "--no-cpu-baseline",
-           "--no-kernel-timing"]
+           "--warmup", "2", "--pairs", "2", "--points", "4096", "--nodes", "128", "--full",
+           "--no-cpu-baseline", "--no-kernel-timing"]
     res = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert res.returncode == 0, res.stderr.decode()[-3000:]
     line, out = _bench_line_and_record(res, tmp_path, 2)

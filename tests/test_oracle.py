@@ -24,18 +24,17 @@ def test_index_max_oracle_matches_reference_cpp(tag):
 
 
 def test_index_max_oracle_matches_live_reference_build():
-    """When oracle/_ref/index_max.so (the reference's own C++) is present, compare live on
-    fresh random inputs as well."""
+    """Two random cases (seed 7) against the reference's own C++: its recorded outputs
+    (index_max_live_cases.npz), and, when oracle/_ref/index_max.so is present, a live call too."""
     from oracle.build_ref import load_ref_index_max
+    g = load_golden("index_max_live_cases.npz")
     ref = load_ref_index_max()
-    if ref is None:
-        pytest.skip("oracle/_ref not built and /root/reference absent")
-    rng = np.random.default_rng(7)
-    for (B, C, N, K) in [(2, 5, 777, 19), (1, 16, 4096, 64)]:
-        d = rng.normal(0, 1, (B, C, N)).astype(np.float32)
-        i = rng.integers(0, K, (B, N)).astype(np.int32)
-        want = ref.forward_cpu(torch.from_numpy(d), torch.from_numpy(i), K).numpy()
-        assert np.array_equal(native.index_max(d, i, K), want)
+    for tag in ("small", "wide"):
+        d, i, K = g[tag + "_data"], g[tag + "_index"], int(g[tag + "_K"])
+        assert np.array_equal(native.index_max(d, i, K), g[tag + "_out"]), tag
+        if ref is not None:
+            want = ref.forward_cpu(torch.from_numpy(d), torch.from_numpy(i), K).numpy()
+            assert np.array_equal(want, g[tag + "_out"]), tag
 
 
 def test_pairwise_dist_oracle_is_bit_exact_vs_torch_norm():

@@ -1,6 +1,7 @@
-"""Drop-in check that needs the reference checkout (build container only; skipped on the GPU box):
-the reference's OWN models/networks.py, imported unchanged on top of usip_amd's modules as INTEGRATION.md
-describes, builds the same detectors with the same state_dict keys and shapes as with its own layers."""
+"""Drop-in checks against the reference checkout: the reference's OWN models/networks.py, imported unchanged on top
+of usip_amd's modules as INTEGRATION.md describes, builds the same detectors with the same state_dict keys and shapes
+as with its own layers.  Without the checkout the forward test skips, and the state_dict test compares
+usip_amd.networks against the keys and shapes recorded from the reference (tests/golden/reference_state_dicts.json)."""
 import os
 import subprocess
 import sys
@@ -48,15 +49,34 @@ SCRIPT = textwrap.dedent("""
 """) % (ROOT, REF)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+DETECTORS = ("RPN_Detector", "RPN_DetectorLite", "RPN_Detector_Ball", "RPN_Detector_KNN")
+
+
 def test_reference_networks_builds_unchanged_on_our_modules():
+    """usip_amd.networks' own classes have the state_dict keys and shapes recorded from the reference's classes
+    (tests/golden/reference_state_dicts.json, tests/golden/make_golden.py).  When the reference checkout is present,
+    also live: its networks.py on our modules and on its own."""
     import json
+    from usip_amd import networks as fused
+
+    class Opt:
+        pass
+    opt = Opt()
+    opt.surface_normal_len, opt.activation, opt.normalization = 4, "relu", "batch"
+    opt.bn_momentum, opt.bn_momentum_decay_step, opt.bn_momentum_decay = 0.1, None, 0.6
+    opt.k, opt.node_knn_k_1, opt.loss_sigma_lower_bound = 1, 16, 1e-3
+    recorded = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_state_dicts.json")))
+    for cls in DETECTORS:
+        assert {k: list(v.shape) for k, v in getattr(fused, cls)(opt).state_dict().items()} == recorded[cls], cls
+    if not os.path.isdir(REF):
+        return
     res = {}
     for mode in ("ours", "theirs"):
         p = subprocess.run([sys.executable, "-c", SCRIPT, mode], capture_output=True, text=True, timeout=300)
         assert p.returncode == 0, p.stderr[-2000:]
         res[mode] = json.loads(p.stdout.strip().splitlines()[-1])
-    for cls in ("RPN_Detector", "RPN_DetectorLite", "RPN_Detector_Ball", "RPN_Detector_KNN"):
+    for cls in DETECTORS:
+        assert res["theirs"][cls] == recorded[cls], cls                # the recording is the reference's own
         assert res["ours"][cls] == res["theirs"][cls], cls           # same keys, same shapes
         assert res["ours"][cls + "/fused"] == res["theirs"][cls], cls    # usip_amd.networks' own classes too
         assert res["ours"][cls + "/layer_module"] == "usip_amd.layers"
