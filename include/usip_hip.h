@@ -587,6 +587,88 @@ int usip_fps_f32(const float* pts, const int32_t* first_idx, int32_t* out_idx, i
 int usip_nms_f32(const float* keypoints, const float* sigmas, float radius, int32_t* order, int32_t* count,
                  int B, int M, void* stream);
 
+/* ------------------------------------------------------------------ f-5  training pairs
+ * Replaces KittiLoader.__getitem__ / OxfordLoader.__getitem__ (data/kitti_detector_loader.py:101-259,
+ * data/oxford_detector_loader.py:99-229) with data/augmentation.py's augment and transform_pc_pytorch (:199-248): P pairs
+ * (src, dst) built from scans resident in device memory, written as DetectorStep.step consumes them.
+ *
+ * bank    f32 [rows][row_len] (x y z nx ny nz curvature reflectance for the reference's Nx8 files), all scans back to back;
+ * offsets i64 [num_scans + 1], scan s = rows offsets[s] .. offsets[s+1]; scan_ids i32 [P] (which scan each pair uses,
+ * clamped into range).
+ * Per cloud: N slots drawn without replacement in random order (fewer rows than N: the reference's fix_idx layout, whole
+ * copies of 0..n-1 then a random remainder); sn = columns 3..3+Cs (sn_last: the row's last column); n_sub of the N slots are
+ * the FPS candidates, the first FPS index is random, FPS (usip_fps_f32) runs on the un-augmented candidates; then, in train
+ * mode, augment (rotation stages in float64 as row vectors p @ R, jitter, scale, shift; rounded to f32 once; sn[0:3] rotated
+ * and rounded per stage, never scaled) and, for dst in both modes, transform_pc_pytorch (f32 R p, * scale, + shift).
+ * Outputs: pc[c] f32 [P][3][N], sn[c] f32 [P][Cs][N], node[c] f32 [P][3][M] (c = 0 src, 1 dst; may be halves of one
+ * buffer), R f32 [P][3][3], scale f32 [P], shift f32 [P][3][1] (the transform's); optional rows i32 [2][P][N] (scan-relative
+ * row of every slot) and node_slots i32 [2][P][M] (the slot every node came from).
+ * Randomness: Philox4x64-10, key (seed, 0), counter (element, stream tag, pair_base + p, step) -- csrc/pairs_rng.h.
+ * usip_pairs_apply_f32 takes every draw explicitly instead (usip_pairs_draws, raw uniforms and standard normals) and runs
+ * the same arithmetic: the reference's fixtures test the code that trains.
+ * USIP_EINVAL: bad shapes (3 + Cs > row_len, n_sub > 16384, M > n_sub, n_sub > N, Cs > 8, row_len > 16), enu_to_cam with
+ * Cs < 3, min_rows (the fewest rows of any scan the ids may name) < 1, or < N with require_full (Oxford). */
+#define USIP_PAIRS_NPARAM 24
+typedef struct usip_pairs_recipe {
+    double aug_scale_lo, aug_scale_hi;     /* augment scale U(lo, hi): KITTI 0.9 1.1, Oxford 0.7 1.3 */
+    double shift_range;                    /* augment shift U(-r, r)^3 with translation_perturbation: 1 */
+    double height_lo, height_hi;           /* Oxford height scaling U(lo, hi) of ENU z, train mode: 0.25 1.2 */
+    double pc_sigma, pc_clip;              /* jitter clip(sigma z, +-clip): points 0.04 0.12 */
+    double sn_sigma, sn_clip;              /*   every sn channel 0.01 0.05 */
+    double node_sigma, node_clip;          /*   nodes 0.04 0.12 */
+    double pert_sigma, pert_clip;          /*   rotation perturbation 0.06 0.18 */
+    double dst_scale_thre, dst_shift_thre; /* transform_pc_pytorch(scale_thre, shift_thre): 0 0.5 */
+    int N, M, Cs, n_sub, row_len;          /* points, nodes, sn channels, FPS candidates, floats per scan row */
+    int sn_last;                           /* sn = the row's last column (KITTI, Cs == 1) */
+    int train;                             /* augment (and height scaling); 0 = test mode: transform only */
+    int rot_horizontal, rot_3d, rot_perturbation, translation_perturbation;
+    int height_scaling;                    /* Oxford is_height_scaling */
+    int enu_to_cam;                        /* Oxford coordinate_ENU_to_cam after FPS */
+    int require_full;                      /* scans need >= N rows (Oxford) */
+    int dst_rot_type;                      /* transform's rot_type: 0 None, 2 '2d', 3 '3d' */
+    int dst_rot_perturbation;
+} usip_pairs_recipe;
+/* Explicit draws, per pair p and cloud c at [p][c]: rows i32 [P][2][N] (scan-relative row of each slot), cand i32 [P][2][n_sub]
+ * (slot of each FPS candidate), first i32 [P][2] (first FPS index among the candidates), jit_pc f64 [P][2][N][3],
+ * jit_sn f64 [P][2][N][Cs], jit_node f64 [P][2][M][3] (standard normals), params f64 [P][USIP_PAIRS_NPARAM]:
+ * 0 augment yaw uniform, 1-3 augment rand(3), 4-6 augment perturbation normals, 7 augment scale uniform, 8-10 augment shift
+ * uniforms, 11 height-scaling uniform, 12-14 transform angle uniforms ('2d' uses 12), 15-17 transform perturbation normals,
+ * 18 transform scale uniform, 19-21 transform shift uniforms. */
+typedef struct usip_pairs_draws {
+    const int32_t* rows;
+    const int32_t* cand;
+    const int32_t* first;
+    const double* jit_pc;
+    const double* jit_sn;
+    const double* jit_node;
+    const double* params;
+} usip_pairs_draws;
+typedef struct usip_pairs_out {
+    float* pc[2];
+    float* sn[2];
+    float* node[2];
+    float* R;
+    float* scale;
+    float* shift;
+    int32_t* rows;          /* optional (NULL) */
+    int32_t* node_slots;    /* optional (NULL) */
+} usip_pairs_out;
+long long usip_pairs_workspace_bytes(const usip_pairs_recipe* recipe, int P);
+/* Byte offset of one part of that workspace, for inspection: 0 the per-pair f64 table, 1 the un-augmented FPS candidates
+ * f32 [2P][3][n_sub] (clouds src 0..P-1, then dst), 2 the first FPS indices i32 [2P], 3 the FPS picks i32 [2P][M],
+ * 4 the total (= usip_pairs_workspace_bytes). */
+long long usip_pairs_workspace_offset(const usip_pairs_recipe* recipe, int P, int part);
+int usip_pairs_build_f32(const usip_pairs_recipe* recipe, const float* bank, const int64_t* offsets, int num_scans,
+                         const int32_t* scan_ids, int P, long long min_rows, uint64_t seed, uint64_t step,
+                         long long pair_base, const usip_pairs_out* out, void* workspace, void* stream);
+int usip_pairs_apply_f32(const usip_pairs_recipe* recipe, const usip_pairs_draws* draws, const float* bank,
+                         const int64_t* offsets, int num_scans, const int32_t* scan_ids, int P, long long min_rows,
+                         const usip_pairs_out* out, void* workspace, void* stream);
+/* HOST twin (every pointer on the host, draws NULL = Philox): the same arithmetic with its own float64 FPS loop. */
+int usip_pairs_build_f32_cpu(const usip_pairs_recipe* recipe, const usip_pairs_draws* draws, const float* bank,
+                             const int64_t* offsets, int num_scans, const int32_t* scan_ids, int P, uint64_t seed,
+                             uint64_t step, long long pair_base, const usip_pairs_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,16 @@ SIGNATURES = {
     "usip_fps_f32": ([_f32p, _i32p, _i32p, _int, _int, _int, _stream], _int),
     "usip_nms_f32": ([_f32p, _f32p, _flt, _i32p, _i32p, _int, _int, _stream], _int),
     "usip_ball_query_coords_f32": ([_f32p, _f32p, _i32p, _flt, _int, _int, _int, _int, _stream], _int),
+    # f-5 training pairs: the structs go by address (usip_amd/pairs.py builds them)
+    "usip_pairs_workspace_bytes": ([ctypes.c_void_p, _int], ctypes.c_longlong),
+    "usip_pairs_workspace_offset": ([ctypes.c_void_p, _int, _int], ctypes.c_longlong),
+    "usip_pairs_build_f32": ([ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int, ctypes.c_longlong,
+                              ctypes.c_uint64, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                              _stream], _int),
+    "usip_pairs_apply_f32": ([ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int,
+                              ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
+    "usip_pairs_build_f32_cpu": ([ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int,
+                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p], _int),
 }
 
 

@@ -1,0 +1,307 @@
+// usip_amd/csrc/pairs_math.h -- the arithmetic of one training pair, shared by the kernels of csrc/pairs.hip
+// and the host twin of csrc/pairs_cpu.cpp.  Two sources of draws feed it through the same interface: PhiloxDraws (training)
+// and ExplicitDraws (the reference's recorded draws, tests/golden/pairs_cases.npz), so the fixtures test the code that trains.
+//
+// Reference semantics (data/kitti_detector_loader.py, data/oxford_detector_loader.py, data/augmentation.py):
+//   angles2rotation_matrix  R = Rz (Ry Rx), float64
+//   augment                 p <- p @ R per active stage (2d yaw, 3d, perturbation; row vectors, float64), + jitter,
+//                           * scale, + shift, one rounding to f32 at the end.  With NO rotation stage the points stay
+//                           the f32 array read from the scan: rounded after the jitter += (added in float64), after
+//                           * scale (an f32 product: numpy multiplies an f32 array by a Python float in f32) and after
+//                           += shift; nodes come out of FPS in float64 and always take the float64 path.  sn[0:3] is
+//                           rotated too, but assigned into the f32 array after every stage, and its jitter is added in
+//                           float64 and rounded (it is an in-place f32 +=); sn is never scaled
+//   transform_pc_pytorch    R, scale, shift of the dst view: f32 R p (torch.matmul), * scale, + shift, on pc, sn[0:3], node
+//   height scaling          Oxford, ENU z *= U(0.25, 1.2) in f32 (numpy multiplies an f32 array by a Python float in f32)
+//   coordinate_ENU_to_cam   (x, y, z) <- (x, -z, y) on pc, sn[0:3] and node, after FPS
+#pragma once
+#include <math.h>
+#include "pairs_rng.h"
+#include "../../include/usip_hip.h"
+
+namespace usip_pairs {
+
+// per-pair float64 table written by the params stage
+enum {
+    T_STAGE = 0,        // 3 rotation matrices of augment, 9 each, row-major
+    T_NSTAGE = 27,
+    T_SCALE = 28,       // augment scale
+    T_SHIFT = 29,       // 3: augment shift (0 without translation_perturbation)
+    T_HEIGHT = 32,      // height scale (an f32 value), T_HEIGHT_ON = 1 when applied
+    T_HEIGHT_ON = 33,
+    T_RD = 34,          // 9: transform R (f32 values)
+    T_DSCALE = 43,      // transform scale (f32 value)
+    T_DSHIFT = 44,      // 3: transform shift (f32 values)
+    T_SIZE = 48,
+};
+constexpr int MAX_CS = 8;
+constexpr int MAX_ROW = 16;
+
+USIP_HD double dot3(double a0, double a1, double a2, double b0, double b1, double b2)
+{
+    return (a0 * b0 + a1 * b1) + a2 * b2;                 // contraction is off
+}
+
+USIP_HD void mat3mul(const double A[9], const double B[9], double C[9])
+{
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) C[3 * i + j] = dot3(A[3 * i], A[3 * i + 1], A[3 * i + 2], B[j], B[3 + j], B[6 + j]);
+}
+
+// angles2rotation_matrix (augmentation.py:15-28)
+USIP_HD void rotation(double ax, double ay, double az, double R[9])
+{
+    const double cx = cos(ax), sx = sin(ax), cy = cos(ay), sy = sin(ay), cz = cos(az), sz = sin(az);
+    const double Rx[9] = {1, 0, 0, 0, cx, -sx, 0, sx, cx};
+    const double Ry[9] = {cy, 0, sy, 0, 1, 0, -sy, 0, cy};
+    const double Rz[9] = {cz, -sz, 0, sz, cz, 0, 0, 0, 1};
+    double A[9];
+    mat3mul(Ry, Rx, A);
+    mat3mul(Rz, A, R);
+}
+
+USIP_HD double clip(double v, double c) { return v < -c ? -c : (v > c ? c : v); }
+USIP_HD double uniform(double lo, double hi, double u) { return lo + (hi - lo) * u; }    // numpy: low + (high - low) * u
+
+// u: the pair's USIP_PAIRS_NPARAM raw draws (layout in include/usip_hip.h) -> T
+USIP_HD void pair_table(const usip_pairs_recipe& r, const double* u, double* T)
+{
+    const double pi = 3.141592653589793;
+    int ns = 0;
+    if (r.train) {
+        if (r.rot_horizontal) rotation(0.0, u[0] * 2 * pi, 0.0, T + 9 * ns++);             // np.random.uniform() * 2 * np.pi
+        if (r.rot_3d) rotation(u[1] * pi * 2, u[2] * pi * 2, u[3] * pi * 2, T + 9 * ns++); // np.random.rand(3) * np.pi * 2
+        if (r.rot_perturbation)
+            rotation(clip(r.pert_sigma * u[4], r.pert_clip), clip(r.pert_sigma * u[5], r.pert_clip),
+                     clip(r.pert_sigma * u[6], r.pert_clip), T + 9 * ns++);
+    }
+    for (int i = 9 * ns; i < 27; ++i) T[i] = 0.0;
+    T[T_NSTAGE] = ns;
+    T[T_SCALE] = r.train ? uniform(r.aug_scale_lo, r.aug_scale_hi, u[7]) : 1.0;
+    for (int k = 0; k < 3; ++k)
+        T[T_SHIFT + k] = (r.train && r.translation_perturbation) ? uniform(-r.shift_range, r.shift_range, u[8 + k]) : 0.0;
+    const bool height = r.train && r.height_scaling;
+    T[T_HEIGHT] = height ? (double)(float)uniform(r.height_lo, r.height_hi, u[11]) : 1.0;
+    T[T_HEIGHT_ON] = height ? 1.0 : 0.0;
+    double ax = 0, ay = 0, az = 0;
+    if (r.dst_rot_type == 2) {
+        ay = u[12] * 2 * pi;
+    } else if (r.dst_rot_type == 3) {
+        ax = u[12] * 2 * pi; ay = u[13] * 2 * pi; az = u[14] * 2 * pi;
+    }
+    if (r.dst_rot_perturbation) {
+        const double c = 3 * 0.06;
+        ax += clip(0.06 * u[15], c); ay += clip(0.06 * u[16], c); az += clip(0.06 * u[17], c);
+    }
+    double Rd[9];
+    rotation(ax, ay, az, Rd);
+    for (int i = 0; i < 9; ++i) T[T_RD + i] = (double)(float)Rd[i];
+    T[T_DSCALE] = (double)(float)uniform(1.0 - r.dst_scale_thre, 1.0 + r.dst_scale_thre, u[18]);
+    for (int k = 0; k < 3; ++k) T[T_DSHIFT + k] = (double)(float)uniform(-r.dst_shift_thre, r.dst_shift_thre, u[19 + k]);
+    for (int i = T_DSHIFT + 3; i < T_SIZE; ++i) T[i] = 0.0;
+}
+
+// The un-augmented coordinates FPS sees: the row's x y z, Oxford's height scaling applied (ENU frame).
+USIP_HD void raw_xyz(const double* T, const float* row, float p[3])
+{
+    p[0] = row[0];
+    p[1] = row[1];
+    p[2] = T[T_HEIGHT_ON] != 0.0 ? row[2] * (float)T[T_HEIGHT] : row[2];
+}
+
+// transform_pc_pytorch on one column vector: f32 R p, * scale, + shift
+USIP_HD void transform3(const double* T, float p[3], bool shift_scale)
+{
+    float o[3];
+    for (int i = 0; i < 3; ++i) {
+        const float r0 = (float)T[T_RD + 3 * i], r1 = (float)T[T_RD + 3 * i + 1], r2 = (float)T[T_RD + 3 * i + 2];
+        o[i] = (r0 * p[0] + r1 * p[1]) + r2 * p[2];
+    }
+    for (int i = 0; i < 3; ++i)
+        p[i] = shift_scale ? o[i] * (float)T[T_DSCALE] + (float)T[T_DSHIFT + i] : o[i];
+}
+
+// A point (f32_array: the reference holds it in the scan's f32 array) or a node (float64 out of FPS): ENU -> cam,
+// augment (train) with jitter z[3] * sigma clipped, rounded as the reference rounds, then dst's transform.
+USIP_HD void finish_xyz(const usip_pairs_recipe& r, const double* T, int cloud, const float in[3], const double z[3],
+                        double sigma, double clp, bool f32_array, float out[3])
+{
+    double p[3] = {in[0], in[1], in[2]};
+    if (r.enu_to_cam) { const double y = p[1]; p[1] = -p[2]; p[2] = y; }
+    if (r.train && f32_array && (int)T[T_NSTAGE] == 0) {
+        for (int k = 0; k < 3; ++k) {
+            float q = (float)(p[k] + clip(sigma * z[k], clp));                 // pc_np += jitter (in-place f32)
+            q = q * (float)T[T_SCALE];                                         // pc_np * scale (f32)
+            out[k] = r.translation_perturbation ? (float)((double)q + T[T_SHIFT + k]) : q;   // pc_np += shift
+        }
+        if (cloud == 1) transform3(T, out, true);
+        return;
+    }
+    if (r.train) {
+        const int ns = (int)T[T_NSTAGE];
+        for (int s = 0; s < ns; ++s) {
+            const double* R = T + T_STAGE + 9 * s;
+            const double q0 = dot3(p[0], p[1], p[2], R[0], R[3], R[6]);
+            const double q1 = dot3(p[0], p[1], p[2], R[1], R[4], R[7]);
+            const double q2 = dot3(p[0], p[1], p[2], R[2], R[5], R[8]);
+            p[0] = q0; p[1] = q1; p[2] = q2;
+        }
+        for (int k = 0; k < 3; ++k) p[k] = (p[k] + clip(sigma * z[k], clp)) * T[T_SCALE] + T[T_SHIFT + k];
+    }
+    for (int k = 0; k < 3; ++k) out[k] = (float)p[k];
+    if (cloud == 1) transform3(T, out, true);
+}
+
+// The sn channels of a point: ENU -> cam on 0:3, augment (train), dst's rotation on 0:3.
+USIP_HD void finish_sn(const usip_pairs_recipe& r, const double* T, int cloud, float* s, const double* z)
+{
+    const int Cs = r.Cs;
+    if (r.enu_to_cam) { const float y = s[1]; s[1] = -s[2]; s[2] = y; }
+    if (r.train) {
+        if (Cs >= 3) {
+            const int ns = (int)T[T_NSTAGE];
+            for (int st = 0; st < ns; ++st) {
+                const double* R = T + T_STAGE + 9 * st;
+                const double a = s[0], b = s[1], c = s[2];
+                s[0] = (float)dot3(a, b, c, R[0], R[3], R[6]);
+                s[1] = (float)dot3(a, b, c, R[1], R[4], R[7]);
+                s[2] = (float)dot3(a, b, c, R[2], R[5], R[8]);
+            }
+        }
+        for (int k = 0; k < Cs; ++k) s[k] = (float)((double)s[k] + clip(r.sn_sigma * z[k], r.sn_clip));
+    }
+    if (cloud == 1 && Cs >= 3) transform3(T, s, false);
+}
+
+// Load one scan row's columns 0..2 and the sn columns.
+USIP_HD void load_row(const usip_pairs_recipe& r, const float* row, float xyz[3], float* s)
+{
+    xyz[0] = row[0]; xyz[1] = row[1]; xyz[2] = row[2];
+    if (r.sn_last) {
+        s[0] = row[r.row_len - 1];
+    } else {
+        for (int k = 0; k < r.Cs; ++k) s[k] = row[3 + k];
+    }
+}
+
+// fix_idx layout of a scan with n < N rows: slot j < F = q n is j % n (q whole copies), the rest a random draw of N - F
+USIP_HD long long fix_copies(long long n, int N)
+{
+    if (n >= N) return 0;
+    return (N - n + n - 1) / n;                 // smallest q >= 1 with n + q n >= N
+}
+
+// ----------------------------------------------------------------------------------------------- sources of draws
+struct PhiloxDraws {
+    uint64_t seed, step;
+    long long base;
+
+    USIP_HD uint64_t gp(int p) const { return (uint64_t)(base + p); }
+    USIP_HD void params(int p, double* u) const
+    {
+        uint64_t b[4];
+        for (int e = 0; e < USIP_PAIRS_NPARAM / 4; ++e) {
+            pairs_block(seed, step, gp(p), TAG_PARAM_U, 0, e, b);
+            for (int i = 0; i < 4; ++i) u[4 * e + i] = u53(b[i]);
+        }
+        double z[4];
+        pairs_block(seed, step, gp(p), TAG_PARAM_N, 0, 0, b);
+        normal4(b, z);
+        u[4] = z[0]; u[5] = z[1]; u[6] = z[2];
+        pairs_block(seed, step, gp(p), TAG_PARAM_N, 0, 1, b);
+        normal4(b, z);
+        u[15] = z[0]; u[16] = z[1]; u[17] = z[2];
+    }
+    USIP_HD PairsPerm perm(int p, int c, uint32_t tag, uint64_t n) const
+    {
+        uint64_t b[4];
+        pairs_block(seed, step, gp(p), tag, c, 0, b);
+        PairsPerm q;
+        q.init(b, n);
+        return q;
+    }
+    // scan-relative row of slot j
+    USIP_HD long long row(int p, int c, long long n, int N, int j) const
+    {
+        const PairsPerm q = perm(p, c, TAG_CHOICE, (uint64_t)n);
+        const long long F = fix_copies(n, N) * n;
+        return j < F ? j % n : (long long)q((uint64_t)(j - F));
+    }
+    USIP_HD int cand(int p, int c, int N, int i) const { return (int)perm(p, c, TAG_CAND, (uint64_t)N)((uint64_t)i); }
+    USIP_HD int first(int p, int c, int n_sub) const { return (int)perm(p, c, TAG_FIRST, (uint64_t)n_sub)(0); }
+    USIP_HD void jit_pc(int p, int c, int, int j, double* z) const
+    {
+        uint64_t b[4];
+        pairs_block(seed, step, gp(p), TAG_JIT_PC, c, (uint64_t)j, b);
+        normal4(b, z);
+    }
+    USIP_HD void jit_sn(int p, int c, int, int Cs, int j, double* z) const
+    {
+        uint64_t b[4];
+        double t[4];
+        for (int e = 0; 4 * e < Cs; ++e) {
+            pairs_block(seed, step, gp(p), TAG_JIT_SN, c, 2 * (uint64_t)j + e, b);
+            normal4(b, t);
+            for (int k = 0; k < 4 && 4 * e + k < Cs; ++k) z[4 * e + k] = t[k];
+        }
+    }
+    USIP_HD void jit_node(int p, int c, int, int m, double* z) const
+    {
+        uint64_t b[4];
+        pairs_block(seed, step, gp(p), TAG_JIT_NODE, c, (uint64_t)m, b);
+        normal4(b, z);
+    }
+};
+
+// The recorded draws (layouts in include/usip_hip.h).  Indices are clamped into range: a bad fixture gives wrong values,
+// never an access outside the bank.
+struct ExplicitDraws {
+    usip_pairs_draws d;
+    int N, n_sub, M, Cs;
+
+    USIP_HD void params(int p, double* u) const
+    {
+        for (int i = 0; i < USIP_PAIRS_NPARAM; ++i) u[i] = d.params[(long long)p * USIP_PAIRS_NPARAM + i];
+    }
+    USIP_HD long long row(int p, int c, long long n, int, int j) const
+    {
+        const long long v = d.rows[((long long)p * 2 + c) * N + j];
+        return v < 0 ? 0 : (v >= n ? n - 1 : v);
+    }
+    USIP_HD int cand(int p, int c, int, int i) const
+    {
+        const int v = d.cand[((long long)p * 2 + c) * n_sub + i];
+        return v < 0 ? 0 : (v >= N ? N - 1 : v);
+    }
+    USIP_HD int first(int p, int c, int) const
+    {
+        const int v = d.first[p * 2 + c];
+        return v < 0 ? 0 : (v >= n_sub ? n_sub - 1 : v);
+    }
+    USIP_HD void jit_pc(int p, int c, int, int j, double* z) const
+    {
+        for (int k = 0; k < 3; ++k) z[k] = d.jit_pc[(((long long)p * 2 + c) * N + j) * 3 + k];
+    }
+    USIP_HD void jit_sn(int p, int c, int, int, int j, double* z) const
+    {
+        for (int k = 0; k < Cs; ++k) z[k] = d.jit_sn[(((long long)p * 2 + c) * N + j) * Cs + k];
+    }
+    USIP_HD void jit_node(int p, int c, int, int m, double* z) const
+    {
+        for (int k = 0; k < 3; ++k) z[k] = d.jit_node[(((long long)p * 2 + c) * M + m) * 3 + k];
+    }
+};
+
+// Shape rules shared by the device and host entry points.
+inline bool recipe_ok(const usip_pairs_recipe* r)
+{
+    if (!r) return false;
+    if (r->N < 1 || r->M < 1 || r->Cs < 1 || r->Cs > MAX_CS || r->n_sub < 1 || r->row_len > MAX_ROW) return false;
+    if (r->n_sub > 16384 || r->M > r->n_sub || r->n_sub > r->N) return false;
+    if (r->sn_last ? (r->Cs != 1 || r->row_len < 4) : (3 + r->Cs > r->row_len)) return false;
+    if (r->enu_to_cam && (r->Cs < 3 || r->sn_last)) return false;
+    if (r->dst_rot_type != 0 && r->dst_rot_type != 2 && r->dst_rot_type != 3) return false;
+    return true;
+}
+
+}  // namespace usip_pairs

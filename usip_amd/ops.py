@@ -1363,3 +1363,116 @@ def index_max_cpu(data: torch.Tensor, index: torch.Tensor, K: int, num_threads: 
     _lib.check(_lib.lib().usip_index_max_f32_cpu(_ptr(data), _ptr(index), _ptr(out), B, C, N, int(K),
                                                  int(num_threads)), "usip_index_max_f32_cpu")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ f-5 training pairs
+class PairsRecipeC(ctypes.Structure):
+    """usip_pairs_recipe (include/usip_hip.h), field for field."""
+    _fields_ = [(n, ctypes.c_double) for n in (
+        "aug_scale_lo", "aug_scale_hi", "shift_range", "height_lo", "height_hi", "pc_sigma", "pc_clip", "sn_sigma",
+        "sn_clip", "node_sigma", "node_clip", "pert_sigma", "pert_clip", "dst_scale_thre", "dst_shift_thre")] + \
+        [(n, ctypes.c_int) for n in (
+            "N", "M", "Cs", "n_sub", "row_len", "sn_last", "train", "rot_horizontal", "rot_3d", "rot_perturbation",
+            "translation_perturbation", "height_scaling", "enu_to_cam", "require_full", "dst_rot_type",
+            "dst_rot_perturbation")]
+
+
+class PairsDrawsC(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rows", "cand", "first", "jit_pc", "jit_sn", "jit_node", "params")]
+
+
+class PairsOutC(ctypes.Structure):
+    _fields_ = [("pc", ctypes.c_void_p * 2), ("sn", ctypes.c_void_p * 2), ("node", ctypes.c_void_p * 2),
+                ("R", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
+                ("rows", ctypes.c_void_p), ("node_slots", ctypes.c_void_p)]
+
+
+PAIRS_KEYS = ("src_pc", "src_sn", "src_node", "dst_pc", "dst_sn", "dst_node", "R", "scale", "shift")
+
+
+def _pairs_out(out: dict, rows, node_slots) -> PairsOutC:
+    o = PairsOutC()
+    for i, side in enumerate(("src", "dst")):
+        o.pc[i], o.sn[i], o.node[i] = (out[side + "_" + k].data_ptr() for k in ("pc", "sn", "node"))
+    o.R, o.scale, o.shift = out["R"].data_ptr(), out["scale"].data_ptr(), out["shift"].data_ptr()
+    o.rows = rows.data_ptr() if rows is not None else None
+    o.node_slots = node_slots.data_ptr() if node_slots is not None else None
+    return o
+
+
+def _pairs_check_out(recipe: PairsRecipeC, out: dict, P: int, device, scan_ids, rows, node_slots, workspace):
+    """Every tensor the launch touches on the bank's device, with its dtype and shape (a pointer to another device's
+    memory would be dereferenced by the kernels)."""
+    shapes = dict(src_pc=(P, 3, recipe.N), src_sn=(P, recipe.Cs, recipe.N), src_node=(P, 3, recipe.M), R=(P, 3, 3),
+                  scale=(P,), shift=(P, 3, 1))
+    for k in PAIRS_KEYS:
+        t = out[k]
+        _need(t, k, torch.float32)
+        if tuple(t.shape) != shapes[k.replace("dst_", "src_")] or t.device != device:
+            raise RuntimeError("pairs: %s must be f32 %s on %s" % (k, shapes[k.replace("dst_", "src_")], device))
+    if scan_ids.device != device:
+        raise RuntimeError("pairs: scan_ids on %s, the bank on %s" % (scan_ids.device, device))
+    if workspace.device != device or workspace.numel() * workspace.element_size() < pairs_workspace_bytes(recipe, P):
+        raise RuntimeError("pairs: the workspace must hold usip_pairs_workspace_bytes() bytes on %s" % device)
+    for name, t, n in (("rows", rows, recipe.N), ("node_slots", node_slots, recipe.M)):
+        if t is not None:
+            _need(t, name, torch.int32)
+            if tuple(t.shape) != (2, P, n) or t.device != device:
+                raise RuntimeError("pairs: %s must be i32 (2, %d, %d) on %s" % (name, P, n, device))
+
+
+def pairs_build(recipe: PairsRecipeC, bank: torch.Tensor, offsets: torch.Tensor, scan_ids: torch.Tensor, min_rows: int,
+                seed: int, step: int, pair_base: int, out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-5: P training pairs with Philox draws (usip_pairs_build_f32) into `out` (PAIRS_KEYS -> f32 tensors)."""
+    _need(bank, "bank", torch.float32)
+    _need(offsets, "offsets", torch.int64)
+    _need(scan_ids, "scan_ids", torch.int32)
+    P = scan_ids.numel()
+    _pairs_check_out(recipe, out, P, bank.device, scan_ids, rows, node_slots, workspace)
+    o = _pairs_out(out, rows, node_slots)
+    with torch.cuda.device(bank.device), prof.kernel("pairs_build", 2.0 * P * recipe.N * (32 + 4 * (3 + recipe.Cs))):
+        _lib.check(_lib.lib().usip_pairs_build_f32(
+            ctypes.addressof(recipe), _ptr(bank), _ptr(offsets), offsets.numel() - 1, _ptr(scan_ids), P, int(min_rows),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(pair_base), ctypes.addressof(o),
+            _ptr(workspace), _stream(bank)), "usip_pairs_build_f32")
+    return out
+
+
+def pairs_apply(recipe: PairsRecipeC, draws: dict, bank: torch.Tensor, offsets: torch.Tensor, scan_ids: torch.Tensor,
+                min_rows: int, out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-5 with explicit draws (usip_pairs_apply_f32): draws = rows, cand, first (i32), jit_pc, jit_sn, jit_node,
+    params (f64) device tensors in the layouts of include/usip_hip.h."""
+    _need(bank, "bank", torch.float32)
+    _need(offsets, "offsets", torch.int64)
+    _need(scan_ids, "scan_ids", torch.int32)
+    P = scan_ids.numel()
+    _pairs_check_out(recipe, out, P, bank.device, scan_ids, rows, node_slots, workspace)
+    d = PairsDrawsC()
+    for k in PairsDrawsC._fields_:
+        t = draws.get(k[0])
+        if t is not None:
+            _need(t, k[0], torch.int32 if k[0] in ("rows", "cand", "first") else torch.float64)
+            if t.device != bank.device:
+                raise RuntimeError("pairs: draw %s on %s, the bank on %s" % (k[0], t.device, bank.device))
+            setattr(d, k[0], t.data_ptr())
+    o = _pairs_out(out, rows, node_slots)
+    with torch.cuda.device(bank.device), prof.kernel("pairs_apply", 2.0 * P * recipe.N * (32 + 4 * (3 + recipe.Cs))):
+        _lib.check(_lib.lib().usip_pairs_apply_f32(
+            ctypes.addressof(recipe), ctypes.addressof(d), _ptr(bank), _ptr(offsets), offsets.numel() - 1,
+            _ptr(scan_ids), P, int(min_rows), ctypes.addressof(o), _ptr(workspace), _stream(bank)), "usip_pairs_apply_f32")
+    return out
+
+
+def pairs_workspace_offset(recipe: PairsRecipeC, P: int, part: int) -> int:
+    """Byte offset of workspace part 0 table, 1 candidates, 2 first indices, 3 FPS picks, 4 total (include/usip_hip.h)."""
+    n = int(_lib.lib().usip_pairs_workspace_offset(ctypes.addressof(recipe), int(P), int(part)))
+    if n < 0:
+        raise RuntimeError("usip_amd: usip_pairs_workspace_offset: invalid recipe or part (USIP_EINVAL)")
+    return n
+
+
+def pairs_workspace_bytes(recipe: PairsRecipeC, P: int) -> int:
+    n = int(_lib.lib().usip_pairs_workspace_bytes(ctypes.addressof(recipe), int(P)))
+    if n < 0:
+        raise RuntimeError("usip_amd: usip_pairs_workspace_bytes: invalid recipe (USIP_EINVAL)")
+    return n

@@ -1,0 +1,332 @@
+"""Training pairs built on the GPU from device-resident scans.
+
+The reference builds every (src, dst) pair on the CPU in DataLoader workers (KittiLoader / OxfordLoader.__getitem__,
+data/kitti_detector_loader.py:101-259, data/oxford_detector_loader.py:99-229, data/augmentation.py:199-248).  Here the
+scans live in HBM (ScanBank) and one call enqueues the whole batch -- subsampling, FPS nodes, augment and the dst
+transform -- on the current stream, with no host synchronisation (csrc/pairs.hip):
+
+    bank = ScanBank.from_paths(sorted(glob.glob("seq/*.npy")), "cuda:0", radius_threshold=opt.radius_threshold)
+    builder = PairBuilder(bank, PairRecipe.kitti(opt), pairs=8, device="cuda:0", seed=0, rank=rank)
+    for step, ids in enumerate(epoch_batches(bank.num_scans, 8, seed=0, epoch=0, rank=rank, world=world)):
+        st.step(builder.build(ids, step))
+
+Randomness is Philox4x64-10 keyed by the seed, with counter (element, stream, rank * P + p, step): a pair's data does not
+depend on the world size, and the same (seed, step, pair) always gives the same batch.
+"""
+import ctypes
+import os
+from dataclasses import dataclass, fields
+from typing import Dict, Iterable, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+KEYS = ops.PAIRS_KEYS
+
+
+@dataclass
+class PairRecipe:
+    """What one pair is made of: the fields of usip_pairs_recipe (include/usip_hip.h) bar `train`, which the builder's
+    mode sets.  Built by the presets below from the reference's option names and defaults."""
+    N: int = 16384
+    M: int = 512
+    Cs: int = 4
+    n_sub: int = 5461
+    row_len: int = 8
+    sn_last: int = 0
+    rot_horizontal: int = 1
+    rot_3d: int = 0
+    rot_perturbation: int = 0
+    translation_perturbation: int = 0
+    height_scaling: int = 0
+    enu_to_cam: int = 0
+    require_full: int = 0
+    dst_rot_type: int = 2
+    dst_rot_perturbation: int = 0
+    aug_scale_lo: float = 0.9
+    aug_scale_hi: float = 1.1
+    shift_range: float = 1.0
+    height_lo: float = 0.25
+    height_hi: float = 1.2
+    pc_sigma: float = 0.04
+    pc_clip: float = 0.12
+    sn_sigma: float = 0.01
+    sn_clip: float = 0.05
+    node_sigma: float = 0.04
+    node_clip: float = 0.12
+    pert_sigma: float = 0.06
+    pert_clip: float = 0.18
+    dst_scale_thre: float = 0.0
+    dst_shift_thre: float = 0.5
+    radius_threshold: float = 100.0          # applied once, by ScanBank (KITTI: rows with xz norm <= r when r < 90)
+
+    @staticmethod
+    def _common(opt):
+        g = lambda k, d: getattr(opt, k, d)   # noqa: E731
+        rot_3d, rot_h, pert = bool(g("rot_3d", False)), bool(g("rot_horizontal", True)), bool(g("rot_perturbation", False))
+        return dict(N=int(g("input_pc_num", 16384)), M=int(g("node_num", 512)), Cs=int(g("surface_normal_len", 4)),
+                    rot_horizontal=int(rot_h), rot_3d=int(rot_3d), rot_perturbation=int(pert),
+                    translation_perturbation=int(bool(g("translation_perturbation", False))),
+                    dst_rot_type=3 if rot_3d else (2 if rot_h else 0), dst_rot_perturbation=int(pert))
+
+    @classmethod
+    def kitti(cls, opt) -> "PairRecipe":
+        """KittiLoader (kitti/options_detector.py): N/3 FPS candidates, augment scale U(0.9, 1.1), Cs == 1 takes the
+        row's last column, scans shorter than N take the fix_idx layout, radius_threshold < 90 filters rows."""
+        kw = cls._common(opt)
+        return cls(n_sub=int(kw["N"] / 3), sn_last=int(kw["Cs"] == 1), aug_scale_lo=0.9, aug_scale_hi=1.1,
+                   radius_threshold=float(getattr(opt, "radius_threshold", 100.0)), **kw)
+
+    @classmethod
+    def oxford(cls, opt) -> "PairRecipe":
+        """OxfordLoader (oxford/options_detector.py): N/8 candidates, height scaling U(0.25, 1.2) of ENU z before FPS
+        (train mode), coordinate_ENU_to_cam after it (Cs >= 3), augment scale U(0.7, 1.3), scans of at least N rows."""
+        kw = cls._common(opt)
+        if kw["Cs"] < 3:
+            raise ValueError("PairRecipe.oxford: coordinate_ENU_to_cam permutes sn columns 0-2, surface_normal_len >= 3")
+        return cls(n_sub=int(kw["N"] / 8), height_scaling=int(bool(getattr(opt, "is_height_scaling", True))),
+                   enu_to_cam=1, require_full=1, aug_scale_lo=0.7, aug_scale_hi=1.3, **kw)
+
+    def c_struct(self, train: bool) -> ops.PairsRecipeC:
+        r = ops.PairsRecipeC()
+        for f in fields(self):
+            if f.name != "radius_threshold":
+                setattr(r, f.name, getattr(self, f.name))
+        r.train = int(bool(train))
+        return r
+
+
+class ScanBank:
+    """All scans in ONE float32 device buffer [rows, row_len] plus int64 row offsets (CSR): scan s is rows
+    offsets[s] .. offsets[s+1].  A float64 scan is rounded to float32 here; KITTI's radius filter (a deterministic
+    function of the file) is applied here, once, on the values as the file holds them.  A scan the filter empties is
+    refused by name."""
+
+    def __init__(self, scans: Sequence, device, row_len: int = 8, radius_threshold: float = 100.0, reserve: float = 0.1):
+        self.device = torch.device(device)
+        arrays = []
+        for s in scans:
+            a = np.load(s, mmap_mode="r") if isinstance(s, (str, os.PathLike)) else s
+            a = np.asarray(a)
+            if a.ndim != 2 or a.shape[1] != row_len:
+                raise ValueError("ScanBank: a scan must be [rows, %d], got %s" % (row_len, a.shape))
+            arrays.append(a)
+        if not arrays:
+            raise ValueError("ScanBank: no scans")
+        masks = []
+        for a in arrays:
+            if radius_threshold < 90:       # in the file's own dtype, as the reference computes it (before rounding)
+                masks.append(np.linalg.norm(np.asarray(a[:, [0, 2]]), axis=1) <= radius_threshold)
+            else:
+                masks.append(None)
+        lengths = np.array([a.shape[0] if m is None else int(m.sum()) for a, m in zip(arrays, masks)], dtype=np.int64)
+        empty = [(s if not isinstance(s, np.ndarray) else "scan %d" % i) for i, s in enumerate(scans) if lengths[i] == 0]
+        if empty:
+            raise ValueError("ScanBank: no rows left in %s (radius_threshold %g)" % (", ".join(map(str, empty)),
+                                                                                    radius_threshold))
+        self.lengths = lengths
+        self.offsets_host = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        total = int(self.offsets_host[-1]) * row_len * 4
+        free, _ = torch.cuda.mem_get_info(self.device)
+        if total > (1.0 - reserve) * free:
+            raise MemoryError("ScanBank: %d scans need %.2f GB of device memory, %s has %.2f GB free (keeping %d%% for "
+                              "the step)" % (len(arrays), total / 1e9, self.device, free / 1e9, int(100 * reserve)))
+        self.rows = torch.empty((int(self.offsets_host[-1]), row_len), dtype=torch.float32, device=self.device)
+        for s, (a, m) in enumerate(zip(arrays, masks)):
+            if lengths[s]:
+                h = np.ascontiguousarray(a if m is None else a[m], dtype=np.float32)
+                self.rows[self.offsets_host[s]:self.offsets_host[s + 1]].copy_(torch.from_numpy(h))
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.row_len = row_len
+        self.num_scans = len(arrays)
+        self.min_rows = int(lengths.min())
+
+    @classmethod
+    def from_paths(cls, paths: Sequence[str], device, **kw) -> "ScanBank":
+        return cls(list(paths), device, **kw)
+
+
+def epoch_order(num_scans: int, seed: int, epoch: int) -> np.ndarray:
+    """DataLoader(shuffle=True) order of one epoch: a permutation of the scans, a function of (seed, epoch) only."""
+    return np.random.default_rng([int(seed), int(epoch)]).permutation(int(num_scans)).astype(np.int32)
+
+
+def epoch_batches(num_scans: int, pairs: int, seed: int, epoch: int, rank: int = 0, world: int = 1):
+    """This rank's scan ids per step of one epoch, drop_last=True: global batch k = order[k*P*W : (k+1)*P*W], rank r
+    takes its r-th slice of P (pair index rank * P + p, as the builder's counter uses)."""
+    order = epoch_order(num_scans, seed, epoch)
+    g = pairs * world
+    for k in range(len(order) // g):
+        yield order[k * g + rank * pairs:k * g + (rank + 1) * pairs]
+
+
+def empty_batch(recipe: PairRecipe, pairs: int, device) -> Dict[str, torch.Tensor]:
+    P, N, M, Cs = pairs, recipe.N, recipe.M, recipe.Cs
+    shapes = dict(src_pc=(P, 3, N), src_sn=(P, Cs, N), src_node=(P, 3, M), dst_pc=(P, 3, N), dst_sn=(P, Cs, N),
+                  dst_node=(P, 3, M), R=(P, 3, 3), scale=(P,), shift=(P, 3, 1))
+    return {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in KEYS}
+
+
+class PairBuilder:
+    """P pairs per call, written as DetectorStep.step consumes them (synth.make_pair_batch's shapes and dtypes).
+
+    build(scan_ids, step, out=None): Philox draws; `out` (e.g. st.static_batch(batch)) is written in place.
+    apply(scan_ids, draws, out=None): the recorded draws of the reference (tests).
+    prefetch(schedule): double-buffered, batch k+1 built on a side stream while the consumer runs batch k.
+    build / apply use one workspace, each prefetch buffer one of its own, so a build on the current stream never races
+    a live prefetch; two builds on two different streams at once are the caller's to order."""
+
+    epoch_order = staticmethod(epoch_order)
+
+    def __init__(self, bank: ScanBank, recipe: PairRecipe, pairs: int, device=None, seed: int = 0, rank: int = 0,
+                 mode: str = "train"):
+        if mode not in ("train", "test"):
+            raise ValueError("PairBuilder: mode is 'train' or 'test'")
+        self.bank, self.recipe, self.pairs = bank, recipe, int(pairs)
+        self.device = torch.device(device) if device is not None else bank.device
+        self.seed, self.rank, self.mode = int(seed), int(rank), mode
+        self.c = recipe.c_struct(mode == "train")
+        if recipe.require_full and bank.min_rows < recipe.N:
+            raise ValueError("PairBuilder: this recipe needs scans of at least N = %d rows; the bank's shortest has %d"
+                             % (recipe.N, bank.min_rows))
+        # [0]: build / apply, [1], [2]: the two prefetch buffers
+        self._ws = [torch.empty(ops.pairs_workspace_bytes(self.c, self.pairs), dtype=torch.uint8, device=self.device)
+                    for _ in range(3)]
+        self.last_rows = self.last_node_slots = None
+
+    def _ids(self, scan_ids) -> torch.Tensor:
+        if isinstance(scan_ids, torch.Tensor) and scan_ids.is_cuda:
+            if scan_ids.device != self.bank.device:
+                raise ValueError("PairBuilder: scan ids on %s, the bank on %s" % (scan_ids.device, self.bank.device))
+            ids = scan_ids.to(torch.int32).contiguous()
+        else:
+            h = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
+            if h.size and (h.min() < 0 or h.max() >= self.bank.num_scans):
+                raise ValueError("PairBuilder: scan id out of range [0, %d)" % self.bank.num_scans)
+            ids = torch.from_numpy(h.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
+        if ids.numel() != self.pairs:
+            raise ValueError("PairBuilder: %d scan ids for %d pairs" % (ids.numel(), self.pairs))
+        return ids
+
+    def _out(self, out, with_indices):
+        out = out if out is not None else empty_batch(self.recipe, self.pairs, self.device)
+        rows = nodes = None
+        if with_indices:
+            rows = torch.empty((2, self.pairs, self.recipe.N), dtype=torch.int32, device=self.device)
+            nodes = torch.empty((2, self.pairs, self.recipe.M), dtype=torch.int32, device=self.device)
+        self.last_rows, self.last_node_slots = rows, nodes
+        return out, rows, nodes
+
+    def build(self, scan_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
+              _ws: int = 0) -> Dict[str, torch.Tensor]:
+        out, rows, nodes = self._out(out, with_indices)
+        ops.pairs_build(self.c, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, self.seed,
+                        int(step), self.rank * self.pairs, out, self._ws[_ws], rows, nodes)
+        return out
+
+    def apply(self, scan_ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
+        out, rows, nodes = self._out(out, with_indices)
+        d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in draws.items() if v is not None}
+        ops.pairs_apply(self.c, d, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, out,
+                        self._ws[0], rows, nodes)
+        return out
+
+    def workspace_candidates(self, which: int = 0):
+        """The un-augmented FPS candidates [2P, 3, n_sub] and first indices [2P] in workspace `which` (0: the last build
+        or apply), at the offsets the library reports (usip_pairs_workspace_offset)."""
+        P, ns = self.pairs, self.recipe.n_sub
+        ws = self._ws[which]
+        o_c, o_f = ops.pairs_workspace_offset(self.c, P, 1), ops.pairs_workspace_offset(self.c, P, 2)
+        cand = ws[o_c:o_c + 2 * P * 3 * ns * 4].view(torch.float32).view(2 * P, 3, ns)
+        first = ws[o_f:o_f + 2 * P * 4].view(torch.int32)
+        return cand, first
+
+    def prefetch(self, schedule: Iterable, outs=None):
+        """schedule: iterable of (scan_ids, step).  Yields each batch on the current stream's order; while the consumer
+        enqueues work on batch k, batch k+1 is built on a side stream into the other buffer.  Events order everything:
+        the consumer's stream waits for 'built', the side stream for 'consumed'; the host never waits.
+
+        Leaving the loop early (break, an exception, closing the generator) is safe: when the generator ends, the
+        current stream waits for every build still in flight on the side stream, so later work on the current stream --
+        reusing `outs`, or memory the allocator hands out again -- is ordered after the last write.  The internal
+        buffers are also marked as used on the side stream, so the allocator does not reuse them before it is done.
+        A yielded batch is valid until the next iteration (it is rebuilt two batches later)."""
+        cur = torch.cuda.current_stream(self.device)
+        side = torch.cuda.Stream(self.device)
+        if outs is None:
+            bufs = [empty_batch(self.recipe, self.pairs, self.device) for _ in range(2)]
+            for b in bufs:
+                for t in b.values():
+                    t.record_stream(side)
+        else:
+            bufs = outs
+        built = [torch.cuda.Event(), torch.cuda.Event()]
+        consumed = [None, None]
+
+        def enqueue(i, ids, step):
+            if consumed[i] is not None:
+                side.wait_event(consumed[i])
+            else:
+                side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self.build(ids, step, out=bufs[i], _ws=1 + i)
+            built[i].record(side)
+
+        try:
+            it = iter(schedule)
+            nxt = next(it, None)
+            if nxt is None:
+                return
+            enqueue(0, *nxt)
+            k = 0
+            while True:
+                nxt = next(it, None)
+                if nxt is not None:
+                    enqueue((k + 1) % 2, *nxt)
+                cur.wait_event(built[k % 2])
+                yield bufs[k % 2]
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                consumed[k % 2] = ev
+                k += 1
+                if nxt is None:
+                    return
+        finally:
+            cur.wait_stream(side)
+
+
+def build_cpu(recipe: PairRecipe, scans: Sequence[np.ndarray], scan_ids, pairs: int, seed: int = 0, step: int = 0,
+              rank: int = 0, mode: str = "train", draws: Optional[Dict[str, np.ndarray]] = None):
+    """The host twin (usip_pairs_build_f32_cpu) on numpy scans: Philox draws, or `draws` (the layouts of
+    include/usip_hip.h).  Returns (batch, rows [2,P,N], node_slots [2,P,M])."""
+    c = recipe.c_struct(mode == "train")
+    bank = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float32) for s in scans]))
+    offsets = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+    ids = np.ascontiguousarray(np.asarray(scan_ids, dtype=np.int32))
+    P, N, M, Cs = pairs, recipe.N, recipe.M, recipe.Cs
+    out = {k: np.zeros(s, dtype=np.float32) for k, s in dict(
+        src_pc=(P, 3, N), src_sn=(P, Cs, N), src_node=(P, 3, M), dst_pc=(P, 3, N), dst_sn=(P, Cs, N), dst_node=(P, 3, M),
+        R=(P, 3, 3), scale=(P,), shift=(P, 3, 1)).items()}
+    rows = np.zeros((2, P, N), dtype=np.int32)
+    nodes = np.zeros((2, P, M), dtype=np.int32)
+    o = ops.PairsOutC()
+    for i, side in enumerate(("src", "dst")):
+        o.pc[i], o.sn[i], o.node[i] = (out[side + "_" + k].ctypes.data for k in ("pc", "sn", "node"))
+    o.R, o.scale, o.shift = out["R"].ctypes.data, out["scale"].ctypes.data, out["shift"].ctypes.data
+    o.rows, o.node_slots = rows.ctypes.data, nodes.ctypes.data
+    keep = []
+    d = None
+    if draws is not None:
+        d = ops.PairsDrawsC()
+        for k, _ in ops.PairsDrawsC._fields_:
+            if draws.get(k) is not None:
+                a = np.ascontiguousarray(draws[k], dtype=np.int32 if k in ("rows", "cand", "first") else np.float64)
+                keep.append(a)
+                setattr(d, k, a.ctypes.data)
+    _lib.check(_lib.lib().usip_pairs_build_f32_cpu(
+        ctypes.addressof(c), ctypes.addressof(d) if d is not None else None, bank.ctypes.data, offsets.ctypes.data,
+        len(scans), ids.ctypes.data, P, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, rank * P,
+        ctypes.addressof(o)), "usip_pairs_build_f32_cpu")
+    return out, rows, nodes
