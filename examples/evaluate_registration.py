@@ -1,0 +1,161 @@
+#!/usr/bin/env python
+"""Scores a detector + descriptor the way the reference's MATLAB does (evaluation/matlab/eval_repeatability/eval_rep.m,
+eval_outdoor/kitti/evaluate_kitti.m), on the GPU: keypoint repeatability and RANSAC registration of scan pairs, printed
+as ONE JSON line.
+
+    python examples/evaluate_registration.py --make-synthetic /tmp/eval_data
+    python examples/evaluate_registration.py --data /tmp/eval_data --detector det.pth --descriptor desc.pth \\
+        --write-descriptors /tmp/descriptors
+
+Data layout: <dir>/<id>.bin float32 rows [x y z nx ny nz curvature] and <dir>/pairs.txt with one pair per line,
+`anc_id pos_id tx ty tz qw qx qy qz`: the pose that moves the positive scan into the anchor's frame.  Without checkpoints
+the weights are the repository's seeded ones (usip_amd.synth.fill_parameters): the numbers then say nothing about USIP,
+only that the pipeline runs."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from usip_amd import evaluation, inference, synth                                  # noqa: E402
+from usip_amd.networks import DescriptorLiteOld, DetectorOptions, build_detector   # noqa: E402
+
+CS = 4
+
+
+def quat_to_rot(q):
+    w, x, y, z = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+
+
+def make_synthetic(rng, frames: int, n: int):
+    """-> (scans [(id, rows float32 [n, 3 + CS])], pairs [(anc_id, pos_id, T_gt 3x4)]): frame 0 is a slab-like scene with
+    a few walls; every other frame is a rigidly moved, re-subsampled, jittered copy of it, paired with frame 0."""
+    big = 2 * n
+    pc = synth.make_cloud(rng, big, "slab:30").astype(np.float64)
+    for k in range(12):                                       # walls: structure a detector can hold on to
+        sel = slice(k * big // 24, (k + 1) * big // 24)
+        pc[1, sel] = rng.uniform(-1, 4, sel.stop - sel.start)
+        pc[0 if k % 2 else 2, sel] = rng.uniform(-30, 30)
+    sn = synth.make_normals(rng, big, CS).astype(np.float64)
+    scans, pairs = [], []
+    for f in range(frames):
+        pick = rng.permutation(big)[:n]
+        if f == 0:
+            R, t, q = np.eye(3), np.zeros(3), np.array([1.0, 0, 0, 0])
+        else:
+            yaw = rng.uniform(-0.3, 0.3)                      # about the vertical axis (y), plus a few metres
+            q = np.array([np.cos(yaw / 2), 0, np.sin(yaw / 2), 0])
+            R, t = quat_to_rot(q), rng.uniform(-3, 3, 3) * np.array([1, 0.1, 1])
+        # the scan as seen from frame f: p_f = R' (p_0 - t), so that p_0 = R p_f + t
+        pts = R.T @ (pc[:, pick] - t[:, None]) + rng.normal(0, 0.02, (3, n))
+        nrm = np.concatenate((R.T @ sn[:3, pick], sn[3:, pick]))
+        scans.append((f, np.ascontiguousarray(np.concatenate((pts, nrm)).T, dtype=np.float32)))
+        if f:
+            pairs.append((0, f, np.concatenate((R, t[:, None]), 1)))
+    return scans, pairs
+
+
+def write_dataset(folder, scans, pairs):
+    os.makedirs(folder, exist_ok=True)
+    for fid, rows in scans:
+        rows.tofile(os.path.join(folder, "%06d.bin" % fid))
+    with open(os.path.join(folder, "pairs.txt"), "w") as f:
+        for a, q, T in pairs:
+            R = T[:, :3]
+            w = np.sqrt(max(0.0, 1 + R[0, 0] + R[1, 1] + R[2, 2])) / 2          # small rotations: w is far from zero
+            quat = [w, (R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w)]
+            f.write("%d %d %s\n" % (a, q, " ".join("%.17g" % v for v in list(T[:, 3]) + quat)))
+
+
+def read_dataset(folder):
+    pairs, ids = [], []
+    for line in open(os.path.join(folder, "pairs.txt")):
+        v = line.split()
+        if not v:
+            continue
+        a, q, rest = int(v[0]), int(v[1]), [float(s) for s in v[2:11]]
+        pairs.append((a, q, np.concatenate((quat_to_rot(rest[3:7]), np.asarray(rest[:3])[:, None]), 1)))
+        ids += [a, q]
+    scans = [(i, np.fromfile(os.path.join(folder, "%06d.bin" % i), dtype=np.float32).reshape(-1, 3 + CS))
+             for i in sorted(set(ids))]
+    return scans, pairs
+
+
+def seeded(module):
+    sd = module.state_dict()
+    filled = synth.fill_parameters({k: tuple(v.shape) for k, v in sd.items()})
+    module.load_state_dict({k: torch.from_numpy(v) for k, v in filled.items()})
+    return module
+
+
+def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, descriptor_ckpt=None, device="cuda:0"):
+    dev = torch.device(device)
+    opt = DetectorOptions(surface_normal_len=CS, node_knn_k_1=16)
+    detector = build_detector(model, opt).to(dev)
+    descriptor = DescriptorLiteOld(opt).to(dev)
+    if detector_ckpt:
+        inference.load_detector_state(detector, torch.load(detector_ckpt, map_location=dev))
+    else:
+        seeded(detector)
+    if descriptor_ckpt:
+        inference.load_detector_state(descriptor, torch.load(descriptor_ckpt, map_location=dev))
+    else:
+        seeded(descriptor)
+    return evaluation.RegistrationEvaluator(detector, descriptor, opt, dev, nms_radius=nms_radius, top=top,
+                                            max_trials=max_trials, seed=seed)
+
+
+def add_scans(evaluator, scans, nodes, seed):
+    dev = evaluator.device
+    for fid, rows in scans:
+        t = torch.from_numpy(np.ascontiguousarray(rows.T)).to(dev)
+        pc, sn = t[:3].unsqueeze(0).contiguous(), t[3:].unsqueeze(0).contiguous()
+        first = torch.tensor([(seed + 7919 * int(fid)) % pc.shape[2]], dtype=torch.int32, device=dev)
+        evaluator.add_frame(fid, pc, sn, inference.sample_nodes(pc, nodes, first))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--make-synthetic", metavar="DIR", help="write a small synthetic dataset there and evaluate it")
+    ap.add_argument("--data", metavar="DIR", help="evaluate the dataset in DIR")
+    ap.add_argument("--frames", type=int, default=4)
+    ap.add_argument("--points", type=int, default=16384)
+    ap.add_argument("--model", default="ball", choices=["ball", "som"])
+    ap.add_argument("--detector", help="detector checkpoint (default: seeded weights)")
+    ap.add_argument("--descriptor", help="descriptor checkpoint (default: seeded weights)")
+    ap.add_argument("--nodes", type=int, default=512)
+    ap.add_argument("--top", type=int, default=256)
+    ap.add_argument("--nms-radius", type=float, default=1.0)
+    ap.add_argument("--max-trials", type=int, default=10000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there")
+    args = ap.parse_args()
+    if args.make_synthetic:
+        scans, pairs = make_synthetic(np.random.default_rng(args.seed), args.frames, args.points)
+        write_dataset(args.make_synthetic, scans, pairs)
+        args.data = args.make_synthetic
+    if not args.data:
+        ap.error("give --data DIR or --make-synthetic DIR")
+    scans, pairs = read_dataset(args.data)
+    evaluator = build_evaluator(args.model, args.detector, args.top, args.nms_radius, args.max_trials,
+                                args.seed, args.descriptor)
+    add_scans(evaluator, scans, args.nodes, args.seed)
+    summary = evaluator.evaluate(pairs)
+    summary.pop("per_pair")
+    summary["seeded_weights"] = not (args.detector and args.descriptor)
+    if args.write_descriptors:
+        os.makedirs(args.write_descriptors, exist_ok=True)
+        for fid, _ in scans:
+            inference.write_descriptors_bin(os.path.join(args.write_descriptors, "%06d.bin" % fid),
+                                            *evaluator.frame_arrays(fid))
+    print(json.dumps({k: (None if isinstance(v, float) and v != v else v) for k, v in summary.items()}))   # NaN: no such pair
+
+
+if __name__ == "__main__":
+    main()

@@ -669,6 +669,73 @@ int usip_pairs_build_f32_cpu(const usip_pairs_recipe* recipe, const usip_pairs_d
                              const int64_t* offsets, int num_scans, const int32_t* scan_ids, int P, uint64_t seed,
                              uint64_t step, long long pair_base, const usip_pairs_out* out);
 
+/* ------------------------------------------------------------------ f-6  evaluation: registration and repeatability
+ * Replaces the reference's MATLAB evaluation: evaluation/matlab/eval_outdoor/kitti/evaluate_kitti.m with
+ * external/ransacfitRt.m, ransac.m, estimateRt.m, estimateRigidTransform.m and Utils.compareTransform, and
+ * eval_repeatability/eval_rep.m.  Float64 arithmetic on float32 inputs (MATLAB reads the float32 files into doubles).
+ *
+ * Padded batches with per-pair counts: x1, x2 f32 [P][3][Nmax] (x1 the anchor keypoints, x2 the positive frame's keypoints
+ * they matched), count i32 [P] (clamped into [0, Nmax]), Nmax <= 1024; entries beyond count[p] are never read.
+ *
+ * usip_ransac_trials_f32: trial t of pair p fits x1 = R x2 + t to three distinct correspondences (estimateRigidTransform:
+ * the quaternion of the smallest eigenvalue of B = sum A'A, a fixed-sweep 4x4 Jacobi) and scores it, counts[p][t] =
+ * #{i < count : |x1_i - (R x2_i + t)| < threshold}; hypotheses f64 [P][T][3][4] and triplets_out i32 [P][T][3] are optional
+ * (NULL).  Draws: perm(0..2) of a PairsPerm bijection on [0, count) keyed from Philox4x64-10, key (seed, 0), counter
+ * (t, 9 << 8, g, 0), g = pair_ids[p] (i64 [P]; NULL: g = p) -- a triplet depends on (seed, g, t) only.  The SAME algorithm
+ * as the reference with our OWN draws: MATLAB's rng(0) / randsample stream cannot be reproduced and is not attempted.
+ * usip_ransac_trials_explicit_f32 takes the triplets i32 [P][T][3] (clamped into range) and runs the same arithmetic.
+ * count < 3: every score 0 (ransacfitRt returns before any trial).  A degenerate triplet still gives a finite orthonormal R.
+ *
+ * usip_ransac_select_f32: ransac.m's sequential loop replayed over counts[p][0..T) -- best = 0, N = 1, trial = 0; while
+ * N > trial: counts[trial] >= best (ties: the later trial) updates best, chosen and N = max(log(1 - 0.99) / log(pNo), 10),
+ * pNo = min(1 - eps, max(eps, 1 - (best / count)^3)); trial += 1; stop when trial > max_trials (<= T - 1) -- then the chosen
+ * hypothesis' inlier set and estimateRt over ALL inliers, summed in a fixed order (bit-reproducible).  triplets NULL: the
+ * Philox draws of (seed, pair_ids).  Rt f64 [P][3][4] (zeros when invalid), inlier_mask u8 [P][Nmax], inliers, trialcount
+ * i32 [P], valid u8 [P], optional chosen i32 [P].  count < 3: invalid; count == 3: the fit of the three, trialcount 0; fewer
+ * than 3 inliers: invalid.  With gt f64 [P][3][4]: delta_t = |t_gt - t|, delta_deg = sum |rotm2eul(R_gt' R)| in degrees
+ * (ZYX); an invalid pair gets evaluate_kitti.m's catch values (3, 6).
+ *
+ * usip_repeatability_f32 (eval_rep.m): anc f32 [P][3][Ma], pos f32 [P][3][Mp] with counts, gt f64 [P][3][4]:
+ * min_dist[p][i] = min_j |anc_i - (R_gt pos_j + t_gt)| (float64; inf beyond anc_count or without positives), hits[p] =
+ * #(min_dist < radius), ratio[p] = hits / anc_count (0 for an empty anchor frame).
+ *
+ * usip_nearest_nd_counted_f32: pdist2(pos, anc, 'euclidean', 'smallest', 1) on ragged batches -- usip_nearest_nd_f32's
+ * arithmetic and first-index tie rule with per-frame counts: a f32 [B][C][Ma], b f32 [B][C][Nb], rows beyond a_count get
+ * (inf, 0), candidates beyond b_count are never read. */
+int usip_ransac_trials_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, double threshold,
+                           uint64_t seed, const int64_t* pair_ids, int32_t* counts, double* hypotheses,
+                           int32_t* triplets_out, void* stream);
+int usip_ransac_trials_explicit_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                    double threshold, const int32_t* triplets, int32_t* counts, double* hypotheses,
+                                    void* stream);
+int usip_ransac_select_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, int max_trials,
+                           double threshold, uint64_t seed, const int64_t* pair_ids, const int32_t* triplets,
+                           const int32_t* counts, const double* gt, double* Rt, uint8_t* inlier_mask, int32_t* inliers,
+                           int32_t* trialcount, uint8_t* valid, int32_t* chosen, double* delta_t, double* delta_deg,
+                           void* stream);
+int usip_compare_transform_f64(const double* gt, const double* Rt, int P, double* delta_t, double* delta_deg, void* stream);
+int usip_repeatability_f32(const float* anc, const int32_t* anc_count, const float* pos, const int32_t* pos_count,
+                           const double* gt, double radius, int P, int Ma, int Mp, double* min_dist, int32_t* hits,
+                           double* ratio, void* stream);
+int usip_nearest_nd_counted_f32(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count,
+                                float* min_d, int32_t* arg, int B, int C, int Ma, int Nb, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; the selection runs ransac.m's loop as
+ * written.  triplets NULL = the Philox draws; num_threads splits the P x T trials. */
+int usip_ransac_trials_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                               double threshold, uint64_t seed, const int64_t* pair_ids, const int32_t* triplets,
+                               int32_t* counts, double* hypotheses, int32_t* triplets_out, int num_threads);
+int usip_ransac_select_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                               int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
+                               const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
+                               uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid, int32_t* chosen,
+                               double* delta_t, double* delta_deg);
+int usip_compare_transform_f64_cpu(const double* gt, const double* Rt, int P, double* delta_t, double* delta_deg);
+int usip_repeatability_f32_cpu(const float* anc, const int32_t* anc_count, const float* pos, const int32_t* pos_count,
+                               const double* gt, double radius, int P, int Ma, int Mp, double* min_dist, int32_t* hits,
+                               double* ratio);
+int usip_nearest_nd_counted_f32_cpu(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count,
+                                    float* min_d, int32_t* arg, int B, int C, int Ma, int Nb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,346 @@
+"""Host twins of the f-6 evaluation entries (csrc/registration_cpu.cpp over csrc/registration_math.h) against the numpy
+float64 restatement of the reference's MATLAB (tests/eval_oracle.py, numpy.linalg.eigh -- not the product's Jacobi).  The
+device runs the same header; tests/test_registration_gpu.py holds it to these twins.
+
+Tolerances on a hypothesis, derived: both sides are float64; an eigenvector's error is bounded by |E| / gap with |E| a few
+eps |B|, so for triplets whose two smallest eigenvalues differ by at least 1e-5 lambda_max the entries of R agree to ~4e-10
+and t (lever <= 70 m) to ~3e-8 m.  The issue's first bounds were 1e-8 and 1e-6 m (25-30x that); measured on the 8 000
+trials below the host twin is at 1.9e-12 on R and 3.7e-11 m on t (smallest gap ratio met: 5.2e-5), far inside, so the
+asserted bounds are tightened to 1e-9 on R and 1e-7 m on t: 2.5-3x the derived bound for the solver's constant.
+A trial is left out when the oracle's gap is below 1e-5 lambda_max or an oracle residual lies within 1e-7 m of the
+threshold; at most 1 % may be (0 of 8 000 are).  The angle: 1e-6 degrees (the R error x 57.3, with room)."""
+import numpy as np
+import pytest
+
+import eval_oracle as eo
+from usip_amd import evaluation as ev
+
+TOL_R, TOL_T, TOL_DEG = 1e-9, 1e-7, 1e-6
+GAP, NEAR = 1e-5, 1e-7
+THR = 1.0
+
+
+@pytest.fixture(scope="module")
+def batch():
+    return eo.make_batch(20260, P=4, n=512, T=2000)
+
+
+def oracle_for(batch):
+    x1, x2, count, gt, tri = batch
+    P, T = tri.shape[:2]
+    Rt, cnt, gap, near = np.zeros((P, T, 3, 4)), np.zeros((P, T), int), np.zeros((P, T)), np.zeros((P, T))
+    for p in range(P):
+        for t in range(T):
+            Rt[p, t], cnt[p, t], gap[p, t], near[p, t] = eo.trial(x1[p], x2[p], tri[p, t], THR)
+    return Rt, cnt, gap, near
+
+
+@pytest.fixture(scope="module")
+def oracle_trials(batch):
+    return oracle_for(batch)
+
+
+def check_trials(counts, hyp, oracle, what):
+    Rt, cnt, gap, near = oracle
+    keep = (gap >= GAP) & (near >= NEAR)
+    left_out = 1.0 - keep.mean()
+    err_r = np.abs(hyp[..., :3] - Rt[..., :3]).max((2, 3))
+    err_t = np.abs(hyp[..., 3] - Rt[..., 3]).max(2)
+    print("%s: left out %d of %d (smallest gap ratio %.2e, nearest residual %.2e m), max |dR| %.3e, max |dt| %.3e m, "
+          "count mismatches %d" % (what, (~keep).sum(), keep.size, gap.min(), near.min(), err_r[keep].max(),
+                                   err_t[keep].max(), (counts != cnt)[keep].sum()))
+    assert left_out <= 0.01
+    assert err_r[keep].max() <= TOL_R and err_t[keep].max() <= TOL_T
+    assert np.array_equal(counts[keep], cnt[keep])
+    assert np.isfinite(hyp).all()
+
+
+def test_per_trial_parity_on_explicit_triplets(batch, oracle_trials):
+    x1, x2, count, gt, tri = batch
+    counts, hyp, drawn = ev.ransac_trials_cpu(x1, x2, count, tri.shape[1], THR, triplets=tri)
+    assert np.array_equal(drawn, tri)
+    check_trials(counts, hyp, oracle_trials, "host twin")
+    # threads split the trials, nothing else
+    c2, h2, _ = ev.ransac_trials_cpu(x1, x2, count, tri.shape[1], THR, triplets=tri, num_threads=5)
+    assert np.array_equal(c2, counts) and np.array_equal(h2, hyp)
+
+
+STOP_CASES = {
+    "late tie": ([5, 200, 3, 200, 7, 200] + [1] * 94, 512, 99),
+    "best in trial 0": ([400] + [10] * 99, 512, 99),
+    "zero everywhere": ([0] * 100, 512, 99),
+    "T exhausted": ([30] * 50, 512, 49),
+    "max_trials below T": ([30] * 50, 512, 20),
+    "max_trials 0": ([7, 9, 11], 512, 0),
+    "improves late": ([3] * 40 + [260] + [3] * 59, 512, 99),
+}
+
+
+def boundary_case():
+    """counts for which N falls below the trial counter exactly at a boundary: with best = b of 512, N = N(b); put the
+    improvement so that the loop stops right after it."""
+    n, b = 512, 300
+    N = eo.trials_needed(b, n)              # ~20.6: the loop runs while N > trialcount
+    at = int(np.ceil(N)) + 3                # the improvement arrives after the budget of b has already passed
+    return [3] * at + [b] + [3] * 40, n, at + 40
+
+
+STOP_CASES["N below trial at a boundary"] = boundary_case()
+
+
+@pytest.mark.parametrize("name", sorted(STOP_CASES))
+def test_stopping_rule_on_hand_made_counts(name):
+    scores, n, max_trials = STOP_CASES[name]
+    T = len(scores)
+    x1, x2, count, gt, tri = eo.make_batch(5, P=1, n=n, T=T)
+    counts = np.asarray(scores, np.int32)[None]
+    chosen, trialcount = eo.replay(scores, n, max_trials)
+    o = ev.ransac_select_cpu(x1, x2, count, counts, max_trials, THR, triplets=tri)
+    assert (int(o["chosen"][0]), int(o["trialcount"][0])) == (chosen, trialcount), name
+
+
+def test_stopping_rule_cases_mean_what_they_say():
+    s, n, m = STOP_CASES["late tie"]
+    assert eo.replay(s, n, m)[0] == 5                                   # ties: the later trial
+    assert eo.replay(*STOP_CASES["zero everywhere"]) == (99, 100)       # >= 0 always updates; runs to max_trials + 1
+    assert eo.replay(*STOP_CASES["T exhausted"])[1] == 50
+    assert eo.replay(*STOP_CASES["max_trials 0"]) == (0, 1)
+    s, n, m = STOP_CASES["N below trial at a boundary"]
+    at = s.index(300)
+    assert eo.replay(s, n, m) == (at, at + 1)                           # stops right after the improvement
+
+
+def test_end_to_end_on_explicit_triplets(batch):
+    x1, x2, count, gt, tri = batch
+    T = tri.shape[1]
+    r = ev.ransac_registration_cpu(x1, x2, count, THR, T - 1, triplets=tri, gt=gt)
+    for p in range(len(count)):
+        o = eo.ransacfit(x1[p], x2[p], THR, T - 1, tri[p], gt[p])
+        assert (int(r.chosen[p]), int(r.trialcount[p])) == (o["chosen"], o["trialcount"])
+        assert np.array_equal(np.nonzero(r.inlier_mask[p])[0], o["inliers"]) and r.inliers[p] == len(o["inliers"])
+        assert r.valid[p] == 1
+        assert np.abs(r.Rt[p][:, :3] - o["Rt"][:, :3]).max() <= TOL_R and np.abs(r.Rt[p][:, 3] - o["Rt"][:, 3]).max() <= TOL_T
+        assert abs(r.delta_t[p] - o["delta_t"]) <= TOL_T and abs(r.delta_deg[p] - o["delta_deg"]) <= TOL_DEG
+    dt, dd = ev.compare_transform_cpu(gt, r.Rt)
+    assert np.array_equal(dt, r.delta_t) and np.array_equal(dd, r.delta_deg)
+
+
+def test_compare_transform_against_oracle_including_the_singular_branch():
+    rng = np.random.default_rng(11)
+    A = np.stack([np.concatenate((eo.random_rotation(rng, rng.uniform(0, 3)), rng.normal(size=(3, 1))), 1) for _ in range(64)])
+    B = np.stack([np.concatenate((eo.random_rotation(rng, rng.uniform(0, 3)), rng.normal(size=(3, 1))), 1) for _ in range(64)])
+    A[0, :, :3] = np.eye(3)
+    B[0, :, :3] = np.array([[0.0, 0, 1], [0, 1, 0], [-1, 0, 0]])        # pitch of 90 degrees: sy = 0
+    dt, dd = ev.compare_transform_cpu(A, B)
+    for p in range(64):
+        et, ed = eo.compare_transform(A[p], B[p])
+        assert abs(dt[p] - et) <= 1e-12 and abs(dd[p] - ed) <= TOL_DEG
+    assert abs(dd[0] - 90.0) <= TOL_DEG
+
+
+def test_edge_counts():
+    x1, x2, count, gt, tri = eo.make_batch(8, P=4, n=64, T=50, counts=[0, 2, 3, 4], nmax=64, inlier_share=1.0)
+    r = ev.ransac_registration_cpu(x1, x2, count, THR, 49, triplets=tri, gt=gt)
+    assert r.valid.tolist() == [0, 0, 1, 1]
+    assert r.trialcount[:3].tolist() == [0, 0, 0] and r.inliers[:3].tolist() == [0, 0, 3]
+    assert (r.delta_t[:2] == 3).all() and (r.delta_deg[:2] == 6).all() and (r.Rt[:2] == 0).all()
+    assert r.inlier_mask[2].tolist() == [1, 1, 1] + [0] * 61
+    o3 = eo.estimate_rigid_transform(x1[2][:, :3], x2[2][:, :3])[0]
+    assert np.abs(r.Rt[2] - o3).max() <= TOL_T
+    o4 = eo.ransacfit(x1[3][:, :4], x2[3][:, :4], THR, 49, tri[3], gt[3])
+    assert int(r.trialcount[3]) == o4["trialcount"] and int(r.chosen[3]) == o4["chosen"]
+    assert np.array_equal(np.nonzero(r.inlier_mask[3])[0], o4["inliers"])
+
+
+def test_degenerate_triplets_give_finite_orthonormal_rotations():
+    n, T = 16, 4
+    x1, x2 = np.zeros((3, 3, n), np.float32), np.zeros((3, 3, n), np.float32)
+    x1[0], x2[0] = 1.5, -2.5                                             # all correspondences identical
+    line = np.linspace(-30, 30, n, dtype=np.float32)
+    x1[1] = np.stack((line, 2 * line, 0.5 * line)) + 1                   # collinear
+    x2[1] = np.stack((line, 2 * line, 0.5 * line))
+    rng = np.random.default_rng(2)
+    x1[2], x2[2] = rng.normal(size=(3, n)), rng.normal(size=(3, n))
+    tri = np.zeros((3, T, 3), np.int32)
+    tri[:, :] = [[0, 1, 2], [3, 9, 15], [5, 5, 5], [7, 7, 2]]            # the last two: coincident picks
+    counts, hyp, _ = ev.ransac_trials_cpu(x1, x2, np.full(3, n, np.int32), T, THR, triplets=tri)
+    assert np.isfinite(hyp).all()
+    R = hyp[..., :3]
+    assert np.abs(np.linalg.det(R) - 1).max() < 1e-9
+    assert np.abs(R @ R.transpose(0, 1, 3, 2) - np.eye(3)).max() < 1e-9
+    assert (counts[0] == n).all()                                        # identical points: R = I, t = the offset
+    r = ev.ransac_registration_cpu(x1, x2, np.full(3, n, np.int32), THR, T - 1, triplets=tri)
+    assert np.isfinite(r.Rt).all()
+
+
+def test_no_inlier_set_of_three_is_invalid():
+    rng = np.random.default_rng(4)
+    n, T = 64, 40
+    x1 = rng.uniform(-40, 40, size=(1, 3, n)).astype(np.float32)
+    x2 = rng.uniform(-40, 40, size=(1, 3, n)).astype(np.float32)
+    tri = np.stack([rng.choice(n, 3, replace=False) for _ in range(T)]).astype(np.int32)[None]
+    gt = np.concatenate((np.eye(3), np.zeros((3, 1))), 1)[None]
+    r = ev.ransac_registration_cpu(x1, x2, np.array([n], np.int32), 1e-3, T - 1, triplets=tri, gt=gt)
+    assert r.counts.max() < 3
+    assert r.valid[0] == 0 and r.inliers[0] == 0 and r.inlier_mask.sum() == 0
+    assert (r.delta_t[0], r.delta_deg[0]) == (3.0, 6.0) and r.trialcount[0] == T
+
+
+def test_ragged_batch_equals_one_by_one_and_ignores_nan_padding():
+    cs = [512, 100, 37, 5]
+    x1, x2, count, gt, tri = eo.make_batch(9, P=4, n=512, T=300, counts=cs, nmax=600)
+    r = ev.ransac_registration_cpu(x1, x2, count, THR, 299, triplets=tri, gt=gt)
+    n1, n2 = x1.copy(), x2.copy()
+    for p, c in enumerate(cs):
+        n1[p, :, c:] = np.nan
+        n2[p, :, c:] = np.nan
+    rn = ev.ransac_registration_cpu(n1, n2, count, THR, 299, triplets=tri, gt=gt)
+    for a, b in zip(r, rn):
+        assert np.array_equal(a, b)
+    for p, c in enumerate(cs):
+        one = ev.ransac_registration_cpu(x1[p:p + 1, :, :c], x2[p:p + 1, :, :c], count[p:p + 1], THR, 299,
+                                         triplets=tri[p:p + 1], gt=gt[p:p + 1])
+        assert np.array_equal(one.Rt[0], r.Rt[p]) and np.array_equal(one.counts[0], r.counts[p])
+        assert np.array_equal(one.inlier_mask[0], r.inlier_mask[p, :c]) and one.trialcount[0] == r.trialcount[p]
+
+
+@pytest.mark.parametrize("n", [3, 4, 5, 511, 512, 1000])
+def test_philox_draws_are_distinct_in_range_and_position_free(n):
+    T = 4000
+    x = np.zeros((3, 3, n), np.float32)
+    cnt = np.full(3, n, np.int32)
+    ids = np.array([7, 123456789012, 7], np.int64)
+    _, _, d = ev.ransac_trials_cpu(x, x, cnt, T, THR, seed=5, pair_ids=ids)
+    assert d.min() >= 0 and d.max() < n
+    assert (d[..., 0] != d[..., 1]).all() and (d[..., 0] != d[..., 2]).all() and (d[..., 1] != d[..., 2]).all()
+    assert np.array_equal(d[0], d[2]) and not np.array_equal(d[0], d[1])          # same g: same triplets
+    _, _, alone = ev.ransac_trials_cpu(x[:1], x[:1], cnt[:1], T, THR, seed=5, pair_ids=ids[:1])
+    assert np.array_equal(alone[0], d[0])                                           # not on P or the others
+    _, _, short = ev.ransac_trials_cpu(x[:1], x[:1], cnt[:1], 10, THR, seed=5, pair_ids=ids[:1])
+    assert np.array_equal(short[0], d[0, :10])                                      # not on T
+    _, _, other = ev.ransac_trials_cpu(x[:1], x[:1], cnt[:1], T, THR, seed=6, pair_ids=ids[:1])
+    assert not np.array_equal(other[0], d[0])
+    _, _, default = ev.ransac_trials_cpu(x, x, cnt, 16, THR, seed=5)
+    _, _, named = ev.ransac_trials_cpu(x, x, cnt, 16, THR, seed=5, pair_ids=np.arange(3))
+    assert np.array_equal(default, named)                                           # default ids: 0..P-1
+    if n <= 512:
+        # every index about equally often: chi-square with n - 1 degrees of freedom over the 3 T draws of one pair;
+        # mean n - 1, standard deviation sqrt(2 (n - 1)); the bound is the mean + 6 standard deviations (loose on purpose)
+        obs = np.bincount(d[1].ravel(), minlength=n)
+        chi2 = ((obs - 3 * T / n) ** 2 / (3 * T / n)).sum()
+        assert chi2 < (n - 1) + 6 * np.sqrt(2 * (n - 1)) + 1, (n, chi2)
+
+
+def test_registration_recovers_a_known_pose_with_philox_draws():
+    x1, x2, count, gt, _ = eo.make_batch(31, P=3, n=512, T=1)
+    ids = np.array([0, 5, 9], np.int64)
+    r = ev.ransac_registration_cpu(x1, x2, count, THR, 10000, seed=1, pair_ids=ids, gt=gt, num_threads=8)
+    assert r.valid.all() and (r.delta_t < 0.1).all() and (r.delta_deg < 0.5).all() and (r.inliers >= 150).all()
+    _, _, drawn = ev.ransac_trials_cpu(x1, x2, count, 10001, THR, seed=1, pair_ids=ids, num_threads=8)
+    for p in range(3):
+        o = eo.ransacfit(x1[p], x2[p], THR, 10000, drawn[p], gt[p])
+        assert (o["chosen"], o["trialcount"]) == (int(r.chosen[p]), int(r.trialcount[p]))
+    again = ev.ransac_registration_cpu(x1, x2, count, THR, 10000, seed=1, pair_ids=ids, gt=gt)
+    for a, b in zip(r, again):
+        assert np.array_equal(a, b)                                                 # bit-identical, threads or not
+
+
+def test_repeatability_against_oracle():
+    rng = np.random.default_rng(6)
+    P, Ma, Mp = 5, 300, 280
+    na, npos = np.array([300, 17, 0, 128, 64], np.int32), np.array([280, 250, 40, 0, 1], np.int32)
+    pos = rng.uniform(-40, 40, size=(P, 3, Mp)).astype(np.float32)
+    gt = np.stack([np.concatenate((eo.random_rotation(rng, 0.4), rng.uniform(-3, 3, size=(3, 1))), 1) for _ in range(P)])
+    anc = np.full((P, 3, Ma), np.nan, np.float32)
+    for p in range(P):
+        m = min(na[p], npos[p])
+        moved = gt[p][:, :3] @ pos[p].astype(np.float64) + gt[p][:, 3:4]
+        anc[p, :, :na[p]] = rng.uniform(-40, 40, size=(3, na[p]))
+        anc[p, :, :m] = moved[:, :m] + rng.normal(0, 0.4, size=(3, m))          # about half inside the radius
+    pos_nan = pos.copy()
+    for p in range(P):
+        pos_nan[p, :, npos[p]:] = np.nan
+    ratio, hits, md = ev.repeatability_cpu(anc, na, pos_nan, npos, gt, 0.5)
+    near = 0
+    for p in range(P):
+        m, h, r = eo.repeatability(anc[p][:, :na[p]], pos[p][:, :npos[p]], gt[p], 0.5)
+        near += int((np.abs(m - 0.5) < 1e-7).sum())
+        if npos[p] and na[p]:
+            assert np.abs(md[p, :na[p]] - m).max() <= 1e-9
+        assert np.isinf(md[p, na[p]:]).all()
+        assert hits[p] == h and ratio[p] == r
+    assert near == 0 and 0.2 < ratio[0] < 0.9
+
+
+def unit_descriptors(rng, B, C, M):
+    d = rng.normal(size=(B, C, M))
+    return (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+
+
+def check_matches(idx, anc, pos, na, nb):
+    rows = unclear = wrong = 0
+    for p in range(len(na)):
+        arg, two = eo.match(anc[p][:, :na[p]], pos[p][:, :nb[p]])
+        close = (two[:, 1] - two[:, 0]) < 1e-5 * two[:, 1]
+        rows += na[p]
+        unclear += int(close.sum())
+        wrong += int((idx[p, :na[p]] != arg)[~close].sum())
+        assert (idx[p, na[p]:] == 0).all()
+    print("matching: %d rows, %d with two nearest within 1e-5 relative, %d mismatches elsewhere" % (rows, unclear, wrong))
+    assert unclear <= 0.01 * rows and wrong == 0
+
+
+def test_descriptor_matching_against_oracle():
+    rng = np.random.default_rng(12)
+    B, C, M = 8, 128, 512
+    anc, pos = unit_descriptors(rng, B, C, M), unit_descriptors(rng, B, C, M)
+    full = np.full(B, M, np.int32)
+    check_matches(ev.match_descriptors_cpu(anc, pos, full, full), anc, pos, full, full)
+    na = np.array([512, 1, 0, 300, 77, 512, 64, 9], np.int32)
+    nb = np.array([512, 400, 30, 1, 65, 129, 64, 500], np.int32)
+    a2, p2 = anc.copy(), pos.copy()
+    for p in range(B):
+        a2[p, :, na[p]:] = np.nan
+        p2[p, :, nb[p]:] = np.nan
+    check_matches(ev.match_descriptors_cpu(a2, p2, na, nb), anc, pos, na, nb)
+
+
+def test_descriptor_matching_takes_the_first_of_exact_ties():
+    rng = np.random.default_rng(13)
+    anc, pos = unit_descriptors(rng, 1, 32, 40), unit_descriptors(rng, 1, 32, 200)
+    pos[0, :, 150] = pos[0, :, 20]                      # duplicates: the lower index wins
+    pos[0, :, 199] = pos[0, :, 70]
+    anc[0, :, 3] = pos[0, :, 20]
+    anc[0, :, 4] = pos[0, :, 199]
+    idx = ev.match_descriptors_cpu(anc, pos, np.array([40], np.int32), np.array([200], np.int32))
+    assert idx[0, 3] == 20 and idx[0, 4] == 70
+
+
+def test_descriptor_bin_round_trip(tmp_path):
+    from usip_amd import inference
+    rng = np.random.default_rng(14)
+    xyz, desc = rng.normal(size=(37, 3)).astype(np.float32), rng.normal(size=(37, 128)).astype(np.float32)
+    path = str(tmp_path / "000000.bin")
+    inference.write_descriptors_bin(path, xyz, desc)
+    raw = np.fromfile(path, dtype=np.float32)
+    assert raw.size == 37 * 131 and np.array_equal(raw.reshape(37, 131)[:, :3], xyz)       # rows [x y z d0 .. d127]
+    x2, d2 = inference.read_descriptors_bin(path, 131)
+    assert np.array_equal(x2, xyz) and np.array_equal(d2, desc)
+    with pytest.raises(ValueError):
+        inference.read_descriptors_bin(path, 130)
+
+
+def test_summary_uses_matlab_statistics():
+    per = dict(delta_t=np.array([0.1, 0.3, 3.0, 0.2]), delta_deg=np.array([0.5, 1.5, 6.0, 5.5]),
+               inliers=np.array([100, 50, 0, 80]), matches=np.array([200, 200, 10, 160]),
+               trialcount=np.array([70, 90, 10001, 100]), repeatability=np.array([0.5, 0.25, 0.0, 0.75]),
+               keypoint_num=np.array([200, 200, 10, 160]))
+    s = ev.summarize(per)
+    assert s["wrong"] == 2 and s["pairs"] == 4                          # delta_t > 2 or delta_deg > 5
+    assert s["rte_mean"] == pytest.approx(0.2) and s["rte_std"] == pytest.approx(np.std([0.1, 0.3], ddof=1))
+    assert s["rre_mean"] == pytest.approx(1.0) and s["inlier_ratio_mean"] == pytest.approx(0.375)
+    assert s["trial_count_mean"] == 80 and s["repeatability_mean"] == 0.375
+    assert (s["repeatability_min"], s["repeatability_max"], s["keypoint_num_mean"]) == (0.0, 0.75, 142.5)
+    for k in ("wrong", "inlier_ratio_mean", "trial_count_mean", "rte_mean", "rte_std", "rre_mean", "rre_std",
+              "repeatability_mean", "repeatability_min", "repeatability_max", "keypoint_num_mean", "per_pair"):
+        assert k in s

@@ -8,6 +8,8 @@ the reference's own Python surface:
                                                 class names, constructors and state_dict keys
   usip_amd.networks                        RPN_Detector / RPN_Detector_Ball built on the above
   usip_amd.step                            ModelDetector.optimize as one data-parallel step
+  usip_amd.evaluation                      keypoint repeatability and RANSAC registration (the reference's MATLAB
+                                           evaluation) on the device: `from usip_amd import evaluation`
 
 `usip_amd.install()` registers the drop-in extension modules under their reference names
 (`import index_max`, `import ball_query`) so that the reference's models/networks.py runs
@@ -23,3 +25,11 @@ def install():
     sys.modules["index_max"] = index_max
     sys.modules["ball_query"] = ball_query
     return index_max, ball_query
+
+
+def __getattr__(name):
+    # `usip_amd.evaluation` without importing torch at package import
+    if name == "evaluation":
+        import importlib
+        return importlib.import_module(".evaluation", __name__)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

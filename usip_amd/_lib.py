@@ -15,6 +15,7 @@ _f32p = ctypes.c_void_p
 _i32p = ctypes.c_void_p
 _int = ctypes.c_int
 _flt = ctypes.c_float
+_dbl = ctypes.c_double
 _stream = ctypes.c_void_p
 
 # name -> argtypes; must list every symbol include/usip_hip.h declares (tests check this).
@@ -154,6 +155,25 @@ SIGNATURES = {
                               ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
     "usip_pairs_build_f32_cpu": ([ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int,
                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p], _int),
+    # f-6 evaluation: RANSAC registration, repeatability, counted matching (usip_amd/evaluation.py)
+    "usip_ransac_trials_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p, _i32p,
+                                ctypes.c_void_p, _i32p, _stream], _int),
+    "usip_ransac_trials_explicit_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, _i32p, _i32p, ctypes.c_void_p,
+                                         _stream], _int),
+    "usip_ransac_select_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p,
+                                _i32p, _i32p] + [ctypes.c_void_p] * 9 + [_stream], _int),
+    "usip_compare_transform_f64": ([ctypes.c_void_p] * 2 + [_int] + [ctypes.c_void_p] * 2 + [_stream], _int),
+    "usip_repeatability_f32": ([_f32p, _i32p, _f32p, _i32p, ctypes.c_void_p, _dbl, _int, _int, _int, ctypes.c_void_p,
+                                _i32p, ctypes.c_void_p, _stream], _int),
+    "usip_nearest_nd_counted_f32": ([_f32p, _f32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _int, _stream], _int),
+    "usip_ransac_trials_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p, _i32p,
+                                    _i32p, ctypes.c_void_p, _i32p, _int], _int),
+    "usip_ransac_select_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p,
+                                    _i32p, _i32p] + [ctypes.c_void_p] * 9, _int),
+    "usip_compare_transform_f64_cpu": ([ctypes.c_void_p] * 2 + [_int] + [ctypes.c_void_p] * 2, _int),
+    "usip_repeatability_f32_cpu": ([_f32p, _i32p, _f32p, _i32p, ctypes.c_void_p, _dbl, _int, _int, _int, ctypes.c_void_p,
+                                    _i32p, ctypes.c_void_p], _int),
+    "usip_nearest_nd_counted_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _int], _int),
 }
 
 

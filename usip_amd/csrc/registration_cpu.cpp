@@ -1,0 +1,289 @@
+// usip_amd/csrc/registration_cpu.cpp -- host twin of csrc/registration.hip: the same draws and arithmetic
+// (csrc/registration_math.h) on host pointers.  The selection runs ransac.m's loop as written (usip_reg::replay); the
+// refit adds in the device's order (REFIT_LANES strided partial sums, then the binary tree).  Never reached from the
+// device entry points.
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include <vector>
+#include "registration_math.h"
+#include "../../include/usip_hip.h"
+
+using namespace usip_reg;
+
+namespace {
+
+int clamp_count(const int32_t* count, int p, int nmax)
+{
+    const int n = count[p];
+    return n < 0 ? 0 : (n > nmax ? nmax : n);
+}
+
+bool shape_ok(int P, int Nmax, int T) { return P >= 0 && P <= 65535 && Nmax >= 1 && Nmax <= NMAX && T >= 1; }
+
+void load3(const float* a, const float* b, int Nmax, const int idx[3], double x[3][3], double y[3][3])
+{
+    for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < 3; ++c) {
+            x[k][c] = (double)a[(long long)c * Nmax + idx[k]];
+            y[k][c] = (double)b[(long long)c * Nmax + idx[k]];
+        }
+}
+
+double residual_at(const double Rt[12], const float* a, const float* b, int Nmax, int i)
+{
+    return residual(Rt, (double)a[i], (double)a[(long long)Nmax + i], (double)a[2LL * Nmax + i], (double)b[i],
+                    (double)b[(long long)Nmax + i], (double)b[2LL * Nmax + i]);
+}
+
+template <class Src>
+void trials_range(const float* x1, const float* x2, const int32_t* count, int Nmax, int T, double threshold,
+                  const Src& src, int32_t* counts, double* hyp, int32_t* drawn, long long lo, long long hi)
+{
+    for (long long o = lo; o < hi; ++o) {
+        const int p = (int)(o / T), t = (int)(o - (long long)p * T);
+        const int n = clamp_count(count, p, Nmax);
+        const float* a = x1 + (long long)p * 3 * Nmax;
+        const float* b = x2 + (long long)p * 3 * Nmax;
+        if (n < 3) {
+            counts[o] = 0;
+            if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = 0.0;
+            if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = 0;
+            continue;
+        }
+        int idx[3];
+        src.get(p, t, n, T, idx);
+        double x[3][3], y[3][3], Rt[12];
+        load3(a, b, Nmax, idx, x, y);
+        fit3(x, y, Rt);
+        int hits = 0;
+        for (int i = 0; i < n; ++i) hits += residual_at(Rt, a, b, Nmax, i) < threshold ? 1 : 0;
+        counts[o] = hits;
+        if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = Rt[k];
+        if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = idx[k];
+    }
+}
+
+template <class Src>
+void trials_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, double threshold,
+                 const Src& src, int32_t* counts, double* hyp, int32_t* drawn, int num_threads)
+{
+    const long long total = (long long)P * T;
+    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
+    if (nt == 1 || total < 2 * nt) {
+        trials_range(x1, x2, count, Nmax, T, threshold, src, counts, hyp, drawn, 0, total);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; ++w) {
+        const long long lo = total * w / nt, hi = total * (w + 1) / nt;
+        pool.emplace_back([=, &src] { trials_range(x1, x2, count, Nmax, T, threshold, src, counts, hyp, drawn, lo, hi); });
+    }
+    for (auto& th : pool) th.join();
+}
+
+template <int W>
+void tree_sum(double (*part)[10])
+{
+    for (int s = REFIT_LANES / 2; s > 0; s >>= 1)
+        for (int l = 0; l < s; ++l)
+            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
+}
+
+template <class Src>
+void select_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, int max_trials,
+                 double threshold, const Src& src, const int32_t* counts, const double* gt, double* Rt_out,
+                 uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid, int32_t* chosen,
+                 double* delta_t, double* delta_deg)
+{
+    std::vector<double> part_store((size_t)REFIT_LANES * 10);
+    double (*part)[10] = reinterpret_cast<double (*)[10]>(part_store.data());
+    std::vector<uint8_t> in((size_t)NMAX);
+    for (int p = 0; p < P; ++p) {
+        const int n = clamp_count(count, p, Nmax);
+        const float* a = x1 + (long long)p * 3 * Nmax;
+        const float* b = x2 + (long long)p * 3 * Nmax;
+        uint8_t* mask = inlier_mask + (long long)p * Nmax;
+        std::memset(mask, 0, (size_t)Nmax);
+        int pick = 0, tc = 0, ninl = 0;
+        double Rt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (n > 3) replay(counts + (long long)p * T, n, max_trials, &pick, &tc);
+        if (n >= 3) {
+            int idx[3] = {0, 1, 2};
+            if (n > 3) src.get(p, pick, n, T, idx);
+            double x[3][3], y[3][3], R0[12];
+            load3(a, b, Nmax, idx, x, y);
+            fit3(x, y, R0);
+            for (int i = 0; i < n; ++i) {
+                in[i] = (n == 3 || residual_at(R0, a, b, Nmax, i) < threshold) ? 1 : 0;
+                ninl += in[i];
+            }
+        }
+        const bool ok = ninl >= 3;
+        if (ok) {
+            double cen[6];
+            for (int l = 0; l < REFIT_LANES; ++l) {
+                for (int k = 0; k < 10; ++k) part[l][k] = 0.0;
+                for (int i = l; i < n; i += REFIT_LANES)
+                    if (in[i])
+                        for (int c = 0; c < 3; ++c) {
+                            part[l][c] += (double)a[(long long)c * Nmax + i];
+                            part[l][3 + c] += (double)b[(long long)c * Nmax + i];
+                        }
+            }
+            tree_sum<6>(part);
+            for (int k = 0; k < 6; ++k) cen[k] = part[0][k] / (double)ninl;
+            for (int l = 0; l < REFIT_LANES; ++l) {
+                double B[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                for (int i = l; i < n; i += REFIT_LANES)
+                    if (in[i]) {
+                        double xc[3], yc[3];
+                        for (int c = 0; c < 3; ++c) {
+                            xc[c] = (double)a[(long long)c * Nmax + i] - cen[c];
+                            yc[c] = (double)b[(long long)c * Nmax + i] - cen[3 + c];
+                        }
+                        accumulate(B, xc, yc);
+                    }
+                for (int k = 0; k < 10; ++k) part[l][k] = B[k];
+            }
+            tree_sum<10>(part);
+            double Bs[10];
+            for (int k = 0; k < 10; ++k) Bs[k] = part[0][k];
+            transform_from(Bs, cen, cen + 3, Rt);
+            for (int i = 0; i < n; ++i) mask[i] = in[i];
+        }
+        for (int k = 0; k < 12; ++k) Rt_out[(long long)p * 12 + k] = Rt[k];
+        inliers[p] = ok ? ninl : 0;
+        trialcount[p] = tc;
+        valid[p] = ok ? 1 : 0;
+        if (chosen) chosen[p] = pick;
+        if (gt) {
+            double dt = 3.0, dd = 6.0;
+            if (ok) compare(gt + (long long)p * 12, Rt, &dt, &dd);
+            delta_t[p] = dt;
+            delta_deg[p] = dd;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int usip_ransac_trials_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                          double threshold, uint64_t seed, const int64_t* pair_ids,
+                                          const int32_t* triplets, int32_t* counts, double* hypotheses,
+                                          int32_t* triplets_out, int num_threads)
+{
+    if (!shape_ok(P, Nmax, T)) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!x1 || !x2 || !count || !counts) return USIP_EINVAL;
+    if (triplets) {
+        const ExplicitTriplets src{triplets};
+        trials_host(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, num_threads);
+    } else {
+        const PhiloxTriplets src{seed, pair_ids};
+        trials_host(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, num_threads);
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_ransac_select_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                          int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
+                                          const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
+                                          uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid,
+                                          int32_t* chosen, double* delta_t, double* delta_deg)
+{
+    if (!shape_ok(P, Nmax, T) || max_trials < 0 || max_trials > T - 1) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!x1 || !x2 || !count || !counts || !Rt || !inlier_mask || !inliers || !trialcount || !valid) return USIP_EINVAL;
+    if (gt && (!delta_t || !delta_deg)) return USIP_EINVAL;
+    if (triplets) {
+        const ExplicitTriplets src{triplets};
+        select_host(x1, x2, count, P, Nmax, T, max_trials, threshold, src, counts, gt, Rt, inlier_mask, inliers,
+                    trialcount, valid, chosen, delta_t, delta_deg);
+    } else {
+        const PhiloxTriplets src{seed, pair_ids};
+        select_host(x1, x2, count, P, Nmax, T, max_trials, threshold, src, counts, gt, Rt, inlier_mask, inliers,
+                    trialcount, valid, chosen, delta_t, delta_deg);
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_compare_transform_f64_cpu(const double* gt, const double* Rt, int P, double* delta_t,
+                                              double* delta_deg)
+{
+    if (P < 0) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!gt || !Rt || !delta_t || !delta_deg) return USIP_EINVAL;
+    for (int p = 0; p < P; ++p) compare(gt + (long long)p * 12, Rt + (long long)p * 12, delta_t + p, delta_deg + p);
+    return USIP_OK;
+}
+
+extern "C" int usip_repeatability_f32_cpu(const float* anc, const int32_t* anc_count, const float* pos,
+                                          const int32_t* pos_count, const double* gt, double radius, int P, int Ma, int Mp,
+                                          double* min_dist, int32_t* hits, double* ratio)
+{
+    if (P < 0 || P > 65535 || Ma < 1 || Mp < 1) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!anc || !anc_count || !pos || !pos_count || !gt || !min_dist || !hits || !ratio) return USIP_EINVAL;
+    std::vector<double> q((size_t)3 * Mp);
+    for (int p = 0; p < P; ++p) {
+        const int na = clamp_count(anc_count, p, Ma), np = clamp_count(pos_count, p, Mp);
+        const float* A = anc + (long long)p * 3 * Ma;
+        const float* Q = pos + (long long)p * 3 * Mp;
+        const double* G = gt + (long long)p * 12;
+        for (int j = 0; j < np; ++j) {
+            const double y0 = (double)Q[j], y1 = (double)Q[(long long)Mp + j], y2 = (double)Q[2LL * Mp + j];
+            for (int c = 0; c < 3; ++c)
+                q[(size_t)c * Mp + j] = ((G[4 * c] * y0 + G[4 * c + 1] * y1) + G[4 * c + 2] * y2) + G[4 * c + 3];
+        }
+        int h = 0;
+        for (int i = 0; i < Ma; ++i) {
+            double best = INFINITY;
+            if (i < na) {
+                const double ax = (double)A[i], ay = (double)A[(long long)Ma + i], az = (double)A[2LL * Ma + i];
+                for (int j = 0; j < np; ++j) {
+                    const double d0 = ax - q[j], d1 = ay - q[(size_t)Mp + j], d2 = az - q[(size_t)2 * Mp + j];
+                    const double d = (d0 * d0 + d1 * d1) + d2 * d2;
+                    best = d < best ? d : best;
+                }
+                best = std::sqrt(best);
+                h += best < radius ? 1 : 0;
+            }
+            min_dist[(long long)p * Ma + i] = best;
+        }
+        hits[p] = h;
+        ratio[p] = na > 0 ? (double)h / (double)na : 0.0;
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_nearest_nd_counted_f32_cpu(const float* a, const float* b, const int32_t* a_count,
+                                               const int32_t* b_count, float* min_d, int32_t* arg, int B, int C, int Ma,
+                                               int Nb)
+{
+    if (B < 0 || B > 65535 || C < 1 || Ma < 0 || Nb < 1) return USIP_EINVAL;
+    if ((long long)B * Ma == 0) return USIP_OK;
+    if (!a || !b || !a_count || !b_count || !min_d || !arg) return USIP_EINVAL;
+    for (int bi = 0; bi < B; ++bi) {
+        const int na = clamp_count(a_count, bi, Ma), nb = clamp_count(b_count, bi, Nb);
+        const float* ab = a + (long long)bi * C * Ma;
+        const float* bb = b + (long long)bi * C * Nb;
+        for (int i = 0; i < Ma; ++i) {
+            float best = INFINITY;
+            int bj = 0;
+            if (i < na)
+                for (int j = 0; j < nb; ++j) {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) {
+                        const float df = ab[(long long)c * Ma + i] - bb[(long long)c * Nb + j];
+                        s = std::fmaf(df, df, s);
+                    }
+                    const float d = std::sqrt(s);
+                    if (d < best) { best = d; bj = j; }
+                }
+            min_d[(long long)bi * Ma + i] = best;
+            arg[(long long)bi * Ma + i] = bj;
+        }
+    }
+    return USIP_OK;
+}

@@ -1,0 +1,227 @@
+// usip_amd/csrc/registration_math.h -- the arithmetic of RANSAC registration and keypoint repeatability,
+// shared by the kernels of csrc/registration.hip and the host twin of csrc/registration_cpu.cpp: both sides run the same
+// float64 operations in the same order on float32 inputs (the reference reads its float32 files into MATLAB doubles).
+//
+// Reference semantics (evaluation/matlab/eval_outdoor/external, kitti/evaluate_kitti.m, eval_repeatability/eval_rep.m):
+//   estimateRigidTransform  x = R y + t: centre both sets, B = sum A_i' A_i with A_i = [0, (y-x)'; (x-y), [y+x]x], the unit
+//                           quaternion (w, x, y, z) of B's smallest eigenvalue, quat2rot, t = xbar - R ybar
+//   euc3Ddist               inlier i: sqrt(sum((x1_i - (R x2_i + t))^2)) < threshold
+//   ransac                  the adaptive stopping rule (replay / update below), ties go to the LATER trial
+//   ransacfitRt             count < 3: nothing; count == 3: the fit of the three; a final refit over all inliers
+//   Utils.compareTransform  |t_gt - t|, sum |rotm2eul(R_gt' R)| in degrees (MATLAB's default ZYX sequence)
+// Draws are our own (MATLAB's rng(0) / randsample stream cannot be reproduced): trial t of the pair with global id g takes
+// perm(0), perm(1), perm(2) of a PairsPerm bijection on [0, count) keyed from the Philox4x64-10 block with key (seed, 0) and
+// counter (t, TAG_RANSAC << 8, g, 0) -- the triplet depends on (seed, g, t) only.
+#pragma once
+#include <math.h>
+#include "pairs_rng.h"
+
+namespace usip_reg {
+
+constexpr uint32_t TAG_RANSAC = 9;      // continues the stream tags of csrc/pairs_rng.h
+constexpr int NMAX = 1024;              // correspondences per pair
+constexpr int JACOBI_SWEEPS = 8;        // 4x4, float64: the off-diagonal mass is below 1e-300 of the norm by then
+constexpr int REFIT_LANES = 256;        // the refit's sums: lane l adds rows l, l + 256, ... in order, then a binary tree
+
+// The ten entries of the symmetric 4x4 B: 00 01 02 03 11 12 13 22 23 33.  x, y: one centred correspondence.
+USIP_HD void accumulate(double B[10], const double x[3], const double y[3])
+{
+    const double d0 = y[0] - x[0], d1 = y[1] - x[1], d2 = y[2] - x[2];
+    const double s0 = y[0] + x[0], s1 = y[1] + x[1], s2 = y[2] + x[2];
+    B[0] += (d0 * d0 + d1 * d1) + d2 * d2;
+    B[1] += d2 * s1 - d1 * s2;
+    B[2] += d0 * s2 - d2 * s0;
+    B[3] += d1 * s0 - d0 * s1;
+    B[4] += (d0 * d0 + s2 * s2) + s1 * s1;
+    B[5] += d0 * d1 - s0 * s1;
+    B[6] += d0 * d2 - s0 * s2;
+    B[7] += (d1 * d1 + s2 * s2) + s0 * s0;
+    B[8] += d1 * d2 - s1 * s2;
+    B[9] += (d2 * d2 + s1 * s1) + s0 * s0;
+}
+
+// One Jacobi rotation in the (P, Q) plane of the symmetric a (full storage), accumulated into the columns of v.
+template <int P, int Q>
+USIP_HD void jacobi_rotate(double a[4][4], double v[4][4])
+{
+    const double apq = a[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
+    const double root = sqrt(theta * theta + 1.0);                     // inf for a vanishing apq: t = 0, no NaN
+    const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + root);
+    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                      // columns P, Q
+        const double akp = a[k][P], akq = a[k][Q];
+        a[k][P] = c * akp - s * akq;
+        a[k][Q] = s * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                                      // rows P, Q
+        const double apk = a[P][k], aqk = a[Q][k];
+        a[P][k] = c * apk - s * aqk;
+        a[Q][k] = s * apk + c * aqk;
+    }
+    a[P][Q] = 0.0;
+    a[Q][P] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double vkp = v[k][P], vkq = v[k][Q];
+        v[k][P] = c * vkp - s * vkq;
+        v[k][Q] = s * vkp + c * vkq;
+    }
+}
+
+// q = the unit eigenvector of B's smallest eigenvalue (the first of equal ones): cyclic Jacobi, a fixed number of sweeps in
+// a fixed order -- no data-dependent exit, so host and device walk the same path.  B = 0 gives q = (1, 0, 0, 0).
+USIP_HD void smallest_eigenvector(const double B[10], double q[4])
+{
+    double a[4][4] = {{B[0], B[1], B[2], B[3]}, {B[1], B[4], B[5], B[6]}, {B[2], B[5], B[7], B[8]}, {B[3], B[6], B[8], B[9]}};
+    double v[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+        jacobi_rotate<0, 1>(a, v);
+        jacobi_rotate<0, 2>(a, v);
+        jacobi_rotate<0, 3>(a, v);
+        jacobi_rotate<1, 2>(a, v);
+        jacobi_rotate<1, 3>(a, v);
+        jacobi_rotate<2, 3>(a, v);
+    }
+    double e = a[0][0];
+    q[0] = v[0][0]; q[1] = v[1][0]; q[2] = v[2][0]; q[3] = v[3][0];
+    if (a[1][1] < e) { e = a[1][1]; q[0] = v[0][1]; q[1] = v[1][1]; q[2] = v[2][1]; q[3] = v[3][1]; }
+    if (a[2][2] < e) { e = a[2][2]; q[0] = v[0][2]; q[1] = v[1][2]; q[2] = v[2][2]; q[3] = v[3][2]; }
+    if (a[3][3] < e) { e = a[3][3]; q[0] = v[0][3]; q[1] = v[1][3]; q[2] = v[2][3]; q[3] = v[3][3]; }
+}
+
+// quat2rot, then t = cx - R cy.  Rt row-major [3][4].
+USIP_HD void transform_from(const double B[10], const double cx[3], const double cy[3], double Rt[12])
+{
+    double q[4];
+    smallest_eigenvector(B, q);
+    const double q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
+    Rt[0] = ((q0 * q0 + q1 * q1) - q2 * q2) - q3 * q3;
+    Rt[1] = 2.0 * (q1 * q2 - q0 * q3);
+    Rt[2] = 2.0 * (q1 * q3 + q0 * q2);
+    Rt[4] = 2.0 * (q1 * q2 + q0 * q3);
+    Rt[5] = ((q0 * q0 - q1 * q1) + q2 * q2) - q3 * q3;
+    Rt[6] = 2.0 * (q2 * q3 - q0 * q1);
+    Rt[8] = 2.0 * (q1 * q3 - q0 * q2);
+    Rt[9] = 2.0 * (q2 * q3 + q0 * q1);
+    Rt[10] = ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        Rt[4 * i + 3] = cx[i] - ((Rt[4 * i] * cy[0] + Rt[4 * i + 1] * cy[1]) + Rt[4 * i + 2] * cy[2]);
+}
+
+// estimateRigidTransform on three correspondences: x[k], y[k] = row k of the triplet.
+USIP_HD void fit3(const double x[3][3], const double y[3][3], double Rt[12])
+{
+    double cx[3], cy[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        cx[k] = ((x[0][k] + x[1][k]) + x[2][k]) / 3.0;
+        cy[k] = ((y[0][k] + y[1][k]) + y[2][k]) / 3.0;
+    }
+    double B[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double xc[3] = {x[i][0] - cx[0], x[i][1] - cx[1], x[i][2] - cx[2]};
+        const double yc[3] = {y[i][0] - cy[0], y[i][1] - cy[1], y[i][2] - cy[2]};
+        accumulate(B, xc, yc);
+    }
+    transform_from(B, cx, cy, Rt);
+}
+
+// euc3Ddist's residual of one correspondence
+USIP_HD double residual(const double Rt[12], double x0, double x1, double x2, double y0, double y1, double y2)
+{
+    const double r0 = x0 - (((Rt[0] * y0 + Rt[1] * y1) + Rt[2] * y2) + Rt[3]);
+    const double r1 = x1 - (((Rt[4] * y0 + Rt[5] * y1) + Rt[6] * y2) + Rt[7]);
+    const double r2 = x2 - (((Rt[8] * y0 + Rt[9] * y1) + Rt[10] * y2) + Rt[11]);
+    return sqrt((r0 * r0 + r1 * r1) + r2 * r2);
+}
+
+// ransac.m's trial budget after a new best score
+USIP_HD double trials_needed(int best, int count)
+{
+    const double eps = 2.220446049250313e-16;
+    const double f = (double)best / (double)count;
+    double p_no = 1.0 - (f * f) * f;
+    p_no = p_no < eps ? eps : p_no;
+    p_no = p_no > 1.0 - eps ? 1.0 - eps : p_no;
+    const double n = log(1.0 - 0.99) / log(p_no);
+    return n < 10.0 ? 10.0 : n;
+}
+
+// ransac.m's loop over precomputed scores, as written: the host twin runs it, the device kernel evaluates the same rule
+// per trial in parallel (csrc/registration.hip) and the tests hold the two together.  max_trials <= T - 1.
+USIP_HD void replay(const int32_t* counts, int count, int max_trials, int* chosen, int* trialcount)
+{
+    int best = 0, trial = 0, pick = 0;
+    double N = 1.0;
+    while (N > (double)trial) {
+        if (counts[trial] >= best) {
+            best = counts[trial];
+            pick = trial;
+            N = trials_needed(best, count);
+        }
+        ++trial;
+        if (trial > max_trials) break;
+    }
+    *chosen = pick;
+    *trialcount = trial;
+}
+
+// Utils.compareTransform: gt, Rt row-major [3][4]
+USIP_HD void compare(const double gt[12], const double Rt[12], double* delta_t, double* delta_deg)
+{
+    const double e0 = gt[3] - Rt[3], e1 = gt[7] - Rt[7], e2 = gt[11] - Rt[11];
+    *delta_t = sqrt((e0 * e0 + e1 * e1) + e2 * e2);
+    double D[3][3];                                                    // R_gt' R
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) D[i][j] = (gt[i] * Rt[j] + gt[4 + i] * Rt[4 + j]) + gt[8 + i] * Rt[8 + j];
+    // rotm2eul, 'ZYX': sy = |(D00, D10)|; the singular branch sets the third angle to zero
+    const double sy = sqrt(D[0][0] * D[0][0] + D[1][0] * D[1][0]);
+    double ex, ey, ez;
+    if (sy < 10.0 * 2.220446049250313e-16) {
+        ex = atan2(-D[1][2], D[1][1]);
+        ey = atan2(-D[2][0], sy);
+        ez = 0.0;
+    } else {
+        ex = atan2(D[2][1], D[2][2]);
+        ey = atan2(-D[2][0], sy);
+        ez = atan2(D[1][0], D[0][0]);
+    }
+    *delta_deg = ((fabs(ex) + fabs(ey)) + fabs(ez)) * 180.0 / 3.141592653589793;
+}
+
+// The three correspondences of one trial, from either source of draws; always inside [0, count), count >= 1.
+struct PhiloxTriplets {
+    uint64_t seed;
+    const int64_t* ids;          // global pair ids (NULL: g = p)
+    USIP_HD void get(int p, int t, int count, int T, int idx[3]) const
+    {
+        uint64_t b[4];
+        usip_pairs::pairs_block(seed, 0, ids ? (uint64_t)ids[p] : (uint64_t)p, TAG_RANSAC, 0, (uint64_t)t, b);
+        usip_pairs::PairsPerm perm;
+        perm.init(b, (uint64_t)count);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) idx[k] = (int)perm((uint64_t)(k < count ? k : count - 1));
+    }
+};
+struct ExplicitTriplets {
+    const int32_t* triplets;     // i32 [P][T][3]
+    USIP_HD void get(int p, int t, int count, int T, int idx[3]) const
+    {
+        const int32_t* s = triplets + ((long long)p * T + t) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int v = s[k];
+            idx[k] = v < 0 ? 0 : (v >= count ? count - 1 : v);
+        }
+    }
+};
+
+}  // namespace usip_reg

@@ -6,6 +6,10 @@
   select_keypoints    sigma-ordered NMS + top-k by sigma (evaluation/save_keypoints.py:180-216, :343-351)
   write_keypoints_bin float32 M x 3 row-major file read by evaluation/matlab/eval_repeatability (:392-393)
   load_detector_state checkpoint loading with the 'module.' prefix fix-up (kitti/train_detector.py:42-51)
+  describe_keypoints  eval-mode descriptor forward around given keypoints (models/keypoint_descriptor.py:178-184) with a
+                      fixed point permutation, so a frame's descriptors do not depend on the call
+  write_descriptors_bin / read_descriptors_bin   float32 rows [x y z d0 .. d(D-1)]: what the reference's
+                      evaluation/matlab Utils.load_descriptors(fname, 3 + D) reads
 """
 from collections import OrderedDict
 from typing import List
@@ -54,3 +58,32 @@ def load_detector_state(detector: torch.nn.Module, state_dict):
     fixed = OrderedDict((k[len("module."):] if k.startswith("module.") else k, v) for k, v in state_dict.items())
     detector.load_state_dict(fixed)
     return detector
+
+
+def describe_keypoints(descriptor: torch.nn.Module, pc: torch.Tensor, sn: torch.Tensor, keypoints: torch.Tensor,
+                       perm_seed: int = 0) -> torch.Tensor:
+    """pc f32 [B,3,N], sn f32 [B,Cs,N], keypoints f32 [B,3,M] -> descriptors f32 [B,D,M] (unit length).  The reference
+    permutes the points at random on every call (networks.py:345-347: ball_query keeps the first K points inside the
+    ball); here the permutation is a function of (perm_seed, N) alone."""
+    descriptor.eval()
+    perm = np.random.default_rng(int(perm_seed)).permutation(pc.shape[2])
+    with torch.no_grad():
+        desc, _ = descriptor(pc, sn, keypoints.contiguous(), False, None, perm=perm)
+    return desc
+
+
+def write_descriptors_bin(path: str, xyz: np.ndarray, desc: np.ndarray):
+    """xyz [M,3], desc [M,D] -> float32 [M, 3 + D] row-major."""
+    xyz, desc = np.asarray(xyz, dtype=np.float32), np.asarray(desc, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or desc.ndim != 2 or desc.shape[0] != xyz.shape[0]:
+        raise ValueError("write_descriptors_bin: expected xyz [M,3] and desc [M,D]")
+    np.ascontiguousarray(np.concatenate((xyz, desc), axis=1)).tofile(path)
+
+
+def read_descriptors_bin(path: str, m: int):
+    """m = 3 + D floats per row -> (xyz float32 [M,3], desc float32 [M,D])."""
+    flat = np.fromfile(path, dtype=np.float32)
+    if m < 4 or flat.size % m:
+        raise ValueError("read_descriptors_bin: %s does not hold rows of %d floats" % (path, m))
+    rows = flat.reshape(-1, m)
+    return rows[:, :3].copy(), rows[:, 3:].copy()

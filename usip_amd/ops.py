@@ -1476,3 +1476,147 @@ def pairs_workspace_bytes(recipe: PairsRecipeC, P: int) -> int:
     if n < 0:
         raise RuntimeError("usip_amd: usip_pairs_workspace_bytes: invalid recipe (USIP_EINVAL)")
     return n
+
+
+# ------------------------------------------------------------------------------------------------ f-6 evaluation
+def _opt_ptr(t):
+    return _ptr(t) if t is not None else None
+
+
+def _need_pairs(x1, x2, count):
+    _need(x1, "x1", torch.float32)
+    _need(x2, "x2", torch.float32)
+    _need(count, "count", torch.int32)
+    if x1.dim() != 3 or x1.shape[1] != 3 or x2.shape != x1.shape or count.shape != (x1.shape[0],):
+        raise RuntimeError("registration: expected x1, x2 f32 [P,3,Nmax] and count i32 [P]")
+    if not 1 <= x1.shape[2] <= 1024:
+        raise RuntimeError("registration: Nmax must be in 1..1024 (got %d)" % x1.shape[2])
+    return x1.shape[0], x1.shape[2]
+
+
+def _need_on(t, name, dtype, shape, device):
+    if t is None:
+        return
+    _need(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise RuntimeError("registration: %s must be %s %s on %s" % (name, dtype, tuple(shape), device))
+
+
+def ransac_trials(x1, x2, count, T: int, threshold: float, seed: int = 0, pair_ids=None, triplets=None,
+                  want_hypotheses: bool = False, want_triplets: bool = False):
+    """f-6: inlier counts of T rigid-fit trials per pair -> (counts i32 [P,T], hypotheses f64 [P,T,3,4] or None, drawn
+    triplets i32 [P,T,3] or None).  triplets i32 [P,T,3]: explicit draws; otherwise Philox draws of (seed, pair_ids)."""
+    P, Nmax = _need_pairs(x1, x2, count)
+    T = int(T)
+    dev = x1.device
+    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
+    _need_on(triplets, "triplets", torch.int32, (P, T, 3), dev)
+    counts = torch.empty((P, T), dtype=torch.int32, device=dev)
+    hyp = torch.empty((P, T, 3, 4), dtype=torch.float64, device=dev) if want_hypotheses else None
+    drawn = torch.empty((P, T, 3), dtype=torch.int32, device=dev) if want_triplets and triplets is None else triplets
+    with torch.cuda.device(dev), prof.kernel("ransac_trials", 24.0 * P * Nmax + 4.0 * P * T, 30.0 * P * T * Nmax):
+        if triplets is None:
+            _lib.check(_lib.lib().usip_ransac_trials_f32(
+                _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                _opt_ptr(pair_ids), _ptr(counts), _opt_ptr(hyp), _opt_ptr(drawn), _stream(x1)), "usip_ransac_trials_f32")
+        else:
+            _lib.check(_lib.lib().usip_ransac_trials_explicit_f32(
+                _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, float(threshold), _ptr(triplets), _ptr(counts),
+                _opt_ptr(hyp), _stream(x1)), "usip_ransac_trials_explicit_f32")
+    return counts, hyp, (drawn if want_triplets else None)
+
+
+def ransac_select(x1, x2, count, counts, max_trials: int, threshold: float, seed: int = 0, pair_ids=None, triplets=None,
+                  gt=None):
+    """f-6: ransac.m's stopping rule replayed over counts i32 [P,T], the chosen hypothesis' inliers and the refit ->
+    dict(Rt f64 [P,3,4], inlier_mask u8 [P,Nmax], inliers, trialcount, chosen i32 [P], valid u8 [P], delta_t, delta_deg
+    f64 [P] or None without gt)."""
+    P, Nmax = _need_pairs(x1, x2, count)
+    dev = x1.device
+    _need(counts, "counts", torch.int32)
+    if counts.dim() != 2 or counts.shape[0] != P or counts.device != dev:
+        raise RuntimeError("registration: counts must be i32 [P,T] on %s" % dev)
+    T = counts.shape[1]
+    if not 0 <= int(max_trials) <= T - 1:
+        raise RuntimeError("registration: max_trials must be in 0..T-1 (T = %d, got %d)" % (T, max_trials))
+    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
+    _need_on(triplets, "triplets", torch.int32, (P, T, 3), dev)
+    _need_on(gt, "gt", torch.float64, (P, 3, 4), dev)
+    out = {"Rt": torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
+           "inlier_mask": torch.empty((P, Nmax), dtype=torch.uint8, device=dev),
+           "inliers": torch.empty((P,), dtype=torch.int32, device=dev),
+           "trialcount": torch.empty((P,), dtype=torch.int32, device=dev),
+           "valid": torch.empty((P,), dtype=torch.uint8, device=dev),
+           "chosen": torch.empty((P,), dtype=torch.int32, device=dev),
+           "delta_t": torch.empty((P,), dtype=torch.float64, device=dev) if gt is not None else None,
+           "delta_deg": torch.empty((P,), dtype=torch.float64, device=dev) if gt is not None else None}
+    with torch.cuda.device(dev), prof.kernel("ransac_select", 4.0 * P * T + 24.0 * P * Nmax, 60.0 * P * Nmax):
+        _lib.check(_lib.lib().usip_ransac_select_f32(
+            _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, int(max_trials), float(threshold),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, _opt_ptr(pair_ids), _opt_ptr(triplets), _ptr(counts), _opt_ptr(gt),
+            _ptr(out["Rt"]), _ptr(out["inlier_mask"]), _ptr(out["inliers"]), _ptr(out["trialcount"]), _ptr(out["valid"]),
+            _ptr(out["chosen"]), _opt_ptr(out["delta_t"]), _opt_ptr(out["delta_deg"]), _stream(x1)),
+            "usip_ransac_select_f32")
+    return out
+
+
+def compare_transform(gt, Rt):
+    """f-6: Utils.compareTransform on gt, Rt f64 [P,3,4] -> (delta_t, delta_deg) f64 [P]."""
+    _need(gt, "gt", torch.float64)
+    _need(Rt, "Rt", torch.float64)
+    if gt.dim() != 3 or tuple(gt.shape[1:]) != (3, 4) or Rt.shape != gt.shape or Rt.device != gt.device:
+        raise RuntimeError("compare_transform: expected gt, Rt f64 [P,3,4] on one device")
+    P = gt.shape[0]
+    dt = torch.empty((P,), dtype=torch.float64, device=gt.device)
+    dd = torch.empty((P,), dtype=torch.float64, device=gt.device)
+    with torch.cuda.device(gt.device), prof.kernel("compare_transform", 208.0 * P):
+        _lib.check(_lib.lib().usip_compare_transform_f64(_ptr(gt), _ptr(Rt), P, _ptr(dt), _ptr(dd), _stream(gt)),
+                   "usip_compare_transform_f64")
+    return dt, dd
+
+
+def repeatability(anc, anc_count, pos, pos_count, gt, radius: float):
+    """f-6: eval_rep.m on ragged batches: anc f32 [P,3,Ma], pos f32 [P,3,Mp], counts i32 [P], gt f64 [P,3,4] ->
+    (min_dist f64 [P,Ma], hits i32 [P], ratio f64 [P])."""
+    _need_pts(anc, "anc")
+    _need_pts(pos, "pos")
+    P, _, Ma = anc.shape
+    Mp = pos.shape[2]
+    dev = anc.device
+    if pos.shape[0] != P or pos.device != dev or Ma < 1 or Mp < 1:
+        raise RuntimeError("repeatability: expected anc [P,3,Ma], pos [P,3,Mp] on one device")
+    _need_on(anc_count, "anc_count", torch.int32, (P,), dev)
+    _need_on(pos_count, "pos_count", torch.int32, (P,), dev)
+    _need_on(gt, "gt", torch.float64, (P, 3, 4), dev)
+    if anc_count is None or pos_count is None or gt is None:
+        raise RuntimeError("repeatability: anc_count, pos_count and gt are required")
+    md = torch.empty((P, Ma), dtype=torch.float64, device=dev)
+    hits = torch.empty((P,), dtype=torch.int32, device=dev)
+    ratio = torch.empty((P,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), prof.kernel("repeatability", 12.0 * P * (Ma + Mp), 8.0 * P * Ma * Mp):
+        _lib.check(_lib.lib().usip_repeatability_f32(_ptr(anc), _ptr(anc_count), _ptr(pos), _ptr(pos_count), _ptr(gt),
+                                                     float(radius), P, Ma, Mp, _ptr(md), _ptr(hits), _ptr(ratio),
+                                                     _stream(anc)), "usip_repeatability_f32")
+    return md, hits, ratio
+
+
+def nearest_nd_counted(a, b, a_count, b_count):
+    """f-6: nearest_nd with per-frame counts: a f32 [B,C,Ma], b f32 [B,C,Nb], counts i32 [B] -> (min distance f32 [B,Ma],
+    first arg-min i32 [B,Ma]); rows beyond a_count get (inf, 0)."""
+    _need(a, "a", torch.float32)
+    _need(b, "b", torch.float32)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[:2] != b.shape[:2] or a.device != b.device or b.shape[2] < 1:
+        raise RuntimeError("nearest_nd_counted: expected a [B,C,Ma] and b [B,C,Nb] on one device")
+    B, C, Ma = a.shape
+    Nb = b.shape[2]
+    _need_on(a_count, "a_count", torch.int32, (B,), a.device)
+    _need_on(b_count, "b_count", torch.int32, (B,), a.device)
+    if a_count is None or b_count is None:
+        raise RuntimeError("nearest_nd_counted: counts are required")
+    d = torch.empty((B, Ma), dtype=torch.float32, device=a.device)
+    arg = torch.empty((B, Ma), dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device), prof.kernel("nearest_nd_counted", 4.0 * B * C * (Ma + Nb), 3.0 * B * C * Ma * Nb):
+        _lib.check(_lib.lib().usip_nearest_nd_counted_f32(_ptr(a), _ptr(b), _ptr(a_count), _ptr(b_count), _ptr(d),
+                                                          _ptr(arg), B, C, Ma, Nb, _stream(a)),
+                   "usip_nearest_nd_counted_f32")
+    return d, arg
