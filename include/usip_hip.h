@@ -50,6 +50,14 @@ enum { USIP_TUNE_INDEX_MAX_CH = 0, USIP_TUNE_INDEX_MAX_UNROLL, USIP_TUNE_X3_WGRA
 int usip_set_tuning(const char* name, int value);
 int usip_tuning_value(int knob);
 
+/* Which kernels did a call launch?  usip_launch_log(1) arms (and empties) the calling thread's log, usip_launch_log(0)
+ * switches it off; both return the number of launches it held.  While armed, every kernel launch the library makes from
+ * that thread is recorded (the first 8).  usip_launch_log_entry(i, &wg): the demangled name of launch i's kernel, as a
+ * rocprofv3 kernel trace prints it ("void (anonymous namespace)::gemm_x2f_kernel<1, 1, false>(...)"), valid until the
+ * thread's next call, and its number of workgroups; NULL when there is no entry i.  No reference counterpart. */
+int usip_launch_log(int on);
+const char* usip_launch_log_entry(int i, unsigned* workgroups);
+
 /* ------------------------------------------------------------------ a-1  index_max
  * Replaces index_max.forward_cuda / forward_cuda_shared_mem
  * (models/index_max_ext/index_max.cpp:132-148 -> index_max_cuda.cu:9-25, :29-61, :65-98).
@@ -59,6 +67,9 @@ int usip_tuning_value(int knob);
  * Lifts the reference's limits (B <= 1024 threads, B*K*4 <= 48 KB shared memory). */
 int usip_index_max_f32(const float* data, const int32_t* index, int32_t* max_idx,
                        int B, int C, int N, int K, void* stream);
+/* The launch geometry usip_index_max_f32 / usip_index_max_values_f32 choose for a shape (knobs applied): channel rows per
+ * workgroup, prefetch depth, threads per workgroup.  Host arithmetic only; lets a benchmark name the launch it times. */
+int usip_index_max_geometry(int B, int C, int N, int K, int* channel_rows, int* prefetch_depth, int* threads);
 
 /* Host twins: index_max.forward_cpu (index_max.cpp:73-112) and forward_multi_thread_cpu
  * (index_max.cpp:33-70; channels split over num_threads std::threads).  HOST pointers. */
@@ -323,12 +334,6 @@ int usip_mlp_gemm_x2h_f32(const void* planes, const float* X, const float* X2, c
  * d and of y.  usip_mlp_gemm_x2d_red_tiles() = tiles of such a launch, 0 when the shape does not take this path (M % 256,
  * P % 128, 256-row tiles): use usip_mlp_gemm_x2h_f32 + usip_bn_backward_reduce_f32 then. */
 int usip_mlp_gemm_x2d_red_tiles(int M, int K, int P, int nb, int red_group);
-/* Round 6 (profiling aid, no reference counterpart): 1 when usip_mlp_gemm_x2h_f32 runs a launch of this shape that reaches
- * the direct kernel as csrc/gemm_x2f.hip -- one wave per SIMD, 256-channel x 256-position tiles, 64 positions per wave; the
- * same products in the same order as csrc/gemm_x2d.hip (bit-identical outputs).  has_stats / has_bias: the pointer is given;
- * rb_group 0: no row bias; y_rows 0: M. */
-int usip_mlp_gemm_x2f_used(int M, int K, int P, int nb, int pro, int has_stats, int has_bias, int rb_group,
-                           int pool_group, int y_rows);
 int usip_mlp_gemm_x2h_red_f32(const void* planes, const float* X, const float* X2, const float* coef, int pro,
                               const float* pool_dp, const int32_t* pool_arg, int pool_group, float* Y,
                               const float* red_y, const float* red_coef, float* red_out, float* red_gsum,
@@ -398,7 +403,6 @@ int usip_bn_pool_backward_reduce_f32(const float* dpooled, const int32_t* arg, c
  * PRE-BatchNorm output of the producing layer and relu(X*xcoef[0][n] + xcoef[1][n]) is formed on the fly
  * (the activated tensor is never stored). */
 long long usip_mlp_wgrad_workspace(int M, int N, int P, int nb);
-int usip_mlp_wgrad_blocks(int M, int N, int P, int nb);        /* workgroups launched (profiling aid) */
 int usip_mlp_wgrad_f32(const float* G, const float* G2, const float* coef, int pro, const float* X,
                        const float* xcoef, const float* pool_dp, const int32_t* pool_arg, int pool_group,
                        float* workspace, float* dW, int ldw, int coloff,
@@ -505,7 +509,6 @@ int usip_mlp_wgrad_x2h_f32(const float* G, const float* G2, const float* coef, i
                         float* workspace, float* dW, int ldw, int coloff,
                         int M, int N, int P, int nb, void* stream);
 int usip_mlp_wgrad_f32x3_used(int M, int N, int P, int nb);
-int usip_mlp_wgrad_f32x3_blocks(int M, int N, int P, int nb);   /* < 0: the 256 x 256-tile kernel, |value| workgroups */
 
 /* ------------------------------------------------------------------ a-6 / a-7 / a-12  grouping, pooling
  * out[b][coff+c][m][k] = x[b][c][idx[b][m][k]] - (c < nsub ? sub[b][c][m] : 0), written into the

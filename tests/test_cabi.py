@@ -28,6 +28,39 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.usip_version()
 
 
+# (channel rows, prefetch depth, threads) for the knob triples (ch, u, th) in (1, 2, 4, 8) x (1, 2, 4) x (256, 512, 1024), in
+# that order -- recorded from the Python function ops.index_max_geometry was before the library answered the question; the
+# three shapes of test_native_ops_gpu.py::test_index_max_launch_geometries_agree all give this table
+_INDEX_MAX_GEOMETRIES = [
+    (1, 1, 256), (1, 1, 512), (1, 1, 1024), (1, 2, 256), (1, 2, 512), (1, 2, 1024), (1, 4, 256), (1, 2, 512), (1, 2, 1024),
+    (2, 1, 256), (2, 1, 512), (2, 1, 1024), (2, 2, 256), (2, 2, 512), (2, 2, 1024), (2, 4, 256), (2, 2, 512), (2, 2, 1024),
+    (4, 1, 256), (4, 1, 512), (4, 1, 1024), (4, 2, 256), (4, 2, 512), (4, 2, 1024), (4, 4, 256), (4, 2, 512), (4, 2, 1024),
+    (8, 1, 256), (8, 1, 512), (8, 1, 1024), (8, 2, 256), (8, 2, 512), (8, 2, 1024), (8, 2, 256), (8, 2, 512), (8, 2, 1024)]
+
+
+def test_index_max_geometry_is_the_launchers_own_choice():
+    """ops.index_max_geometry asks the library (usip_index_max_geometry, the function the launcher itself calls) and
+    returns what its Python predecessor returned: the sweep of test_index_max_launch_geometries_agree and bench.py's two
+    stand-alone shapes with the knobs at rest."""
+    import itertools
+    from usip_amd import _lib, ops
+    lib = _lib.lib()
+    try:
+        for shape in [(2, 64, 16384, 512), (3, 8, 5000, 37), (1, 16, 1028, 5)]:
+            got = []
+            for ch, u, th in itertools.product((1, 2, 4, 8), (1, 2, 4), (256, 512, 1024)):
+                lib.usip_set_tuning(b"index_max_ch", ch)
+                lib.usip_set_tuning(b"index_max_unroll", u)
+                lib.usip_set_tuning(b"index_max_threads", th)
+                got.append(ops.index_max_geometry(*shape))
+            assert got == _INDEX_MAX_GEOMETRIES, shape
+    finally:
+        for knob in (b"index_max_ch", b"index_max_unroll", b"index_max_threads"):
+            lib.usip_set_tuning(knob, 0)
+    assert ops.index_max_geometry(16, 64, 16384, 512) == (2, 2, 256)
+    assert ops.index_max_geometry(16, 128, 16384, 512) == (2, 2, 256)
+
+
 def test_dropin_modules_have_reference_entry_points():
     import usip_amd
     im, bq = usip_amd.install()

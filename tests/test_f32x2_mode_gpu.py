@@ -715,6 +715,18 @@ def test_all_dma_forward_gemm_equals_the_direct_one_bit_for_bit(shape, stats, x2
         ops.PLANES_CACHE = None
 
 
+def _launched(lib, call):
+    """-> (call(), the demangled names of the kernels the library launched for it on this thread, in order)"""
+    lib.usip_launch_log(1)
+    try:
+        out, names = call(), []
+        while (name := lib.usip_launch_log_entry(len(names), None)) is not None:
+            names.append(name.decode())
+    finally:
+        lib.usip_launch_log(0)
+    return out, names
+
+
 X2F_SHAPES = [(4, 256, 256, 8192), (16, 256, 512, 8192), (16, 512, 512, 4096), (2, 640, 512, 8192), (8, 128, 256, 8192)]
 
 
@@ -730,7 +742,6 @@ def test_one_wave_per_simd_gemm_equals_the_direct_one_bit_for_bit(shape, x2_forc
     nb, K, M, P = shape
     lib = _lib.lib()
     assert lib.usip_mlp_x3p_tile_rows(M, P, nb) == 256
-    assert lib.usip_mlp_gemm_x2f_used(M, K, P, nb, 1, 1, 1, 0, 0, 0) == 1
     g = torch.Generator().manual_seed(K * 5 + M + P + nb)
     At = (torch.randn(K, M, generator=g) * (2.0 / K) ** 0.5).to(DEV)
     X = (torch.randn(nb, K, P, generator=g) * 1.7 + 0.2).to(DEV)
@@ -744,7 +755,8 @@ def test_one_wave_per_simd_gemm_equals_the_direct_one_bit_for_bit(shape, x2_forc
         for rb in (None, rowbias):
             for stats in (True, False):
                 kw = dict(want_stats=stats, pro=1, coef=coef, rowbias=rb, rb_group=16 if rb is not None else 1)
-                y1, s1 = ops.mlp_gemm(At, X, bias, **kw)
+                (y1, s1), ran = _launched(lib, lambda: ops.mlp_gemm(At, X, bias, **kw))
+                assert "::gemm_x2f_kernel<1, %d, false>(" % stats in ran[-1], ran       # (weight split first, the GEMM last)
                 lib.usip_set_tuning(b"x2_direct", 12)
                 y0, s0 = ops.mlp_gemm(At, X, bias, **kw)
                 lib.usip_set_tuning(b"x2_direct", 0)
@@ -780,6 +792,32 @@ def test_one_wave_per_simd_gemm_equals_the_direct_one_bit_for_bit(shape, x2_forc
     finally:
         lib.usip_set_tuning(b"x2_direct", 0)
         ops.PLANES_CACHE = None
+
+
+def test_profiled_gemm_is_keyed_by_the_kernel_it_launched(x2_forced):
+    """The rocprof key of a profiled operator (usip_amd/prof.py) comes from the library's launch log, not from a Python
+    restatement of the dispatch: the same call is keyed gemm_x2f_kernel by default and gemm_x2d_kernel with knob
+    x2_direct = 12, workgroup count attached."""
+    from usip_amd import _lib, ops, prof
+    lib = _lib.lib()
+    prof.reset()
+    prof.enable(True)
+    try:
+        for nb, K, M, P in X2F_SHAPES[:2]:
+            g = torch.Generator().manual_seed(K + M + P + nb)
+            At = (torch.randn(K, M, generator=g) * (2.0 / K) ** 0.5).to(DEV)
+            X = (torch.randn(nb, K, P, generator=g) * 1.7 + 0.2).to(DEV)
+            bias = torch.randn(M, generator=g).to(DEV)
+            coef = _bn_coef(X, torch.ones(K, device=DEV), torch.zeros(K, device=DEV))
+            for knob, want in ((0, "gemm_x2f_kernel<1, 1, false> |wg="), (12, "gemm_x2d_kernel<")):
+                lib.usip_set_tuning(b"x2_direct", knob)
+                ops.mlp_gemm(At, X, bias, want_stats=True, pro=1, coef=coef)
+                key = prof.summary()["shared_mlp_gemm_fwd %dx%d" % (M, K)]["rocprof_key"]
+                assert key.startswith(want) and int(key.split(" |wg=")[1]) >= 1, (knob, key)
+    finally:
+        lib.usip_set_tuning(b"x2_direct", 0)
+        prof.enable(False)
+        prof.reset()
 
 
 @pytest.mark.parametrize("shape", [s for s in DIRECT_SHAPES if s[1] <= 512])

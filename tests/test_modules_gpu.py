@@ -1325,3 +1325,31 @@ def test_first_layer_weight_gradient_from_the_next_layers_fused_backward(model, 
             assert_close(g1[k].cpu().numpy(), g0[k].cpu().numpy(), rel=2e-6, name=k)
         else:
             assert torch.equal(g1[k], g0[k]), k
+
+
+def test_profiled_step_keys_every_shared_mlp_operator_from_the_launch_log():
+    """One eager profiled step: every shared-MLP operator carries the rocprof key "<kernel template> |wg=<workgroups>" of
+    the kernel the library launched for it (usip_launch_log behind usip_amd/prof.py) -- the form the committed traffic
+    tables (profiles/r*_traffic_<mode>.json, tools/pmc_summary.py) are keyed by."""
+    import re
+    from usip_amd import ops, prof, synth
+    from usip_amd.networks import DetectorOptions
+    from usip_amd.step import DetectorStep, batch_to_device
+    prev_mode = ops.set_matmul_mode("f32x2")
+    batch = batch_to_device(synth.make_pair_batch(31, 2, 2048, 64, 4, "sphere"), DEV)
+    prof.reset()
+    prof.enable(True)
+    try:
+        torch.manual_seed(11)
+        DetectorStep("ball", DetectorOptions(surface_normal_len=4, node_knn_k_1=8), DEV).step(batch)
+        summ = prof.summary()
+    finally:
+        prof.enable(False)
+        prof.reset()
+        ops.set_matmul_mode(prev_mode)
+    mlp = {name: r["rocprof_key"] for name, r in summ.items() if name.startswith("shared_mlp_")}
+    assert any(n.startswith("shared_mlp_gemm_fwd") for n in mlp) and any(n.startswith("shared_mlp_wgrad") for n in mlp), sorted(summ)
+    for name, key in mlp.items():
+        assert key is not None and re.match(r"^[A-Za-z0-9_]+<[^|]*> \|wg=[1-9][0-9]*$", key), (name, key)
+    assert all(r["rocprof_key"] is None for name, r in summ.items() if not name.startswith("shared_mlp_"))
+

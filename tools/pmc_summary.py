@@ -10,18 +10,11 @@ import csv
 import glob
 import json
 import os
-import re
 import sys
 from collections import defaultdict
 
-
-def short(name):
-    name = re.sub(r"\(anonymous namespace\)::", "", name)
-    name = re.sub(r"^void ", "", name)
-    m = re.match(r"([A-Za-z0-9_:]+)(<[^(]*>)?\(", name)
-    if name.startswith("Cijk_"):
-        return "rocBLAS " + name[:20]
-    return (m.group(1) + (m.group(2) or "")) if m else name[:80]
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from usip_amd.prof import short                              # noqa: E402  (the one copy of the name-shortening rule)
 
 
 def key(row):

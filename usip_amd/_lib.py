@@ -8,7 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # USIP_LIB=<path>: load another BUILD of the same library (same-box A/B of two builds, tools/ab_build.sh); never a fallback
 LIB_PATH = os.environ.get("USIP_LIB") or os.path.join(_HERE, "libusip_hip.so")
-ABI = 5                      # = "abi=<n>" of usip_version(): bumped with every incompatible change of include/usip_hip.h
+ABI = 6                      # = "abi=<n>" of usip_version(): bumped with every incompatible change of include/usip_hip.h
 _lib = None
 
 _f32p = ctypes.c_void_p
@@ -23,11 +23,14 @@ SIGNATURES = {
     "usip_version": ([], ctypes.c_char_p),
     "usip_set_tuning": ([ctypes.c_char_p, _int], _int),
     "usip_tuning_value": ([_int], _int),
+    "usip_launch_log": ([_int], _int),
+    "usip_launch_log_entry": ([_int, ctypes.POINTER(ctypes.c_uint)], ctypes.c_char_p),
     "usip_wgrad_defer": ([_int], _int),
     "usip_wgrad_defer_on": ([_stream], _int),
     "usip_wgrad_defer_hold": ([_int], _int),
     "usip_wgrad_flush": ([_stream], _int),
     "usip_index_max_f32": ([_f32p, _i32p, _i32p, _int, _int, _int, _int, _stream], _int),
+    "usip_index_max_geometry": ([_int, _int, _int, _int] + [ctypes.POINTER(_int)] * 3, _int),
     "usip_index_max_f32_cpu": ([_f32p, _i32p, _i32p, _int, _int, _int, _int, _int], _int),
     "usip_ball_query_f32": ([_f32p, _i32p, _flt, _int, _int, _int, _int, _stream], _int),
     "usip_ball_query_f32_cpu": ([_f32p, _i32p, _flt, _int, _int, _int, _int], _int),
@@ -84,11 +87,9 @@ SIGNATURES = {
     "usip_mlp_gemm_x2h_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int,
                                _f32p, _int, _f32p, _int, _int, _int, _int, _stream], _int),
     "usip_mlp_gemm_x2d_red_tiles": ([_int, _int, _int, _int, _int], _int),
-    "usip_mlp_gemm_x2f_used": ([_int] * 10, _int),
     "usip_mlp_gemm_x2h_red_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _int, _f32p, _i32p, _int, _f32p, _f32p, _f32p, _f32p,
                                    _f32p, _int, _int, _int, _int, _int, _stream], _int),
     "usip_mlp_wgrad_f32x3_used": ([_int, _int, _int, _int], _int),
-    "usip_mlp_wgrad_f32x3_blocks": ([_int, _int, _int, _int], _int),
     "usip_bn_pool_backward_reduce_f32": ([_f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _f32p, _f32p,
                                           _f32p, _f32p, _int, _int, _int, _int, _int, _stream], _int),
     "usip_bn_finalize_f32": ([_f32p, _int, _int, ctypes.c_longlong, _f32p, _f32p, _flt, _flt, _f32p, _f32p, _f32p,
@@ -97,7 +98,6 @@ SIGNATURES = {
     "usip_bn_backward_reduce_f32": ([_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _f32p,
                                      _f32p, _int, _int, _int, _int, _int, _stream], _int),
     "usip_mlp_wgrad_workspace": ([_int, _int, _int, _int], ctypes.c_longlong),
-    "usip_mlp_wgrad_blocks": ([_int, _int, _int, _int], _int),
     "usip_mlp_wgrad_f32": ([_f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _f32p, _int, _int,
                             _int, _int, _int, _int, _stream], _int),
     "usip_mlp_wgrad_bf16": ([_f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _f32p, _int, _int,

@@ -6,13 +6,27 @@
 
 #define USIP_WAVE 64
 
+// The launch log behind usip_launch_log() / usip_launch_log_entry() (host_cpu.cpp): while a thread has it armed
+// (count >= 0), every USIP_LAUNCH of that thread leaves its kernel's host-side function pointer and its number of
+// workgroups; names are resolved only when an entry is read.
+#define USIP_LAUNCH_LOG_CAP 8
+struct usip_launch_rec { const void* fn; unsigned wg; };
+extern thread_local int usip_launch_count;                    // < 0: not armed
+extern thread_local usip_launch_rec usip_launch_recs[USIP_LAUNCH_LOG_CAP];
+
 // hipGetLastError() is sticky per thread: clear whatever an unrelated earlier runtime call left
 // behind, launch, then USIP_LAUNCH_CHECK() reports this launch only.
-#define USIP_LAUNCH(...)                                      \
-    do {                                                      \
-        (void)hipGetLastError();                              \
-        hipLaunchKernelGGL(__VA_ARGS__);                      \
+#define USIP_LAUNCH(kernel, grid, ...)                                                          \
+    do {                                                                                        \
+        const dim3 g__ = (grid);                                                                \
+        if ((unsigned)usip_launch_count < USIP_LAUNCH_LOG_CAP)                                  \
+            usip_launch_recs[usip_launch_count++] = {(const void*)(kernel), g__.x * g__.y * g__.z}; \
+        (void)hipGetLastError();                                                                \
+        hipLaunchKernelGGL(kernel, g__, __VA_ARGS__);                                           \
     } while (0)
+
+// Compute units of the CURRENT device (cached per device id); 256 when the query fails or answers fewer than 8.
+int usip_cu_count();
 
 #define USIP_LAUNCH_CHECK()                                   \
     do {                                                      \

@@ -692,12 +692,7 @@ int launch_gemm_x2d(const GemmArgs& a_in, const uint4* pl, int pro, hipStream_t 
     // two stages of operand loads in flight (DEPTH 2) needs an even number of stages; knob x2_direct = 2: DEPTH 1
     const bool deep = !tail && ((a.K / XBK) % 2 == 0) && (usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) != 2;
     // persistent: two workgroups per CU (LDS: 70 KiB each); 8-aligned so that v & 7 is the same XCD for every tile of a block
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-            n = 256;
-        return n;
-    }();
+    const int cus = usip_cu_count();
     const long long slots = (long long)(2 * cus) / 8 * 8;
     // the lean epilogue needs every tile inside the tensor, 16-B vector stores, 32-bit offsets, a row bias per run of 4
     const bool gen = !(a.y_vec && a.M % DBM == 0 && a.P % DBN == 0 && (!a.rowbias || a.rb_group % 4 == 0) &&

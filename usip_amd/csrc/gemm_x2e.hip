@@ -357,12 +357,7 @@ int launch_gemm_x2e(const GemmArgs& a, const uint4* pl, hipStream_t st)
     const int tpc = a.P / EBN, nmt = a.M / EBM;
     const long long total = (long long)a.nb * tpc * nmt;
     if (total > 0x7fffffffLL) return USIP_EINVAL;
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-            n = 256;
-        return n;
-    }();
+    const int cus = usip_cu_count();
     const long long slots = (long long)cus / 8 * 8;            // one workgroup per CU
     dim3 grid((unsigned)((total <= slots || (total & 7)) ? total : slots)), block(ENT);
     if (a.stats) USIP_LAUNCH((gemm_x2e_kernel<EPI_STATS>), grid, block, 0, st, a, pl);

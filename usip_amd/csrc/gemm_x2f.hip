@@ -663,12 +663,7 @@ int launch_gemm_x2f(const GemmArgs& a_in, const uint4* pl, int pro, hipStream_t 
     const int tpc = a.P / FBN, nmt = a.M / FBM;
     const long long total = (long long)a.nb * tpc * nmt;
     if (total > 0x7fffffffLL) return USIP_EINVAL;
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-            n = 256;
-        return n;
-    }();
+    const int cus = usip_cu_count();
     const long long slots = (long long)cus / 8 * 8;            // one workgroup per CU (LDS: ~120 KB, 512 registers per wave)
     dim3 grid((unsigned)((total <= slots || (total & 7)) ? total : slots)), block(FNT);
     if (pro == PRO_AFFINE_RELU) {

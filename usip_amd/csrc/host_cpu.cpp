@@ -6,7 +6,7 @@
 #include <thread>
 #include <vector>
 #include <stdint.h>
-#include "../../include/usip_hip.h"
+#include "common.h"
 
 static void index_max_rows(const float* data, const int32_t* index, int32_t* out,
                            int B, int C, int N, int K, int c_begin, int c_end)
@@ -101,7 +101,7 @@ extern "C" int usip_pairwise_dist_f32_cpu(const float* a, const float* x, float*
 #ifndef USIP_BUILD_FLAGS
 #define USIP_BUILD_FLAGS "unknown"
 #endif
-extern "C" const char* usip_version(void) { return "usip_hip 0.5 gfx950 abi=5 flags=" USIP_BUILD_FLAGS; }
+extern "C" const char* usip_version(void) { return "usip_hip 0.5 gfx950 abi=6 flags=" USIP_BUILD_FLAGS; }
 
 // Launch-geometry knobs (speed only, never results): 0 = the library's own heuristic.  tools/ sweeps set them to
 // measure alternatives on the GPU; the product never does.
@@ -117,4 +117,44 @@ extern "C" int usip_set_tuning(const char* name, int value)
     for (int i = 0; i < USIP_TUNE_COUNT; ++i)
         if (strcmp(name, g_tuning_names[i]) == 0) { g_tuning[i] = value; return USIP_OK; }
     return USIP_EINVAL;
+}
+
+// Compute units of the current device: the persistent kernels size their grids by it.
+int usip_cu_count()
+{
+    static int cached[64];                                    // per device id, 0 = not asked yet (racing threads store the same value)
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 256;
+    if (dev >= 0 && dev < 64 && cached[dev]) return cached[dev];
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
+    if (dev >= 0 && dev < 64) cached[dev] = n;
+    return n;
+}
+
+// The launch log (common.h, USIP_LAUNCH).
+#include <cxxabi.h>
+#include <stdlib.h>
+#include <string>
+thread_local int usip_launch_count = -1;
+thread_local usip_launch_rec usip_launch_recs[USIP_LAUNCH_LOG_CAP];
+
+extern "C" int usip_launch_log(int on)
+{
+    const int had = usip_launch_count < 0 ? 0 : usip_launch_count;
+    usip_launch_count = on ? 0 : -1;
+    return had;
+}
+
+extern "C" const char* usip_launch_log_entry(int i, unsigned* workgroups)
+{
+    static thread_local std::string text;
+    if (i < 0 || i >= usip_launch_count) return nullptr;
+    const char* mangled = hipKernelNameRefByPtr(usip_launch_recs[i].fn, nullptr);
+    if (!mangled) return nullptr;
+    int status = 0;
+    char* plain = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+    text = (status == 0 && plain) ? plain : mangled;
+    free(plain);
+    if (workgroups) *workgroups = usip_launch_recs[i].wg;
+    return text.c_str();
 }

@@ -200,29 +200,26 @@ int launch(const float* data, const int32_t* index, int32_t* out, int B, int C, 
     return USIP_OK;
 }
 
+// (U, T) as usip_index_max_geometry hands them out
 template <int CH>
 int launch_u(int U, int T, const float* data, const int32_t* index, int32_t* out, int B, int C, int N, int K, hipStream_t st, Extra x)
 {
-    if (T >= 1024) return U >= 2 ? launch<CH, 2, 1024>(data, index, out, B, C, N, K, st, x)
+    if (T == 1024) return U == 2 ? launch<CH, 2, 1024>(data, index, out, B, C, N, K, st, x)
                                  : launch<CH, 1, 1024>(data, index, out, B, C, N, K, st, x);
-    if (T >= 512) return U >= 2 ? launch<CH, 2, 512>(data, index, out, B, C, N, K, st, x)
+    if (T == 512) return U == 2 ? launch<CH, 2, 512>(data, index, out, B, C, N, K, st, x)
                                 : launch<CH, 1, 512>(data, index, out, B, C, N, K, st, x);
-    if (U >= 4 && CH <= 4) return launch<CH, 4, 256>(data, index, out, B, C, N, K, st, x);
-    if (U >= 2) return launch<CH, 2, 256>(data, index, out, B, C, N, K, st, x);
+    if (U == 4 && CH <= 4) return launch<CH, 4, 256>(data, index, out, B, C, N, K, st, x);
+    if (U == 2) return launch<CH, 2, 256>(data, index, out, B, C, N, K, st, x);
     return launch<CH, 1, 256>(data, index, out, B, C, N, K, st, x);
 }
 
 }  // namespace
 
-static int index_max_impl(const float* data, const int32_t* index, int32_t* max_idx, int B, int C, int N, int K,
-                          void* stream, Extra x)
+// The launch geometry of usip_index_max_f32 / usip_index_max_values_f32 for a shape: channel rows per workgroup (1, 2, 4
+// or 8), prefetch depth (1, 2 or 4) and threads per workgroup (256, 512 or 1024), knobs applied.
+extern "C" int usip_index_max_geometry(int B, int C, int N, int K, int* ch_out, int* u_out, int* t_out)
 {
-    if (B < 0 || C < 0 || N < 0 || K < 0) return USIP_EINVAL;
-    if ((long long)B * C * K == 0) return USIP_OK;
-    if (!max_idx || (N > 0 && (!data || !index))) return USIP_EINVAL;
-    if ((long long)B * C > 0x7fffffffLL) return USIP_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (K > 8192) return USIP_EINVAL;                            // 64 KiB table
+    if (B < 0 || C < 0 || N < 0 || K < 0 || !ch_out || !u_out || !t_out) return USIP_EINVAL;
     // A workgroup owns CH channel rows of one cloud (the index row is read once for CH value rows) and keeps
     // U*(CH+1)*16 B per lane in flight.  Measured at B'=16, N=16384, K=512 (tools/index_max_sweep.py, ring of
     // inputs larger than the Infinity Cache): two rows per workgroup is the best trade at C=64 and C=128 --
@@ -236,6 +233,24 @@ static int index_max_impl(const float* data, const int32_t* index, int32_t* max_
     if (tch > 0 && C % tch == 0 && (long long)tch * K * 8 <= 65536) ch = tch;
     if (tu > 0) u = tu;
     if (tt == 512 || tt == 1024) t = tt;
+    if (ch != 2 && ch != 4 && ch != 8) ch = 1;
+    if (t > 256) u = (u >= 2) ? 2 : 1;
+    else u = (u >= 4 && ch <= 4) ? 4 : (u >= 2) ? 2 : 1;
+    *ch_out = ch; *u_out = u; *t_out = t;
+    return USIP_OK;
+}
+
+static int index_max_impl(const float* data, const int32_t* index, int32_t* max_idx, int B, int C, int N, int K,
+                          void* stream, Extra x)
+{
+    if (B < 0 || C < 0 || N < 0 || K < 0) return USIP_EINVAL;
+    if ((long long)B * C * K == 0) return USIP_OK;
+    if (!max_idx || (N > 0 && (!data || !index))) return USIP_EINVAL;
+    if ((long long)B * C > 0x7fffffffLL) return USIP_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (K > 8192) return USIP_EINVAL;                            // 64 KiB table
+    int ch, u, t;
+    usip_index_max_geometry(B, C, N, K, &ch, &u, &t);
     switch (ch) {
     case 8: return launch_u<8>(u, t, data, index, max_idx, B, C, N, K, st, x);
     case 4: return launch_u<4>(u, t, data, index, max_idx, B, C, N, K, st, x);

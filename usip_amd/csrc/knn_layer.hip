@@ -295,11 +295,7 @@ extern "C" int usip_knn_layer_backward_f32(const float* dZ, const float* Y, cons
     // two rows and 512 threads per workgroup where they fit 64 KiB of LDS (two workgroups per CU); knob r5_forms bit 7
     // (128): one row and 256 threads (five per CU by LDS) -- measured slower, 94 against 72 us at the step's shape
     // (profiles/r06aj_knn_layer_kernels.txt)
-    static const int cus = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) n = 256;
-        return n;
-    }();
+    const int cus = usip_cu_count();
     // channel chunks per workgroup (they share the cloud's neighbour lists): as many as leave >= 2 workgroups per CU
     int tpw = 1;
     { const long long chunks = (long long)B * Cout / 2; while (tpw < 8 && chunks / (tpw * 2) >= 2LL * cus) tpw *= 2; }

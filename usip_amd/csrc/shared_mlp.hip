@@ -1091,14 +1091,6 @@ extern "C" long long usip_mlp_wgrad_workspace(int M, int N, int P, int nb)
     return (long long)nb * (segs > sg3 ? segs : sg3) * M * N;
 }
 
-// Number of workgroups usip_mlp_wgrad_f32 launches (lets a profiler match launches to layer shapes).
-extern "C" int usip_mlp_wgrad_blocks(int M, int N, int P, int nb)
-{
-    int seglen, segs, small, tiles;
-    wgrad_plan(M, N, P, nb, &seglen, &segs, &small, &tiles);
-    return tiles * nb * segs;
-}
-
 static bool x3_wgrad_pays(int M, int N, int P, int nb)
 {
     const int t = usip_tuning_value(USIP_TUNE_GEMM_SPLIT3);
@@ -1110,19 +1102,6 @@ static bool x3_wgrad_pays(int M, int N, int P, int nb)
     return M >= 128 && N >= 128 && ((long long)nb * P >= 32768 || few_ok);
 }
 extern "C" int usip_mlp_wgrad_f32x3_used(int M, int N, int P, int nb) { return x3_wgrad_pays(M, N, P, nb) ? 1 : 0; }
-
-// Workgroups usip_mlp_wgrad_f32x3 launches, negative when it runs the 256 x 256-tile kernel (profiling aid).
-extern "C" int usip_mlp_wgrad_f32x3_blocks(int M, int N, int P, int nb)
-{
-    int seglen, segs, small, tiles;
-    wgrad_plan(M, N, P, nb, &seglen, &segs, &small, &tiles);
-    const bool x3 = !small && x3_wgrad_pays(M, N, P, nb);
-    if (x3 && P % 4 == 0 && M > 128 && N > 128 && usip_tuning_value(USIP_TUNE_X3_WGRAD_TILE) != 1) {
-        wgrad_x3_plan(M, N, P, nb, &seglen, &segs, &tiles);
-        return -(tiles * nb * segs);
-    }
-    return tiles * nb * segs;
-}
 
 static int mlp_wgrad_impl(int mode, const float* G, const float* G2, const float* coef, int pro,
                           const float* X, const float* xcoef, const float* pool_dp, const int32_t* pool_arg,

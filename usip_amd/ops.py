@@ -132,23 +132,11 @@ def segment_sum(src, start, perm, C: int, coff: int = 0):
 
 def index_max_geometry(B: int, C: int, N: int, K: int):
     """(channel rows per workgroup, prefetch depth, threads) usip_index_max_f32 picks for this shape
-    (csrc/index_max.hip); lets a profiler name the launch."""
-    rows = B * C
-    ch = 2 if (C % 2 == 0 and rows // 2 >= 512 and 2 * K * 8 <= 65536) else 1
-    u = 2 if N >= 4096 else 1
-    t = 256
-    tch, tu, tt = (_lib.lib().usip_tuning_value(i) for i in (0, 1, 5))
-    if tch > 0 and C % tch == 0 and tch * K * 8 <= 65536:
-        ch = tch
-    if tu > 0:
-        u = tu
-    if tt in (512, 1024):
-        t = tt
-    if t > 256:
-        u = 2 if u >= 2 else 1
-    else:
-        u = 4 if (u >= 4 and ch <= 4) else (2 if u >= 2 else 1)
-    return ch, u, t
+    (usip_index_max_geometry, csrc/index_max.hip); lets a profiler name the launch."""
+    ch, u, t = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _lib.check(_lib.lib().usip_index_max_geometry(int(B), int(C), int(N), int(K), ctypes.byref(ch), ctypes.byref(u),
+                                                  ctypes.byref(t)), "usip_index_max_geometry")
+    return ch.value, u.value, t.value
 
 
 def ball_query(dist: torch.Tensor, radius: float, K: int) -> torch.Tensor:
@@ -520,16 +508,12 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
     if nf_blocks:
         stats = torch.empty((2, M, nf_blocks), dtype=torch.float32, device=X.device) if want_stats else None
         with torch.cuda.device(X.device), prof.kernel(
-                "shared_mlp_gemm_%s %dx%d" % (tag, M, K), 4.0 * nb * P * (K + M), 2.0 * M * K * nb * P,
-                rocprof_key="narrow_fwd_kernel<%d, %s, %s, %s> |wg=%d" % (
-                    M // 32, "true" if pro else "false", "true" if want_stats else "false",
-                    "true" if rowbias is not None else "false", nf_blocks)):
+                "shared_mlp_gemm_%s %dx%d" % (tag, M, K), 4.0 * nb * P * (K + M), 2.0 * M * K * nb * P, keyed=True):
             _lib.check(_lib.lib().usip_mlp_narrow_forward_f32(a_ptr, lda, _ptr(X), _opt(coef), int(pro), _opt(bias),
                                                               _opt(rowbias), int(rb_group), y_ptr, int(y_rows),
                                                               _opt(stats), M, K, P, nb, _stream(X)),
                        "usip_mlp_narrow_forward_f32")
         return (Y, stats, None) if red is not None else (Y, stats)
-    bf16 = _matmul_mode == "bf16"
     fn_name = {"bf16": "usip_mlp_gemm_bf16", "f32x3": "usip_mlp_gemm_f32x3",
                "f32x2": "usip_mlp_gemm_f32x3"}.get(_matmul_mode, "usip_mlp_gemm_f32")
     x3 = _x3_family() and (x2r_direct or bool(_lib.lib().usip_mlp_gemm_f32x3_used(M, K, P, nb)))
@@ -545,59 +529,6 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
         tiles = _lib.lib().usip_mlp_gemm_x2r_tiles(P, nb) if x2r else _lib.lib().usip_mlp_gemm_tiles(M, P, nb)
         stats = torch.empty((2, M, tiles), dtype=torch.float32, device=X.device)
 
-    def _key():
-        wm, wn = (1, 4) if M <= 64 else (2, 2)
-        tiles = _lib.lib().usip_mlp_gemm_tiles(M, P, nb)
-        e = 1 if want_stats else 0
-        if bf16:
-            return "gemm_bf16_kernel<%d, %d, 16, %d, %d, 1> |wg=%d" % (wm, wn, pro, e, tiles * ((M + wm * 64 - 1) // (wm * 64)))
-        if x3p:
-            bm = _lib.lib().usip_mlp_x3p_tile_rows(M, P, nb)
-            bn = _lib.lib().usip_mlp_x3p_tile_cols(M, P, nb, int(pro), e)
-            if x2r:
-                return "gemm_x2r_kernel<%d, %d, %s> |wg=%d" % (pro, e, "true" if rowbias is not None else "false",
-                                                               min(512, nb * ((P + 63) // 64)))
-            if x2h:
-                # (tile_cols == 256 -- a measurement knob -- sends the launch to launch_x3p<4, 4, 2> in the C dispatcher
-                # before the direct kernel is considered: usip_mlp_gemm_x2h_f32; mirrored here)
-                wide = bm == 256 and bn == 256
-                if not wide:
-                    bn = 128
-                if bm == 256 and not wide and (_lib.lib().usip_tuning_value(6) & 15) != 1 and K * P * 4 < 2 ** 31:
-                    # csrc/gemm_x2d.hip: <pro, stats, K % 16 != 0, stages of operand loads in flight>; persistent, two
-                    # workgroups per CU once there are more tiles than that
-                    if red is None and _lib.lib().usip_mlp_gemm_x2f_used(
-                            M, K, P, nb, int(pro), e, 1 if bias is not None else 0, int(rb_group) if rowbias is not None else 0,
-                            int(pool_group), int(y_rows)):
-                        # round 6, csrc/gemm_x2f.hip: <pro, stats, DIRECT>; one persistent workgroup per CU
-                        tiles_ = nb * (P // 256) * (M // 256)
-                        return "gemm_x2f_kernel<%d, %d, %s> |wg=%d" % (pro, e, "true" if pro >= 2 else "false",
-                                                                       tiles_ if (tiles_ <= 256 or tiles_ % 8) else 256)
-                    tail = K % 16 != 0
-                    depth = 2 if (not tail and (K // 16) % 2 == 0 and (_lib.lib().usip_tuning_value(6) & 15) != 2) else 1
-                    tiles_ = nb * ((P + 127) // 128) * ((M + 255) // 256)
-                    wg = tiles_ if (tiles_ <= 512 or tiles_ % 8) else 512
-                    # (+ the epilogue instantiations: <.., RED, general, DIRECT>; the general one runs DEPTH 1; DIRECT =
-                    # data gradients that need nothing but the scale: stores straight from the registers)
-                    gen = M % 256 != 0 or P % 128 != 0
-                    direct = (not gen and not tail and depth == 2 and e == 0 and red is None and bias is None
-                              and rowbias is None and pro >= 2 and (_lib.lib().usip_tuning_value(6) & 15) != 8)
-                    return "gemm_x2d_kernel<%d, %d, %s, %d, %s, %s, %s> |wg=%d" % (
-                        pro, e, "true" if tail else "false", 1 if gen else depth,
-                        "true" if red is not None else "false", "true" if gen else "false",
-                        "true" if direct else "false", wg)
-            slots = 3 if (bm == 128 and not (_lib.lib().usip_tuning_value(7) & 32)) else 2    # round 5: weight-ring slots
-            return "gemm_x3p_kernel<%d, %d, %d, %d, %d, %d> |wg=%d" % (pro, e, bm // 64, bn // 64, 2 if x2h else 3, slots,
-                                                                       nb * ((P + bn - 1) // bn) * ((M + bm - 1) // bm))
-        if x3:
-            return "gemm_bf16_kernel<2, 2, 16, %d, %d, 3> |wg=%d" % (pro, e, nb * ((P + 127) // 128) * ((M + 127) // 128))
-        # csrc/shared_mlp.hip mlp_gemm_impl: 32 rows per wave when 128-row tiles would not fill the chip
-        tm = 1 if ((M > 64 and nb * ((P + 127) // 128) * ((M + 127) // 128) < 512)
-                   or (M <= 32 and nb * ((P + 255) // 256) < 512)) else 2
-        bm = wm * 32 * tm
-        return "gemm_kernel<%d, %d, 16, %d, %d, %s, %d> |wg=%d" % (wm, wn, pro, e, "true" if P % 4 == 0 else "false", tm,
-                                                                   tiles * ((M + bm - 1) // bm))
-
     planes = weight_planes(At, a_offset, M, K, 2 if x2h else 3, P, nb) if x3p else None
     moved = 0.0
     if x3p:      # bytes into the CUs: per (tile, 16-k stage) the weight planes (L2) + the streamed operand, + the output
@@ -610,7 +541,7 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
             moved = 4.0 * nb * P * (K * (2 if pro == 2 else 1) + M)
     with torch.cuda.device(X.device), prof.kernel("shared_mlp_gemm_%s %dx%d" % (tag, M, K),
                                                   4.0 * nb * P * (K * (2 if pro == 2 else 1) + M),
-                                                  2.0 * M * K * nb * P, rocprof_key=_key, moved=moved):
+                                                  2.0 * M * K * nb * P, keyed=True, moved=moved):
         if x2r:
             _lib.check(_lib.lib().usip_mlp_gemm_x2r_f32(_ptr(planes), None if pool is not None else _ptr(X), _opt(X2),
                                                         _opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group),
@@ -836,7 +767,6 @@ def mlp_wgrad(G, X, pro: int = 0, G2=None, coef4=None, out=None, coloff: int = 0
     ws = _keep(torch.empty(max(int(ws_n), 1), dtype=torch.float32, device=dev))
     dW = out if out is not None else torch.empty((M, N), dtype=torch.float32, device=dev)
     ldw = dW.shape[1]
-    bf16 = _matmul_mode == "bf16"
     fn_name = {"bf16": "usip_mlp_wgrad_bf16", "f32x3": "usip_mlp_wgrad_f32x3",
                "f32x2": "usip_mlp_wgrad_f32x3"}.get(_matmul_mode, "usip_mlp_wgrad_f32")
     x3 = _x3_family() and not (M <= 64 and N <= 64) and bool(_lib.lib().usip_mlp_wgrad_f32x3_used(M, N, P, nb))
@@ -846,24 +776,9 @@ def mlp_wgrad(G, X, pro: int = 0, G2=None, coef4=None, out=None, coloff: int = 0
     if x2h:
         fn_name = "usip_mlp_wgrad_x2h_f32"
 
-    def _key():
-        t = 1 if (M <= 64 and N <= 64) else 2
-        if x3:
-            blocks = _lib.lib().usip_mlp_wgrad_f32x3_blocks(M, N, P, nb)
-            if blocks < 0:
-                if x2h and not (_lib.lib().usip_tuning_value(7) & 1) and max(M, N) * P < (1 << 30):
-                    return "wgrad_x2l_kernel<%d> |wg=%d" % (pro, -blocks)         # round 5: the full-line form
-                return "wgrad_x3_kernel<%d, %s, %d> |wg=%d" % (pro, "true" if xcoef is not None else "false",
-                                                               2 if x2h else 3, -blocks)
-        planes = ", 1" if bf16 else (", 3" if x3 else "")
-        return "%s<%d, %d, %d, %s, %s%s> |wg=%d" % ("wgrad_bf16_kernel" if (bf16 or x3) else "wgrad_kernel", t, t, pro,
-                                                    "true" if xcoef is not None else "false",
-                                                    "true" if P % 4 == 0 else "false", planes,
-                                                    _lib.lib().usip_mlp_wgrad_blocks(M, N, P, nb))
-
     with torch.cuda.device(dev), _reduce_now(out is None), prof.kernel(
             "shared_mlp_wgrad %dx%d" % (M, N), 4.0 * nb * P * (M * (2 if pro == 2 else 1) + N), 2.0 * M * N * nb * P,
-            rocprof_key=_key):
+            keyed=True):
         _lib.check(getattr(_lib.lib(), fn_name)(_opt(G), _opt(G2), _opt(coef4), int(pro), _ptr(X), _opt(xcoef),
                                                 _opt(pool_dp), _opt(pool_arg), int(pool_group), _ptr(ws), _ptr(dW),
                                                 int(ldw), int(coloff), M, N, P, nb, _stream(X)), fn_name)
@@ -926,10 +841,7 @@ def mlp_narrow_backward(dz, y, coef4, x, xcoef, w2, wcol: int = 0, dw_out=None, 
         blocks = int(_lib.lib().usip_mlp_narrow_backward_blocks(Cout, P, nb))
         red = torch.empty(2 * blocks * Cin + blocks, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev), _reduce_now(dw_out is None), prof.kernel("shared_mlp_narrow_bwd %dx%d" % (Cout, Cin),
-                                             4.0 * nb * P * (2 * Cout + 2 * Cin), 4.0 * Cout * Cin * nb * P,
-                                             rocprof_key="narrow_bwd_kernel<%d, %s, %s> |wg=%d" % (
-                                                 Cout, "true" if xcoef is not None else "false",
-                                                 "true" if want_red else "false", ws.numel() // (Cout * 64))):
+                                             4.0 * nb * P * (2 * Cout + 2 * Cin), 4.0 * Cout * Cin * nb * P, keyed=True):
         _lib.check(_lib.lib().usip_mlp_narrow_backward_f32(
             _ptr(dz), _ptr(y), _ptr(coef4), _ptr(x), int(x.shape[1]), _opt(xcoef),
             ctypes.c_void_p(w2.data_ptr() + 4 * int(wcol)), int(ldw), _ptr(dx), Cin, _ptr(ws),
@@ -995,20 +907,14 @@ def mlp_layer_backward_x2(dz, y, coef4, x, xcoef, w2, wcol: int = 0, dw_out=None
             gsum = torch.empty((2, nb, Cin, P // group), dtype=torch.float32, device=dev)
     else:
         _need(dz, "dz", torch.float32)
-    pg = pool is not None and group % 32 == 0
     wsum = wsum3 = None
     if want_red and wsum_supported(wsrc, Cin, Cout, P, pool is not None):
         wsum = torch.empty((blocks, Cin, 16), dtype=torch.float32, device=dev)
         wsum3 = torch.empty((blocks, 8), dtype=torch.float32, device=dev)
-    key = ("layer_bwd_x2ws_kernel<%d, %d, 4, 32> |wg=%d" % (Cin, Cout, blocks)) if wsum is not None else (
-        "layer_bwd_x2_kernel<%d, %d, %s, %s, %d, 32, %s, %s, %s> |wg=%d" % (
-            Cin, Cout, "true" if pool is not None else "false", "true" if want_red else "false", 8 if Cin == 128 else 4,
-            "true" if (Cin == 128 and not (want_red and pg)) else "false", "true" if pg else "false",
-            "true" if (pg or (Cin == 64 and Cout == 128)) else "false", blocks))
     with torch.cuda.device(dev), _reduce_now(dw_out is None), prof.kernel(
             "shared_mlp_layer_bwd_x2%s %dx%d" % ("ws" if wsum is not None else "", Cout, Cin),
             4.0 * nb * P * ((1 if pool is not None else 2) * Cout + 2 * Cin + (wsrc.shape[1] if wsum is not None else 0)),
-            4.0 * Cout * Cin * nb * P, rocprof_key=key):
+            4.0 * Cout * Cin * nb * P, keyed=True):
         if wsum is not None:
             _lib.check(lib.usip_mlp_layer_backward_x2h_ws_f32(
                 _ptr(dz), _ptr(y), _ptr(coef4), _ptr(x), int(x.shape[1]), _ptr(xcoef), ctypes.c_void_p(planes.data_ptr()),
