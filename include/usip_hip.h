@@ -739,6 +739,54 @@ int usip_repeatability_f32_cpu(const float* anc, const int32_t* anc_count, const
 int usip_nearest_nd_counted_f32_cpu(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count,
                                     float* min_d, int32_t* arg, int B, int C, int Ma, int Nb);
 
+/* ------------------------------------------------------------------ f-7  raw scans prepared: normals, curvature, voxel grid
+ * Replaces the reference's MATLAB preparation of a raw scan (evaluation/matlab/kitti_data_prepare/kitti_test_prepare.m:95-108:
+ * findPointNormals(pc, 9, [0, 0, 1], true) of external/findPointNormals.m, then pcdownsample(pc, 'gridAverage', 0.2)) that
+ * makes the [rows, 8] scans `x y z nx ny nz curvature reflectance` the loaders read (data/kitti_detector_loader.py:32,116).
+ * Float64 arithmetic on float32 inputs (MATLAB reads the float32 file into doubles).  csrc/prepare_math.h is the arithmetic.
+ *
+ * xyzi f32 [n][4] row-major (x y z reflectance: a KITTI velodyne .bin as it lies in the file), finite values,
+ * K + 1 <= n <= 2^20, 1 <= K <= 16.
+ *
+ * usip_scan_knn_f32 (findPointNormals.m:75-79, knnsearch k + 1 and "remove self"): idx i32 [n][K] = for every point i the K
+ * points j != i with the smallest d2 = (dx*dx + dy*dy) + dz*dz in float64, ascending, ties towards the lower j.  The point is
+ * left out by INDEX (MATLAB drops the first column, which among exact duplicates need not be the point itself).  perm i32 [n]:
+ * the permutation that sorts the points along x, ascending (any stable or unstable sort) -- the kernel walks outward from a
+ * query's own position and stops where the x gap alone exceeds the K-th distance; the result is the all-pairs answer.  A perm
+ * that does not sort gives wrong neighbours, never a read outside xyzi.  tiles_visited i32 [ceil(n / 256)], optional (NULL): the
+ * number of 256-point tiles each workgroup of 256 queries walked.
+ *
+ * usip_scan_normals_f32 (findPointNormals.m:81-130, dirLargest = true): C = sum_k d_k d_k' / K with d_k = p_i - p_idx[i][k],
+ * summed in the order of idx; its eigenvector of the smallest eigenvalue (the first of equal ones) by 8 cyclic Jacobi sweeps
+ * in a fixed order; curvature = lambda_min / (l0 + l1 + l2); the normal negated when normal[c] * (p[c] - viewpoint[c]) > 0,
+ * c = the first arg max |normal|.  A zero trace gives curvature 0 and normal (0, 0, 1) before the flip (MATLAB: 0 / 0).
+ * viewpoint: 3 doubles on the HOST.  normals_f64 f64 [n][4] and normals_f32 f32 [n][4] (nx ny nz curvature; the float32
+ * rounding of the same values); either may be NULL, not both.  The "normalized_curvature" output of findPointNormals is not
+ * used by the preparation and is not built.
+ *
+ * usip_scan_voxel_keys_f32 / usip_scan_voxel_average_f32 (pcdownsample 'gridAverage' -- a MATLAB builtin whose source the
+ * reference does not carry: this definition is the project's own).  lohi f32 [6]: per-axis minimum, then maximum of the scan
+ * (device memory for the device entry).  cell = floor(((double)p - (double)lo) / leaf) per axis, clamped into [0, 2^20);
+ * keys i64 [n] = (cz * ny + cy) * nx + cx with nx, ny the cell counts along x, y.  The caller sorts the keys (stable): perm
+ * i32 [n] = point indices in (key, index) order, start i32 [m + 1] = the first position of every occupied cell, start[m] = n.
+ * rows f32 [m][8], in ascending key order: the members of a cell are added in ascending original index in float64; mean xyz,
+ * mean normal (of normals_f64) divided by its norm -- the first member's normal when the mean is exactly zero --, mean
+ * curvature, mean reflectance. */
+int usip_scan_knn_f32(const float* xyzi, const int32_t* perm, int n, int K, int32_t* idx, int32_t* tiles_visited, void* stream);
+int usip_scan_normals_f32(const float* xyzi, const int32_t* idx, int n, int K, const double* viewpoint, double* normals_f64,
+                          float* normals_f32, void* stream);
+int usip_scan_voxel_keys_f32(const float* xyzi, int n, const float* lohi, double leaf, int64_t* keys, void* stream);
+int usip_scan_voxel_average_f32(const float* xyzi, const double* normals_f64, const int32_t* perm, const int32_t* start,
+                                int n, int m, float* rows, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order.  The neighbour search is the plain all-pairs
+ * walk (no perm); num_threads splits the queries. */
+int usip_scan_knn_f32_cpu(const float* xyzi, int n, int K, int32_t* idx, int num_threads);
+int usip_scan_normals_f32_cpu(const float* xyzi, const int32_t* idx, int n, int K, const double* viewpoint,
+                              double* normals_f64, float* normals_f32);
+int usip_scan_voxel_keys_f32_cpu(const float* xyzi, int n, const float* lohi, double leaf, int64_t* keys);
+int usip_scan_voxel_average_f32_cpu(const float* xyzi, const double* normals_f64, const int32_t* perm, const int32_t* start,
+                                    int n, int m, float* rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,15 @@ SIGNATURES = {
     "usip_repeatability_f32_cpu": ([_f32p, _i32p, _f32p, _i32p, ctypes.c_void_p, _dbl, _int, _int, _int, ctypes.c_void_p,
                                     _i32p, ctypes.c_void_p], _int),
     "usip_nearest_nd_counted_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _int], _int),
+    # f-7 raw scans prepared: neighbours, normals + curvature, voxel grid average (usip_amd/prepare.py)
+    "usip_scan_knn_f32": ([_f32p, _i32p, _int, _int, _i32p, _i32p, _stream], _int),
+    "usip_scan_normals_f32": ([_f32p, _i32p, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _f32p, _stream], _int),
+    "usip_scan_voxel_keys_f32": ([_f32p, _int, _f32p, _dbl, ctypes.c_void_p, _stream], _int),
+    "usip_scan_voxel_average_f32": ([_f32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _f32p, _stream], _int),
+    "usip_scan_knn_f32_cpu": ([_f32p, _int, _int, _i32p, _int], _int),
+    "usip_scan_normals_f32_cpu": ([_f32p, _i32p, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _f32p], _int),
+    "usip_scan_voxel_keys_f32_cpu": ([_f32p, _int, _f32p, _dbl, ctypes.c_void_p], _int),
+    "usip_scan_voxel_average_f32_cpu": ([_f32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _f32p], _int),
 }
 
 

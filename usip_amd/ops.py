@@ -1526,3 +1526,76 @@ def nearest_nd_counted(a, b, a_count, b_count):
                                                           _ptr(arg), B, C, Ma, Nb, _stream(a)),
                    "usip_nearest_nd_counted_f32")
     return d, arg
+
+
+# ------------------------------------------------------------------------------------------------ f-7 scan preparation
+def _need_scan(xyzi, K=None):
+    _need(xyzi, "xyzi", torch.float32)
+    if xyzi.dim() != 2 or xyzi.shape[1] != 4:
+        raise RuntimeError("prepare: expected xyzi f32 [n,4] (x y z reflectance)")
+    n = xyzi.shape[0]
+    if not 1 <= n <= 1 << 20:
+        raise RuntimeError("prepare: n must be in 1..2^20 (got %d)" % n)
+    if K is not None and not (1 <= int(K) <= 16 and n >= int(K) + 1):
+        raise RuntimeError("prepare: K must be in 1..16 and n >= K + 1 (got K = %d, n = %d)" % (K, n))
+    return n
+
+
+def scan_knn(xyzi, perm, K: int, want_visits: bool = False):
+    """f-7: xyzi f32 [n,4], perm i32 [n] (the order of the points along x) -> idx i32 [n,K]: the K nearest OTHER points of
+    every point, ascending (d2, index); with want_visits also the 256-point tiles each workgroup walked, i32 [ceil(n/256)]."""
+    K = int(K)
+    n = _need_scan(xyzi, K)
+    _need_on(perm, "perm", torch.int32, (n,), xyzi.device)
+    idx = torch.empty((n, K), dtype=torch.int32, device=xyzi.device)
+    visits = torch.empty(((n + 255) // 256,), dtype=torch.int32, device=xyzi.device) if want_visits else None
+    with torch.cuda.device(xyzi.device), prof.kernel("scan_knn", 16.0 * n + 4.0 * n * K, keyed=True):
+        _lib.check(_lib.lib().usip_scan_knn_f32(_ptr(xyzi), _ptr(perm), n, K, _ptr(idx), _opt_ptr(visits), _stream(xyzi)),
+                   "usip_scan_knn_f32")
+    return (idx, visits) if want_visits else idx
+
+
+def scan_normals(xyzi, idx, viewpoint=(0.0, 0.0, 1.0)):
+    """f-7: xyzi f32 [n,4], idx i32 [n,K] -> (f64 [n,4], f32 [n,4]): nx ny nz curvature, flipped towards `viewpoint`."""
+    if not isinstance(idx, torch.Tensor) or idx.dim() != 2:
+        raise RuntimeError("prepare: idx must be i32 [n,K]")
+    K = idx.shape[1]
+    n = _need_scan(xyzi, K)
+    _need_on(idx, "idx", torch.int32, (n, K), xyzi.device)
+    view = (ctypes.c_double * 3)(*[float(v) for v in viewpoint])
+    n64 = torch.empty((n, 4), dtype=torch.float64, device=xyzi.device)
+    n32 = torch.empty((n, 4), dtype=torch.float32, device=xyzi.device)
+    with torch.cuda.device(xyzi.device), prof.kernel("scan_normals", (16.0 * (K + 1) + 4.0 * K + 48.0) * n, keyed=True):
+        _lib.check(_lib.lib().usip_scan_normals_f32(_ptr(xyzi), _ptr(idx), n, K, ctypes.addressof(view), _ptr(n64),
+                                                    _ptr(n32), _stream(xyzi)), "usip_scan_normals_f32")
+    return n64, n32
+
+
+def scan_voxel_keys(xyzi, lohi, leaf: float):
+    """f-7: xyzi f32 [n,4], lohi f32 [6] (per-axis minimum, then maximum, on the device) -> keys i64 [n]."""
+    n = _need_scan(xyzi)
+    _need_on(lohi, "lohi", torch.float32, (6,), xyzi.device)
+    if not float(leaf) > 0.0:
+        raise RuntimeError("prepare: leaf must be positive")
+    keys = torch.empty((n,), dtype=torch.int64, device=xyzi.device)
+    with torch.cuda.device(xyzi.device), prof.kernel("scan_voxel_keys", 24.0 * n, keyed=True):
+        _lib.check(_lib.lib().usip_scan_voxel_keys_f32(_ptr(xyzi), n, _ptr(lohi), float(leaf), _ptr(keys), _stream(xyzi)),
+                   "usip_scan_voxel_keys_f32")
+    return keys
+
+
+def scan_voxel_average(xyzi, normals_f64, perm, start):
+    """f-7: the members perm[start[c] : start[c + 1]] of every occupied cell c averaged -> rows f32 [m,8]."""
+    n = _need_scan(xyzi)
+    dev = xyzi.device
+    _need_on(normals_f64, "normals_f64", torch.float64, (n, 4), dev)
+    _need_on(perm, "perm", torch.int32, (n,), dev)
+    _need(start, "start", torch.int32)
+    if start.dim() != 1 or start.device != dev or not 1 <= start.shape[0] <= n + 1:
+        raise RuntimeError("prepare: start must be i32 [m + 1] on %s with m <= n" % dev)
+    m = start.shape[0] - 1
+    rows = torch.empty((m, 8), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), prof.kernel("scan_voxel_average", 52.0 * n + 36.0 * m, keyed=True):
+        _lib.check(_lib.lib().usip_scan_voxel_average_f32(_ptr(xyzi), _ptr(normals_f64), _ptr(perm), _ptr(start), n, m,
+                                                          _ptr(rows), _stream(xyzi)), "usip_scan_voxel_average_f32")
+    return rows

@@ -147,6 +147,37 @@ class ScanBank:
     def from_paths(cls, paths: Sequence[str], device, **kw) -> "ScanBank":
         return cls(list(paths), device, **kw)
 
+    @classmethod
+    def from_device_rows(cls, scans: Sequence[torch.Tensor], device=None, row_len: int = 8,
+                         radius_threshold: float = 100.0) -> "ScanBank":
+        """The bank of float32 [rows, row_len] tensors that are already in device memory (usip_amd.prepare's output):
+        the same bank as ScanBank([t.cpu().numpy() for t in scans], ...) without the trip through the host.  Only the
+        row counts are read back."""
+        scans = list(scans)
+        if not scans:
+            raise ValueError("ScanBank: no scans")
+        self = cls.__new__(cls)
+        self.device = torch.device(device) if device is not None else scans[0].device
+        kept = []
+        for i, t in enumerate(scans):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != row_len or t.dtype != torch.float32:
+                raise ValueError("ScanBank: a scan must be a float32 tensor [rows, %d], got %s" % (
+                    row_len, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
+            t = t.to(self.device)
+            if radius_threshold < 90:       # sqrt(x * x + z * z) in float32: what numpy's norm computes on the host path
+                t = t[torch.sqrt(t[:, 0] * t[:, 0] + t[:, 2] * t[:, 2]) <= radius_threshold]
+            if t.shape[0] == 0:
+                raise ValueError("ScanBank: no rows left in scan %d (radius_threshold %g)" % (i, radius_threshold))
+            kept.append(t)
+        self.lengths = np.array([t.shape[0] for t in kept], dtype=np.int64)
+        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.rows = torch.cat(kept).contiguous()
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.row_len = row_len
+        self.num_scans = len(kept)
+        self.min_rows = int(self.lengths.min())
+        return self
+
 
 def epoch_order(num_scans: int, seed: int, epoch: int) -> np.ndarray:
     """DataLoader(shuffle=True) order of one epoch: a permutation of the scans, a function of (seed, epoch) only."""

@@ -115,3 +115,31 @@ def grad_projections(name: str, g: np.ndarray, count: int = 4) -> np.ndarray:
         signs = rng.integers(0, 2, g.size).astype(np.float64) * 2.0 - 1.0
         out[i] = float(signs @ g) / math.sqrt(max(g.size, 1))
     return out
+
+
+def make_ring_scan(seed: int, rings: int = 64, az: int = 1920, max_range: float = 80.0, boxes: int = 40) -> np.ndarray:
+    """A raw spinning-LiDAR scan, float32 [n,4] x y z reflectance (the layout of a KITTI velodyne .bin): `rings` elevations
+    from -24.8 to 2 degrees x `az` azimuths from a sensor 1.73 m above a ground plane, `boxes` random axis-aligned boxes,
+    the nearest hit per ray, hits beyond max_range dropped, 2 cm range noise.  What usip_amd.prepare turns into an Nx8
+    scan; 119 768 points for seed 3 at the defaults."""
+    r = np.random.default_rng(seed)
+    el = np.deg2rad(np.linspace(-24.8, 2.0, rings))
+    a = np.linspace(0, 2 * np.pi, az, endpoint=False)
+    E, A = np.meshgrid(el, a, indexing="ij")
+    d = np.stack([np.cos(E) * np.cos(A), np.cos(E) * np.sin(A), np.sin(E)], -1).reshape(-1, 3)
+    t = np.full(len(d), np.inf)
+    g = d[:, 2] < 0
+    t[g] = -1.73 / d[g, 2]                                   # the ground plane z = -1.73
+    c = np.stack([r.uniform(-70, 70, boxes), r.choice([-1, 1], boxes) * r.uniform(6, 25, boxes), np.zeros(boxes)], 1)
+    h = np.stack([r.uniform(2, 10, boxes), r.uniform(2, 6, boxes), r.uniform(1, 8, boxes)], 1)
+    for ci, hi in zip(c, h):                                 # slab test against each box, nearest entry wins
+        lo, up = ci - hi * [1, 1, 0] - [0, 0, 1.73], ci + hi * [1, 1, 1] - [0, 0, 1.73]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t0, t1 = lo / d, up / d
+        tn, tf = np.minimum(t0, t1).max(1), np.maximum(t0, t1).min(1)
+        hit = (tn <= tf) & (tn > 0)
+        t = np.where(hit & (tn < t), tn, t)
+    keep = t < max_range
+    t = t[keep] + r.normal(0, 0.02, keep.sum())
+    p = d[keep] * t[:, None]
+    return np.concatenate([p, r.uniform(0, 0.99, (len(p), 1))], 1).astype(np.float32)
