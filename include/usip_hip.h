@@ -787,6 +787,96 @@ int usip_scan_voxel_keys_f32_cpu(const float* xyzi, int n, const float* lohi, do
 int usip_scan_voxel_average_f32_cpu(const float* xyzi, const double* normals_f64, const int32_t* perm, const int32_t* start,
                                     int n, int m, float* rows);
 
+/* ------------------------------------------------------------------ f-8  descriptor training batches from posed scans
+ * Replaces KittiDescriptorLoader.__getitem__ (data/kitti_descriptor_loader.py:102-347: get_instance_unaugmented_np,
+ * get_nearby_instance_unagumented_np, augment) and mine_negative_sample (:278-317, called from kitti/train_descriptor.py):
+ * P (anchor, positive) clouds built from scans resident in device memory, the positive scan chosen on the device, the
+ * negatives mined from the anchors' poses.  One call enqueues everything on the caller's stream; nothing is read back.
+ *
+ * The posed bank: rows / offsets as in f-5; poses f64 [S][4][4] row-major (the 'pose' of the .npz files); seq_of i32 [S] the
+ * index of every scan's sequence in [0, num_seq); seq_start i32 [num_seq + 1]: sequence q = scans seq_start[q] ..
+ * seq_start[q+1], contiguous and in trajectory order.  seq_start_host is the same array on the HOST (the entry points
+ * check it there: seq_start[0] = 0, strictly ascending, seq_start[num_seq] = num_scans); for the host twin both are host.
+ *
+ * Positive of anchor a (index ia in its sequence of n scans), the reference's loop taken literally: interval =
+ * (int)(positive_radius / 0.8 * 2); lo = max(ia - interval, 0), hi = min(ia + interval, n - 1); draw t in [lo, hi]; accept when
+ * ||t_t - t_a||_2 < positive_radius (float64, the translations of the float64 poses); else lo = t + 1 when t < ia, hi = t - 1
+ * otherwise; after 3 * interval refused tries the anchor itself.  [lo, hi] always holds ia, which accepts at distance 0, so
+ * the loop ends within 2 * interval + 1 tries.
+ * Negative of anchor i: the candidates are the j != i, ascending, with seq[j] != seq[i] or dist(i, j) > negative_radius;
+ * neg_idx[i] = candidate number `draw`.  No candidate: neg_idx[i] = 0 as the reference leaves it, and neg_fail[0] counts such
+ * rows of this call.  dist(i, j) is the float64 Euclidean distance between the translations of the two poses ROUNDED TO
+ * FLOAT32 (the reference mines on the batch's FloatTensor poses).  The reference computes ||(P_i^-1 P_j)[0:3,3]|| =
+ * ||R_i' (t_j - t_i)||, which equals ||t_j - t_i|| for a rigid pose (R_i orthonormal); the two differ by rounding only.
+ * Mining is within the call's own P anchors.
+ * Per cloud (c = 0 anchor, 1 positive): f-5's per-slot work with cloud.require_full (rows drawn without replacement through
+ * the keyed bijection, sn = columns 3..3+Cs, n_sub FPS candidates, usip_fps_f32 on the un-augmented candidates, then in train
+ * mode augment: float64 rotations, jitter, scale, shift, one rounding).  Each cloud has its own rotations, jitters and shift;
+ * the pair shares ONE scale.  There is no transform (R / scale / shift) of the second cloud.  Test mode: no augmentation.
+ * Outputs: pc[c] f32 [P][3][N], sn[c] f32 [P][Cs][N], node[c] f32 [P][3][M], anc_pose / pos_pose f32 [P][4][4], anc_seq
+ * i32 [P] (sequence index), pos_id i32 [P] (the bank-global scan chosen), neg_idx i64 [P], neg_fail i32 [1]; optional rows
+ * i32 [2][P][N], node_slots i32 [2][P][M].
+ * Randomness (usip_desc_pairs_build_f32): Philox4x64-10, counter (element, stream tag, pair_base + p, step), stream tags
+ * 17-26 (csrc/desc_pairs_math.h) -- none shared with f-5's 1-8, so no draw collides with the detector builder's.
+ * usip_desc_pairs_apply_f32 takes every draw explicitly: the per-cloud draws in f-5's layouts (cloud.params unused),
+ * params f64 [P][USIP_DESC_PAIRS_NPARAM]: 0 the pair's scale uniform; cloud c at 1 + 10 c: +0 yaw uniform, +1..3 rand(3),
+ * +4..6 perturbation normals, +7..9 shift uniforms; tries i32 [P][T]: the in-sequence indices random.randint returned, in
+ * order (entries past the accepted try are not read; a search that outruns T takes the anchor); neg_pick i32 [P]: the
+ * candidate number np.random.randint returned.
+ * USIP_EINVAL: as f-5 for cloud (with sn_last, height_scaling, enu_to_cam and dst_* zero), min_rows < N, mine with P < 2,
+ * num_seq < 1, seq_start_host not as above, a radius that is not positive. */
+#define USIP_DESC_PAIRS_NPARAM 24
+typedef struct usip_desc_pairs_recipe {
+    usip_pairs_recipe cloud;
+    double positive_radius, negative_radius;   /* KITTI: 5, 50 */
+    int mine;                                  /* 1: mine negatives; 0: neg_idx and neg_fail are left untouched */
+} usip_desc_pairs_recipe;
+typedef struct usip_desc_pairs_bank {
+    const float* rows;
+    const int64_t* offsets;
+    const double* poses;
+    const int32_t* seq_of;
+    const int32_t* seq_start;
+    const int32_t* seq_start_host;
+    int num_scans, num_seq;
+    long long min_rows;                        /* the fewest rows of any scan */
+} usip_desc_pairs_bank;
+typedef struct usip_desc_pairs_draws {
+    usip_pairs_draws cloud;
+    const double* params;
+    const int32_t* tries;
+    const int32_t* neg_pick;
+    int T;
+} usip_desc_pairs_draws;
+typedef struct usip_desc_pairs_out {
+    float* pc[2];
+    float* sn[2];
+    float* node[2];
+    float* anc_pose;
+    float* pos_pose;
+    int32_t* anc_seq;
+    int32_t* pos_id;
+    int64_t* neg_idx;
+    int32_t* neg_fail;
+    int32_t* rows;          /* optional (NULL) */
+    int32_t* node_slots;    /* optional (NULL) */
+} usip_desc_pairs_out;
+long long usip_desc_pairs_workspace_bytes(const usip_desc_pairs_recipe* recipe, int P);
+/* Byte offset of one part: 0 the per-cloud f64 tables [2P], 1 the un-augmented FPS candidates f32 [2P][3][n_sub] (anchors
+ * 0..P-1, then positives), 2 the first FPS indices i32 [2P], 3 the FPS picks i32 [2P][M], 4 every cloud's scan id i32 [2P],
+ * 5 the total. */
+long long usip_desc_pairs_workspace_offset(const usip_desc_pairs_recipe* recipe, int P, int part);
+int usip_desc_pairs_build_f32(const usip_desc_pairs_recipe* recipe, const usip_desc_pairs_bank* bank,
+                              const int32_t* scan_ids, int P, uint64_t seed, uint64_t step, long long pair_base,
+                              const usip_desc_pairs_out* out, void* workspace, void* stream);
+int usip_desc_pairs_apply_f32(const usip_desc_pairs_recipe* recipe, const usip_desc_pairs_draws* draws,
+                              const usip_desc_pairs_bank* bank, const int32_t* scan_ids, int P,
+                              const usip_desc_pairs_out* out, void* workspace, void* stream);
+/* HOST twin (every pointer on the host, draws NULL = Philox): the same arithmetic in the same order, its own float64 FPS. */
+int usip_desc_pairs_build_f32_cpu(const usip_desc_pairs_recipe* recipe, const usip_desc_pairs_draws* draws,
+                                  const usip_desc_pairs_bank* bank, const int32_t* scan_ids, int P, uint64_t seed,
+                                  uint64_t step, long long pair_base, const usip_desc_pairs_out* out);
+
 #ifdef __cplusplus
 }
 #endif

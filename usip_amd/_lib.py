@@ -183,6 +183,15 @@ SIGNATURES = {
     "usip_scan_normals_f32_cpu": ([_f32p, _i32p, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _f32p], _int),
     "usip_scan_voxel_keys_f32_cpu": ([_f32p, _int, _f32p, _dbl, ctypes.c_void_p], _int),
     "usip_scan_voxel_average_f32_cpu": ([_f32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _f32p], _int),
+    # f-8 descriptor training batches from posed scans: the structs go by address (usip_amd/desc_pairs.py builds them)
+    "usip_desc_pairs_workspace_bytes": ([ctypes.c_void_p, _int], ctypes.c_longlong),
+    "usip_desc_pairs_workspace_offset": ([ctypes.c_void_p, _int, _int], ctypes.c_longlong),
+    "usip_desc_pairs_build_f32": ([ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_uint64, ctypes.c_uint64,
+                                   ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
+    "usip_desc_pairs_apply_f32": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_void_p,
+                                   ctypes.c_void_p, _stream], _int),
+    "usip_desc_pairs_build_f32_cpu": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_uint64,
+                                       ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p], _int),
 }
 
 

@@ -1384,6 +1384,164 @@ def pairs_workspace_bytes(recipe: PairsRecipeC, P: int) -> int:
     return n
 
 
+# ------------------------------------------------------------------------------- f-8 descriptor batches from posed scans
+class DescPairsRecipeC(ctypes.Structure):
+    """usip_desc_pairs_recipe (include/usip_hip.h), field for field."""
+    _fields_ = [("cloud", PairsRecipeC), ("positive_radius", ctypes.c_double), ("negative_radius", ctypes.c_double),
+                ("mine", ctypes.c_int)]
+
+
+class DescPairsBankC(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("rows", "offsets", "poses", "seq_of", "seq_start", "seq_start_host")] + \
+        [("num_scans", ctypes.c_int), ("num_seq", ctypes.c_int), ("min_rows", ctypes.c_longlong)]
+
+
+class DescPairsDrawsC(ctypes.Structure):
+    _fields_ = [("cloud", PairsDrawsC), ("params", ctypes.c_void_p), ("tries", ctypes.c_void_p),
+                ("neg_pick", ctypes.c_void_p), ("T", ctypes.c_int)]
+
+
+class DescPairsOutC(ctypes.Structure):
+    _fields_ = [("pc", ctypes.c_void_p * 2), ("sn", ctypes.c_void_p * 2), ("node", ctypes.c_void_p * 2)] + \
+        [(n, ctypes.c_void_p) for n in ("anc_pose", "pos_pose", "anc_seq", "pos_id", "neg_idx", "neg_fail", "rows",
+                                        "node_slots")]
+
+
+DESC_PAIRS_KEYS = ("anc_pc", "anc_sn", "anc_node", "pos_pc", "pos_sn", "pos_node", "anc_pose", "pos_pose", "anc_seq",
+                   "pos_id", "neg_idx", "neg_fail")
+DESC_PAIRS_DRAWS = dict(rows=torch.int32, cand=torch.int32, first=torch.int32, jit_pc=torch.float64,
+                        jit_sn=torch.float64, jit_node=torch.float64, params=torch.float64, tries=torch.int32,
+                        neg_pick=torch.int32)
+
+
+def desc_pairs_shapes(recipe: DescPairsRecipeC, P: int) -> dict:
+    """key -> (shape, dtype) of one batch of P pairs."""
+    c = recipe.cloud
+    f, i32 = torch.float32, torch.int32
+    return dict(anc_pc=((P, 3, c.N), f), anc_sn=((P, c.Cs, c.N), f), anc_node=((P, 3, c.M), f),
+                pos_pc=((P, 3, c.N), f), pos_sn=((P, c.Cs, c.N), f), pos_node=((P, 3, c.M), f),
+                anc_pose=((P, 4, 4), f), pos_pose=((P, 4, 4), f), anc_seq=((P,), i32), pos_id=((P,), i32),
+                neg_idx=((P,), torch.int64), neg_fail=((1,), i32))
+
+
+def desc_pairs_out_struct(ptr, out: dict, rows, node_slots) -> DescPairsOutC:
+    """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
+    o = DescPairsOutC()
+    for i, side in enumerate(("anc", "pos")):
+        o.pc[i], o.sn[i], o.node[i] = (ptr(out[side + "_" + k]) for k in ("pc", "sn", "node"))
+    for k in DESC_PAIRS_KEYS[6:]:
+        setattr(o, k, ptr(out[k]))
+    o.rows = ptr(rows) if rows is not None else None
+    o.node_slots = ptr(node_slots) if node_slots is not None else None
+    return o
+
+
+def _desc_pairs_check(recipe: DescPairsRecipeC, bank: dict, scan_ids, out: dict, rows, node_slots, workspace):
+    """Every tensor the launch touches on the bank's device, with its dtype and shape (a pointer to another device's
+    memory would be dereferenced by the kernels).  Returns (P, the bank struct)."""
+    dev = bank["rows"].device
+    for k, dt in (("rows", torch.float32), ("offsets", torch.int64), ("poses", torch.float64), ("seq_of", torch.int32),
+                  ("seq_start", torch.int32)):
+        _need(bank[k], "bank " + k, dt)
+        if bank[k].device != dev:
+            raise RuntimeError("desc_pairs: bank %s on %s, the rows on %s" % (k, bank[k].device, dev))
+    import numpy as np
+    S, Q = bank["offsets"].numel() - 1, bank["seq_start"].numel() - 1
+    host = bank["seq_start_host"]
+    if tuple(bank["poses"].shape) != (S, 4, 4) or bank["seq_of"].numel() != S or host.dtype != np.int32 or \
+            host.size != Q + 1 or not host.flags.c_contiguous:
+        raise RuntimeError("desc_pairs: poses f64 (S, 4, 4), seq_of i32 (S,), seq_start i32 (num_seq + 1,) on the "
+                           "device and as a C-contiguous int32 numpy array")
+    _need(scan_ids, "scan_ids", torch.int32)
+    P = scan_ids.numel()
+    if scan_ids.device != dev:
+        raise RuntimeError("desc_pairs: scan_ids on %s, the bank on %s" % (scan_ids.device, dev))
+    for k, (shape, dt) in desc_pairs_shapes(recipe, P).items():
+        _need(out[k], k, dt)
+        if tuple(out[k].shape) != shape or out[k].device != dev:
+            raise RuntimeError("desc_pairs: %s must be %s %s on %s" % (k, dt, shape, dev))
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < desc_pairs_workspace_bytes(recipe, P):
+        raise RuntimeError("desc_pairs: the workspace must hold usip_desc_pairs_workspace_bytes() bytes on %s" % dev)
+    for name, t, n in (("rows", rows, recipe.cloud.N), ("node_slots", node_slots, recipe.cloud.M)):
+        if t is not None:
+            _need(t, name, torch.int32)
+            if tuple(t.shape) != (2, P, n) or t.device != dev:
+                raise RuntimeError("desc_pairs: %s must be i32 (2, %d, %d) on %s" % (name, P, n, dev))
+    b = DescPairsBankC()
+    for k in ("rows", "offsets", "poses", "seq_of", "seq_start"):
+        setattr(b, k, bank[k].data_ptr())
+    b.seq_start_host, b.num_scans, b.num_seq, b.min_rows = host.ctypes.data, S, Q, int(bank["min_rows"])
+    return P, b
+
+
+def _desc_pairs_bytes(recipe: DescPairsRecipeC, P: int) -> float:
+    c = recipe.cloud
+    return 2.0 * P * c.N * (32 + 4 * (3 + c.Cs))
+
+
+def desc_pairs_build(recipe: DescPairsRecipeC, bank: dict, scan_ids: torch.Tensor, seed: int, step: int, pair_base: int,
+                     out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-8: P descriptor pairs with Philox draws (usip_desc_pairs_build_f32) into `out` (DESC_PAIRS_KEYS -> tensors).
+    bank: rows, offsets, poses, seq_of, seq_start (device tensors), seq_start_host (int32 numpy), min_rows."""
+    P, b = _desc_pairs_check(recipe, bank, scan_ids, out, rows, node_slots, workspace)
+    o = desc_pairs_out_struct(lambda t: t.data_ptr(), out, rows, node_slots)
+    dev = bank["rows"].device
+    with torch.cuda.device(dev), prof.kernel("desc_pairs_build", _desc_pairs_bytes(recipe, P)):
+        _lib.check(_lib.lib().usip_desc_pairs_build_f32(
+            ctypes.addressof(recipe), ctypes.addressof(b), _ptr(scan_ids), P, int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(step) & 0xFFFFFFFFFFFFFFFF, int(pair_base), ctypes.addressof(o), _ptr(workspace),
+            _stream(bank["rows"])), "usip_desc_pairs_build_f32")
+    return out
+
+
+def desc_pairs_draws_struct(ptr, draws: dict, T: int) -> DescPairsDrawsC:
+    d = DescPairsDrawsC()
+    for k in DESC_PAIRS_DRAWS:
+        if draws.get(k) is not None:
+            setattr(d if k in ("params", "tries", "neg_pick") else d.cloud, k, ptr(draws[k]))
+    d.T = int(T)
+    return d
+
+
+def desc_pairs_apply(recipe: DescPairsRecipeC, draws: dict, bank: dict, scan_ids: torch.Tensor, out: dict,
+                     workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-8 with explicit draws (usip_desc_pairs_apply_f32): DESC_PAIRS_DRAWS -> device tensors in the layouts of
+    include/usip_hip.h; tries is i32 [P][T]."""
+    P, b = _desc_pairs_check(recipe, bank, scan_ids, out, rows, node_slots, workspace)
+    dev = bank["rows"].device
+    for k, dt in DESC_PAIRS_DRAWS.items():
+        t = draws.get(k)
+        if t is not None:
+            _need(t, k, dt)
+            if t.device != dev:
+                raise RuntimeError("desc_pairs: draw %s on %s, the bank on %s" % (k, t.device, dev))
+    tries = draws.get("tries")
+    if tries is None or tries.dim() != 2 or tries.shape[0] != P:
+        raise RuntimeError("desc_pairs: draw tries must be i32 (%d, T)" % P)
+    d = desc_pairs_draws_struct(lambda t: t.data_ptr(), draws, tries.shape[1])
+    o = desc_pairs_out_struct(lambda t: t.data_ptr(), out, rows, node_slots)
+    with torch.cuda.device(dev), prof.kernel("desc_pairs_apply", _desc_pairs_bytes(recipe, P)):
+        _lib.check(_lib.lib().usip_desc_pairs_apply_f32(
+            ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(scan_ids), P, ctypes.addressof(o),
+            _ptr(workspace), _stream(bank["rows"])), "usip_desc_pairs_apply_f32")
+    return out
+
+
+def desc_pairs_workspace_offset(recipe: DescPairsRecipeC, P: int, part: int) -> int:
+    """Byte offset of workspace part 0 tables, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud scan ids, 5 total."""
+    n = int(_lib.lib().usip_desc_pairs_workspace_offset(ctypes.addressof(recipe), int(P), int(part)))
+    if n < 0:
+        raise RuntimeError("usip_amd: usip_desc_pairs_workspace_offset: invalid recipe or part (USIP_EINVAL)")
+    return n
+
+
+def desc_pairs_workspace_bytes(recipe: DescPairsRecipeC, P: int) -> int:
+    n = int(_lib.lib().usip_desc_pairs_workspace_bytes(ctypes.addressof(recipe), int(P)))
+    if n < 0:
+        raise RuntimeError("usip_amd: usip_desc_pairs_workspace_bytes: invalid recipe (USIP_EINVAL)")
+    return n
+
+
 # ------------------------------------------------------------------------------------------------ f-6 evaluation
 def _opt_ptr(t):
     return _ptr(t) if t is not None else None
