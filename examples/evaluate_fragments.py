@@ -1,0 +1,104 @@
+#!/usr/bin/env python
+"""Registration recall / precision on scene fragments, the reference's indoor benchmark
+(evaluation/matlab/eval_indoor/3dmatch: runFragmentRegistration.m, writeLog.m, evaluate.m), on the device.
+
+    python examples/evaluate_fragments.py --make-synthetic DIR [--fragments 6] [--points 20000]
+        builds a synthetic room of planes and boxes cut into overlapping posed fragments under DIR:
+        DIR/scenes/synthetic/<i>.npy, DIR/gt/synthetic-evaluation/gt.log and gt.info (from the poses; gt.info over the
+        points overlapping under the true pose) and DIR/results/synthetic/<i>.bin ([xyz, descriptor] rows; the descriptor
+        of a keypoint is the one-hot id of its landmark, so overlapping fragments share the true correspondences), then
+        evaluates it.
+    python examples/evaluate_fragments.py --scenes DIR --results DIR --gt DIR [--scene-names livingroom1 ...]
+        evaluates data laid out as the reference's scripts expect: <scenes>/<scene>/<i>.npy, <results>/<scene>/<i>.bin,
+        <gt>/<scene>-evaluation/gt.log and gt.info.
+
+Prints ONE JSON line (what evaluate.m prints, per scene and as means) and writes <results>/<scene>.log as writeLog.m does;
+with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
+import argparse
+import glob
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from usip_amd import fragments as fr            # noqa: E402
+
+
+def make_synthetic(root, fragments, points, dim, seed):
+    sc = fr.synthetic_scene(seed, fragments, points, dim)
+    scene, results, gt = (os.path.join(root, "scenes", "synthetic"), os.path.join(root, "results", "synthetic"),
+                          os.path.join(root, "gt", "synthetic-evaluation"))
+    for d in (scene, results, gt):
+        os.makedirs(d, exist_ok=True)
+    for i, cloud in enumerate(sc["clouds"]):
+        np.save(os.path.join(scene, "%d.npy" % i), cloud)
+        fr.write_descriptors_bin(os.path.join(results, "%d.bin" % i), sc["xyz"][i], sc["desc"][i])
+    fr.write_log(os.path.join(gt, "gt.log"), sc["gt"])
+    fr.write_info(os.path.join(gt, "gt.info"), sc["gt_info"])
+    return os.path.join(root, "scenes"), os.path.join(root, "results"), os.path.join(root, "gt")
+
+
+def evaluate_scene(name, scenes, results, gt_root, args):
+    clouds = sorted(glob.glob(os.path.join(scenes, name, "*.npy")), key=lambda p: int(os.path.basename(p)[:-4]))
+    if not clouds:
+        raise SystemExit("no fragments under %s" % os.path.join(scenes, name))
+    rows = [fr.read_descriptors_bin(os.path.join(results, name, "%d.bin" % i), args.dim) for i in range(len(clouds))]
+    top = max(len(x) for x, _ in rows)
+    ev = fr.FragmentEvaluator(None, None, None, args.device, top=top, k=args.k, max_trials=args.trials, seed=args.seed,
+                              batch_pairs=args.batch_pairs)
+    for i, path in enumerate(clouds):
+        ev.add_fragment_result(i, rows[i][0], rows[i][1], np.load(path))
+    gt = fr.read_log(os.path.join(gt_root, "%s-evaluation" % name, "gt.log"))
+    gt_info = fr.read_info(os.path.join(gt_root, "%s-evaluation" % name, "gt.info"))
+    out = ev.evaluate(None, gt, gt_info)
+    fr.write_result_log(os.path.join(results, "%s.log" % name), out["entries"])
+    if args.pair_files:
+        pp, ids = out["per_pair"], ev.ids()
+        os.makedirs(os.path.join(results, name, "registration-results"), exist_ok=True)
+        for p in range(out["pairs"]):
+            a, b = ids[pp["frag1"][p]], ids[pp["frag2"][p]]
+            fr.write_pair_file(os.path.join(results, name, "registration-results", "%d-%d.rt.txt" % (a, b)),
+                               fr.PairFile(a, b, int(pp["inliers"][p]), float(pp["inlier_ratio"][p]),
+                                           tuple(pp["ratio_aligned"][p]), fr.to4x4(pp["Rt"][p]), pp["information"][p]))
+    return {k: out[k] for k in ("pairs", "written", "recall", "precision", "inlier_num_mean", "inlier_ratio_mean", "good",
+                                "bad", "false_pos", "gt_num", "rs_num")}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--make-synthetic", metavar="DIR")
+    ap.add_argument("--fragments", type=int, default=6)
+    ap.add_argument("--points", type=int, default=20000)
+    ap.add_argument("--scenes")
+    ap.add_argument("--results")
+    ap.add_argument("--gt")
+    ap.add_argument("--scene-names", nargs="+", default=["livingroom1", "livingroom2", "office1", "office2"])
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--k", type=int, default=fr.K_MATCH)
+    ap.add_argument("--trials", type=int, default=fr.MAX_TRIALS)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--batch-pairs", type=int, default=32)
+    ap.add_argument("--pair-files", action="store_true")
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args()
+    if args.make_synthetic:
+        scenes, results, gt = make_synthetic(args.make_synthetic, args.fragments, args.points, args.dim, args.seed)
+        names = ["synthetic"]
+    elif args.scenes and args.results and args.gt:
+        scenes, results, gt, names = args.scenes, args.results, args.gt, args.scene_names
+    else:
+        ap.error("give --make-synthetic DIR, or --scenes, --results and --gt")
+    per_scene = {n: evaluate_scene(n, scenes, results, gt, args) for n in names}
+    out = {"scenes": per_scene}
+    for k in ("recall", "precision", "inlier_num_mean", "inlier_ratio_mean"):          # evaluate.m's last line: means
+        out[k] = float(np.mean([s[k] for s in per_scene.values()]))
+    for k in ("pairs", "written"):
+        out[k] = int(sum(s[k] for s in per_scene.values()))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

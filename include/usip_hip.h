@@ -877,6 +877,78 @@ int usip_desc_pairs_build_f32_cpu(const usip_desc_pairs_recipe* recipe, const us
                                   const usip_desc_pairs_bank* bank, const int32_t* scan_ids, int P, uint64_t seed,
                                   uint64_t step, long long pair_base, const usip_desc_pairs_out* out);
 
+/* ------------------------------------------------------------------ f-9  indoor fragment registration (Redwood / 3DMatch)
+ * Replaces the per-pair work of evaluation/matlab/eval_indoor/3dmatch/register2Fragments.m: k-nearest matching in both
+ * directions and the union of the two lists, ransacfitRt on up to 10240 correspondences, the information matrix over
+ * the inliers and ratioAligned over the full fragments.  f-6's convention: float64 arithmetic on float32 inputs, sums in
+ * a fixed order.  csrc/fragments_math.h is the arithmetic.
+ *
+ * usip_knn_nd_counted_f32: pdist2(b, a, 'euclidean', 'smallest', k), 1 <= k <= 8, on ragged batches with
+ * usip_nearest_nd_counted_f32's distance: dist f32 / idx i32 [B][Ma][k] ascending, the lower index on ties; valid[B] =
+ * min(k, b_count) columns hold data, the rest and the rows beyond a_count hold (inf, 0).  k = 1 is
+ * usip_nearest_nd_counted_f32 bit for bit.
+ *
+ * usip_match_union_i32: nn12 i32 [P][Ma][k] (for keypoint i of fragment 1 its neighbours in fragment 2), nn21 i32
+ * [P][Mp][k] (the converse), the fragments' keypoint counts a_count, p_count i32 [P] (of a list min(k, the other count)
+ * columns are read, indices are clamped into range) -> the rows (i, q) of union([i, nn12(i, :)], [nn21(q, :), q], 'rows'):
+ * pairs i32 [P][Cmax][2] sorted by (i, q), zeros beyond count i32 [P]; Cmax = k (Ma + Mp) <= 10240.
+ *
+ * usip_ransac_trials_large_f32 / _explicit_f32 / usip_ransac_select_large_f32: the f-6 entries above with Nmax <= 10240 --
+ * the same draws, hypotheses, scores, replay and refit order; every output equals theirs bit for bit at Nmax <= 1024.
+ *
+ * usip_information_f32: x f32 [P][3][Nmax] (the fragment-1 keypoint of every correspondence), mask u8 [P][Nmax] ->
+ * info f64 [P][6][6] = sum over the masked points of A'A, A = [I3 | 0 2sz -2sy; -2sz 0 2sx; 2sy -2sx 0]; exactly symmetric.
+ *
+ * usip_overlap_ratio_f32: the fragments' full clouds in one CSR bank (rows f32 [total_rows][row_len], x y z first;
+ * offsets i64 [num_frags + 1]), pairs (frag1[p], frag2[p]) with the estimate Rt f64 [P][3][4] moving fragment 2 into
+ * fragment 1's frame: hits[p][0] = the fragment-1 points a with a moved fragment-2 point b' = R b + t at sqrt(d2) < radius,
+ * hits[p][1] = the b' with such an a, ratio f64 [P][2] = hits over the fragment's rows.  perm1 i32 [total_rows]: for every
+ * fragment, at its offset, its local row indices ascending along x; perm2 i32 [P][Lmax]: fragment 2's local row indices
+ * ascending along the moved x, which usip_overlap_keys_f32 writes (keys f64 [P][Lmax], +inf beyond the fragment); Lmax >=
+ * the longest fragment.  The answer is the all-pairs one as long as the permutations sort. */
+int usip_knn_nd_counted_f32(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count, int k,
+                            float* dist, int32_t* idx, int32_t* valid, int B, int C, int Ma, int Nb, void* stream);
+int usip_match_union_i32(const int32_t* nn12, const int32_t* nn21, const int32_t* a_count, const int32_t* p_count, int P,
+                         int Ma, int Mp, int k, int32_t* pairs, int32_t* count, void* stream);
+int usip_ransac_trials_large_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                 double threshold, uint64_t seed, const int64_t* pair_ids, int32_t* counts,
+                                 double* hypotheses, int32_t* triplets_out, void* stream);
+int usip_ransac_trials_large_explicit_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                          double threshold, const int32_t* triplets, int32_t* counts, double* hypotheses,
+                                          void* stream);
+int usip_ransac_select_large_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                 int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
+                                 const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
+                                 uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid,
+                                 int32_t* chosen, double* delta_t, double* delta_deg, void* stream);
+int usip_information_f32(const float* x, const uint8_t* mask, int P, int Nmax, double* info, void* stream);
+int usip_overlap_keys_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                          const int32_t* frag2, const double* Rt, int P, int Lmax, double* keys, void* stream);
+int usip_overlap_ratio_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                           const int32_t* frag1, const int32_t* frag2, const double* Rt, const int32_t* perm1,
+                           const int32_t* perm2, int P, int Lmax, double radius, int32_t* hits, double* ratio, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order.  prune = 0 makes the overlap twin test
+ * all pairs instead of walking outward along x. */
+int usip_knn_nd_counted_f32_cpu(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count, int k,
+                                float* dist, int32_t* idx, int32_t* valid, int B, int C, int Ma, int Nb, int num_threads);
+int usip_match_union_i32_cpu(const int32_t* nn12, const int32_t* nn21, const int32_t* a_count, const int32_t* p_count,
+                             int P, int Ma, int Mp, int k, int32_t* pairs, int32_t* count);
+int usip_ransac_trials_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                     double threshold, uint64_t seed, const int64_t* pair_ids, const int32_t* triplets,
+                                     int32_t* counts, double* hypotheses, int32_t* triplets_out, int num_threads);
+int usip_ransac_select_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
+                                     int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
+                                     const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
+                                     uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid,
+                                     int32_t* chosen, double* delta_t, double* delta_deg);
+int usip_information_f32_cpu(const float* x, const uint8_t* mask, int P, int Nmax, double* info);
+int usip_overlap_keys_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                              const int32_t* frag2, const double* Rt, int P, int Lmax, double* keys);
+int usip_overlap_ratio_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                               const int32_t* frag1, const int32_t* frag2, const double* Rt, const int32_t* perm1,
+                               const int32_t* perm2, int P, int Lmax, double radius, int prune, int32_t* hits,
+                               double* ratio, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,447 @@
+// usip_amd/csrc/fragments_cpu.cpp -- host twin of csrc/fragments.hip: the same arithmetic
+// (csrc/fragments_math.h over csrc/registration_math.h) on host pointers.  The trial scores, the replay of ransac.m's loop
+// and the refit are those of csrc/registration_cpu.cpp with the limit at 10240; the sums run in the device's order
+// (REFIT_LANES strided partial sums, then the binary tree).  Never reached from the device entry points.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <thread>
+#include <vector>
+#include "fragments_math.h"
+#include "../../include/usip_hip.h"
+
+using namespace usip_reg;
+using namespace usip_frag;
+
+namespace {
+
+int clamp_count(const int32_t* count, int p, int nmax)
+{
+    const int n = count[p];
+    return n < 0 ? 0 : (n > nmax ? nmax : n);
+}
+int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+bool shape_ok(int P, int Nmax, int T) { return P >= 0 && P <= 65535 && Nmax >= 1 && Nmax <= NMAX_LARGE && T >= 1; }
+
+template <class F>
+void split(long long total, int num_threads, const F& body)
+{
+    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
+    if (nt == 1 || total < 2 * nt) {
+        body(0, total);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (int w = 0; w < nt; ++w) {
+        const long long lo = total * w / nt, hi = total * (w + 1) / nt;
+        pool.emplace_back([=, &body] { body(lo, hi); });
+    }
+    for (auto& th : pool) th.join();
+}
+
+template <int K>
+void knn_host(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count, float* dist, int32_t* idx,
+              int32_t* valid, int B, int C, int Ma, int Nb, int num_threads)
+{
+    for (int bi = 0; bi < B; ++bi) {
+        const int nb = clamp_count(b_count, bi, Nb);
+        valid[bi] = nb < K ? nb : K;
+    }
+    split((long long)B * Ma, num_threads, [=](long long lo, long long hi) {
+        for (long long r = lo; r < hi; ++r) {
+            const int bi = (int)(r / Ma), i = (int)(r - (long long)bi * Ma);
+            const int na = clamp_count(a_count, bi, Ma), nb = clamp_count(b_count, bi, Nb);
+            const float* ab = a + (long long)bi * C * Ma;
+            const float* bb = b + (long long)bi * C * Nb;
+            TopK<K> list;
+            list.clear();
+            if (i < na)
+                for (int j = 0; j < nb; ++j) {
+                    float s = 0.f;
+                    for (int c = 0; c < C; ++c) {
+                        const float df = ab[(long long)c * Ma + i] - bb[(long long)c * Nb + j];
+                        s = std::fmaf(df, df, s);
+                    }
+                    list.offer(std::sqrt(s), j);
+                }
+            for (int s = 0; s < K; ++s) {
+                const bool have = list.j[s] != 0x7fffffff;
+                dist[r * K + s] = have ? list.d[s] : INFINITY;
+                idx[r * K + s] = have ? list.j[s] : 0;
+            }
+        }
+    });
+}
+
+void load3(const float* a, const float* b, int Nmax, const int idx[3], double x[3][3], double y[3][3])
+{
+    for (int k = 0; k < 3; ++k)
+        for (int c = 0; c < 3; ++c) {
+            x[k][c] = (double)a[(long long)c * Nmax + idx[k]];
+            y[k][c] = (double)b[(long long)c * Nmax + idx[k]];
+        }
+}
+
+double residual_at(const double Rt[12], const float* a, const float* b, int Nmax, int i)
+{
+    return residual(Rt, (double)a[i], (double)a[(long long)Nmax + i], (double)a[2LL * Nmax + i], (double)b[i],
+                    (double)b[(long long)Nmax + i], (double)b[2LL * Nmax + i]);
+}
+
+template <class Src>
+void trials_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, double threshold,
+                 const Src& src, int32_t* counts, double* hyp, int32_t* drawn, int num_threads)
+{
+    split((long long)P * T, num_threads, [=, &src](long long lo, long long hi) {
+        for (long long o = lo; o < hi; ++o) {
+            const int p = (int)(o / T), t = (int)(o - (long long)p * T);
+            const int n = clamp_count(count, p, Nmax);
+            const float* a = x1 + (long long)p * 3 * Nmax;
+            const float* b = x2 + (long long)p * 3 * Nmax;
+            if (n < 3) {
+                counts[o] = 0;
+                if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = 0.0;
+                if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = 0;
+                continue;
+            }
+            int idx[3];
+            src.get(p, t, n, T, idx);
+            double x[3][3], y[3][3], Rt[12];
+            load3(a, b, Nmax, idx, x, y);
+            fit3(x, y, Rt);
+            int hits = 0;
+            for (int i = 0; i < n; ++i) hits += residual_at(Rt, a, b, Nmax, i) < threshold ? 1 : 0;
+            counts[o] = hits;
+            if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = Rt[k];
+            if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = idx[k];
+        }
+    });
+}
+
+template <int W>
+void tree_sum(double (*part)[10])
+{
+    for (int s = REFIT_LANES / 2; s > 0; s >>= 1)
+        for (int l = 0; l < s; ++l)
+            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
+}
+
+template <class Src>
+void select_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, int max_trials,
+                 double threshold, const Src& src, const int32_t* counts, const double* gt, double* Rt_out,
+                 uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid, int32_t* chosen,
+                 double* delta_t, double* delta_deg)
+{
+    std::vector<double> part_store((size_t)REFIT_LANES * 10);
+    double (*part)[10] = reinterpret_cast<double (*)[10]>(part_store.data());
+    std::vector<uint8_t> in((size_t)NMAX_LARGE);
+    for (int p = 0; p < P; ++p) {
+        const int n = clamp_count(count, p, Nmax);
+        const float* a = x1 + (long long)p * 3 * Nmax;
+        const float* b = x2 + (long long)p * 3 * Nmax;
+        uint8_t* mask = inlier_mask + (long long)p * Nmax;
+        std::memset(mask, 0, (size_t)Nmax);
+        int pick = 0, tc = 0, ninl = 0;
+        double Rt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        if (n > 3) replay(counts + (long long)p * T, n, max_trials, &pick, &tc);
+        if (n >= 3) {
+            int idx[3] = {0, 1, 2};
+            if (n > 3) src.get(p, pick, n, T, idx);
+            double x[3][3], y[3][3], R0[12];
+            load3(a, b, Nmax, idx, x, y);
+            fit3(x, y, R0);
+            for (int i = 0; i < n; ++i) {
+                in[i] = (n == 3 || residual_at(R0, a, b, Nmax, i) < threshold) ? 1 : 0;
+                ninl += in[i];
+            }
+        }
+        const bool ok = ninl >= 3;
+        if (ok) {
+            double cen[6];
+            for (int l = 0; l < REFIT_LANES; ++l) {
+                for (int k = 0; k < 10; ++k) part[l][k] = 0.0;
+                for (int i = l; i < n; i += REFIT_LANES)
+                    if (in[i])
+                        for (int c = 0; c < 3; ++c) {
+                            part[l][c] += (double)a[(long long)c * Nmax + i];
+                            part[l][3 + c] += (double)b[(long long)c * Nmax + i];
+                        }
+            }
+            tree_sum<6>(part);
+            for (int k = 0; k < 6; ++k) cen[k] = part[0][k] / (double)ninl;
+            for (int l = 0; l < REFIT_LANES; ++l) {
+                double B[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                for (int i = l; i < n; i += REFIT_LANES)
+                    if (in[i]) {
+                        double xc[3], yc[3];
+                        for (int c = 0; c < 3; ++c) {
+                            xc[c] = (double)a[(long long)c * Nmax + i] - cen[c];
+                            yc[c] = (double)b[(long long)c * Nmax + i] - cen[3 + c];
+                        }
+                        accumulate(B, xc, yc);
+                    }
+                for (int k = 0; k < 10; ++k) part[l][k] = B[k];
+            }
+            tree_sum<10>(part);
+            double Bs[10];
+            for (int k = 0; k < 10; ++k) Bs[k] = part[0][k];
+            transform_from(Bs, cen, cen + 3, Rt);
+            for (int i = 0; i < n; ++i) mask[i] = in[i];
+        }
+        for (int k = 0; k < 12; ++k) Rt_out[(long long)p * 12 + k] = Rt[k];
+        inliers[p] = ok ? ninl : 0;
+        trialcount[p] = tc;
+        valid[p] = ok ? 1 : 0;
+        if (chosen) chosen[p] = pick;
+        if (gt) {
+            double dt = 3.0, dd = 6.0;
+            if (ok) compare(gt + (long long)p * 12, Rt, &dt, &dd);
+            delta_t[p] = dt;
+            delta_deg[p] = dd;
+        }
+    }
+}
+
+struct Range {
+    long long first;
+    int n;
+};
+
+Range fragment_range(const int64_t* offsets, int num_frags, long long total, int f, int lmax)
+{
+    f = clamp_index(f, num_frags);
+    long long lo = offsets[f], hi = offsets[f + 1];
+    lo = lo < 0 ? 0 : (lo > total ? total : lo);
+    hi = hi < lo ? lo : (hi > total ? total : hi);
+    return {lo, (int)(hi - lo > (long long)lmax ? (long long)lmax : hi - lo)};
+}
+
+int safe_index(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }
+
+bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, int P, int Lmax)
+{
+    return rows && offsets && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
+           Lmax <= (1 << 24);
+}
+
+// queries q[3][nq] against the database d[3][nd] sorted along x: the number of queries with a point within the radius
+int count_hits(const std::vector<double>& q, int nq, const std::vector<double>& d, int nd, double radius, bool prune,
+               int num_threads)
+{
+    const double r2hi = radius_sq_hi(radius);
+    std::vector<int> found((size_t)64, 0);
+    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
+    const double* dx = d.data();
+    const double* dy = dx + nd;
+    const double* dz = dy + nd;
+    auto body = [&](int w, long long lo, long long hi) {
+        int mine = 0;
+        for (long long i = lo; i < hi; ++i) {
+            const double xi = q[i], yi = q[(size_t)nq + i], zi = q[(size_t)2 * nq + i];
+            bool hit = false;
+            if (!prune) {
+                for (int j = 0; j < nd && !hit; ++j) hit = within(sqdist3(xi, yi, zi, dx[j], dy[j], dz[j]), radius, r2hi);
+            } else {
+                const int s = (int)(std::lower_bound(dx, dx + nd, xi) - dx);
+                for (int j = s; j < nd && !hit; ++j) {                 // outward, until the x-gap alone reaches the radius
+                    if (beyond(dx[j] - xi, radius)) break;
+                    hit = within(sqdist3(xi, yi, zi, dx[j], dy[j], dz[j]), radius, r2hi);
+                }
+                for (int j = s - 1; j >= 0 && !hit; --j) {
+                    if (beyond(xi - dx[j], radius)) break;
+                    hit = within(sqdist3(xi, yi, zi, dx[j], dy[j], dz[j]), radius, r2hi);
+                }
+            }
+            mine += hit ? 1 : 0;
+        }
+        found[w] = mine;
+    };
+    if (nt == 1 || nq < 2 * nt) {
+        body(0, 0, nq);
+    } else {
+        std::vector<std::thread> pool;
+        for (int w = 0; w < nt; ++w) pool.emplace_back(body, w, (long long)nq * w / nt, (long long)nq * (w + 1) / nt);
+        for (auto& th : pool) th.join();
+    }
+    int total = 0;
+    for (int w = 0; w < 64; ++w) total += found[w];
+    return total;
+}
+
+}  // namespace
+
+extern "C" int usip_knn_nd_counted_f32_cpu(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count,
+                                           int k, float* dist, int32_t* idx, int32_t* valid, int B, int C, int Ma, int Nb,
+                                           int num_threads)
+{
+    if (B < 0 || B > 65535 || C < 1 || Ma < 0 || Nb < 1 || k < 1 || k > KMAX) return USIP_EINVAL;
+    if ((long long)B * Ma == 0) return USIP_OK;
+    if (!a || !b || !a_count || !b_count || !dist || !idx || !valid) return USIP_EINVAL;
+    switch (k) {
+#define USIP_TOPK_CASE(k_) \
+    case k_: knn_host<k_>(a, b, a_count, b_count, dist, idx, valid, B, C, Ma, Nb, num_threads); return USIP_OK
+        USIP_TOPK_CASE(1); USIP_TOPK_CASE(2); USIP_TOPK_CASE(3); USIP_TOPK_CASE(4);
+        USIP_TOPK_CASE(5); USIP_TOPK_CASE(6); USIP_TOPK_CASE(7); USIP_TOPK_CASE(8);
+#undef USIP_TOPK_CASE
+    }
+    return USIP_EINVAL;
+}
+
+extern "C" int usip_match_union_i32_cpu(const int32_t* nn12, const int32_t* nn21, const int32_t* a_count,
+                                        const int32_t* p_count, int P, int Ma, int Mp, int k, int32_t* pairs, int32_t* count)
+{
+    if (P < 0 || P > 65535 || Ma < 1 || Mp < 1 || k < 1 || k > KMAX) return USIP_EINVAL;
+    if ((long long)k * ((long long)Ma + Mp) > UNION_MAX) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!nn12 || !nn21 || !a_count || !p_count || !pairs || !count) return USIP_EINVAL;
+    const int Cmax = k * (Ma + Mp);
+    std::vector<uint32_t> key;
+    for (int p = 0; p < P; ++p) {
+        const int na = clamp_count(a_count, p, Ma), np = clamp_count(p_count, p, Mp);
+        const int k12 = np < k ? np : k, k21 = na < k ? na : k;
+        const int32_t* A = nn12 + (long long)p * Ma * k;
+        const int32_t* Q = nn21 + (long long)p * Mp * k;
+        key.clear();
+        for (int i = 0; i < na; ++i)
+            for (int c = 0; c < k12; ++c) key.push_back((uint32_t)(i * Mp + clamp_index(A[(long long)i * k + c], Mp)));
+        for (int q = 0; q < np; ++q)
+            for (int c = 0; c < k21; ++c) key.push_back((uint32_t)(clamp_index(Q[(long long)q * k + c], Ma) * Mp + q));
+        std::sort(key.begin(), key.end());
+        key.erase(std::unique(key.begin(), key.end()), key.end());
+        int32_t* out = pairs + (long long)p * Cmax * 2;
+        std::memset(out, 0, (size_t)Cmax * 2 * sizeof(int32_t));
+        for (size_t e = 0; e < key.size(); ++e) {
+            const int i = (int)(key[e] / (uint32_t)Mp);
+            out[2 * e] = i;
+            out[2 * e + 1] = (int)key[e] - i * Mp;
+        }
+        count[p] = (int)key.size();
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_ransac_trials_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax,
+                                                int T, double threshold, uint64_t seed, const int64_t* pair_ids,
+                                                const int32_t* triplets, int32_t* counts, double* hypotheses,
+                                                int32_t* triplets_out, int num_threads)
+{
+    if (!shape_ok(P, Nmax, T)) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!x1 || !x2 || !count || !counts) return USIP_EINVAL;
+    if (triplets) {
+        const ExplicitTriplets src{triplets};
+        trials_host(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, num_threads);
+    } else {
+        const PhiloxTriplets src{seed, pair_ids};
+        trials_host(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, num_threads);
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_ransac_select_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax,
+                                                int T, int max_trials, double threshold, uint64_t seed,
+                                                const int64_t* pair_ids, const int32_t* triplets, const int32_t* counts,
+                                                const double* gt, double* Rt, uint8_t* inlier_mask, int32_t* inliers,
+                                                int32_t* trialcount, uint8_t* valid, int32_t* chosen, double* delta_t,
+                                                double* delta_deg)
+{
+    if (!shape_ok(P, Nmax, T) || max_trials < 0 || max_trials > T - 1) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!x1 || !x2 || !count || !counts || !Rt || !inlier_mask || !inliers || !trialcount || !valid) return USIP_EINVAL;
+    if (gt && (!delta_t || !delta_deg)) return USIP_EINVAL;
+    if (triplets) {
+        const ExplicitTriplets src{triplets};
+        select_host(x1, x2, count, P, Nmax, T, max_trials, threshold, src, counts, gt, Rt, inlier_mask, inliers,
+                    trialcount, valid, chosen, delta_t, delta_deg);
+    } else {
+        const PhiloxTriplets src{seed, pair_ids};
+        select_host(x1, x2, count, P, Nmax, T, max_trials, threshold, src, counts, gt, Rt, inlier_mask, inliers,
+                    trialcount, valid, chosen, delta_t, delta_deg);
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_information_f32_cpu(const float* x, const uint8_t* mask, int P, int Nmax, double* info)
+{
+    if (P < 0 || P > 65535 || Nmax < 1 || Nmax > NMAX_LARGE) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!x || !mask || !info) return USIP_EINVAL;
+    std::vector<double> part_store((size_t)REFIT_LANES * 10);
+    double (*part)[10] = reinterpret_cast<double (*)[10]>(part_store.data());
+    for (int p = 0; p < P; ++p) {
+        const float* a = x + (long long)p * 3 * Nmax;
+        const uint8_t* m = mask + (long long)p * Nmax;
+        int n = 0;
+        for (int l = 0; l < REFIT_LANES; ++l) {
+            double s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int i = l; i < Nmax; i += REFIT_LANES)
+                if (m[i]) {
+                    double t[9];
+                    info_terms((double)a[i], (double)a[(long long)Nmax + i], (double)a[2LL * Nmax + i], t);
+                    for (int k = 0; k < 9; ++k) s[k] += t[k];
+                    ++n;
+                }
+            for (int k = 0; k < 9; ++k) part[l][k] = s[k];
+            part[l][9] = 0.0;
+        }
+        tree_sum<9>(part);
+        double sum[9];
+        for (int k = 0; k < 9; ++k) sum[k] = part[0][k];
+        info_fill(sum, n, info + (long long)p * 36);
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_overlap_keys_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
+                                         long long total_rows, const int32_t* frag2, const double* Rt, int P, int Lmax,
+                                         double* keys)
+{
+    if (!bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax)) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!frag2 || !Rt || !keys) return USIP_EINVAL;
+    for (int p = 0; p < P; ++p) {
+        const Range r = fragment_range(offsets, num_frags, total_rows, frag2[p], Lmax);
+        for (int s = 0; s < Lmax; ++s) {
+            double v = INFINITY;
+            if (s < r.n) {
+                const float* row = rows + (r.first + s) * row_len;
+                v = xform(Rt + (long long)p * 12, 0, (double)row[0], (double)row[1], (double)row[2]);
+            }
+            keys[(long long)p * Lmax + s] = v;
+        }
+    }
+    return USIP_OK;
+}
+
+extern "C" int usip_overlap_ratio_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
+                                          long long total_rows, const int32_t* frag1, const int32_t* frag2, const double* Rt,
+                                          const int32_t* perm1, const int32_t* perm2, int P, int Lmax, double radius,
+                                          int prune, int32_t* hits, double* ratio, int num_threads)
+{
+    if (!bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) || !(radius > 0.0)) return USIP_EINVAL;
+    if (P == 0) return USIP_OK;
+    if (!frag1 || !frag2 || !Rt || !perm1 || !perm2 || !hits || !ratio) return USIP_EINVAL;
+    std::vector<double> a, b;
+    for (int p = 0; p < P; ++p) {
+        const Range r1 = fragment_range(offsets, num_frags, total_rows, frag1[p], Lmax);
+        const Range r2 = fragment_range(offsets, num_frags, total_rows, frag2[p], Lmax);
+        const double* G = Rt + (long long)p * 12;
+        a.assign((size_t)3 * r1.n, 0.0);                               // both in their sorted order
+        b.assign((size_t)3 * r2.n, 0.0);
+        for (int s = 0; s < r1.n; ++s) {
+            const float* row = rows + (r1.first + safe_index(perm1[r1.first + s], r1.n)) * row_len;
+            for (int c = 0; c < 3; ++c) a[(size_t)c * r1.n + s] = (double)row[c];
+        }
+        for (int s = 0; s < r2.n; ++s) {
+            const float* row = rows + (r2.first + safe_index(perm2[(long long)p * Lmax + s], r2.n)) * row_len;
+            for (int c = 0; c < 3; ++c)
+                b[(size_t)c * r2.n + s] = xform(G, c, (double)row[0], (double)row[1], (double)row[2]);
+        }
+        hits[2 * p] = r2.n > 0 ? count_hits(a, r1.n, b, r2.n, radius, prune != 0, num_threads) : 0;
+        hits[2 * p + 1] = r1.n > 0 ? count_hits(b, r2.n, a, r1.n, radius, prune != 0, num_threads) : 0;
+        ratio[2 * p] = r1.n > 0 ? (double)hits[2 * p] / (double)r1.n : 0.0;
+        ratio[2 * p + 1] = r2.n > 0 ? (double)hits[2 * p + 1] / (double)r2.n : 0.0;
+    }
+    return USIP_OK;
+}

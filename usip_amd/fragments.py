@@ -1,0 +1,632 @@
+"""Indoor fragment registration on the device: the number the reference reports for its indoor models,
+registration recall / precision on the Redwood / 3DMatch fragment benchmark (evaluation/matlab/eval_indoor/3dmatch:
+runFragmentRegistration.m -> clusterCallback.m -> register2Fragments.m -> writeLog.m -> evaluate.m ->
+mrEvaluateRegistrationMy.m).
+
+  match_descriptors_topk   pdist2(b, a, 'euclidean', 'smallest', k) on ragged batches
+  match_union              union([i, nn12(i, :)], [nn21(q, :), q], 'rows')
+  fragment_registration    ransacfitRt on up to 10240 correspondences (threshold 0.2, ransac.m's default 30000 trials)
+  information_matrix       the 6 x 6 sum of A'A over the inliers' fragment-1 keypoints
+  overlap_ratio            ratioAligned: the share of each full fragment with a point of the other closer than 0.2 m
+  *_cpu                    the same on numpy arrays over the library's host twins (csrc/fragments_cpu.cpp)
+  transformation_error     mrComputeTransformationError with the file's own dcm2quat
+  evaluate_log             mrEvaluateRegistrationMy: recall, precision, mean inlier number and ratio (host numpy)
+  read_* / write_*         gt.log (mrLoadLog), gt.info (mrLoadInfo), <scene>.log (writeLog.m / mrLoadLogMy) and the
+                           per-pair i-j.rt.txt of clusterCallback.m
+  FragmentEvaluator        detector -> NMS / top-k -> descriptor per fragment, cached beside the fragment's full cloud;
+                           evaluate() runs every pair on the device, reads the host once and scores
+
+RANSAC draws are f-6's (usip_amd/evaluation.py): the reference's algorithm on Philox draws keyed by (seed, pair id, trial).
+"""
+from collections import namedtuple
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, inference, ops
+from .evaluation import _np, _p, _pairs_np, select_keypoints_device
+
+FragmentResult = namedtuple("FragmentResult",
+                            "Rt inliers inlier_mask trialcount valid delta_t delta_deg chosen counts inlier_ratio")
+LogEntry = namedtuple("LogEntry", "info trans")                               # gt.log: (i, j, n), 4 x 4
+InfoEntry = namedtuple("InfoEntry", "info mat")                               # gt.info: (i, j, n), 6 x 6
+ResultEntry = namedtuple("ResultEntry", "info trans inlier_num inlier_ratio information")
+PairFile = namedtuple("PairFile", "fragment1 fragment2 inlier_num inlier_ratio ratio_aligned trans information")
+
+INLIER_THRESHOLD, MAX_TRIALS, OVERLAP_RADIUS, K_MATCH = 0.2, 30000, 0.2, 5
+GATE_ALIGNED, GATE_INLIER_RATIO = 0.23, 0.025                                # writeLog.m
+
+
+# ------------------------------------------------------------------------------------------------ device
+def match_descriptors_topk(anc_desc, pos_desc, anc_count, pos_count, k: int = K_MATCH):
+    """anc_desc f32 [P,C,Ma], pos_desc f32 [P,C,Mp], counts i32 [P] -> (idx i32 [P,Ma,k], valid i32 [P]): for every anchor
+    descriptor its k nearest positive descriptors, ascending, the lower index on ties; valid = min(k, pos_count) columns
+    hold data."""
+    _, idx, valid = ops.knn_nd_counted(anc_desc, pos_desc, anc_count, pos_count, k)
+    return idx, valid
+
+
+def match_union(nn12, nn21, count1, count2):
+    """-> (pairs i32 [P,Cmax,2], count i32 [P]): the unique rows (i, q) of both lists, sorted."""
+    return ops.match_union(nn12, nn21, count1, count2)
+
+
+def _finish(o, count, counts, eye):
+    valid = o["valid"]
+    ok = valid.reshape(-1, 1, 1) != 0
+    Rt = (torch.where if isinstance(valid, torch.Tensor) else np.where)(ok, o["Rt"], eye)
+    ratio = o["inliers"] / (torch.clamp(count, min=1) if isinstance(count, torch.Tensor) else np.maximum(count, 1))
+    return FragmentResult(Rt, o["inliers"], o["inlier_mask"], o["trialcount"], valid, None, None, o["chosen"], counts, ratio)
+
+
+def fragment_registration(x1, x2, count, threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, seed: int = 0,
+                          pair_ids=None, triplets=None) -> FragmentResult:
+    """x1 = R x2 + t from matched coordinates x1, x2 f32 [P,3,Nmax] with count i32 [P], Nmax <= 10240.  The fields of
+    evaluation.RegistrationResult plus inlier_ratio = inliers / count (0 without correspondences).  An invalid pair (fewer
+    than 3 correspondences or inliers) gets [I | 0], 0 inliers and an empty mask, as register2Fragments.m's catch branch.
+    Device tensors, no host synchronisation."""
+    T = int(max_trials) + 1 if triplets is None else int(triplets.shape[1])
+    counts, _, _ = ops.ransac_trials_large(x1, x2, count, T, threshold, seed, pair_ids, triplets)
+    o = ops.ransac_select_large(x1, x2, count, counts, min(int(max_trials), T - 1), threshold, seed, pair_ids, triplets)
+    eye = torch.eye(3, 4, dtype=torch.float64, device=x1.device)
+    return _finish(o, count.to(torch.float64), counts, eye)
+
+
+def information_matrix(x1, inlier_mask):
+    """x1 f32 [P,3,Nmax] (the fragment-1 keypoint of every correspondence), inlier_mask u8 [P,Nmax] -> f64 [P,6,6]."""
+    return ops.information(x1, inlier_mask)
+
+
+class FragmentBank:
+    """The fragments' full clouds in ONE float32 device buffer [rows, 3] with int64 offsets (CSR, as pairs.ScanBank holds
+    scans), plus, per fragment, its local row indices ascending along x."""
+
+    def __init__(self, clouds: Sequence, device):
+        self.device = torch.device(device)
+        parts = [c.to(self.device, torch.float32)[:, :3] if isinstance(c, torch.Tensor)
+                 else torch.from_numpy(np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32)).to(self.device)
+                 for c in clouds]
+        if not parts:
+            raise ValueError("FragmentBank: no fragments")
+        self.lengths = [int(p.shape[0]) for p in parts]
+        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.rows = torch.cat(parts).contiguous()
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.perm = torch.cat([torch.argsort(p[:, 0], stable=True).to(torch.int32) for p in parts]).contiguous()
+        self.lmax = max(max(self.lengths), 1)
+
+    def host(self):
+        return HostBank(self.rows.cpu().numpy(), self.offsets_host.copy(), self.perm.cpu().numpy(), self.lmax)
+
+
+HostBank = namedtuple("HostBank", "rows offsets perm lmax")
+
+
+def host_bank(clouds: Sequence) -> HostBank:
+    parts = [np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32) for c in clouds]
+    offsets = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+    perm = np.concatenate([np.argsort(p[:, 0], kind="stable").astype(np.int32) for p in parts])
+    return HostBank(np.concatenate(parts), offsets, perm, max(max(p.shape[0] for p in parts), 1))
+
+
+def overlap_ratio(bank: FragmentBank, frag1, frag2, Rt, radius: float = OVERLAP_RADIUS):
+    """frag1, frag2 i32 [P] (fragments of the bank), Rt f64 [P,3,4] moving fragment 2 into fragment 1's frame ->
+    (ratio f64 [P,2], hits i32 [P,2]): register2Fragments.m's ratioAligned.  The moved fragment is sorted along x here,
+    on the device, by the keys the library computes."""
+    Rt = Rt.contiguous()
+    keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
+    perm2 = torch.argsort(keys, dim=1, stable=True).to(torch.int32)
+    return ops.overlap_ratio(bank.rows, bank.offsets, frag1, frag2, Rt, bank.perm, perm2, radius)
+
+
+# ------------------------------------------------------------------------------------------------ host twins (numpy)
+def match_descriptors_topk_cpu(anc_desc, pos_desc, anc_count, pos_count, k: int = K_MATCH, num_threads: int = 1,
+                               want_dist: bool = False):
+    a, b = _np(anc_desc, np.float32, "anc_desc"), _np(pos_desc, np.float32, "pos_desc")
+    B, C, Ma = a.shape
+    Nb = b.shape[2]
+    ac, bc = _np(anc_count, np.int32, "anc_count", (B,)), _np(pos_count, np.int32, "pos_count", (B,))
+    k = int(k)
+    d, idx, valid = np.zeros((B, Ma, k), np.float32), np.zeros((B, Ma, k), np.int32), np.zeros(B, np.int32)
+    _lib.check(_lib.lib().usip_knn_nd_counted_f32_cpu(_p(a), _p(b), _p(ac), _p(bc), k, _p(d), _p(idx), _p(valid), B, C, Ma,
+                                                      Nb, int(num_threads)), "usip_knn_nd_counted_f32_cpu")
+    return (idx, valid, d) if want_dist else (idx, valid)
+
+
+def match_union_cpu(nn12, nn21, count1, count2):
+    a, b = _np(nn12, np.int32, "nn12"), _np(nn21, np.int32, "nn21")
+    P, Ma, k = a.shape
+    Mp = b.shape[1]
+    c1, c2 = _np(count1, np.int32, "count1", (P,)), _np(count2, np.int32, "count2", (P,))
+    pairs, count = np.zeros((P, k * (Ma + Mp), 2), np.int32), np.zeros(P, np.int32)
+    _lib.check(_lib.lib().usip_match_union_i32_cpu(_p(a), _p(b), _p(c1), _p(c2), P, Ma, Mp, k, _p(pairs), _p(count)),
+               "usip_match_union_i32_cpu")
+    return pairs, count
+
+
+def ransac_trials_large_cpu(x1, x2, count, T: int, threshold: float = INLIER_THRESHOLD, seed: int = 0, pair_ids=None,
+                            triplets=None, num_threads: int = 1):
+    """-> (counts i32 [P,T], hypotheses f64 [P,T,3,4], triplets i32 [P,T,3]) on the host."""
+    x1, x2, count = _pairs_np(x1, x2, count)
+    P, _, Nmax = x1.shape
+    T = int(T)
+    ids = _np(pair_ids, np.int64, "pair_ids", (P,)) if pair_ids is not None else None
+    tri = _np(triplets, np.int32, "triplets", (P, T, 3)) if triplets is not None else None
+    counts = np.zeros((P, T), np.int32)
+    hyp = np.zeros((P, T, 3, 4), np.float64)
+    drawn = np.zeros((P, T, 3), np.int32)
+    _lib.check(_lib.lib().usip_ransac_trials_large_f32_cpu(
+        _p(x1), _p(x2), _p(count), P, Nmax, T, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids), _p(tri),
+        _p(counts), _p(hyp), _p(drawn), int(num_threads)), "usip_ransac_trials_large_f32_cpu")
+    return counts, hyp, drawn
+
+
+def ransac_select_large_cpu(x1, x2, count, counts, max_trials: int, threshold: float = INLIER_THRESHOLD, seed: int = 0,
+                            pair_ids=None, triplets=None) -> Dict[str, np.ndarray]:
+    x1, x2, count = _pairs_np(x1, x2, count)
+    P, _, Nmax = x1.shape
+    counts = _np(counts, np.int32, "counts")
+    T = counts.shape[1]
+    ids = _np(pair_ids, np.int64, "pair_ids", (P,)) if pair_ids is not None else None
+    tri = _np(triplets, np.int32, "triplets", (P, T, 3)) if triplets is not None else None
+    o = {"Rt": np.zeros((P, 3, 4)), "inlier_mask": np.zeros((P, Nmax), np.uint8), "inliers": np.zeros(P, np.int32),
+         "trialcount": np.zeros(P, np.int32), "valid": np.zeros(P, np.uint8), "chosen": np.zeros(P, np.int32)}
+    _lib.check(_lib.lib().usip_ransac_select_large_f32_cpu(
+        _p(x1), _p(x2), _p(count), P, Nmax, T, int(max_trials), float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids),
+        _p(tri), _p(counts), None, _p(o["Rt"]), _p(o["inlier_mask"]), _p(o["inliers"]), _p(o["trialcount"]),
+        _p(o["valid"]), _p(o["chosen"]), None, None), "usip_ransac_select_large_f32_cpu")
+    return o
+
+
+def fragment_registration_cpu(x1, x2, count, threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,
+                              seed: int = 0, pair_ids=None, triplets=None, num_threads: int = 1) -> FragmentResult:
+    T = int(max_trials) + 1 if triplets is None else int(np.shape(triplets)[1])
+    counts, _, _ = ransac_trials_large_cpu(x1, x2, count, T, threshold, seed, pair_ids, triplets, num_threads)
+    o = ransac_select_large_cpu(x1, x2, count, counts, min(int(max_trials), T - 1), threshold, seed, pair_ids, triplets)
+    return _finish(o, np.asarray(count, np.float64), counts, np.eye(3, 4))
+
+
+def information_matrix_cpu(x1, inlier_mask):
+    x = _np(x1, np.float32, "x1")
+    P, _, Nmax = x.shape
+    m = _np(inlier_mask, np.uint8, "inlier_mask", (P, Nmax))
+    info = np.zeros((P, 6, 6))
+    _lib.check(_lib.lib().usip_information_f32_cpu(_p(x), _p(m), P, Nmax, _p(info)), "usip_information_f32_cpu")
+    return info
+
+
+def overlap_ratio_cpu(bank: HostBank, frag1, frag2, Rt, radius: float = OVERLAP_RADIUS, prune: bool = True,
+                      num_threads: int = 1):
+    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
+    perm1 = _np(bank.perm, np.int32, "perm", (rows.shape[0],))
+    f2 = _np(frag2, np.int32, "frag2")
+    P = f2.shape[0]
+    f1, G = _np(frag1, np.int32, "frag1", (P,)), _np(Rt, np.float64, "Rt", (P, 3, 4))
+    L, nf = int(bank.lmax), offsets.shape[0] - 1
+    keys = np.zeros((P, L))
+    _lib.check(_lib.lib().usip_overlap_keys_f32_cpu(_p(rows), rows.shape[1], _p(offsets), nf, rows.shape[0], _p(f2), _p(G),
+                                                    P, L, _p(keys)), "usip_overlap_keys_f32_cpu")
+    perm2 = np.ascontiguousarray(np.argsort(keys, axis=1, kind="stable").astype(np.int32))
+    hits, ratio = np.zeros((P, 2), np.int32), np.zeros((P, 2))
+    _lib.check(_lib.lib().usip_overlap_ratio_f32_cpu(_p(rows), rows.shape[1], _p(offsets), nf, rows.shape[0], _p(f1), _p(f2),
+                                                     _p(G), _p(perm1), _p(perm2), P, L, float(radius), 1 if prune else 0,
+                                                     _p(hits), _p(ratio), int(num_threads)), "usip_overlap_ratio_f32_cpu")
+    return ratio, hits
+
+
+# ------------------------------------------------------------------------------------------------ the per-pair pipeline
+def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, frag2, pair_ids, k: int = K_MATCH,
+                   threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
+                   seed: int = 0) -> Dict[str, torch.Tensor]:
+    """register2Fragments.m for a batch of pairs, on the device: kp f32 [P,3,M], desc f32 [P,D,M], n i32 [P] of either
+    fragment; frag1, frag2 i32 [P] into the bank; pair_ids i64 [P] key the draws.  No host synchronisation."""
+    nn12, _ = match_descriptors_topk(desc1, desc2, n1, n2, k)
+    nn21, _ = match_descriptors_topk(desc2, desc1, n2, n1, k)
+    pairs, count = match_union(nn12, nn21, n1, n2)
+    i1 = pairs[:, :, 0].long().unsqueeze(1).expand(-1, 3, -1)
+    i2 = pairs[:, :, 1].long().unsqueeze(1).expand(-1, 3, -1)
+    x1, x2 = torch.gather(kp1, 2, i1).contiguous(), torch.gather(kp2, 2, i2).contiguous()
+    reg = fragment_registration(x1, x2, count, threshold, max_trials, seed, pair_ids)
+    info = information_matrix(x1, reg.inlier_mask)
+    ratio, hits = overlap_ratio(bank, frag1, frag2, reg.Rt, radius)
+    gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
+    return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, trialcount=reg.trialcount, valid=reg.valid,
+                chosen=reg.chosen, matches=count, information=info, ratio_aligned=ratio, overlap_hits=hits, gate=gate,
+                frag1=frag1, frag2=frag2)
+
+
+def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, frag2, pair_ids, k: int = K_MATCH,
+                       threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
+                       seed: int = 0, num_threads: int = 1) -> Dict[str, np.ndarray]:
+    """register_pairs assembled from the host twins, on numpy arrays."""
+    nn12, _ = match_descriptors_topk_cpu(desc1, desc2, n1, n2, k, num_threads)
+    nn21, _ = match_descriptors_topk_cpu(desc2, desc1, n2, n1, k, num_threads)
+    pairs, count = match_union_cpu(nn12, nn21, n1, n2)
+    kp1, kp2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
+    x1 = np.ascontiguousarray(np.take_along_axis(kp1, np.broadcast_to(pairs[:, None, :, 0], (len(kp1), 3, pairs.shape[1])), 2))
+    x2 = np.ascontiguousarray(np.take_along_axis(kp2, np.broadcast_to(pairs[:, None, :, 1], (len(kp2), 3, pairs.shape[1])), 2))
+    reg = fragment_registration_cpu(x1, x2, count, threshold, max_trials, seed, pair_ids, None, num_threads)
+    info = information_matrix_cpu(x1, reg.inlier_mask)
+    ratio, hits = overlap_ratio_cpu(bank, frag1, frag2, reg.Rt, radius, True, num_threads)
+    gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
+    return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, trialcount=reg.trialcount, valid=reg.valid,
+                chosen=reg.chosen, matches=count, information=info, ratio_aligned=ratio, overlap_hits=hits, gate=gate,
+                frag1=np.asarray(frag1, np.int32), frag2=np.asarray(frag2, np.int32))
+
+
+# ------------------------------------------------------------------------------------------------ the score
+def dcm2quat(R):
+    """ElasticReconstruction's own dcm2quat (mrEvaluateRegistrationMy.m), float64; NaN / inf when the trace is -1."""
+    R = np.asarray(R, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        q0 = 0.5 * np.sqrt(1.0 + R[0, 0] + R[1, 1] + R[2, 2])
+        return np.array([q0, -(R[2, 1] - R[1, 2]) / (4 * q0), -(R[0, 2] - R[2, 0]) / (4 * q0),
+                         -(R[1, 0] - R[0, 1]) / (4 * q0)])
+
+
+def transformation_error(gt_trans, result_trans, gt_info) -> float:
+    """mrComputeTransformationError(gt_trans^-1 * result_trans, gt_info): er = [t; -q(2:4)], er' info er / info(1, 1)."""
+    trans = np.linalg.inv(np.asarray(gt_trans, np.float64)) @ np.asarray(result_trans, np.float64)
+    info = np.asarray(gt_info, np.float64)
+    er = np.concatenate((trans[:3, 3], -dcm2quat(trans[:3, :3])[1:]))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(er @ info @ er / info[0, 0])
+
+
+def evaluate_log(result: Sequence, gt: Sequence, gt_info: Sequence, err2: float = 0.04) -> Dict:
+    """mrEvaluateRegistrationMy: result = ResultEntry rows, gt = LogEntry rows, gt_info = InfoEntry rows (same order as
+    gt).  Only pairs with j - i > 1 count; a result pair absent from gt is a false positive; a NaN error is not good."""
+    if not len(gt):
+        raise ValueError("evaluate_log: the ground truth is empty")
+    num = int(gt[0].info[2])
+    mask, gt_num = {}, 0
+    for k, g in enumerate(gt):
+        if g.info[1] - g.info[0] > 1:
+            mask[int(g.info[0]) + int(g.info[1]) * num] = k
+            gt_num += 1
+    rs_num = good = bad = false_pos = 0
+    errors, inlier_num, inlier_ratio = [], [], []
+    for r in result:
+        if r.info[1] - r.info[0] > 1:
+            rs_num += 1
+            k = mask.get(int(r.info[0]) + int(r.info[1]) * num)
+            if k is None:
+                false_pos += 1
+                continue
+            p = transformation_error(gt[k].trans, r.trans, gt_info[k].mat)
+            errors.append(p)
+            if p <= err2:
+                good += 1
+                inlier_num.append(r.inlier_num)
+                inlier_ratio.append(r.inlier_ratio)
+            else:
+                bad += 1
+    nan = float("nan")
+    return {"recall": good / gt_num if gt_num else nan, "precision": good / rs_num if rs_num else nan,
+            "inlier_num_mean": float(np.mean(inlier_num)) if inlier_num else nan,
+            "inlier_ratio_mean": float(np.mean(inlier_ratio)) if inlier_ratio else nan,
+            "good": good, "bad": bad, "false_pos": false_pos, "gt_num": gt_num, "rs_num": rs_num,
+            "errors": np.asarray(errors, np.float64)}
+
+
+# ------------------------------------------------------------------------------------------------ files
+def _tokens(path):
+    with open(path) as f:
+        return f.read().split()
+
+
+def _blocks(path, floats):
+    tok, out, at = _tokens(path), [], 0
+    while at + 3 <= len(tok):
+        info = tuple(int(v) for v in tok[at:at + 3])
+        vals = [float(v) for v in tok[at + 3:at + 3 + floats]]
+        if len(vals) < floats:
+            break
+        out.append((info, vals))
+        at += 3 + floats
+    return out
+
+
+def read_log(path) -> List[LogEntry]:
+    """mrLoadLog: blocks of `i j n` and a 4 x 4 matrix, row by row."""
+    return [LogEntry(i, np.array(v).reshape(4, 4)) for i, v in _blocks(path, 16)]
+
+
+def write_log(path, entries: Sequence):
+    with open(path, "w") as f:
+        for e in entries:
+            f.write("%d\t%d\t%d\n" % tuple(e.info))
+            for row in np.asarray(e.trans, np.float64).reshape(4, 4):
+                f.write("%.8e\t%.8e\t%.8e\t%.8e\n" % tuple(row))
+
+
+def read_info(path) -> List[InfoEntry]:
+    """mrLoadInfo: blocks of `i j n` and a 6 x 6 matrix, row by row."""
+    return [InfoEntry(i, np.array(v).reshape(6, 6)) for i, v in _blocks(path, 36)]
+
+
+def write_info(path, entries: Sequence):
+    with open(path, "w") as f:
+        for e in entries:
+            f.write("%d\t%d\t%d\n" % tuple(e.info))
+            for row in np.asarray(e.mat, np.float64).reshape(6, 6):
+                f.write(" ".join("%.8f" % v for v in row) + "\n")
+
+
+def read_result_log(path) -> List[ResultEntry]:
+    """mrLoadLogMy: `i j n`, the 4 x 4 estimate row by row, `inliers ratio`, the 6 x 6 information column by column."""
+    out = []
+    for info, v in _blocks(path, 16 + 2 + 36):
+        out.append(ResultEntry(info, np.array(v[:16]).reshape(4, 4), int(round(v[16])), v[17],
+                               np.array(v[18:]).reshape(6, 6).T))
+    return out
+
+
+def write_result_log(path, entries: Sequence):
+    """writeLog.m's block per pair that passed the gate."""
+    with open(path, "w") as f:
+        for e in entries:
+            f.write("%d\t %d\t %d\t\n" % tuple(e.info))
+            for row in np.asarray(e.trans, np.float64).reshape(4, 4):
+                f.write("%.10f\t%.10f\t%.10f\t%.10f\n" % tuple(row))
+            f.write("%d\t%f\n" % (int(e.inlier_num), float(e.inlier_ratio)))
+            for col in np.asarray(e.information, np.float64).reshape(6, 6).T:
+                f.write("%.10f\t%.10f\t%.10f\t%.10f\t%.10f\t%.10f\n" % tuple(col))
+
+
+def write_pair_file(path, p: PairFile):
+    """clusterCallback.m:32-34, the i-j.rt.txt of one pair."""
+    with open(path, "w") as f:
+        f.write("%d\t %d\t\n%d\t %15.8e\t %15.8e\t %15.8e\t\n" % (p.fragment1, p.fragment2, p.inlier_num, p.inlier_ratio,
+                                                                  p.ratio_aligned[0], p.ratio_aligned[1]))
+        for row in np.asarray(p.trans, np.float64).reshape(4, 4):
+            f.write("%15.8e\t %15.8e\t %15.8e\t %15.8e\t\n" % tuple(row))
+        for col in np.asarray(p.information, np.float64).reshape(6, 6).T:
+            f.write("%15.8e\t %15.8e\t %15.8e\t %15.8e\t %15.8e\t %15.8e\t\n" % tuple(col))
+
+
+def read_pair_file(path) -> PairFile:
+    """What writeLog.m's dlmread calls take from an i-j.rt.txt."""
+    v = _tokens(path)
+    if len(v) < 2 + 4 + 16 + 36:
+        raise ValueError("%s: not a pair file" % path)
+    x = [float(t) for t in v[2:]]
+    return PairFile(int(v[0]), int(v[1]), int(round(x[0])), x[1], (x[2], x[3]), np.array(x[4:20]).reshape(4, 4),
+                    np.array(x[20:56]).reshape(6, 6).T)
+
+
+def read_descriptors_bin(path, dim: int):
+    """Utils.load_descriptors: float32 rows [x y z descriptor(dim)] -> (xyz [M,3], desc [M,dim])."""
+    a = np.fromfile(path, dtype=np.float32).reshape(-1, 3 + int(dim))
+    return a[:, :3].copy(), a[:, 3:].copy()
+
+
+def write_descriptors_bin(path, xyz, desc):
+    np.concatenate((np.asarray(xyz, np.float32), np.asarray(desc, np.float32)), 1).astype(np.float32).tofile(path)
+
+
+def to4x4(Rt):
+    return np.concatenate((np.asarray(Rt, np.float64).reshape(3, 4), [[0.0, 0.0, 0.0, 1.0]]))
+
+
+def result_entries(per_pair: Dict[str, np.ndarray], fragment_ids: Sequence[int], num_fragments: int) -> List[ResultEntry]:
+    """writeLog.m: the pairs that pass `ratioAligned(1) > 0.23 && inlierRatio > 0.025`, in the order they were run."""
+    out = []
+    for p in np.nonzero(per_pair["gate"])[0]:
+        out.append(ResultEntry((int(fragment_ids[per_pair["frag1"][p]]), int(fragment_ids[per_pair["frag2"][p]]),
+                                int(num_fragments)), to4x4(per_pair["Rt"][p]), int(per_pair["inliers"][p]),
+                               float(per_pair["inlier_ratio"][p]), per_pair["information"][p]))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the evaluator
+class FragmentEvaluator:
+    """Scores a detector + descriptor pair on scene fragments the way the reference's MATLAB does, without leaving the
+    device: the indoor sibling of evaluation.RegistrationEvaluator.
+
+    add_fragment(id, pc, sn, node, cloud) runs detector -> NMS / top-k -> descriptor on one fragment ([1,3,N], [1,Cs,N],
+    [1,3,M] device tensors) and caches keypoints, descriptors and count beside the fragment's full cloud ([rows, >= 3]);
+    add_fragment_result(id, xyz, desc, cloud) takes precomputed [xyz, descriptor] rows, what the .bin files hold.  Ids
+    are the fragments' integer indices in the scene.  evaluate(pairs, gt, gt_info) runs the pairs (default: all i < j) in
+    batches through register_pairs, reads the host once, applies writeLog.m's gate and scores with evaluate_log."""
+
+    def __init__(self, detector, descriptor, opt, device, nms_radius: float = 0.1, top: int = 512, k: int = K_MATCH,
+                 inlier_threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,
+                 overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32):
+        self.detector, self.descriptor, self.opt = detector, descriptor, opt
+        self.device = torch.device(device)
+        self.nms_radius, self.top, self.k = float(nms_radius), int(top), int(k)
+        self.inlier_threshold, self.max_trials = float(inlier_threshold), int(max_trials)
+        self.overlap_radius, self.seed, self.batch_pairs = float(overlap_radius), int(seed), int(batch_pairs)
+        self.fragments = {}
+        self._bank = None
+
+    def _store(self, fragment_id, kp, desc, count, cloud):
+        width = self.top
+        if kp.shape[1] > width:
+            raise ValueError("FragmentEvaluator: fragment %s has %d keypoints, top is %d" % (fragment_id, kp.shape[1], width))
+        if kp.shape[1] < width:                                    # one width for batching; padding is never read
+            kp = torch.cat((kp, kp.new_zeros(3, width - kp.shape[1])), 1)
+            desc = torch.cat((desc, desc.new_zeros(desc.shape[0], width - desc.shape[1])), 1)
+        cloud = cloud if isinstance(cloud, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cloud)[:, :3], dtype=np.float32))
+        self.fragments[int(fragment_id)] = (kp.contiguous(), desc.contiguous(), count,
+                                            cloud.to(self.device, torch.float32)[:, :3].contiguous())
+        self._bank = None
+        return self.fragments[int(fragment_id)]
+
+    def add_fragment(self, fragment_id, pc, sn, node, cloud):
+        keypoints, sigmas = inference.run_model(self.detector, pc, sn, node)
+        kp, count = select_keypoints_device(keypoints, sigmas, self.nms_radius, self.top)
+        desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
+        return self._store(fragment_id, kp[0], desc[0], count[0], cloud)
+
+    def add_fragment_result(self, fragment_id, xyz, desc, cloud):
+        xyz = torch.as_tensor(np.asarray(xyz, np.float32) if not isinstance(xyz, torch.Tensor) else xyz).to(self.device, torch.float32)
+        desc = torch.as_tensor(np.asarray(desc, np.float32) if not isinstance(desc, torch.Tensor) else desc).to(self.device, torch.float32)
+        count = torch.tensor(xyz.shape[0], dtype=torch.int32, device=self.device)
+        return self._store(fragment_id, xyz.t(), desc.t(), count, cloud)
+
+    def fragment_arrays(self, fragment_id):
+        """(xyz [M',3], desc [M',D]) of a cached fragment on the host: what write_descriptors_bin takes."""
+        kp, desc, count, _ = self.fragments[int(fragment_id)]
+        n = int(count)
+        return kp[:, :n].t().cpu().numpy(), desc[:, :n].t().cpu().numpy()
+
+    def ids(self) -> List[int]:
+        return sorted(self.fragments)
+
+    def bank(self) -> FragmentBank:
+        if self._bank is None:
+            self._bank = FragmentBank([self.fragments[i][3] for i in self.ids()], self.device)
+        return self._bank
+
+    def all_pairs(self):
+        ids = self.ids()
+        return [(a, b) for x, a in enumerate(ids) for b in ids[x + 1:]]
+
+    def stacked(self):
+        """(kp f32 [F,3,top], desc f32 [F,D,top], count i32 [F]) over the fragments in id order."""
+        fr = [self.fragments[i] for i in self.ids()]
+        return torch.stack([f[0] for f in fr]), torch.stack([f[1] for f in fr]), torch.stack([f[2] for f in fr])
+
+    def evaluate_device(self, pairs: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
+        """Every pair through register_pairs, batch by batch -> per-pair device tensors; nothing synchronises."""
+        pairs = self.all_pairs() if pairs is None else list(pairs)
+        slot = {i: s for s, i in enumerate(self.ids())}
+        bank = self.bank()
+        kp, desc, cnt = self.stacked()
+        parts = []
+        for base in range(0, len(pairs), self.batch_pairs):
+            chunk = pairs[base:base + self.batch_pairs]
+            f1 = torch.tensor([slot[int(a)] for a, _ in chunk], dtype=torch.int32).to(self.device, non_blocking=True)
+            f2 = torch.tensor([slot[int(b)] for _, b in chunk], dtype=torch.int32).to(self.device, non_blocking=True)
+            ids = torch.arange(base, base + len(chunk), dtype=torch.int64, device=self.device)
+            a, b = f1.long(), f2.long()
+            parts.append(register_pairs(kp[a], desc[a], cnt[a].contiguous(), kp[b], desc[b], cnt[b].contiguous(), bank, f1,
+                                        f2, ids, self.k, self.inlier_threshold, self.max_trials, self.overlap_radius,
+                                        self.seed))
+        if not parts:
+            return {}
+        return {key: torch.cat([p[key] for p in parts]) for key in parts[0]}
+
+    def evaluate(self, pairs: Optional[Sequence] = None, gt: Optional[Sequence] = None,
+                 gt_info: Optional[Sequence] = None) -> Dict:
+        dev = self.evaluate_device(pairs)
+        host = {k: v.cpu().numpy() for k, v in dev.items()}                # the one read
+        return summarize(host, self.ids(), gt, gt_info)
+
+
+def summarize(per_pair: Dict[str, np.ndarray], fragment_ids: Sequence[int], gt=None, gt_info=None,
+              num_fragments: Optional[int] = None) -> Dict:
+    """What evaluate.m prints (when gt and gt_info are given) plus the result log's entries and the per-pair arrays."""
+    n = int(num_fragments if num_fragments is not None else (gt[0].info[2] if gt else len(fragment_ids)))
+    entries = result_entries(per_pair, fragment_ids, n) if per_pair else []
+    out = {"pairs": int(len(per_pair["gate"])) if per_pair else 0, "written": len(entries), "entries": entries,
+           "per_pair": per_pair}
+    if gt is not None and gt_info is not None:
+        out.update(evaluate_log(entries, gt, gt_info))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ a synthetic scene
+def synthetic_scene(seed: int = 0, fragments: int = 6, points: int = 20000, dim: int = 128, span: float = 5.0,
+                    step: float = 1.0, landmarks: Optional[int] = None, ground_truth: bool = True):
+    """A room of planes and boxes cut into overlapping posed fragments, with the ground truth the benchmark's files hold.
+
+    The room is `span + (fragments - 1) step` long; fragment i holds the surface points and the landmarks of the slab
+    [i step, i step + span] along the room, expressed in its own frame (a random rigid pose).  Landmark l carries the
+    one-hot descriptor l, so overlapping fragments share exact correspondences; with `landmarks` given there are that
+    many, each with a random unit descriptor.  -> dict(clouds [f32 [n,3]], xyz, desc (per fragment), poses [4x4, fragment
+    -> world], gt (LogEntry, pairs overlapping >= 30 %), gt_info (InfoEntry)); ground_truth False leaves gt, gt_info empty."""
+    rng = np.random.default_rng(seed)
+    length, width, height = span + (fragments - 1) * step, 4.0, 2.6
+    total = int(points * length / span)
+    # surfaces: floor, ceiling, two long walls, and boxes standing on the floor
+    boxes = [(rng.uniform(0.3, length - 0.9), rng.uniform(0.2, width - 1.0), rng.uniform(0.4, 0.8), rng.uniform(0.4, 0.8),
+              rng.uniform(0.4, 1.2)) for _ in range(2 * fragments + 4)]
+    areas = [length * width] * 2 + [length * height] * 2 + [2 * (bx * bz + by * bz) + bx * by for _, _, bx, by, bz in boxes]
+    share = np.asarray(areas) / np.sum(areas)
+    parts = []
+    for s, n in enumerate(rng.multinomial(total, share)):
+        u, v = rng.uniform(size=n), rng.uniform(size=n)
+        if s == 0:
+            parts.append(np.stack((u * length, v * width, np.zeros(n)), 1))
+        elif s == 1:
+            parts.append(np.stack((u * length, v * width, np.full(n, height)), 1))
+        elif s == 2:
+            parts.append(np.stack((u * length, np.zeros(n), v * height), 1))
+        elif s == 3:
+            parts.append(np.stack((u * length, np.full(n, width), v * height), 1))
+        else:
+            x0, y0, bx, by, bz = boxes[s - 4]
+            face = rng.integers(0, 5, size=n)
+            p = np.stack((x0 + u * bx, y0 + v * by, np.full(n, bz)), 1)                    # top
+            side = np.stack((x0 + u * bx, np.where(face == 1, y0, y0 + by), v * bz), 1)
+            p = np.where(((face == 1) | (face == 2))[:, None], side, p)
+            side = np.stack((np.where(face == 3, x0, x0 + bx), y0 + u * by, v * bz), 1)
+            p = np.where(((face == 3) | (face == 4))[:, None], side, p)
+            parts.append(p)
+    world = np.concatenate(parts)
+    world = world[rng.permutation(len(world))]
+    marks = world[rng.choice(len(world), dim if landmarks is None else int(landmarks), replace=False)]
+    if landmarks is None:
+        codes = np.eye(dim, dtype=np.float32)
+    else:
+        codes = rng.normal(size=(int(landmarks), dim))
+        codes = (codes / np.linalg.norm(codes, axis=1, keepdims=True)).astype(np.float32)
+    clouds, xyz, desc, poses = [], [], [], []
+    for i in range(fragments):
+        axis = rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        ang = rng.uniform(0.2, 1.0)
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
+        T = np.eye(4)
+        T[:3, :3], T[:3, 3] = R, rng.uniform(-2, 2, size=3)                               # fragment -> world
+        poses.append(T)
+        inv = np.linalg.inv(T)
+        lo, hi = i * step, i * step + span
+        pts = world[(world[:, 0] >= lo) & (world[:, 0] <= hi)]
+        clouds.append(np.ascontiguousarray((pts @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)))
+        seen = np.nonzero((marks[:, 0] >= lo) & (marks[:, 0] <= hi))[0]
+        xyz.append(np.ascontiguousarray((marks[seen] @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)))
+        desc.append(codes[seen])
+    gt, gt_info = [], []
+    for i in range(fragments if ground_truth else 0):
+        for j in range(i + 1, fragments):
+            trans = np.linalg.inv(poses[i]) @ poses[j]                                      # fragment j -> fragment i
+            a = clouds[i].astype(np.float64)
+            b = clouds[j].astype(np.float64) @ trans[:3, :3].T + trans[:3, 3]
+            near = _has_neighbour(a, b, 0.05)
+            if near.mean() < 0.3:
+                continue
+            gt.append(LogEntry((i, j, fragments), trans))
+            gt_info.append(InfoEntry((i, j, fragments), information_numpy(a[near])))
+    return dict(clouds=clouds, xyz=xyz, desc=desc, poses=poses, gt=gt, gt_info=gt_info)
+
+
+def _has_neighbour(a, b, cell):
+    """For every row of a: does b have a row in the same or an adjacent grid cell of size `cell` (so within cell .. 2 cell
+    per axis)?  Host numpy; only the synthetic scene's ground truth is built from it."""
+    origin = np.floor(np.minimum(a.min(0), b.min(0)) / cell).astype(np.int64) - 1
+    ka, kb = np.floor(a / cell).astype(np.int64) - origin, np.floor(b / cell).astype(np.int64) - origin
+    m = int(max(ka.max(), kb.max())) + 3
+    occupied = np.unique((kb[:, 0] * m + kb[:, 1]) * m + kb[:, 2])
+    out = np.zeros(len(a), bool)
+    for x in (-1, 0, 1):
+        for y in (-1, 0, 1):
+            for z in (-1, 0, 1):
+                out |= np.isin(((ka[:, 0] + x) * m + ka[:, 1] + y) * m + ka[:, 2] + z, occupied)
+    return out
+
+
+def information_numpy(points):
+    """register2Fragments.m:78-87 over `points` [n,3]: the sum of A'A, float64 host numpy."""
+    s = np.asarray(points, np.float64).reshape(-1, 3)
+    A = np.zeros((len(s), 3, 6))
+    A[:, 0, 0] = A[:, 1, 1] = A[:, 2, 2] = 1.0
+    A[:, 0, 4], A[:, 0, 5] = 2 * s[:, 2], -2 * s[:, 1]
+    A[:, 1, 3], A[:, 1, 5] = -2 * s[:, 2], 2 * s[:, 0]
+    A[:, 2, 3], A[:, 2, 4] = 2 * s[:, 1], -2 * s[:, 0]
+    return np.einsum("nki,nkj->ij", A, A)

@@ -1757,3 +1757,180 @@ def scan_voxel_average(xyzi, normals_f64, perm, start):
         _lib.check(_lib.lib().usip_scan_voxel_average_f32(_ptr(xyzi), _ptr(normals_f64), _ptr(perm), _ptr(start), n, m,
                                                           _ptr(rows), _stream(xyzi)), "usip_scan_voxel_average_f32")
     return rows
+
+
+# ------------------------------------------------------------------------------------------------ f-9 fragment registration
+def knn_nd_counted(a, b, a_count, b_count, k: int):
+    """f-9: the k nearest rows of b for every row of a on ragged batches: a f32 [B,C,Ma], b f32 [B,C,Nb], counts i32 [B]
+    -> (dist f32 [B,Ma,k], idx i32 [B,Ma,k] ascending, lower index on ties; valid i32 [B] = min(k, b_count) columns)."""
+    _need(a, "a", torch.float32)
+    _need(b, "b", torch.float32)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[:2] != b.shape[:2] or a.device != b.device or b.shape[2] < 1:
+        raise RuntimeError("knn_nd_counted: expected a [B,C,Ma] and b [B,C,Nb] on one device")
+    k = int(k)
+    if not 1 <= k <= 8:
+        raise RuntimeError("knn_nd_counted: k must be in 1..8 (got %d)" % k)
+    B, C, Ma = a.shape
+    Nb = b.shape[2]
+    _need_on(a_count, "a_count", torch.int32, (B,), a.device)
+    _need_on(b_count, "b_count", torch.int32, (B,), a.device)
+    if a_count is None or b_count is None:
+        raise RuntimeError("knn_nd_counted: counts are required")
+    d = torch.empty((B, Ma, k), dtype=torch.float32, device=a.device)
+    idx = torch.empty((B, Ma, k), dtype=torch.int32, device=a.device)
+    valid = torch.zeros((B,), dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device), prof.kernel("knn_nd_counted", 4.0 * B * C * (Ma + Nb), 3.0 * B * C * Ma * Nb):
+        _lib.check(_lib.lib().usip_knn_nd_counted_f32(_ptr(a), _ptr(b), _ptr(a_count), _ptr(b_count), k, _ptr(d),
+                                                      _ptr(idx), _ptr(valid), B, C, Ma, Nb, _stream(a)),
+                   "usip_knn_nd_counted_f32")
+    return d, idx, valid
+
+
+def match_union(nn12, nn21, a_count, p_count):
+    """f-9: nn12 i32 [P,Ma,k], nn21 i32 [P,Mp,k], keypoint counts i32 [P] -> (pairs i32 [P,Cmax,2] sorted by (i, q), count
+    i32 [P]); Cmax = k (Ma + Mp) <= 10240."""
+    _need(nn12, "nn12", torch.int32)
+    _need(nn21, "nn21", torch.int32)
+    if nn12.dim() != 3 or nn21.dim() != 3 or nn12.shape[0] != nn21.shape[0] or nn12.shape[2] != nn21.shape[2] or \
+            nn12.device != nn21.device:
+        raise RuntimeError("match_union: expected nn12 [P,Ma,k] and nn21 [P,Mp,k] on one device")
+    P, Ma, k = nn12.shape
+    Mp = nn21.shape[1]
+    Cmax = k * (Ma + Mp)
+    if not (1 <= k <= 8 and Ma >= 1 and Mp >= 1 and Cmax <= 10240):
+        raise RuntimeError("match_union: k (Ma + Mp) must be at most 10240 with k in 1..8 (got k = %d, Ma = %d, Mp = %d)"
+                           % (k, Ma, Mp))
+    _need_on(a_count, "a_count", torch.int32, (P,), nn12.device)
+    _need_on(p_count, "p_count", torch.int32, (P,), nn12.device)
+    if a_count is None or p_count is None:
+        raise RuntimeError("match_union: counts are required")
+    pairs = torch.empty((P, Cmax, 2), dtype=torch.int32, device=nn12.device)
+    count = torch.empty((P,), dtype=torch.int32, device=nn12.device)
+    with torch.cuda.device(nn12.device), prof.kernel("match_union", 12.0 * P * Cmax):
+        _lib.check(_lib.lib().usip_match_union_i32(_ptr(nn12), _ptr(nn21), _ptr(a_count), _ptr(p_count), P, Ma, Mp, k,
+                                                   _ptr(pairs), _ptr(count), _stream(nn12)), "usip_match_union_i32")
+    return pairs, count
+
+
+def _need_pairs_large(x1, x2, count):
+    _need(x1, "x1", torch.float32)
+    _need(x2, "x2", torch.float32)
+    _need(count, "count", torch.int32)
+    if x1.dim() != 3 or x1.shape[1] != 3 or x2.shape != x1.shape or count.shape != (x1.shape[0],):
+        raise RuntimeError("fragments: expected x1, x2 f32 [P,3,Nmax] and count i32 [P]")
+    if not 1 <= x1.shape[2] <= 10240:
+        raise RuntimeError("fragments: Nmax must be in 1..10240 (got %d)" % x1.shape[2])
+    return x1.shape[0], x1.shape[2]
+
+
+def ransac_trials_large(x1, x2, count, T: int, threshold: float, seed: int = 0, pair_ids=None, triplets=None,
+                        want_hypotheses: bool = False, want_triplets: bool = False):
+    """f-9: ransac_trials with Nmax <= 10240 (the correspondences go through LDS in chunks)."""
+    P, Nmax = _need_pairs_large(x1, x2, count)
+    T = int(T)
+    dev = x1.device
+    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
+    _need_on(triplets, "triplets", torch.int32, (P, T, 3), dev)
+    counts = torch.empty((P, T), dtype=torch.int32, device=dev)
+    hyp = torch.empty((P, T, 3, 4), dtype=torch.float64, device=dev) if want_hypotheses else None
+    drawn = torch.empty((P, T, 3), dtype=torch.int32, device=dev) if want_triplets and triplets is None else triplets
+    with torch.cuda.device(dev), prof.kernel("ransac_trials_large", 24.0 * P * Nmax + 4.0 * P * T, 30.0 * P * T * Nmax):
+        if triplets is None:
+            _lib.check(_lib.lib().usip_ransac_trials_large_f32(
+                _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                _opt_ptr(pair_ids), _ptr(counts), _opt_ptr(hyp), _opt_ptr(drawn), _stream(x1)),
+                "usip_ransac_trials_large_f32")
+        else:
+            _lib.check(_lib.lib().usip_ransac_trials_large_explicit_f32(
+                _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, float(threshold), _ptr(triplets), _ptr(counts),
+                _opt_ptr(hyp), _stream(x1)), "usip_ransac_trials_large_explicit_f32")
+    return counts, hyp, (drawn if want_triplets else None)
+
+
+def ransac_select_large(x1, x2, count, counts, max_trials: int, threshold: float, seed: int = 0, pair_ids=None,
+                        triplets=None, gt=None):
+    """f-9: ransac_select with Nmax <= 10240 -> the same dict."""
+    P, Nmax = _need_pairs_large(x1, x2, count)
+    dev = x1.device
+    _need(counts, "counts", torch.int32)
+    if counts.dim() != 2 or counts.shape[0] != P or counts.device != dev:
+        raise RuntimeError("fragments: counts must be i32 [P,T] on %s" % dev)
+    T = counts.shape[1]
+    if not 0 <= int(max_trials) <= T - 1:
+        raise RuntimeError("fragments: max_trials must be in 0..T-1 (T = %d, got %d)" % (T, max_trials))
+    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
+    _need_on(triplets, "triplets", torch.int32, (P, T, 3), dev)
+    _need_on(gt, "gt", torch.float64, (P, 3, 4), dev)
+    out = {"Rt": torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
+           "inlier_mask": torch.empty((P, Nmax), dtype=torch.uint8, device=dev),
+           "inliers": torch.empty((P,), dtype=torch.int32, device=dev),
+           "trialcount": torch.empty((P,), dtype=torch.int32, device=dev),
+           "valid": torch.empty((P,), dtype=torch.uint8, device=dev),
+           "chosen": torch.empty((P,), dtype=torch.int32, device=dev),
+           "delta_t": torch.empty((P,), dtype=torch.float64, device=dev) if gt is not None else None,
+           "delta_deg": torch.empty((P,), dtype=torch.float64, device=dev) if gt is not None else None}
+    with torch.cuda.device(dev), prof.kernel("ransac_select_large", 4.0 * P * T + 24.0 * P * Nmax, 60.0 * P * Nmax):
+        _lib.check(_lib.lib().usip_ransac_select_large_f32(
+            _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, int(max_trials), float(threshold),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, _opt_ptr(pair_ids), _opt_ptr(triplets), _ptr(counts), _opt_ptr(gt),
+            _ptr(out["Rt"]), _ptr(out["inlier_mask"]), _ptr(out["inliers"]), _ptr(out["trialcount"]), _ptr(out["valid"]),
+            _ptr(out["chosen"]), _opt_ptr(out["delta_t"]), _opt_ptr(out["delta_deg"]), _stream(x1)),
+            "usip_ransac_select_large_f32")
+    return out
+
+
+def information(x, mask):
+    """f-9: x f32 [P,3,Nmax], mask u8 [P,Nmax] -> info f64 [P,6,6]: the sum of A'A over the masked points."""
+    _need(x, "x", torch.float32)
+    _need(mask, "mask", torch.uint8)
+    if x.dim() != 3 or x.shape[1] != 3 or tuple(mask.shape) != (x.shape[0], x.shape[2]) or mask.device != x.device or \
+            not 1 <= x.shape[2] <= 10240:
+        raise RuntimeError("information: expected x f32 [P,3,Nmax] and mask u8 [P,Nmax] on one device, Nmax <= 10240")
+    P, _, Nmax = x.shape
+    info = torch.empty((P, 6, 6), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device), prof.kernel("information", 13.0 * P * Nmax):
+        _lib.check(_lib.lib().usip_information_f32(_ptr(x), _ptr(mask), P, Nmax, _ptr(info), _stream(x)),
+                   "usip_information_f32")
+    return info
+
+
+def _need_bank(rows, offsets, frag1, frag2, Rt):
+    _need(rows, "rows", torch.float32)
+    _need(offsets, "offsets", torch.int64)
+    if rows.dim() != 2 or rows.shape[1] < 3 or offsets.dim() != 1 or offsets.shape[0] < 2 or offsets.device != rows.device:
+        raise RuntimeError("overlap: expected rows f32 [total,row_len >= 3] and offsets i64 [fragments + 1] on one device")
+    P = frag2.shape[0]
+    _need_on(frag2, "frag2", torch.int32, (P,), rows.device)
+    _need_on(frag1, "frag1", torch.int32, (P,), rows.device)
+    _need_on(Rt, "Rt", torch.float64, (P, 3, 4), rows.device)
+    return P
+
+
+def overlap_keys(rows, offsets, frag2, Rt, Lmax: int):
+    """f-9: x of every fragment-2 point moved by Rt -> keys f64 [P,Lmax] (+inf beyond the fragment), to sort by."""
+    P = _need_bank(rows, offsets, None, frag2, Rt)
+    keys = torch.empty((P, int(Lmax)), dtype=torch.float64, device=rows.device)
+    with torch.cuda.device(rows.device), prof.kernel("overlap_keys", 20.0 * P * Lmax):
+        _lib.check(_lib.lib().usip_overlap_keys_f32(_ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1,
+                                                    rows.shape[0], _ptr(frag2), _ptr(Rt), P, int(Lmax), _ptr(keys),
+                                                    _stream(rows)), "usip_overlap_keys_f32")
+    return keys
+
+
+def overlap_ratio(rows, offsets, frag1, frag2, Rt, perm1, perm2, radius: float):
+    """f-9: ratioAligned of register2Fragments.m on a CSR bank -> (ratio f64 [P,2], hits i32 [P,2]).  perm1 i32 [total]:
+    every fragment's local rows ascending along x; perm2 i32 [P,Lmax]: fragment 2's ascending along overlap_keys."""
+    P = _need_bank(rows, offsets, frag1, frag2, Rt)
+    _need_on(perm1, "perm1", torch.int32, (rows.shape[0],), rows.device)
+    _need(perm2, "perm2", torch.int32)
+    if perm2.dim() != 2 or perm2.shape[0] != P or perm2.device != rows.device or perm2.shape[1] < 1:
+        raise RuntimeError("overlap: perm2 must be i32 [P,Lmax] on %s" % rows.device)
+    Lmax = perm2.shape[1]
+    hits = torch.empty((P, 2), dtype=torch.int32, device=rows.device)
+    ratio = torch.empty((P, 2), dtype=torch.float64, device=rows.device)
+    with torch.cuda.device(rows.device), prof.kernel("overlap_ratio", 32.0 * P * Lmax):
+        _lib.check(_lib.lib().usip_overlap_ratio_f32(_ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1,
+                                                     rows.shape[0], _ptr(frag1), _ptr(frag2), _ptr(Rt), _ptr(perm1),
+                                                     _ptr(perm2), P, Lmax, float(radius), _ptr(hits), _ptr(ratio),
+                                                     _stream(rows)), "usip_overlap_ratio_f32")
+    return ratio, hits
