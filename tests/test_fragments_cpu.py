@@ -50,6 +50,28 @@ def test_topk_matching_against_oracle(k):
     assert np.array_equal(i2, idx) and np.array_equal(v2, valid)
 
 
+@pytest.mark.parametrize("k", [2, 3, 4, 6, 7])
+def test_topk_matching_against_oracle_at_the_remaining_k(k):
+    """knn_counted_kernel<K> is instantiated for K = 1 .. 8: the five the test above leaves, on the same fixture."""
+    test_topk_matching_against_oracle(k)
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_topk_awkward_shapes_against_oracle(k):
+    """C = 33, Ma = 45 (a workgroup's four rows run past it), databases of 515, 257, 256 and 255 rows."""
+    anc, pos, na, nb = fo.awkward_topk_fixture()
+    a2, p2 = anc.copy(), pos.copy()
+    for p in range(len(na)):                                            # rows beyond the counts are never read
+        a2[p, :, na[p]:] = np.nan
+        p2[p, :, nb[p]:] = np.nan
+    idx, valid = fr.match_descriptors_topk_cpu(a2, p2, na, nb, k)
+    assert check_topk(idx, valid, anc, pos, na, nb, k) == 0             # the fixture leaves out no row
+    i2, v2 = fr.match_descriptors_topk_cpu(a2, p2, na, nb, k, num_threads=5)
+    assert np.array_equal(i2, idx) and np.array_equal(v2, valid)
+    if k == 1:
+        assert np.array_equal(idx[:, :, 0], ev.match_descriptors_cpu(anc, pos, na, nb))
+
+
 def tie_case():
     rng = np.random.default_rng(13)
     anc, pos = fo.unit_descriptors(rng, 1, 32, 40), fo.unit_descriptors(rng, 1, 32, 200)
@@ -271,6 +293,93 @@ def test_overlap_hits_equal_brute_force():
     assert np.array_equal(h2, hits) and np.array_equal(r2, ratio)
     r3, h3 = fr.overlap_ratio_cpu(bank, f1, f2, G, 0.2, num_threads=5)
     assert np.array_equal(h3, hits) and np.array_equal(r3, ratio)
+
+
+def lattice_bank(size):
+    """The lattice pair both ways round: (clouds, f1, f2, G, expected hits [P, 2]).  Pair 1 swaps the fragments and takes
+    the inverse pose, so either direction's queries meet the equality cases as the moved side and as the static side."""
+    a, b, Rt, hits, _ = fo.lattice_pair(size)
+    f1, f2 = np.array([0, 1], np.int32), np.array([1, 0], np.int32)
+    return [a, b], f1, f2, np.stack([Rt, fo.inverse_pose(Rt)]), np.stack([hits, hits[::-1]])
+
+
+@pytest.mark.parametrize("threads", [1, 5])
+@pytest.mark.parametrize("prune", [True, False])
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_overlap_on_the_exact_lattice_equals_integer_arithmetic(size, prune, threads):
+    """Hundreds of queries have their nearest point at exactly the radius (the fixture asserts it): sqrt(d2) < radius must
+    say no to each of them, and yes to the planted partners at squared distance 398 and 393 of 400."""
+    clouds, f1, f2, G, want = lattice_bank(size)
+    ratio, hits = fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.LATTICE_RADIUS, prune=prune, num_threads=threads)
+    print("lattice %s: hits %s, integer oracle %s" % (size, hits.tolist(), want.tolist()))
+    assert np.array_equal(hits, want)
+    assert np.array_equal(ratio, want / np.array([[len(clouds[0]), len(clouds[1])], [len(clouds[1]), len(clouds[0])]]))
+
+
+def wall_bank():
+    """(clouds, f1, f2, G): the two rooms both ways round beside a 300-point, a 512-point and an empty fragment, so that
+    Lmax padding and ragged lengths are in one launch."""
+    clouds, Rt, _ = fo.wall_rooms()
+    f1, f2 = np.array([0, 1, 2, 0, 0, 3, 4, 1], np.int32), np.array([1, 0, 1, 2, 3, 1, 1, 4], np.int32)
+    inv = fo.inverse_pose(Rt)
+    return clouds, f1, f2, np.stack([Rt, inv, Rt, inv, Rt, Rt, Rt, inv])
+
+
+_WALL_ORACLE = {}
+
+
+def wall_oracle():
+    if not _WALL_ORACLE:
+        clouds, f1, f2, G = wall_bank()
+        got = [fo.tree_overlap(clouds[f1[p]], clouds[f2[p]], G[p], fo.WALL_RADIUS) for p in range(len(f1))]
+        _WALL_ORACLE.update(hits=np.stack([g[0] for g in got]), ratio=np.stack([g[1] for g in got]),
+                            near=sum(g[2] for g in got))
+    return _WALL_ORACLE
+
+
+def test_overlap_across_constant_x_walls_equals_the_tree():
+    """Runs of about 16 700 equal x (65 tiles of the device's walk) in the static and in the moved fragment, at the
+    benchmark's 100 000 points."""
+    clouds, f1, f2, G = wall_bank()
+    o = wall_oracle()
+    ratio, hits = fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.WALL_RADIUS, num_threads=16)
+    print("walls: hits %s, tree %s (near the radius: %d)" % (hits.tolist(), o["hits"].tolist(), o["near"]))
+    assert o["near"] == 0
+    assert np.array_equal(hits, o["hits"]) and np.array_equal(ratio, o["ratio"])
+    assert np.array_equal(hits[0], fo.wall_rooms()[2]) and np.array_equal(hits[1], hits[0][::-1])
+    assert not hits[4].any() and not hits[5].any() and hits[2, 0] > 0 and hits[3, 1] > 0
+    r2, h2 = fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.WALL_RADIUS, prune=False, num_threads=16)
+    assert np.array_equal(h2, hits) and np.array_equal(r2, ratio)
+
+
+# ------------------------------------------------------------------------------------------------ the real configuration
+_FULL = {}
+
+
+def full_scene():
+    """The scene of fragments_oracle.FULL_SCENE through the host twins at the reference's protocol (top 1024, k = 5,
+    30 000 trials): (scene, stacked arrays, per-pair results), computed once for the CPU and the GPU tests."""
+    if not _FULL:
+        sc = fr.synthetic_scene(fo.FULL_SCENE["seed"], fo.FULL_SCENE["fragments"], fo.FULL_SCENE["points"],
+                                landmarks=fo.FULL_SCENE["landmarks"])
+        kp, de, cnt, f1, f2 = fo.stack_scene(sc, 1024)
+        o = fr.register_pairs_cpu(kp[f1], de[f1], cnt[f1], kp[f2], de[f2], cnt[f2], fr.host_bank(sc["clouds"]), f1, f2,
+                                  np.arange(len(f1)), num_threads=16)
+        _FULL.update(sc=sc, stacked=(kp, de, cnt, f1, f2), per_pair=o)
+    return _FULL["sc"], _FULL["stacked"], _FULL["per_pair"]
+
+
+def test_full_size_scene_through_the_host_twins():
+    """1024 keypoints, k = 5, 30 000 trials: the union is beyond 6000 rows (seven LDS chunks of the large kernels)."""
+    sc, (kp, de, cnt, f1, f2), o = full_scene()
+    assert tuple(cnt) == fo.FULL_KEYPOINTS and len(sc["gt"]) == 3
+    assert tuple(o["matches"]) == fo.FULL_MATCHES and tuple(o["trialcount"]) == fo.FULL_TRIALCOUNT
+    assert o["gate"].all() and o["valid"].all()
+    s = fr.summarize(o, [0, 1, 2], sc["gt"], sc["gt_info"])
+    assert {k: s[k] for k in fo.FULL_SCORE} == fo.FULL_SCORE
+    over = fr.synthetic_scene(fo.FULL_SCENE["seed"], fo.FULL_SCENE["fragments"], fo.FULL_SCENE["points"], landmarks=1430,
+                              ground_truth=False)
+    assert max(len(x) for x in over["xyz"]) > 1024                       # what FragmentEvaluator(top=1024) refuses
 
 
 # ------------------------------------------------------------------------------------------------ the score

@@ -50,6 +50,39 @@ def test_topk_at_k_1_is_the_one_nearest_kernel_bit_for_bit():
     assert torch.equal(idx[:, :, 0], i1) and torch.equal(d[:, :, 0].view(torch.int32), d1.view(torch.int32))
 
 
+def topk_device_case(fixture, k):
+    """Device against twin (indices, valid, distance bits) and against the oracle; rows and columns beyond the counts
+    are NaN: they are never read."""
+    anc, pos, na, nb = fixture
+    a2, p2 = anc.copy(), pos.copy()
+    for p in range(len(na)):
+        a2[p, :, na[p]:] = np.nan
+        p2[p, :, nb[p]:] = np.nan
+    d, idx, valid = ops.knn_nd_counted(dev(a2), dev(p2), dev(na), dev(nb), k)
+    ti, tv, td = fr.match_descriptors_topk_cpu(a2, p2, na, nb, k, want_dist=True)
+    assert np.array_equal(host(idx), ti) and np.array_equal(host(valid), tv)
+    assert np.array_equal(host(d).view(np.uint32), td.view(np.uint32))
+    assert tc.check_topk(host(idx), host(valid), anc, pos, na, nb, k, "device") == 0
+    return a2, p2, d, idx
+
+
+@pytest.mark.parametrize("k", [2, 3, 4, 6, 7])
+def test_topk_matching_equals_twin_and_oracle_at_the_remaining_k(k):
+    """knn_counted_kernel<K> is instantiated for K = 1 .. 8; the test above runs three of them."""
+    topk_device_case(fo.topk_fixture(), k)
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7, 8])
+def test_topk_awkward_shapes_equal_twin_and_oracle(k):
+    """C = 33; Ma = 45, so the last workgroup's rows 45 .. 47 leave at `i >= Ma`; databases of 515, 257, 256 and 255 rows
+    around one pass of a wave (64 * NJ = 256), where the tail clamp min(j, nb - 1) decides what is read."""
+    a2, p2, d, idx = topk_device_case(fo.awkward_topk_fixture(), k)
+    if k == 1:
+        _, _, na, nb = fo.awkward_topk_fixture()
+        d1, i1 = ops.nearest_nd_counted(dev(a2), dev(p2), dev(na), dev(nb))
+        assert torch.equal(idx[:, :, 0], i1) and torch.equal(d[:, :, 0].view(torch.int32), d1.view(torch.int32))
+
+
 def test_topk_ties_and_wide_batches():
     anc, pos, na, nb = tc.tie_case()
     idx, _ = fr.match_descriptors_topk(dev(anc), dev(pos), dev(na), dev(nb), 5)
@@ -153,6 +186,27 @@ def test_up_to_1024_the_large_entries_are_the_existing_ones_bit_for_bit():
                           dev(np.array([5], np.int32)), 4, THR)
 
 
+def test_large_entries_take_a_count_outside_0_to_nmax_as_the_nearer_end():
+    """clamp_count of the large kernels: a count above Nmax behaves as Nmax and a count below 0 as 0, draws included."""
+    x1, x2, count, gt, tri = eo.make_batch(36, P=4, n=3000, T=1, noise=0.05)
+    ids = np.array([40, 41, 42, 43], np.int64)
+    wild, tame = np.array([5000, 3000, -7, 0], np.int32), np.array([3000, 3000, 0, 0], np.int32)
+    got = {}
+    for name, c in (("wild", wild), ("tame", tame)):
+        r = fr.fragment_registration(dev(x1), dev(x2), dev(c), THR, 700, 23, dev(ids))
+        got[name] = fr.FragmentResult(*[host(f) if f is not None else None for f in r])
+        compare_results(got[name], fr.fragment_registration_cpu(x1, x2, c, THR, 700, 23, ids, num_threads=16))
+    for f in ("inliers", "inlier_mask", "trialcount", "valid", "chosen", "counts"):
+        assert np.array_equal(getattr(got["wild"], f), getattr(got["tame"], f)), f
+    assert same_bits(got["wild"].Rt, got["tame"].Rt)
+    w = got["wild"]
+    assert list(w.valid) == [1, 1, 0, 0] and w.inliers[0] > 900 and not w.inlier_mask[2:].any() and not w.counts[2:].any()
+    assert np.array_equal(w.Rt[2], np.eye(3, 4)) and list(w.trialcount[2:]) == [0, 0]
+    _, _, drawn = ops.ransac_trials_large(dev(x1), dev(x2), dev(wild), 50, THR, 23, dev(ids), want_triplets=True)
+    assert np.array_equal(host(drawn), fr.ransac_trials_large_cpu(x1, x2, tame, 50, THR, 23, ids)[2])
+    assert host(drawn)[:2].max() >= 2900 and host(drawn).max() < 3000
+
+
 @pytest.mark.parametrize("at", [254, 255, 256, 257, 511, 512])
 def test_stopping_rule_exits_on_either_side_of_a_scan_edge(at):
     """The select kernel scans 256 trials at a time; the loop's exit is placed just before, at and after an edge."""
@@ -209,6 +263,52 @@ def test_overlap_equals_twin_and_brute_force():
     assert np.array_equal(hb.rows, fr.host_bank(clouds).rows) and np.array_equal(hb.offsets, fr.host_bank(clouds).offsets)
 
 
+def device_overlap(clouds, f1, f2, G, radius):
+    ratio, hits = fr.overlap_ratio(fr.FragmentBank(clouds, DEV), dev(f1), dev(f2), dev(G), radius)
+    return host(ratio), host(hits)
+
+
+@pytest.mark.parametrize("size", ["small", "large"])
+def test_overlap_on_the_exact_lattice_equals_integer_arithmetic(size):
+    """Pair 0 is the lattice under Rt, pair 1 the fragments swapped under the inverse: either instantiation of
+    overlap_kernel<XQ> meets the queries whose nearest point is at exactly the radius from both sides."""
+    clouds, f1, f2, G, want = tc.lattice_bank(size)
+    ratio, hits = device_overlap(clouds, f1, f2, G, fo.LATTICE_RADIUS)
+    print("lattice %s: device hits %s, integer oracle %s, decided by equality alone %s"
+          % (size, hits.tolist(), want.tolist(), fo.lattice_pair(size)[4].tolist()))
+    assert np.array_equal(hits, want)
+    tr, th = fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.LATTICE_RADIUS, num_threads=16)
+    assert np.array_equal(hits, th) and same_bits(ratio, tr)
+    assert np.array_equal(hits, fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.LATTICE_RADIUS, prune=False,
+                                                     num_threads=16)[1])
+
+
+def test_overlap_across_constant_x_walls_equals_twin_and_tree():
+    """100 000-point rooms (391 tiles) whose static and moved x hold runs of about 16 700 equal values (65 tiles), beside
+    300-, 512- and 0-point fragments in the same launch."""
+    clouds, f1, f2, G = tc.wall_bank()
+    o = tc.wall_oracle()
+    ratio, hits = device_overlap(clouds, f1, f2, G, fo.WALL_RADIUS)
+    print("walls: device hits %s, tree %s" % (hits.tolist(), o["hits"].tolist()))
+    assert o["near"] == 0 and np.array_equal(hits, o["hits"]) and np.array_equal(ratio, o["ratio"])
+    tr, th = fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.WALL_RADIUS, num_threads=16)
+    assert np.array_equal(hits, th) and same_bits(ratio, tr)
+    assert np.array_equal(hits, fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.WALL_RADIUS, prune=False,
+                                                     num_threads=16)[1])
+
+
+def test_overlap_of_fragments_50_m_apart_is_exactly_zero():
+    """Fragment 2 moved 50 m along x, once to either side: for one instantiation every binary search ends at lo == nd
+    (with nd = 512 the start tile is the clamp's tiles - 1), for the other at 0, and no tile is within the radius."""
+    clouds, Rt, _ = fo.wall_rooms()
+    f1, f2 = np.array([0, 0, 0, 0, 2, 4], np.int32), np.array([1, 1, 4, 4, 1, 0], np.int32)
+    up, down = fo.far_pose(Rt, 50.0), fo.far_pose(Rt, -50.0)
+    G = np.stack([up, down, up, down, down, up])
+    ratio, hits = device_overlap(clouds, f1, f2, G, fo.WALL_RADIUS)
+    assert not hits.any() and not ratio.any()
+    assert not fr.overlap_ratio_cpu(fr.host_bank(clouds), f1, f2, G, fo.WALL_RADIUS, num_threads=16)[1].any()
+
+
 # ------------------------------------------------------------------------------------------------ the evaluator
 def scene_evaluator(sc, **kw):
     e = fr.FragmentEvaluator(None, None, None, DEV, top=128, **kw)
@@ -249,6 +349,69 @@ def test_evaluator_equals_the_pipeline_of_host_twins_without_synchronising():
     assert s["recall"] == 1.0 and s["precision"] == 1.0 and s["gt_num"] >= 6
     full = e.evaluate(None, sc["gt"], sc["gt_info"])                      # the public call: the same numbers
     assert full["recall"] == 1.0 and full["pairs"] == 15 and same_bits(full["per_pair"]["Rt"], got["Rt"])
+
+
+def full_evaluator(sc, stage=lambda t: t):
+    e = fr.FragmentEvaluator(None, None, None, DEV, top=1024)            # the reference's protocol: k = 5, 30 000 trials
+    for i in range(len(sc["clouds"])):
+        e.add_fragment_result(i, stage(dev(sc["xyz"][i])), stage(dev(sc["desc"][i])), stage(dev(sc["clouds"][i])))
+    return e
+
+
+def same_outputs(got, want):
+    assert set(got) == set(want)
+    for k in want:
+        a, b = (host(v) if isinstance(v, torch.Tensor) else v for v in (got[k], want[k]))
+        assert a.dtype == b.dtype, k
+        if b.dtype == np.float64:
+            assert same_bits(a, b), k
+        else:
+            assert np.array_equal(a, b), k
+
+
+def test_evaluator_at_the_reference_protocol_equals_the_host_twins_without_synchronising():
+    """1024 keypoints, k = 5, 30 000 trials: unions beyond 6000 rows, so the large kernels walk seven LDS chunks and the
+    select kernel keeps its flags in the mask, chained as the benchmark chains them."""
+    sc, _, want = tc.full_scene()
+    e = full_evaluator(sc)
+    e.bank()
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        per_pair = e.evaluate_device()
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    got = {k: host(v) for k, v in per_pair.items()}
+    same_outputs(got, want)
+    assert tuple(got["matches"]) == fo.FULL_MATCHES and tuple(got["trialcount"]) == fo.FULL_TRIALCOUNT
+    s = fr.summarize(got, e.ids(), sc["gt"], sc["gt_info"])
+    assert s["recall"] == 1.0 and s["precision"] == 1.0 and {k: s[k] for k in fo.FULL_SCORE} == fo.FULL_SCORE
+    over = fr.synthetic_scene(fo.FULL_SCENE["seed"], fo.FULL_SCENE["fragments"], fo.FULL_SCENE["points"], landmarks=1430,
+                              ground_truth=False)
+    with pytest.raises(ValueError):                                      # more than 1024 keypoints in a fragment
+        full_evaluator(over)
+
+
+def test_two_calls_agree_and_a_side_stream_is_ordered():
+    sc, _, want = tc.full_scene()
+    e = full_evaluator(sc)
+    first = e.evaluate_device()
+    second = e.evaluate_device()
+    same_outputs(first, want)
+    same_outputs(second, want)
+    # the fragments are produced on the side stream right before the call: only stream order makes the result right
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream(DEV)
+    side.wait_stream(torch.cuda.current_stream())
+
+    def ahead(t):
+        for _ in range(50):                                              # work ahead of the call on the same stream;
+            t = t * 1.0                                                  # (x * 1.0 is exact: the values are unchanged)
+        return t
+    with torch.cuda.stream(side):
+        third = full_evaluator(sc, ahead).evaluate_device()
+    side.synchronize()
+    same_outputs(third, want)
 
 
 def test_sync_debug_mode_sees_a_host_read():
