@@ -678,7 +678,9 @@ int usip_pairs_build_f32_cpu(const usip_pairs_recipe* recipe, const usip_pairs_d
  * eval_repeatability/eval_rep.m.  Float64 arithmetic on float32 inputs (MATLAB reads the float32 files into doubles).
  *
  * Padded batches with per-pair counts: x1, x2 f32 [P][3][Nmax] (x1 the anchor keypoints, x2 the positive frame's keypoints
- * they matched), count i32 [P] (clamped into [0, Nmax]), Nmax <= 1024; entries beyond count[p] are never read.
+ * they matched), count i32 [P] (clamped into [0, Nmax]), Nmax <= 10240; entries beyond count[p] are never read.  The three
+ * RANSAC entries and their host twins take any Nmax up to that limit: the outdoor evaluation stops at 1024 (one frame's
+ * keypoints), the indoor one (f-9 below) brings the union of two k-nearest lists; the kernels are the same.
  *
  * usip_ransac_trials_f32: trial t of pair p fits x1 = R x2 + t to three distinct correspondences (estimateRigidTransform:
  * the quaternion of the smallest eigenvalue of B = sum A'A, a fixed-sweep 4x4 Jacobi) and scores it, counts[p][t] =
@@ -893,8 +895,7 @@ int usip_desc_pairs_build_f32_cpu(const usip_desc_pairs_recipe* recipe, const us
  * columns are read, indices are clamped into range) -> the rows (i, q) of union([i, nn12(i, :)], [nn21(q, :), q], 'rows'):
  * pairs i32 [P][Cmax][2] sorted by (i, q), zeros beyond count i32 [P]; Cmax = k (Ma + Mp) <= 10240.
  *
- * usip_ransac_trials_large_f32 / _explicit_f32 / usip_ransac_select_large_f32: the f-6 entries above with Nmax <= 10240 --
- * the same draws, hypotheses, scores, replay and refit order; every output equals theirs bit for bit at Nmax <= 1024.
+ * ransacfitRt on the union's rows is f-6's usip_ransac_trials_f32 / _explicit_f32 / usip_ransac_select_f32 above.
  *
  * usip_information_f32: x f32 [P][3][Nmax] (the fragment-1 keypoint of every correspondence), mask u8 [P][Nmax] ->
  * info f64 [P][6][6] = sum over the masked points of A'A, A = [I3 | 0 2sz -2sy; -2sz 0 2sx; 2sy -2sx 0]; exactly symmetric.
@@ -910,17 +911,6 @@ int usip_knn_nd_counted_f32(const float* a, const float* b, const int32_t* a_cou
                             float* dist, int32_t* idx, int32_t* valid, int B, int C, int Ma, int Nb, void* stream);
 int usip_match_union_i32(const int32_t* nn12, const int32_t* nn21, const int32_t* a_count, const int32_t* p_count, int P,
                          int Ma, int Mp, int k, int32_t* pairs, int32_t* count, void* stream);
-int usip_ransac_trials_large_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                 double threshold, uint64_t seed, const int64_t* pair_ids, int32_t* counts,
-                                 double* hypotheses, int32_t* triplets_out, void* stream);
-int usip_ransac_trials_large_explicit_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                          double threshold, const int32_t* triplets, int32_t* counts, double* hypotheses,
-                                          void* stream);
-int usip_ransac_select_large_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                 int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
-                                 const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
-                                 uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid,
-                                 int32_t* chosen, double* delta_t, double* delta_deg, void* stream);
 int usip_information_f32(const float* x, const uint8_t* mask, int P, int Nmax, double* info, void* stream);
 int usip_overlap_keys_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
                           const int32_t* frag2, const double* Rt, int P, int Lmax, double* keys, void* stream);
@@ -933,14 +923,6 @@ int usip_knn_nd_counted_f32_cpu(const float* a, const float* b, const int32_t* a
                                 float* dist, int32_t* idx, int32_t* valid, int B, int C, int Ma, int Nb, int num_threads);
 int usip_match_union_i32_cpu(const int32_t* nn12, const int32_t* nn21, const int32_t* a_count, const int32_t* p_count,
                              int P, int Ma, int Mp, int k, int32_t* pairs, int32_t* count);
-int usip_ransac_trials_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                     double threshold, uint64_t seed, const int64_t* pair_ids, const int32_t* triplets,
-                                     int32_t* counts, double* hypotheses, int32_t* triplets_out, int num_threads);
-int usip_ransac_select_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                     int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
-                                     const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
-                                     uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid,
-                                     int32_t* chosen, double* delta_t, double* delta_deg);
 int usip_information_f32_cpu(const float* x, const uint8_t* mask, int P, int Nmax, double* info);
 int usip_overlap_keys_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
                               const int32_t* frag2, const double* Rt, int P, int Lmax, double* keys);

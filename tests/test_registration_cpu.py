@@ -9,11 +9,18 @@ trials below the host twin is at 1.9e-12 on R and 3.7e-11 m on t (smallest gap r
 asserted bounds are tightened to 1e-9 on R and 1e-7 m on t: 2.5-3x the derived bound for the solver's constant.
 A trial is left out when the oracle's gap is below 1e-5 lambda_max or an oracle residual lies within 1e-7 m of the
 threshold; at most 1 % may be (0 of 8 000 are).  The angle: 1e-6 degrees (the R error x 57.3, with room)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 
 import eval_oracle as eo
+from conftest import GOLDEN, load_golden
 from usip_amd import evaluation as ev
+
+sys.path.insert(0, GOLDEN)
+import make_ransac_golden as rg  # noqa: E402   (the cases of tests/golden/ransac_parent_bits.npz and how they are stored)
 
 TOL_R, TOL_T, TOL_DEG = 1e-9, 1e-7, 1e-6
 GAP, NEAR = 1e-5, 1e-7
@@ -123,6 +130,30 @@ def test_end_to_end_on_explicit_triplets(batch):
         assert abs(r.delta_t[p] - o["delta_t"]) <= TOL_T and abs(r.delta_deg[p] - o["delta_deg"]) <= TOL_DEG
     dt, dd = ev.compare_transform_cpu(gt, r.Rt)
     assert np.array_equal(dt, r.delta_t) and np.array_equal(dd, r.delta_deg)
+
+
+@pytest.fixture(scope="module")
+def parent_bits():
+    return load_golden(os.path.basename(rg.PATH))
+
+
+def check_parent_bits(name, got, want, what):
+    """Every stored output of case `name`, bit for bit; the inputs' digest first (nothing is skipped when it moves)."""
+    x1, x2, count = rg.inputs(name)[:3]
+    assert bytes(want["%s_sha256" % name]).hex() == rg.digest(x1, x2, count), "make_batch no longer gives the fixture's inputs"
+    differ = {k: int((got[k] != want["%s_%s" % (name, k)]).sum()) for k in rg.fields(name)}
+    print("%s, case %s: entries that differ from the pinned bits %s" % (what, name, differ))
+    for k in rg.fields(name):
+        e = want["%s_%s" % (name, k)]
+        assert got[k].dtype == e.dtype and got[k].shape == e.shape, k
+    assert not any(differ.values()), differ
+
+
+@pytest.mark.parametrize("name", sorted(rg.CASES))
+def test_host_twin_gives_the_bits_pinned_before_the_kernels_were_merged(name, parent_bits):
+    """Twin and device are held together everywhere else; this holds the twin to what the f-6 twin (A) and the f-9 twin
+    (B) computed before they became one."""
+    check_parent_bits(name, rg.host_twin(name), parent_bits, "host twin")
 
 
 def test_compare_transform_against_oracle_including_the_singular_branch():

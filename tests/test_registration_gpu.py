@@ -98,6 +98,21 @@ def test_stopping_rule_across_scan_chunks():
         assert (int(o["chosen"][0]), int(o["trialcount"][0])) == (chosen, trialcount)
 
 
+@pytest.mark.parametrize("name", sorted(host.rg.CASES))
+def test_device_gives_the_bits_pinned_before_the_kernels_were_merged(name):
+    """tests/golden/ransac_parent_bits.npz: A runs through the f-6 names, B (counts on either side of a chunk edge, beyond
+    one chunk) through the f-9 names; the differing entries per field are printed before the assertion."""
+    from usip_amd import ops
+    rg = host.rg
+    x1, x2, count, gt, ids, seed, large = rg.inputs(name)
+    trials, select = (ops.ransac_trials_large, ops.ransac_select_large) if large else (ops.ransac_trials, ops.ransac_select)
+    d = [dev(x1), dev(x2), dev(count)]
+    out = trials(*d, rg.T, rg.THR, seed, dev(ids), want_hypotheses=True, want_triplets=True)
+    o = select(*d, out[0], rg.MAX_TRIALS, rg.THR, seed, dev(ids), gt=None if gt is None else dev(gt))
+    got = rg.collect([t.cpu().numpy() for t in out], {k: None if v is None else v.cpu().numpy() for k, v in o.items()})
+    host.check_parent_bits(name, got, host.load_golden(os.path.basename(rg.PATH)), "device")
+
+
 def test_end_to_end_on_explicit_triplets(batch):
     x1, x2, count, gt, tri = batch
     T = tri.shape[1]

@@ -1,7 +1,9 @@
-"""Build-time guard for the RANSAC trial kernel (csrc/registration.hip): one lane per trial keeps a 4x4 Jacobi eigen-solve
-in float64 registers -- two 4x4 arrays indexed by compile-time constants only.  If an index became dynamic, or the register
-budget were exceeded, the arrays would move to scratch memory and every rotation would go through it; hipcc
-cross-compiles gfx950 without a GPU, so the ISA is checked here on every run of the suite."""
+"""Build-time guard for the RANSAC kernels (csrc/registration.hip), which serve the outdoor (f-6) and the indoor (f-9)
+evaluation: one lane per trial keeps a 4x4 Jacobi eigen-solve in float64 registers -- two 4x4 arrays indexed by compile-time
+constants only.  If an index became dynamic, or the register budget were exceeded, the arrays would move to scratch memory
+and every rotation would go through it.  The trial kernel stages ONE chunk of correspondences in LDS (not the largest pair)
+and the select kernel keeps no flag per correspondence in registers.  hipcc cross-compiles gfx950 without a GPU, so the ISA
+is checked here on every run of the suite."""
 import os
 import re
 import shutil
@@ -17,6 +19,7 @@ sys.path.insert(0, ROOT)
 from usip_amd.build import FLAGS as BUILD_FLAGS  # noqa: E402   (the ISA checked here is the ISA that ships)
 
 FLAGS = [f for f in BUILD_FLAGS if f != "-fPIC"] + ["-S", "--cuda-device-only"]
+CHUNK = 1024                                        # csrc/registration_math.h
 
 pytestmark = pytest.mark.skipif(shutil.which(HIPCC) is None and not os.path.exists(HIPCC), reason="hipcc not present")
 
@@ -38,16 +41,43 @@ def kernels(asm):
     return out
 
 
-def test_trial_kernels_keep_the_eigen_solve_in_registers(asm):
-    meta = {k: v for k, v in kernels(asm).items() if "ransac_trials_kernel" in k}
+def test_header_and_test_agree_on_the_chunk():
+    text = open(os.path.join(ROOT, "usip_amd", "csrc", "registration_math.h")).read()
+    assert int(re.search(r"constexpr int CHUNK = (\d+);", text).group(1)) == CHUNK
+    assert int(re.search(r"constexpr int NMAX = (\d+);", text).group(1)) == 10240
+
+
+def check_trial_kernels(asm, kernel, built):
+    meta = {k: v for k, v in kernels(asm).items() if kernel in k}
     assert len(meta) == 2, sorted(meta)                                  # Philox and explicit draws
     for name, m in meta.items():
         print("%s: %d VGPRs, %d SGPRs, %d B LDS" % (name, m["vgpr_count"], m["sgpr_count"], m["group_segment_fixed_size"]))
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0 and m["sgpr_spill_count"] == 0, name
-        assert m["vgpr_count"] <= 128, name                               # 106 / 108 as built: four waves per SIMD
-        assert m["group_segment_fixed_size"] == 6 * 1024 * 4, name        # the pair's coordinates, float32
-    body = asm[asm.index("ransac_trials_kernel"):]
+        assert m["vgpr_count"] <= 128, (name, built)                      # four waves per SIMD
+        assert m["group_segment_fixed_size"] == 6 * CHUNK * 4, name       # one chunk of coordinates, float32
+    body = asm[asm.index(kernel):]
     assert "scratch_" not in body[:body.index(".Lfunc_end")]
+
+
+def test_trial_kernels_keep_the_eigen_solve_in_registers(asm):
+    """The form for pairs of one chunk (the outdoor evaluation's): the whole pair staged once."""
+    check_trial_kernels(asm, "ransac_trials_resident_kernel", "106 / 108 as built")
+
+
+def test_trial_kernels_stage_one_chunk_and_keep_four_waves(asm):
+    """The general form: one chunk in LDS, not 6 * 10240 * 4 bytes."""
+    check_trial_kernels(asm, "ransac_trials_kernel", "112 as built")
+
+
+def test_select_kernel_keeps_no_flags_per_correspondence(asm):
+    meta = {k: v for k, v in kernels(asm).items() if "ransac_select_kernel" in k}
+    assert len(meta) == 2, sorted(meta)
+    resident = {k: v for k, v in kernels(asm).items() if "ransac_select_resident_kernel" in k}
+    assert len(resident) == 2, sorted(resident)                          # pairs of one chunk: four flags per lane
+    meta.update(resident)
+    for name, m in meta.items():
+        assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, name
+        assert m["vgpr_count"] <= 128, name                               # 92 as built; 40 flags per lane would show
 
 
 def test_no_new_kernel_uses_scratch_or_float_atomics(asm):

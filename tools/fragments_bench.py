@@ -3,10 +3,9 @@
 57 fragments (1596 pairs) of 100 000 points, 512 keypoints, D = 128, k = 5, 30 000 RANSAC trials.  Per stage -- top-k
 matching in both directions, union, gather, trial scores, selection + refit, information matrix, overlap (keys, sort,
 walk) -- HIP events on the launch stream after a warm-up batch, summed over all batches; pairs per second end to end;
-and beside every stage the library's host twin (csrc/fragments_cpu.cpp) on `--threads` threads, timed on `--host-pairs`
+and beside every stage the library's host twins (csrc/fragments_cpu.cpp, csrc/registration_cpu.cpp) on `--threads` threads, timed on `--host-pairs`
 pairs and scaled to the scene.  The host twin is what each device figure is compared against: the reference runs this
-path in MATLAB, which cannot be run here, so no ratio to it is claimed.  Also the large-N trial kernel against f-6's at
-n = 512 (information, not a gate).  One JSON line; --out writes it to a file as well.
+path in MATLAB, which cannot be run here, so no ratio to it is claimed.  One JSON line; --out writes it to a file as well.
 
     python tools/fragments_bench.py [--fragments 57] [--points 100000] [--keypoints 512] [--trials 30000]
                                     [--batch-pairs 32] [--threads 16] [--host-pairs 4] [--out profiles/f9_fragments_bench.json]"""
@@ -91,32 +90,6 @@ def host_batch(kp1, d1, n1, kp2, d2, n2, bank, f1, f2, ids, a):
     return t
 
 
-def trial_kernel_comparison(a):
-    """f-6's trial kernel against the large-N one at n = 512, 64 pairs: microseconds per call, median of 5 windows."""
-    rng = np.random.default_rng(3)
-    P, n, T = 64, 512, a.trials + 1
-    x1 = torch.from_numpy(rng.uniform(-4, 4, size=(P, 3, n)).astype(np.float32)).cuda()
-    x2 = torch.from_numpy(rng.uniform(-4, 4, size=(P, 3, n)).astype(np.float32)).cuda()
-    count = torch.full((P,), n, dtype=torch.int32, device="cuda")
-    out = {}
-    for name, fn in (("f6", ops.ransac_trials), ("large", ops.ransac_trials_large)):
-        for _ in range(2):
-            fn(x1, x2, count, T, fr.INLIER_THRESHOLD)
-        torch.cuda.synchronize()
-        w = []
-        for _ in range(5):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _ in range(3):
-                fn(x1, x2, count, T, fr.INLIER_THRESHOLD)
-            e.record()
-            e.synchronize()
-            w.append(s.elapsed_time(e) * 1e3 / 3)
-        out[name + "_us"] = round(float(np.median(w)), 1)
-    out.update(pairs=P, n=n, trials=T)
-    return out
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fragments", type=int, default=57)
@@ -183,7 +156,6 @@ def main():
                          "total_ms_scaled_to_scene": round(sum(host.values()) * scale, 1)},
            "compared_against": "the library's host twin on %d threads, timed on %d pairs and scaled to %d; the reference's "
                                "MATLAB cannot be run here" % (a.threads, hp, len(pairs)),
-           "trial_kernel_at_n_512": trial_kernel_comparison(a),
            "sanity": {"pairs_with_inliers": int((inliers > 0).sum()),
                       "pairs_past_gate": int(((ratio[:, 0] > fr.GATE_ALIGNED) & (inliers / np.maximum(matches, 1) > fr.GATE_INLIER_RATIO)).sum())},
            "device": torch.cuda.get_device_name(0), "host": platform.processor() or platform.machine()}

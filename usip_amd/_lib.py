@@ -192,16 +192,10 @@ SIGNATURES = {
                                    ctypes.c_void_p, _stream], _int),
     "usip_desc_pairs_build_f32_cpu": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_uint64,
                                        ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p], _int),
-    # f-9 indoor fragment registration: top-k matching, union, RANSAC beyond 1024, information, overlap (usip_amd/fragments.py)
+    # f-9 indoor fragment registration: top-k matching, union, information, overlap (usip_amd/fragments.py); RANSAC is f-6's
     "usip_knn_nd_counted_f32": ([_f32p, _f32p, _i32p, _i32p, _int, _f32p, _i32p, _i32p, _int, _int, _int, _int, _stream],
                                 _int),
     "usip_match_union_i32": ([_i32p] * 4 + [_int] * 4 + [_i32p, _i32p, _stream], _int),
-    "usip_ransac_trials_large_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p, _i32p,
-                                      ctypes.c_void_p, _i32p, _stream], _int),
-    "usip_ransac_trials_large_explicit_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, _i32p, _i32p, ctypes.c_void_p,
-                                               _stream], _int),
-    "usip_ransac_select_large_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p,
-                                      _i32p, _i32p] + [ctypes.c_void_p] * 9 + [_stream], _int),
     "usip_information_f32": ([_f32p, ctypes.c_void_p, _int, _int, ctypes.c_void_p, _stream], _int),
     "usip_overlap_keys_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _int, _int,
                                ctypes.c_void_p, _stream], _int),
@@ -210,10 +204,6 @@ SIGNATURES = {
     "usip_knn_nd_counted_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, _int, _f32p, _i32p, _i32p, _int, _int, _int, _int, _int],
                                     _int),
     "usip_match_union_i32_cpu": ([_i32p] * 4 + [_int] * 4 + [_i32p, _i32p], _int),
-    "usip_ransac_trials_large_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p,
-                                          _i32p, _i32p, ctypes.c_void_p, _i32p, _int], _int),
-    "usip_ransac_select_large_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _dbl, ctypes.c_uint64,
-                                          ctypes.c_void_p, _i32p, _i32p] + [ctypes.c_void_p] * 9, _int),
     "usip_information_f32_cpu": ([_f32p, ctypes.c_void_p, _int, _int, ctypes.c_void_p], _int),
     "usip_overlap_keys_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _int, _int,
                                    ctypes.c_void_p], _int),

@@ -1,7 +1,8 @@
 // usip_amd/csrc/fragments.hip -- indoor fragment registration on the device: the per-pair work of the
 // Redwood / 3DMatch benchmark (evaluation/matlab/eval_indoor/3dmatch/register2Fragments.m).  csrc/fragments_math.h has
-// the semantics and the arithmetic, which the host twin (csrc/fragments_cpu.cpp) shares; the rigid fit, the draws, the
-// stopping rule and the refit are csrc/registration_math.h's.  No launch synchronises, no floating-point atomics.
+// the semantics and the arithmetic, which the host twin (csrc/fragments_cpu.cpp) shares.  RANSAC itself is not here: the
+// pair's correspondences (up to 10240) go through csrc/registration.hip's one trial and one select kernel.  No launch
+// synchronises, no floating-point atomics.
 //
 //   knn_counted_kernel<K>        one wave per query descriptor, nearest_counted_kernel's distance (an FMA chain over the
 //                                channels, sqrtf); every lane keeps the K best of its candidates in registers, then K
@@ -9,9 +10,6 @@
 //   match_union_kernel           one workgroup per pair: the keys i Mp + q of both lists in LDS (40 KB at the limit), a
 //                                bitonic network whose comparators all point the same way (so a length that is no power of
 //                                two needs no padding), adjacent-unique, a prefix scan, the rows in order.
-//   ransac_trials_large_kernel   ransac_trials_kernel with the correspondences going through LDS in chunks of 1024: a lane
-//                                reads its triplet from memory, keeps its hypothesis and a running count across chunks.
-//   ransac_select_large_kernel   ransac_select_kernel with the inlier flags kept in the mask it writes, not in registers.
 //   information_kernel           one workgroup per pair: lane-strided partial sums of A'A's nine distinct terms, the tree.
 //   overlap_keys_kernel          x of every fragment-2 point under the pair's estimate: what the caller sorts by.
 //   overlap_kernel<XQ>           an existence query.  A workgroup owns 256 queries; database tiles of 256 points, sorted
@@ -27,15 +25,7 @@ using namespace usip_frag;
 
 namespace {
 
-constexpr int RT = 256;
 constexpr int UT = 1024;    // lanes of the union's workgroup
-
-__device__ __forceinline__ int clamp_count(const int32_t* count, int p, int nmax)
-{
-    const int n = count[p];
-    return n < 0 ? 0 : (n > nmax ? nmax : n);
-}
-__device__ __forceinline__ int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
 
 // ------------------------------------------------------------------------------------------------ top-k matching
 constexpr int NJ = 4;       // candidates in flight per lane
@@ -188,247 +178,6 @@ __global__ __launch_bounds__(UT) void match_union_kernel(const int32_t* __restri
         }
     for (int e = unique + l; e < Cmax; e += UT) { out[2LL * e] = 0; out[2LL * e + 1] = 0; }
     if (l == 0) count[p] = unique;
-}
-
-// ------------------------------------------------------------------------------------------------ RANSAC beyond 1024
-template <class Src>
-__global__ __launch_bounds__(RT) void ransac_trials_large_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
-                                                                 const int32_t* __restrict__ count, int Nmax, int T,
-                                                                 double threshold, Src src, int32_t* __restrict__ counts,
-                                                                 double* __restrict__ hyp, int32_t* __restrict__ drawn)
-{
-    __shared__ float pts[CHUNK][6];
-    const int p = blockIdx.y, t = blockIdx.x * RT + threadIdx.x;
-    const int n = clamp_count(count, p, Nmax);
-    const float* a = x1 + (long long)p * 3 * Nmax;
-    const float* b = x2 + (long long)p * 3 * Nmax;
-    const long long o = (long long)p * T + t;
-    if (n < 3) {                                          // ransacfitRt returns before any trial (workgroup-uniform)
-        if (t < T) {
-            counts[o] = 0;
-            if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = 0.0;
-            if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = 0;
-        }
-        return;
-    }
-    const bool live = t < T;
-    int idx[3] = {0, 0, 0};
-    double Rt[12];
-    {
-        if (live) src.get(p, t, n, T, idx);
-        double x[3][3], y[3][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                x[k][c] = (double)a[(long long)c * Nmax + idx[k]];
-                y[k][c] = (double)b[(long long)c * Nmax + idx[k]];
-            }
-        fit3(x, y, Rt);
-    }
-    int hits = 0;
-    for (int base = 0; base < n; base += CHUNK) {
-        const int m = min(CHUNK, n - base);
-        __syncthreads();                                  // the previous chunk has been read
-        for (int i = threadIdx.x; i < m; i += RT) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                pts[i][k] = a[(long long)k * Nmax + base + i];
-                pts[i][3 + k] = b[(long long)k * Nmax + base + i];
-            }
-        }
-        __syncthreads();
-        for (int i = 0; i < m; ++i) {
-            const double d = residual(Rt, (double)pts[i][0], (double)pts[i][1], (double)pts[i][2], (double)pts[i][3],
-                                      (double)pts[i][4], (double)pts[i][5]);
-            hits += d < threshold ? 1 : 0;
-        }
-    }
-    if (!live) return;
-    counts[o] = hits;
-    if (hyp)
-#pragma unroll
-        for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = Rt[k];
-    if (drawn)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = idx[k];
-}
-
-struct SelectOut {
-    double* Rt;               // [P][3][4]
-    uint8_t* inlier_mask;     // [P][Nmax]
-    int32_t* inliers;         // [P]
-    int32_t* trialcount;      // [P]
-    uint8_t* valid;           // [P]
-    int32_t* chosen;          // [P], optional
-    double* delta_t;          // [P], with gt
-    double* delta_deg;
-};
-
-// part[l][0..W) summed over l into part[0]: csrc/registration.hip's binary tree, the one the host twins walk
-template <int W>
-__device__ __forceinline__ void tree_sum(double (*part)[10], int l)
-{
-    for (int s = REFIT_LANES / 2; s > 0; s >>= 1) {
-        __syncthreads();
-        if (l < s)
-#pragma unroll
-            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
-    }
-    __syncthreads();
-}
-
-template <class Src>
-__global__ __launch_bounds__(REFIT_LANES) void ransac_select_large_kernel(const float* __restrict__ x1,
-                                                                          const float* __restrict__ x2,
-                                                                          const int32_t* __restrict__ count, int Nmax, int T,
-                                                                          int max_trials, double threshold, Src src,
-                                                                          const int32_t* __restrict__ counts,
-                                                                          const double* __restrict__ gt, SelectOut out)
-{
-    __shared__ double part[REFIT_LANES][10];
-    __shared__ double sRt[12], cen[6];
-    __shared__ int scan[REFIT_LANES];
-    __shared__ int s_exit, s_best, s_chosen, s_inl;
-    const int p = blockIdx.x, l = threadIdx.x;
-    const int n = clamp_count(count, p, Nmax);
-    const float* a = x1 + (long long)p * 3 * Nmax;
-    const float* b = x2 + (long long)p * 3 * Nmax;
-    uint8_t* mask = out.inlier_mask + (long long)p * Nmax;
-    if (l == 0) { s_exit = 0x7fffffff; s_best = 0; s_chosen = 0; s_inl = 0; }
-    __syncthreads();
-
-    int trialcount = 0;
-    if (n > 3) {
-        const int32_t* sc = counts + (long long)p * T;
-        int carry = 0;
-        for (int base = 0; base <= max_trials; base += REFIT_LANES) {
-            const int t = base + l;
-            scan[l] = t <= max_trials ? sc[t] : -1;
-            __syncthreads();
-            for (int off = 1; off < REFIT_LANES; off <<= 1) {          // inclusive max-scan
-                const int v = l >= off ? scan[l - off] : -1;
-                __syncthreads();
-                scan[l] = max(scan[l], v);
-                __syncthreads();
-            }
-            const int pm = max(carry, scan[l]);                        // ransac.m's bestscore after trial t
-            if (t <= max_trials && (t + 1 > max_trials || !(trials_needed(pm, n) > (double)(t + 1))))
-                atomicMin(&s_exit, t);
-            carry = max(carry, scan[REFIT_LANES - 1]);
-            __syncthreads();
-            if (s_exit != 0x7fffffff) {
-                if (t == s_exit) s_best = pm;
-                break;
-            }
-        }
-        __syncthreads();
-        const int te = s_exit, best = s_best;
-        for (int t = l; t <= te; t += REFIT_LANES)
-            if (sc[t] == best) atomicMax(&s_chosen, t);                // ties: the later trial
-        __syncthreads();
-        trialcount = te + 1;
-    }
-
-    if (n >= 3 && l == 0) {
-        int idx[3] = {0, 1, 2};
-        if (n > 3) src.get(p, s_chosen, n, T, idx);
-        double x[3][3], y[3][3];
-        for (int k = 0; k < 3; ++k)
-            for (int c = 0; c < 3; ++c) {
-                x[k][c] = (double)a[(long long)c * Nmax + idx[k]];
-                y[k][c] = (double)b[(long long)c * Nmax + idx[k]];
-            }
-        double Rt[12];
-        fit3(x, y, Rt);
-        for (int k = 0; k < 12; ++k) sRt[k] = Rt[k];
-    }
-    __syncthreads();
-
-    // the chosen hypothesis' inlier set (count == 3: the three, unconditionally), kept in the mask: lane l owns the rows
-    // l, l + 256, ... in every pass below, so it reads back only what it wrote itself
-    int mine = 0;
-    {
-        double Rt[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) Rt[k] = sRt[k];
-        for (int i = l; i < Nmax; i += REFIT_LANES) {
-            bool in = false;
-            if (i < n && n >= 3)
-                in = n == 3 || residual(Rt, (double)a[i], (double)a[(long long)Nmax + i], (double)a[2LL * Nmax + i],
-                                        (double)b[i], (double)b[(long long)Nmax + i], (double)b[2LL * Nmax + i]) < threshold;
-            mask[i] = in ? 1 : 0;
-            mine += in ? 1 : 0;
-        }
-    }
-    if (mine) atomicAdd(&s_inl, mine);
-    __syncthreads();
-    const int ninl = s_inl;
-    const bool ok = ninl >= 3;
-    if (!ok && mine)
-        for (int i = l; i < n; i += REFIT_LANES) mask[i] = 0;
-
-    if (ok) {                                                          // block-uniform
-        // centroids: lane l adds its rows in index order, then the tree
-#pragma unroll
-        for (int k = 0; k < 10; ++k) part[l][k] = 0.0;
-        for (int i = l; i < n; i += REFIT_LANES)
-            if (mask[i]) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    part[l][c] += (double)a[(long long)c * Nmax + i];
-                    part[l][3 + c] += (double)b[(long long)c * Nmax + i];
-                }
-            }
-        tree_sum<6>(part, l);
-        if (l < 6) cen[l] = part[0][l] / (double)ninl;
-        __syncthreads();
-        double B[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = l; i < n; i += REFIT_LANES)
-            if (mask[i]) {
-                double xc[3], yc[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    xc[c] = (double)a[(long long)c * Nmax + i] - cen[c];
-                    yc[c] = (double)b[(long long)c * Nmax + i] - cen[3 + c];
-                }
-                accumulate(B, xc, yc);
-            }
-#pragma unroll
-        for (int k = 0; k < 10; ++k) part[l][k] = B[k];
-        tree_sum<10>(part, l);
-    }
-    if (l != 0) return;
-    double Rt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (ok) {
-        double Bs[10];
-        for (int k = 0; k < 10; ++k) Bs[k] = part[0][k];
-        const double cx[3] = {cen[0], cen[1], cen[2]}, cy[3] = {cen[3], cen[4], cen[5]};
-        transform_from(Bs, cx, cy, Rt);
-    }
-    for (int k = 0; k < 12; ++k) out.Rt[(long long)p * 12 + k] = Rt[k];
-    out.inliers[p] = ok ? ninl : 0;
-    out.trialcount[p] = trialcount;
-    out.valid[p] = ok ? 1 : 0;
-    if (out.chosen) out.chosen[p] = s_chosen;
-    if (gt) {
-        double dt = 3.0, dd = 6.0;                                     // evaluate_kitti.m's catch values
-        if (ok) compare(gt + (long long)p * 12, Rt, &dt, &dd);
-        out.delta_t[p] = dt;
-        out.delta_deg[p] = dd;
-    }
-}
-
-bool shape_ok(int P, int Nmax, int T) { return P >= 0 && P <= 65535 && Nmax >= 1 && Nmax <= NMAX_LARGE && T >= 1; }
-
-template <class Src>
-int launch_trials(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, double threshold,
-                  const Src& src, int32_t* counts, double* hyp, int32_t* drawn, hipStream_t stream)
-{
-    USIP_LAUNCH(ransac_trials_large_kernel<Src>, dim3(usip_ceil_div(T, RT), P), dim3(RT), 0, stream, x1, x2, count, Nmax,
-                T, threshold, src, counts, hyp, drawn);
-    USIP_LAUNCH_CHECK();
-    return USIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ information matrix
@@ -683,56 +432,9 @@ extern "C" int usip_match_union_i32(const int32_t* nn12, const int32_t* nn21, co
     return USIP_OK;
 }
 
-extern "C" int usip_ransac_trials_large_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                            double threshold, uint64_t seed, const int64_t* pair_ids, int32_t* counts,
-                                            double* hypotheses, int32_t* triplets_out, void* stream)
-{
-    if (!shape_ok(P, Nmax, T)) return USIP_EINVAL;
-    if (P == 0) return USIP_OK;
-    if (!x1 || !x2 || !count || !counts) return USIP_EINVAL;
-    const PhiloxTriplets src{seed, pair_ids};
-    return launch_trials(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, (hipStream_t)stream);
-}
-
-extern "C" int usip_ransac_trials_large_explicit_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax,
-                                                     int T, double threshold, const int32_t* triplets, int32_t* counts,
-                                                     double* hypotheses, void* stream)
-{
-    if (!shape_ok(P, Nmax, T)) return USIP_EINVAL;
-    if (P == 0) return USIP_OK;
-    if (!x1 || !x2 || !count || !counts || !triplets) return USIP_EINVAL;
-    const ExplicitTriplets src{triplets};
-    return launch_trials(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, nullptr, (hipStream_t)stream);
-}
-
-extern "C" int usip_ransac_select_large_f32(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T,
-                                            int max_trials, double threshold, uint64_t seed, const int64_t* pair_ids,
-                                            const int32_t* triplets, const int32_t* counts, const double* gt, double* Rt,
-                                            uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid,
-                                            int32_t* chosen, double* delta_t, double* delta_deg, void* stream)
-{
-    if (!shape_ok(P, Nmax, T) || max_trials < 0 || max_trials > T - 1) return USIP_EINVAL;
-    if (P == 0) return USIP_OK;
-    if (!x1 || !x2 || !count || !counts || !Rt || !inlier_mask || !inliers || !trialcount || !valid) return USIP_EINVAL;
-    if (gt && (!delta_t || !delta_deg)) return USIP_EINVAL;
-    const SelectOut out{Rt, inlier_mask, inliers, trialcount, valid, chosen, delta_t, delta_deg};
-    hipStream_t st = (hipStream_t)stream;
-    if (triplets) {
-        const ExplicitTriplets src{triplets};
-        USIP_LAUNCH(ransac_select_large_kernel<ExplicitTriplets>, dim3(P), dim3(REFIT_LANES), 0, st, x1, x2, count, Nmax, T,
-                    max_trials, threshold, src, counts, gt, out);
-    } else {
-        const PhiloxTriplets src{seed, pair_ids};
-        USIP_LAUNCH(ransac_select_large_kernel<PhiloxTriplets>, dim3(P), dim3(REFIT_LANES), 0, st, x1, x2, count, Nmax, T,
-                    max_trials, threshold, src, counts, gt, out);
-    }
-    USIP_LAUNCH_CHECK();
-    return USIP_OK;
-}
-
 extern "C" int usip_information_f32(const float* x, const uint8_t* mask, int P, int Nmax, double* info, void* stream)
 {
-    if (P < 0 || P > 65535 || Nmax < 1 || Nmax > NMAX_LARGE) return USIP_EINVAL;
+    if (P < 0 || P > 65535 || Nmax < 1 || Nmax > NMAX) return USIP_EINVAL;
     if (P == 0) return USIP_OK;
     if (!x || !mask || !info) return USIP_EINVAL;
     USIP_LAUNCH(information_kernel, dim3(P), dim3(REFIT_LANES), 0, (hipStream_t)stream, x, mask, Nmax, info);

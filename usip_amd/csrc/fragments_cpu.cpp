@@ -1,7 +1,7 @@
 // usip_amd/csrc/fragments_cpu.cpp -- host twin of csrc/fragments.hip: the same arithmetic
-// (csrc/fragments_math.h over csrc/registration_math.h) on host pointers.  The trial scores, the replay of ransac.m's loop
-// and the refit are those of csrc/registration_cpu.cpp with the limit at 10240; the sums run in the device's order
-// (REFIT_LANES strided partial sums, then the binary tree).  Never reached from the device entry points.
+// (csrc/fragments_math.h over csrc/registration_math.h) on host pointers.  RANSAC is csrc/registration_cpu.cpp's; the sums
+// here run in the device's order (REFIT_LANES strided partial sums, then the binary tree).  Never reached from the device
+// entry points.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -14,15 +14,6 @@ using namespace usip_reg;
 using namespace usip_frag;
 
 namespace {
-
-int clamp_count(const int32_t* count, int p, int nmax)
-{
-    const int n = count[p];
-    return n < 0 ? 0 : (n > nmax ? nmax : n);
-}
-int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
-bool shape_ok(int P, int Nmax, int T) { return P >= 0 && P <= 65535 && Nmax >= 1 && Nmax <= NMAX_LARGE && T >= 1; }
 
 template <class F>
 void split(long long total, int num_threads, const F& body)
@@ -72,135 +63,6 @@ void knn_host(const float* a, const float* b, const int32_t* a_count, const int3
             }
         }
     });
-}
-
-void load3(const float* a, const float* b, int Nmax, const int idx[3], double x[3][3], double y[3][3])
-{
-    for (int k = 0; k < 3; ++k)
-        for (int c = 0; c < 3; ++c) {
-            x[k][c] = (double)a[(long long)c * Nmax + idx[k]];
-            y[k][c] = (double)b[(long long)c * Nmax + idx[k]];
-        }
-}
-
-double residual_at(const double Rt[12], const float* a, const float* b, int Nmax, int i)
-{
-    return residual(Rt, (double)a[i], (double)a[(long long)Nmax + i], (double)a[2LL * Nmax + i], (double)b[i],
-                    (double)b[(long long)Nmax + i], (double)b[2LL * Nmax + i]);
-}
-
-template <class Src>
-void trials_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, double threshold,
-                 const Src& src, int32_t* counts, double* hyp, int32_t* drawn, int num_threads)
-{
-    split((long long)P * T, num_threads, [=, &src](long long lo, long long hi) {
-        for (long long o = lo; o < hi; ++o) {
-            const int p = (int)(o / T), t = (int)(o - (long long)p * T);
-            const int n = clamp_count(count, p, Nmax);
-            const float* a = x1 + (long long)p * 3 * Nmax;
-            const float* b = x2 + (long long)p * 3 * Nmax;
-            if (n < 3) {
-                counts[o] = 0;
-                if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = 0.0;
-                if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = 0;
-                continue;
-            }
-            int idx[3];
-            src.get(p, t, n, T, idx);
-            double x[3][3], y[3][3], Rt[12];
-            load3(a, b, Nmax, idx, x, y);
-            fit3(x, y, Rt);
-            int hits = 0;
-            for (int i = 0; i < n; ++i) hits += residual_at(Rt, a, b, Nmax, i) < threshold ? 1 : 0;
-            counts[o] = hits;
-            if (hyp) for (int k = 0; k < 12; ++k) hyp[o * 12 + k] = Rt[k];
-            if (drawn) for (int k = 0; k < 3; ++k) drawn[o * 3 + k] = idx[k];
-        }
-    });
-}
-
-template <int W>
-void tree_sum(double (*part)[10])
-{
-    for (int s = REFIT_LANES / 2; s > 0; s >>= 1)
-        for (int l = 0; l < s; ++l)
-            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
-}
-
-template <class Src>
-void select_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, int max_trials,
-                 double threshold, const Src& src, const int32_t* counts, const double* gt, double* Rt_out,
-                 uint8_t* inlier_mask, int32_t* inliers, int32_t* trialcount, uint8_t* valid, int32_t* chosen,
-                 double* delta_t, double* delta_deg)
-{
-    std::vector<double> part_store((size_t)REFIT_LANES * 10);
-    double (*part)[10] = reinterpret_cast<double (*)[10]>(part_store.data());
-    std::vector<uint8_t> in((size_t)NMAX_LARGE);
-    for (int p = 0; p < P; ++p) {
-        const int n = clamp_count(count, p, Nmax);
-        const float* a = x1 + (long long)p * 3 * Nmax;
-        const float* b = x2 + (long long)p * 3 * Nmax;
-        uint8_t* mask = inlier_mask + (long long)p * Nmax;
-        std::memset(mask, 0, (size_t)Nmax);
-        int pick = 0, tc = 0, ninl = 0;
-        double Rt[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        if (n > 3) replay(counts + (long long)p * T, n, max_trials, &pick, &tc);
-        if (n >= 3) {
-            int idx[3] = {0, 1, 2};
-            if (n > 3) src.get(p, pick, n, T, idx);
-            double x[3][3], y[3][3], R0[12];
-            load3(a, b, Nmax, idx, x, y);
-            fit3(x, y, R0);
-            for (int i = 0; i < n; ++i) {
-                in[i] = (n == 3 || residual_at(R0, a, b, Nmax, i) < threshold) ? 1 : 0;
-                ninl += in[i];
-            }
-        }
-        const bool ok = ninl >= 3;
-        if (ok) {
-            double cen[6];
-            for (int l = 0; l < REFIT_LANES; ++l) {
-                for (int k = 0; k < 10; ++k) part[l][k] = 0.0;
-                for (int i = l; i < n; i += REFIT_LANES)
-                    if (in[i])
-                        for (int c = 0; c < 3; ++c) {
-                            part[l][c] += (double)a[(long long)c * Nmax + i];
-                            part[l][3 + c] += (double)b[(long long)c * Nmax + i];
-                        }
-            }
-            tree_sum<6>(part);
-            for (int k = 0; k < 6; ++k) cen[k] = part[0][k] / (double)ninl;
-            for (int l = 0; l < REFIT_LANES; ++l) {
-                double B[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                for (int i = l; i < n; i += REFIT_LANES)
-                    if (in[i]) {
-                        double xc[3], yc[3];
-                        for (int c = 0; c < 3; ++c) {
-                            xc[c] = (double)a[(long long)c * Nmax + i] - cen[c];
-                            yc[c] = (double)b[(long long)c * Nmax + i] - cen[3 + c];
-                        }
-                        accumulate(B, xc, yc);
-                    }
-                for (int k = 0; k < 10; ++k) part[l][k] = B[k];
-            }
-            tree_sum<10>(part);
-            double Bs[10];
-            for (int k = 0; k < 10; ++k) Bs[k] = part[0][k];
-            transform_from(Bs, cen, cen + 3, Rt);
-            for (int i = 0; i < n; ++i) mask[i] = in[i];
-        }
-        for (int k = 0; k < 12; ++k) Rt_out[(long long)p * 12 + k] = Rt[k];
-        inliers[p] = ok ? ninl : 0;
-        trialcount[p] = tc;
-        valid[p] = ok ? 1 : 0;
-        if (chosen) chosen[p] = pick;
-        if (gt) {
-            double dt = 3.0, dd = 6.0;
-            if (ok) compare(gt + (long long)p * 12, Rt, &dt, &dd);
-            delta_t[p] = dt;
-            delta_deg[p] = dd;
-        }
-    }
 }
 
 struct Range {
@@ -321,50 +183,9 @@ extern "C" int usip_match_union_i32_cpu(const int32_t* nn12, const int32_t* nn21
     return USIP_OK;
 }
 
-extern "C" int usip_ransac_trials_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax,
-                                                int T, double threshold, uint64_t seed, const int64_t* pair_ids,
-                                                const int32_t* triplets, int32_t* counts, double* hypotheses,
-                                                int32_t* triplets_out, int num_threads)
-{
-    if (!shape_ok(P, Nmax, T)) return USIP_EINVAL;
-    if (P == 0) return USIP_OK;
-    if (!x1 || !x2 || !count || !counts) return USIP_EINVAL;
-    if (triplets) {
-        const ExplicitTriplets src{triplets};
-        trials_host(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, num_threads);
-    } else {
-        const PhiloxTriplets src{seed, pair_ids};
-        trials_host(x1, x2, count, P, Nmax, T, threshold, src, counts, hypotheses, triplets_out, num_threads);
-    }
-    return USIP_OK;
-}
-
-extern "C" int usip_ransac_select_large_f32_cpu(const float* x1, const float* x2, const int32_t* count, int P, int Nmax,
-                                                int T, int max_trials, double threshold, uint64_t seed,
-                                                const int64_t* pair_ids, const int32_t* triplets, const int32_t* counts,
-                                                const double* gt, double* Rt, uint8_t* inlier_mask, int32_t* inliers,
-                                                int32_t* trialcount, uint8_t* valid, int32_t* chosen, double* delta_t,
-                                                double* delta_deg)
-{
-    if (!shape_ok(P, Nmax, T) || max_trials < 0 || max_trials > T - 1) return USIP_EINVAL;
-    if (P == 0) return USIP_OK;
-    if (!x1 || !x2 || !count || !counts || !Rt || !inlier_mask || !inliers || !trialcount || !valid) return USIP_EINVAL;
-    if (gt && (!delta_t || !delta_deg)) return USIP_EINVAL;
-    if (triplets) {
-        const ExplicitTriplets src{triplets};
-        select_host(x1, x2, count, P, Nmax, T, max_trials, threshold, src, counts, gt, Rt, inlier_mask, inliers,
-                    trialcount, valid, chosen, delta_t, delta_deg);
-    } else {
-        const PhiloxTriplets src{seed, pair_ids};
-        select_host(x1, x2, count, P, Nmax, T, max_trials, threshold, src, counts, gt, Rt, inlier_mask, inliers,
-                    trialcount, valid, chosen, delta_t, delta_deg);
-    }
-    return USIP_OK;
-}
-
 extern "C" int usip_information_f32_cpu(const float* x, const uint8_t* mask, int P, int Nmax, double* info)
 {
-    if (P < 0 || P > 65535 || Nmax < 1 || Nmax > NMAX_LARGE) return USIP_EINVAL;
+    if (P < 0 || P > 65535 || Nmax < 1 || Nmax > NMAX) return USIP_EINVAL;
     if (P == 0) return USIP_OK;
     if (!x || !mask || !info) return USIP_EINVAL;
     std::vector<double> part_store((size_t)REFIT_LANES * 10);

@@ -1,7 +1,7 @@
 // usip_amd/csrc/fragments_math.h -- the arithmetic of indoor fragment registration, shared by the kernels of
 // csrc/fragments.hip and the host twin of csrc/fragments_cpu.cpp.  The convention is f-6's: float32 inputs, float64
-// arithmetic, sums in a fixed order.  The rigid fit, the residual, the draws, the stopping rule and the refit are
-// csrc/registration_math.h's own; this header adds what register2Fragments.m does around them.
+// arithmetic, sums in a fixed order.  RANSAC (the rigid fit, the residual, the draws, the stopping rule and the refit), the
+// clamps and the tree sum are csrc/registration_math.h's own; this header adds what register2Fragments.m does around them.
 //
 // Reference semantics (evaluation/matlab/eval_indoor/3dmatch/register2Fragments.m):
 //   pdist2(b, a, 'euclidean', 'smallest', k)   per row of a the k nearest rows of b, ascending, the lower index on ties
@@ -15,10 +15,9 @@
 
 namespace usip_frag {
 
-constexpr int NMAX_LARGE = 10240;       // correspondences per pair: 2 k M at k = 5, M = 1024
-constexpr int CHUNK = 1024;             // correspondences staged in LDS at a time (24 KB: four workgroups per CU)
 constexpr int KMAX = 8;                 // neighbours per descriptor
-constexpr int UNION_MAX = 10240;        // k (Ma + Mp)
+constexpr int UNION_MAX = 10240;        // k (Ma + Mp): every row of the union is a correspondence of the pair's RANSAC
+static_assert(UNION_MAX <= usip_reg::NMAX, "the union of a pair must fit the RANSAC entry points");
 constexpr int OTILE = 256;              // database points per LDS tile of the overlap walk
 constexpr int INFO_W = 10;              // partial sums per lane of the information matrix (9 used)
 

@@ -1,7 +1,7 @@
 // usip_amd/csrc/registration_cpu.cpp -- host twin of csrc/registration.hip: the same draws and arithmetic
 // (csrc/registration_math.h) on host pointers.  The selection runs ransac.m's loop as written (usip_reg::replay); the
-// refit adds in the device's order (REFIT_LANES strided partial sums, then the binary tree).  Never reached from the
-// device entry points.
+// refit adds in the device's order (REFIT_LANES strided partial sums, then the binary tree).  Also the twin of the indoor
+// fragment evaluation's RANSAC: Nmax <= 10240.  Never reached from the device entry points.
 #include <cmath>
 #include <cstring>
 #include <thread>
@@ -12,12 +12,6 @@
 using namespace usip_reg;
 
 namespace {
-
-int clamp_count(const int32_t* count, int p, int nmax)
-{
-    const int n = count[p];
-    return n < 0 ? 0 : (n > nmax ? nmax : n);
-}
 
 bool shape_ok(int P, int Nmax, int T) { return P >= 0 && P <= 65535 && Nmax >= 1 && Nmax <= NMAX && T >= 1; }
 
@@ -82,14 +76,6 @@ void trials_host(const float* x1, const float* x2, const int32_t* count, int P, 
     for (auto& th : pool) th.join();
 }
 
-template <int W>
-void tree_sum(double (*part)[10])
-{
-    for (int s = REFIT_LANES / 2; s > 0; s >>= 1)
-        for (int l = 0; l < s; ++l)
-            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
-}
-
 template <class Src>
 void select_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, int max_trials,
                  double threshold, const Src& src, const int32_t* counts, const double* gt, double* Rt_out,
@@ -98,7 +84,7 @@ void select_host(const float* x1, const float* x2, const int32_t* count, int P, 
 {
     std::vector<double> part_store((size_t)REFIT_LANES * 10);
     double (*part)[10] = reinterpret_cast<double (*)[10]>(part_store.data());
-    std::vector<uint8_t> in((size_t)NMAX);
+    std::vector<uint8_t> in((size_t)Nmax);
     for (int p = 0; p < P; ++p) {
         const int n = clamp_count(count, p, Nmax);
         const float* a = x1 + (long long)p * 3 * Nmax;

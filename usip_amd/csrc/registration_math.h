@@ -1,6 +1,8 @@
 // usip_amd/csrc/registration_math.h -- the arithmetic of RANSAC registration and keypoint repeatability,
 // shared by the kernels of csrc/registration.hip and the host twin of csrc/registration_cpu.cpp: both sides run the same
 // float64 operations in the same order on float32 inputs (the reference reads its float32 files into MATLAB doubles).
+// The indoor evaluation (csrc/fragments.hip, csrc/fragments_cpu.cpp) runs the same RANSAC entry points on up
+// to NMAX correspondences and takes the clamps and the tree sum from here.
 //
 // Reference semantics (evaluation/matlab/eval_outdoor/external, kitti/evaluate_kitti.m, eval_repeatability/eval_rep.m):
 //   estimateRigidTransform  x = R y + t: centre both sets, B = sum A_i' A_i with A_i = [0, (y-x)'; (x-y), [y+x]x], the unit
@@ -19,9 +21,53 @@
 namespace usip_reg {
 
 constexpr uint32_t TAG_RANSAC = 9;      // continues the stream tags of csrc/pairs_rng.h
-constexpr int NMAX = 1024;              // correspondences per pair
+constexpr int NMAX = 10240;             // correspondences per pair: 2 k M at k = 5, M = 1024 (register2Fragments.m's union)
+constexpr int CHUNK = 1024;             // correspondences staged in LDS at a time (24 KB: four workgroups per CU)
 constexpr int JACOBI_SWEEPS = 8;        // 4x4, float64: the off-diagonal mass is below 1e-300 of the norm by then
 constexpr int REFIT_LANES = 256;        // the refit's sums: lane l adds rows l, l + 256, ... in order, then a binary tree
+
+// A count outside 0 .. nmax behaves as the nearer end; an index outside 0 .. n - 1 likewise.
+USIP_HD int clamp_count(const int32_t* count, int p, int nmax)
+{
+    const int n = count[p];
+    return n < 0 ? 0 : (n > nmax ? nmax : n);
+}
+USIP_HD int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+// part[l][0..W) summed over l into part[0]: one binary tree, walked by a workgroup of REFIT_LANES lanes on the device and
+// by a loop on the host, so both add in the same order.
+#if defined(__HIP__)
+template <int W>
+__device__ __forceinline__ void tree_sum(double (*part)[10], int l)
+{
+    for (int s = REFIT_LANES / 2; s > 0; s >>= 1) {
+        __syncthreads();
+        if (l < s)
+#pragma unroll
+            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
+    }
+    __syncthreads();
+}
+#endif
+template <int W>
+inline void tree_sum(double (*part)[10])
+{
+    for (int s = REFIT_LANES / 2; s > 0; s >>= 1)
+        for (int l = 0; l < s; ++l)
+            for (int k = 0; k < W; ++k) part[l][k] += part[l + s][k];
+}
+
+// What the selection writes, per pair.
+struct SelectOut {
+    double* Rt;               // [P][3][4]
+    uint8_t* inlier_mask;     // [P][Nmax]
+    int32_t* inliers;         // [P]
+    int32_t* trialcount;      // [P]
+    uint8_t* valid;           // [P]
+    int32_t* chosen;          // [P], optional
+    double* delta_t;          // [P], with gt
+    double* delta_deg;
+};
 
 // The ten entries of the symmetric 4x4 B: 00 01 02 03 11 12 13 22 23 33.  x, y: one centred correspondence.
 USIP_HD void accumulate(double B[10], const double x[3], const double y[3])

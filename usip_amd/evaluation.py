@@ -70,17 +70,19 @@ def _p(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
 
 
-def _pairs_np(x1, x2, count):
+def _pairs_np(x1, x2, count, limit):
     x1, x2 = _np(x1, np.float32, "x1"), _np(x2, np.float32, "x2")
     if x1.ndim != 3 or x1.shape[1] != 3 or x2.shape != x1.shape:
         raise ValueError("expected x1, x2 [P,3,Nmax]")
+    if not 1 <= x1.shape[2] <= limit:                              # the device entries' rule and error (ops._need_pairs)
+        raise RuntimeError("registration: Nmax must be in 1..%d (got %d)" % (limit, x1.shape[2]))
     return x1, x2, _np(count, np.int32, "count", (x1.shape[0],))
 
 
 def ransac_trials_cpu(x1, x2, count, T: int, threshold: float = 1.0, seed: int = 0, pair_ids=None, triplets=None,
-                      num_threads: int = 1):
+                      num_threads: int = 1, _nmax: int = ops.RANSAC_NMAX):
     """-> (counts i32 [P,T], hypotheses f64 [P,T,3,4], triplets i32 [P,T,3]) on the host."""
-    x1, x2, count = _pairs_np(x1, x2, count)
+    x1, x2, count = _pairs_np(x1, x2, count, _nmax)
     P, _, Nmax = x1.shape
     T = int(T)
     ids = _np(pair_ids, np.int64, "pair_ids", (P,)) if pair_ids is not None else None
@@ -95,8 +97,8 @@ def ransac_trials_cpu(x1, x2, count, T: int, threshold: float = 1.0, seed: int =
 
 
 def ransac_select_cpu(x1, x2, count, counts, max_trials: int, threshold: float = 1.0, seed: int = 0, pair_ids=None,
-                      triplets=None, gt=None) -> Dict[str, np.ndarray]:
-    x1, x2, count = _pairs_np(x1, x2, count)
+                      triplets=None, gt=None, _nmax: int = ops.RANSAC_NMAX) -> Dict[str, np.ndarray]:
+    x1, x2, count = _pairs_np(x1, x2, count, _nmax)
     P, _, Nmax = x1.shape
     counts = _np(counts, np.int32, "counts")
     T = counts.shape[1]

@@ -8,7 +8,8 @@ mrEvaluateRegistrationMy.m).
   fragment_registration    ransacfitRt on up to 10240 correspondences (threshold 0.2, ransac.m's default 30000 trials)
   information_matrix       the 6 x 6 sum of A'A over the inliers' fragment-1 keypoints
   overlap_ratio            ratioAligned: the share of each full fragment with a point of the other closer than 0.2 m
-  *_cpu                    the same on numpy arrays over the library's host twins (csrc/fragments_cpu.cpp)
+  *_cpu                    the same on numpy arrays over the library's host twins (csrc/fragments_cpu.cpp; RANSAC:
+                           evaluation.ransac_*_cpu with the limit at 10240)
   transformation_error     mrComputeTransformationError with the file's own dcm2quat
   evaluate_log             mrEvaluateRegistrationMy: recall, precision, mean inlier number and ratio (host numpy)
   read_* / write_*         gt.log (mrLoadLog), gt.info (mrLoadInfo), <scene>.log (writeLog.m / mrLoadLogMy) and the
@@ -25,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, inference, ops
-from .evaluation import _np, _p, _pairs_np, select_keypoints_device
+from .evaluation import _np, _p, ransac_select_cpu, ransac_trials_cpu, select_keypoints_device
 
 FragmentResult = namedtuple("FragmentResult",
                             "Rt inliers inlier_mask trialcount valid delta_t delta_deg chosen counts inlier_ratio")
@@ -147,36 +148,15 @@ def match_union_cpu(nn12, nn21, count1, count2):
 
 def ransac_trials_large_cpu(x1, x2, count, T: int, threshold: float = INLIER_THRESHOLD, seed: int = 0, pair_ids=None,
                             triplets=None, num_threads: int = 1):
-    """-> (counts i32 [P,T], hypotheses f64 [P,T,3,4], triplets i32 [P,T,3]) on the host."""
-    x1, x2, count = _pairs_np(x1, x2, count)
-    P, _, Nmax = x1.shape
-    T = int(T)
-    ids = _np(pair_ids, np.int64, "pair_ids", (P,)) if pair_ids is not None else None
-    tri = _np(triplets, np.int32, "triplets", (P, T, 3)) if triplets is not None else None
-    counts = np.zeros((P, T), np.int32)
-    hyp = np.zeros((P, T, 3, 4), np.float64)
-    drawn = np.zeros((P, T, 3), np.int32)
-    _lib.check(_lib.lib().usip_ransac_trials_large_f32_cpu(
-        _p(x1), _p(x2), _p(count), P, Nmax, T, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids), _p(tri),
-        _p(counts), _p(hyp), _p(drawn), int(num_threads)), "usip_ransac_trials_large_f32_cpu")
-    return counts, hyp, drawn
+    """evaluation.ransac_trials_cpu with Nmax <= 10240."""
+    return ransac_trials_cpu(x1, x2, count, T, threshold, seed, pair_ids, triplets, num_threads, _nmax=ops.RANSAC_NMAX_LARGE)
 
 
 def ransac_select_large_cpu(x1, x2, count, counts, max_trials: int, threshold: float = INLIER_THRESHOLD, seed: int = 0,
                             pair_ids=None, triplets=None) -> Dict[str, np.ndarray]:
-    x1, x2, count = _pairs_np(x1, x2, count)
-    P, _, Nmax = x1.shape
-    counts = _np(counts, np.int32, "counts")
-    T = counts.shape[1]
-    ids = _np(pair_ids, np.int64, "pair_ids", (P,)) if pair_ids is not None else None
-    tri = _np(triplets, np.int32, "triplets", (P, T, 3)) if triplets is not None else None
-    o = {"Rt": np.zeros((P, 3, 4)), "inlier_mask": np.zeros((P, Nmax), np.uint8), "inliers": np.zeros(P, np.int32),
-         "trialcount": np.zeros(P, np.int32), "valid": np.zeros(P, np.uint8), "chosen": np.zeros(P, np.int32)}
-    _lib.check(_lib.lib().usip_ransac_select_large_f32_cpu(
-        _p(x1), _p(x2), _p(count), P, Nmax, T, int(max_trials), float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids),
-        _p(tri), _p(counts), None, _p(o["Rt"]), _p(o["inlier_mask"]), _p(o["inliers"]), _p(o["trialcount"]),
-        _p(o["valid"]), _p(o["chosen"]), None, None), "usip_ransac_select_large_f32_cpu")
-    return o
+    """evaluation.ransac_select_cpu with Nmax <= 10240."""
+    return ransac_select_cpu(x1, x2, count, counts, max_trials, threshold, seed, pair_ids, triplets,
+                             _nmax=ops.RANSAC_NMAX_LARGE)
 
 
 def fragment_registration_cpu(x1, x2, count, threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,

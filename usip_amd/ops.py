@@ -5,6 +5,7 @@ memory + stream plumbing only), enqueues the HIP kernels on torch's CURRENT stre
 returns without synchronising.  Host tensors raise RuntimeError: there is no CPU path here.
 """
 import ctypes
+import functools
 import os
 from typing import Optional
 
@@ -1547,14 +1548,14 @@ def _opt_ptr(t):
     return _ptr(t) if t is not None else None
 
 
-def _need_pairs(x1, x2, count):
+def _need_pairs(x1, x2, count, limit):
     _need(x1, "x1", torch.float32)
     _need(x2, "x2", torch.float32)
     _need(count, "count", torch.int32)
     if x1.dim() != 3 or x1.shape[1] != 3 or x2.shape != x1.shape or count.shape != (x1.shape[0],):
         raise RuntimeError("registration: expected x1, x2 f32 [P,3,Nmax] and count i32 [P]")
-    if not 1 <= x1.shape[2] <= 1024:
-        raise RuntimeError("registration: Nmax must be in 1..1024 (got %d)" % x1.shape[2])
+    if not 1 <= x1.shape[2] <= limit:
+        raise RuntimeError("registration: Nmax must be in 1..%d (got %d)" % (limit, x1.shape[2]))
     return x1.shape[0], x1.shape[2]
 
 
@@ -1566,11 +1567,15 @@ def _need_on(t, name, dtype, shape, device):
         raise RuntimeError("registration: %s must be %s %s on %s" % (name, dtype, tuple(shape), device))
 
 
+RANSAC_NMAX, RANSAC_NMAX_LARGE = 1024, 10240      # the outdoor evaluation's keypoints per frame; the library's limit
+
+
 def ransac_trials(x1, x2, count, T: int, threshold: float, seed: int = 0, pair_ids=None, triplets=None,
-                  want_hypotheses: bool = False, want_triplets: bool = False):
+                  want_hypotheses: bool = False, want_triplets: bool = False, _nmax: int = RANSAC_NMAX):
     """f-6: inlier counts of T rigid-fit trials per pair -> (counts i32 [P,T], hypotheses f64 [P,T,3,4] or None, drawn
-    triplets i32 [P,T,3] or None).  triplets i32 [P,T,3]: explicit draws; otherwise Philox draws of (seed, pair_ids)."""
-    P, Nmax = _need_pairs(x1, x2, count)
+    triplets i32 [P,T,3] or None).  triplets i32 [P,T,3]: explicit draws; otherwise Philox draws of (seed, pair_ids).
+    Nmax <= 1024; ransac_trials_large (f-9) is the same call with Nmax <= 10240."""
+    P, Nmax = _need_pairs(x1, x2, count, _nmax)
     T = int(T)
     dev = x1.device
     _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
@@ -1591,11 +1596,11 @@ def ransac_trials(x1, x2, count, T: int, threshold: float, seed: int = 0, pair_i
 
 
 def ransac_select(x1, x2, count, counts, max_trials: int, threshold: float, seed: int = 0, pair_ids=None, triplets=None,
-                  gt=None):
+                  gt=None, _nmax: int = RANSAC_NMAX):
     """f-6: ransac.m's stopping rule replayed over counts i32 [P,T], the chosen hypothesis' inliers and the refit ->
     dict(Rt f64 [P,3,4], inlier_mask u8 [P,Nmax], inliers, trialcount, chosen i32 [P], valid u8 [P], delta_t, delta_deg
-    f64 [P] or None without gt)."""
-    P, Nmax = _need_pairs(x1, x2, count)
+    f64 [P] or None without gt).  Nmax <= 1024; ransac_select_large (f-9) is the same call with Nmax <= 10240."""
+    P, Nmax = _need_pairs(x1, x2, count, _nmax)
     dev = x1.device
     _need(counts, "counts", torch.int32)
     if counts.dim() != 2 or counts.shape[0] != P or counts.device != dev:
@@ -1812,71 +1817,8 @@ def match_union(nn12, nn21, a_count, p_count):
     return pairs, count
 
 
-def _need_pairs_large(x1, x2, count):
-    _need(x1, "x1", torch.float32)
-    _need(x2, "x2", torch.float32)
-    _need(count, "count", torch.int32)
-    if x1.dim() != 3 or x1.shape[1] != 3 or x2.shape != x1.shape or count.shape != (x1.shape[0],):
-        raise RuntimeError("fragments: expected x1, x2 f32 [P,3,Nmax] and count i32 [P]")
-    if not 1 <= x1.shape[2] <= 10240:
-        raise RuntimeError("fragments: Nmax must be in 1..10240 (got %d)" % x1.shape[2])
-    return x1.shape[0], x1.shape[2]
-
-
-def ransac_trials_large(x1, x2, count, T: int, threshold: float, seed: int = 0, pair_ids=None, triplets=None,
-                        want_hypotheses: bool = False, want_triplets: bool = False):
-    """f-9: ransac_trials with Nmax <= 10240 (the correspondences go through LDS in chunks)."""
-    P, Nmax = _need_pairs_large(x1, x2, count)
-    T = int(T)
-    dev = x1.device
-    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
-    _need_on(triplets, "triplets", torch.int32, (P, T, 3), dev)
-    counts = torch.empty((P, T), dtype=torch.int32, device=dev)
-    hyp = torch.empty((P, T, 3, 4), dtype=torch.float64, device=dev) if want_hypotheses else None
-    drawn = torch.empty((P, T, 3), dtype=torch.int32, device=dev) if want_triplets and triplets is None else triplets
-    with torch.cuda.device(dev), prof.kernel("ransac_trials_large", 24.0 * P * Nmax + 4.0 * P * T, 30.0 * P * T * Nmax):
-        if triplets is None:
-            _lib.check(_lib.lib().usip_ransac_trials_large_f32(
-                _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, float(threshold), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                _opt_ptr(pair_ids), _ptr(counts), _opt_ptr(hyp), _opt_ptr(drawn), _stream(x1)),
-                "usip_ransac_trials_large_f32")
-        else:
-            _lib.check(_lib.lib().usip_ransac_trials_large_explicit_f32(
-                _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, float(threshold), _ptr(triplets), _ptr(counts),
-                _opt_ptr(hyp), _stream(x1)), "usip_ransac_trials_large_explicit_f32")
-    return counts, hyp, (drawn if want_triplets else None)
-
-
-def ransac_select_large(x1, x2, count, counts, max_trials: int, threshold: float, seed: int = 0, pair_ids=None,
-                        triplets=None, gt=None):
-    """f-9: ransac_select with Nmax <= 10240 -> the same dict."""
-    P, Nmax = _need_pairs_large(x1, x2, count)
-    dev = x1.device
-    _need(counts, "counts", torch.int32)
-    if counts.dim() != 2 or counts.shape[0] != P or counts.device != dev:
-        raise RuntimeError("fragments: counts must be i32 [P,T] on %s" % dev)
-    T = counts.shape[1]
-    if not 0 <= int(max_trials) <= T - 1:
-        raise RuntimeError("fragments: max_trials must be in 0..T-1 (T = %d, got %d)" % (T, max_trials))
-    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
-    _need_on(triplets, "triplets", torch.int32, (P, T, 3), dev)
-    _need_on(gt, "gt", torch.float64, (P, 3, 4), dev)
-    out = {"Rt": torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
-           "inlier_mask": torch.empty((P, Nmax), dtype=torch.uint8, device=dev),
-           "inliers": torch.empty((P,), dtype=torch.int32, device=dev),
-           "trialcount": torch.empty((P,), dtype=torch.int32, device=dev),
-           "valid": torch.empty((P,), dtype=torch.uint8, device=dev),
-           "chosen": torch.empty((P,), dtype=torch.int32, device=dev),
-           "delta_t": torch.empty((P,), dtype=torch.float64, device=dev) if gt is not None else None,
-           "delta_deg": torch.empty((P,), dtype=torch.float64, device=dev) if gt is not None else None}
-    with torch.cuda.device(dev), prof.kernel("ransac_select_large", 4.0 * P * T + 24.0 * P * Nmax, 60.0 * P * Nmax):
-        _lib.check(_lib.lib().usip_ransac_select_large_f32(
-            _ptr(x1), _ptr(x2), _ptr(count), P, Nmax, T, int(max_trials), float(threshold),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, _opt_ptr(pair_ids), _opt_ptr(triplets), _ptr(counts), _opt_ptr(gt),
-            _ptr(out["Rt"]), _ptr(out["inlier_mask"]), _ptr(out["inliers"]), _ptr(out["trialcount"]), _ptr(out["valid"]),
-            _ptr(out["chosen"]), _opt_ptr(out["delta_t"]), _opt_ptr(out["delta_deg"]), _stream(x1)),
-            "usip_ransac_select_large_f32")
-    return out
+ransac_trials_large = functools.partial(ransac_trials, _nmax=RANSAC_NMAX_LARGE)      # f-9: up to 10240 correspondences
+ransac_select_large = functools.partial(ransac_select, _nmax=RANSAC_NMAX_LARGE)
 
 
 def information(x, mask):
