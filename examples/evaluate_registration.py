@@ -6,11 +6,13 @@ as ONE JSON line.
     python examples/evaluate_registration.py --make-synthetic /tmp/eval_data
     python examples/evaluate_registration.py --data /tmp/eval_data --detector det.pth --descriptor desc.pth \\
         --write-descriptors /tmp/descriptors
+    python examples/evaluate_registration.py --data /tmp/eval_data --method iss      # or random: the baselines' numbers
 
 Data layout: <dir>/<id>.bin float32 rows [x y z nx ny nz curvature] and <dir>/pairs.txt with one pair per line,
 `anc_id pos_id tx ty tz qw qx qy qz`: the pose that moves the positive scan into the anchor's frame.  Without checkpoints
 the weights are the repository's seeded ones (usip_amd.synth.fill_parameters): the numbers then say nothing about USIP,
-only that the pipeline runs."""
+only that the pipeline runs.  --method iss | random scores the reference's baseline detectors (evaluation/save_keypoints.py)
+instead of the learned one: --top keypoints per frame from usip_amd.baselines, described by the same descriptor."""
 import argparse
 import json
 import os
@@ -20,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from usip_amd import evaluation, inference, synth                                  # noqa: E402
+from usip_amd import baselines, evaluation, inference, synth                       # noqa: E402
 from usip_amd.networks import DescriptorLiteOld, DetectorOptions, build_detector   # noqa: E402
 
 CS = 4
@@ -94,12 +96,15 @@ def seeded(module):
     return module
 
 
-def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, descriptor_ckpt=None, device="cuda:0"):
+def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, descriptor_ckpt=None, device="cuda:0",
+                    method="tsf"):
     dev = torch.device(device)
     opt = DetectorOptions(surface_normal_len=CS, node_knn_k_1=16)
-    detector = build_detector(model, opt).to(dev)
+    detector = build_detector(model, opt).to(dev) if method == "tsf" else None     # the baselines need none
     descriptor = DescriptorLiteOld(opt).to(dev)
-    if detector_ckpt:
+    if detector is None:
+        pass
+    elif detector_ckpt:
         inference.load_detector_state(detector, torch.load(detector_ckpt, map_location=dev))
     else:
         seeded(detector)
@@ -111,13 +116,20 @@ def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, des
                                             max_trials=max_trials, seed=seed)
 
 
-def add_scans(evaluator, scans, nodes, seed):
+def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None):
+    """method 'iss' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss: IssDetector's parameters)."""
     dev = evaluator.device
+    detect = baselines.IssDetector(num=evaluator.top, seed=seed, **(iss or {})) if method == "iss" else None
     for fid, rows in scans:
         t = torch.from_numpy(np.ascontiguousarray(rows.T)).to(dev)
         pc, sn = t[:3].unsqueeze(0).contiguous(), t[3:].unsqueeze(0).contiguous()
-        first = torch.tensor([(seed + 7919 * int(fid)) % pc.shape[2]], dtype=torch.int32, device=dev)
-        evaluator.add_frame(fid, pc, sn, inference.sample_nodes(pc, nodes, first))
+        if method == "tsf":
+            first = torch.tensor([(seed + 7919 * int(fid)) % pc.shape[2]], dtype=torch.int32, device=dev)
+            evaluator.add_frame(fid, pc, sn, inference.sample_nodes(pc, nodes, first))
+        else:
+            kp, count = detect(pc, None, [int(fid)]) if method == "iss" else \
+                baselines.random_keypoints(pc, None, evaluator.top, seed, [int(fid)])
+            evaluator.add_frame_keypoints(fid, pc, sn, kp, count)
 
 
 def main():
@@ -135,6 +147,13 @@ def main():
     ap.add_argument("--max-trials", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there")
+    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "random"],
+                    help="tsf: the learned detector; iss, random: the baselines, --top keypoints per frame")
+    ap.add_argument("--salient-radius", type=float, default=2.0)
+    ap.add_argument("--non-max-radius", type=float, default=2.0)
+    ap.add_argument("--gamma-21", type=float, default=0.975)
+    ap.add_argument("--gamma-32", type=float, default=0.975)
+    ap.add_argument("--min-neighbors", type=int, default=5)
     args = ap.parse_args()
     if args.make_synthetic:
         scans, pairs = make_synthetic(np.random.default_rng(args.seed), args.frames, args.points)
@@ -144,11 +163,14 @@ def main():
         ap.error("give --data DIR or --make-synthetic DIR")
     scans, pairs = read_dataset(args.data)
     evaluator = build_evaluator(args.model, args.detector, args.top, args.nms_radius, args.max_trials,
-                                args.seed, args.descriptor)
-    add_scans(evaluator, scans, args.nodes, args.seed)
+                                args.seed, args.descriptor, method=args.method)
+    add_scans(evaluator, scans, args.nodes, args.seed, args.method,
+              dict(salient_radius=args.salient_radius, non_max_radius=args.non_max_radius, gamma_21=args.gamma_21,
+                   gamma_32=args.gamma_32, min_neighbors=args.min_neighbors))
     summary = evaluator.evaluate(pairs)
     summary.pop("per_pair")
-    summary["seeded_weights"] = not (args.detector and args.descriptor)
+    summary["seeded_weights"] = not ((args.detector or args.method != "tsf") and args.descriptor)
+    summary["method"] = args.method
     if args.write_descriptors:
         os.makedirs(args.write_descriptors, exist_ok=True)
         for fid, _ in scans:

@@ -3,7 +3,11 @@
 (evaluation/save_keypoints.py:336-393: per frame a float32 M x 3 row-major .bin of the sigma-ordered NMS
 survivors, at most --top of them).
 
-    python examples/extract_keypoints.py --checkpoint /tmp/detector.pth --out /tmp/keypoints"""
+    python examples/extract_keypoints.py --checkpoint /tmp/detector.pth --out /tmp/keypoints
+    python examples/extract_keypoints.py --method iss --out /tmp/keypoints_iss      # or random: the reference's baselines
+
+--method iss | random (save_keypoints.py's method switch) needs no checkpoint: exactly --top keypoints per frame from
+usip_amd.baselines, ISS keypoints first and random cloud points behind them where ISS finds fewer."""
 import argparse
 import os
 import sys
@@ -12,14 +16,21 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from usip_amd import inference, synth                        # noqa: E402
+from usip_amd import baselines, inference, synth             # noqa: E402
 from usip_amd.networks import DetectorOptions, build_detector  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="ball", choices=["ball", "som"])
-    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--checkpoint", help="detector checkpoint; required for --method tsf")
+    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "random"])
+    ap.add_argument("--salient-radius", type=float, default=2.0)
+    ap.add_argument("--non-max-radius", type=float, default=2.0)
+    ap.add_argument("--gamma-21", type=float, default=0.975)
+    ap.add_argument("--gamma-32", type=float, default=0.975)
+    ap.add_argument("--min-neighbors", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=0, help="of the baselines' random picks")
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--n", type=int, default=16384)
     ap.add_argument("--m", type=int, default=512)
@@ -27,20 +38,36 @@ def main():
     ap.add_argument("--top", type=int, default=128)
     ap.add_argument("--out", default="keypoints")
     args = ap.parse_args()
+    if args.method == "tsf" and not args.checkpoint:
+        ap.error("the following arguments are required: --checkpoint")
     dev = torch.device("cuda", 0)
-    opt = DetectorOptions(surface_normal_len=4, node_knn_k_1=16)
-    detector = build_detector(args.model, opt).to(dev)
-    inference.load_detector_state(detector, torch.load(args.checkpoint, map_location=dev))   # 'module.' keys accepted
     rng = np.random.default_rng(7)
     clouds = np.stack([synth.make_cloud(rng, args.n, "slab") for _ in range(args.frames)])
     normals = np.stack([synth.make_normals(rng, args.n, 4) for _ in range(args.frames)])
     pc, sn = torch.from_numpy(clouds).to(dev), torch.from_numpy(normals).to(dev)
+    os.makedirs(args.out, exist_ok=True)
+    if args.method != "tsf":
+        if args.method == "iss":
+            detect = baselines.IssDetector(args.top, True, args.seed, args.salient_radius, args.non_max_radius,
+                                           args.gamma_21, args.gamma_32, args.min_neighbors)
+            kp, count = detect(pc, None, range(args.frames))
+            found = detect.last[0].sum(1).tolist()
+        else:
+            kp, count = baselines.random_keypoints(pc, None, args.top, args.seed, range(args.frames))
+            found = None
+        for i, n in enumerate(count.tolist()):
+            path = os.path.join(args.out, "%06d.bin" % i)
+            inference.write_keypoints_bin(path, kp[i, :, :n].t().cpu().numpy())
+            print("%s  %d keypoints  (%s)" % (path, n, "random" if found is None else "iss found %d" % found[i]))
+        return
+    opt = DetectorOptions(surface_normal_len=4, node_knn_k_1=16)
+    detector = build_detector(args.model, opt).to(dev)
+    inference.load_detector_state(detector, torch.load(args.checkpoint, map_location=dev))   # 'module.' keys accepted
     # SOM nodes by farthest-point sampling on the GPU (the reference: numpy in the loader, first index random)
     first = torch.from_numpy(rng.integers(0, args.n, args.frames).astype(np.int32)).to(dev)
     node = inference.sample_nodes(pc, args.m, first)
     keypoints, sigmas = inference.run_model(detector, pc, sn, node)
     frames = inference.select_keypoints(keypoints, sigmas, args.nms_radius, args.top)
-    os.makedirs(args.out, exist_ok=True)
     for i, kp in enumerate(frames):
         path = os.path.join(args.out, "%06d.bin" % i)
         inference.write_keypoints_bin(path, kp)

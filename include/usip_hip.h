@@ -931,6 +931,41 @@ int usip_overlap_ratio_f32_cpu(const float* rows, int row_len, const int64_t* of
                                const int32_t* perm2, int P, int Lmax, double radius, int prune, int32_t* hits,
                                double* ratio, int num_threads);
 
+/* ------------------------------------------------------------------ f-11  baseline keypoints: ISS (Intrinsic Shape Signatures)
+ * The hand-crafted detector the reference compares its learned one with (evaluation/save_keypoints.py:44-50, method = 'iss':
+ * PCLKeypoint.keypointIss(pc, salient_radius 2, non_max_radius 2, gamma_21 0.975, gamma_32 0.975, min_neighbors 5)).  The PCL
+ * binding is not part of the reference; the definition below is this project's own, written from PCL's ISSKeypoint3D
+ * (iss_3d.hpp) with border estimation off.  Float64 arithmetic on float32 inputs, never contracted; csrc/iss_math.h is the
+ * arithmetic.
+ *
+ * pc f32 [B][3][N]; count i32 [B] (NULL: N): the first count[b] points of frame b are live; 1 <= N <= 2^20, B <= 65535.
+ * j is a member of N_r(i) iff d2(i, j) = (dx*dx + dy*dy) + dz*dz < r * r (strict; r * r once, in float64); i is one itself.
+ *
+ * usip_iss_saliency_f32: neighbours i32 [B][N] = |N_rs(i)|; saliency f64 [B][N]: 0 when fewer than min_neighbors members,
+ * else from C = sum over N_rs(i) of (p_j - p_i)(p_j - p_i)' (not divided by the count), the six sums taken in ascending
+ * position of the frame's stable order along x; its eigenvalues e1 >= e2 >= e3 by 8 cyclic Jacobi sweeps in a fixed order;
+ * saliency = e3 when the three are finite, e3 >= 0, e2 / e1 < gamma_21 and e3 / e2 < gamma_32 (a NaN ratio fails), else 0.
+ * perm i32 [B][N]: per frame, in its first count[b] entries, the live points in that order (x ascending, ties towards the
+ * lower index) -- the kernel walks only the 256-point tiles of that order that can hold a member; the result is the all-pairs
+ * answer.  A perm that does not sort gives wrong values, never a read outside pc.  tiles_visited i32 [B][ceil(N / 256)],
+ * optional (NULL): the tiles each workgroup of 256 queries walked (0 for a workgroup without a live query).
+ *
+ * usip_iss_nms_f32: keypoint u8 [B][N] = 1 iff saliency[i] > 0, |N_rn(i)| >= min_neighbors and no member of N_rn(i) has a
+ * larger saliency (equal ones do not suppress each other).
+ * Slots beyond count[b] get saliency 0, neighbours 0, keypoint 0.  USIP_EINVAL: a shape outside the limits, min_neighbors < 1,
+ * a radius that is not positive and finite, a NULL among the required pointers. */
+int usip_iss_saliency_f32(const float* pc, const int32_t* count, const int32_t* perm, int B, int N, double salient_radius,
+                          double gamma_21, double gamma_32, int min_neighbors, double* saliency, int32_t* neighbours,
+                          int32_t* tiles_visited, void* stream);
+int usip_iss_nms_f32(const float* pc, const int32_t* count, const int32_t* perm, const double* saliency, int B, int N,
+                     double non_max_radius, int min_neighbors, uint8_t* keypoint, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; every query tests all live points of its
+ * frame, in the frame's own stable order along x (no perm); num_threads splits the queries. */
+int usip_iss_saliency_f32_cpu(const float* pc, const int32_t* count, int B, int N, double salient_radius, double gamma_21,
+                              double gamma_32, int min_neighbors, double* saliency, int32_t* neighbours, int num_threads);
+int usip_iss_nms_f32_cpu(const float* pc, const int32_t* count, const double* saliency, int B, int N, double non_max_radius,
+                         int min_neighbors, uint8_t* keypoint, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,12 @@ SIGNATURES = {
                                    ctypes.c_void_p], _int),
     "usip_overlap_ratio_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, ctypes.c_void_p,
                                     _i32p, _i32p, _int, _int, _dbl, _int, _i32p, ctypes.c_void_p, _int], _int),
+    # f-11 baseline keypoints: ISS saliency and non-maximum suppression (usip_amd/baselines.py)
+    "usip_iss_saliency_f32": ([_f32p, _i32p, _i32p, _int, _int, _dbl, _dbl, _dbl, _int, ctypes.c_void_p, _i32p, _i32p,
+                               _stream], _int),
+    "usip_iss_nms_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _stream], _int),
+    "usip_iss_saliency_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, _dbl, _dbl, _int, ctypes.c_void_p, _i32p, _int], _int),
+    "usip_iss_nms_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _int], _int),
 }
 
 

@@ -181,7 +181,8 @@ class RegistrationEvaluator:
     """Scores a detector + descriptor pair the way the reference's MATLAB does, without leaving the device.
 
     add_frame(id, pc, sn, node) runs detector -> NMS / top-k -> descriptor on one frame ([1,3,N], [1,Cs,N], [1,3,M]
-    device tensors) and caches its keypoints f32 [3,top], descriptors f32 [D,top] and count.  evaluate(pairs) with
+    device tensors) and caches its keypoints f32 [3,top], descriptors f32 [D,top] and count; add_frame_keypoints(id, pc,
+    sn, kp, count) takes a baseline detector's keypoints instead (the detector may then be None).  evaluate(pairs) with
     pairs = [(anc_id, pos_id, T_gt 3x4 mapping the positive frame into the anchor's)] matches descriptors, runs RANSAC
     and repeatability in batches and returns evaluate_kitti.m's and eval_rep.m's printed quantities; the poses are in
     the frame the keypoints are in.  One host read at the end."""
@@ -202,6 +203,22 @@ class RegistrationEvaluator:
         desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
         width = self.top
         if kp.shape[2] < width:                                   # fewer nodes than top: pad to one width for batching
+            kp = torch.cat((kp, kp[:, :, :1].expand(-1, -1, width - kp.shape[2])), 2)
+            desc = torch.cat((desc, desc[:, :, :1].expand(-1, -1, width - desc.shape[2])), 2)
+        self.frames[frame_id] = (kp[0].contiguous(), desc[0].contiguous(), count[0])
+        return self.frames[frame_id]
+
+    def add_frame_keypoints(self, frame_id, pc, sn, kp, count):
+        """Keypoints from elsewhere (usip_amd.baselines: ISS, random) instead of the detector's: kp f32 [1,3,M'] with M' <=
+        top, count i32 [1] on the device.  Described and cached exactly as add_frame does."""
+        if kp.dim() != 3 or kp.shape[0] != 1 or kp.shape[1] != 3 or not 1 <= kp.shape[2] <= self.top:
+            raise ValueError("add_frame_keypoints: expected kp [1,3,M'] with 1 <= M' <= top = %d, got %s"
+                             % (self.top, tuple(kp.shape)))
+        kp = kp.to(self.device, torch.float32).contiguous()
+        count = torch.clamp(count.to(self.device, torch.int32).reshape(1), max=kp.shape[2])
+        desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
+        width = self.top
+        if kp.shape[2] < width:
             kp = torch.cat((kp, kp[:, :, :1].expand(-1, -1, width - kp.shape[2])), 2)
             desc = torch.cat((desc, desc[:, :, :1].expand(-1, -1, width - desc.shape[2])), 2)
         self.frames[frame_id] = (kp[0].contiguous(), desc[0].contiguous(), count[0])

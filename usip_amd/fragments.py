@@ -441,6 +441,16 @@ class FragmentEvaluator:
         desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
         return self._store(fragment_id, kp[0], desc[0], count[0], cloud)
 
+    def add_fragment_keypoints(self, fragment_id, pc, sn, kp, count, cloud):
+        """Keypoints from elsewhere (usip_amd.baselines: ISS, random) instead of the detector's: kp f32 [1,3,M'] with M' <=
+        top, count i32 [1] on the device.  Described and cached exactly as add_fragment does."""
+        if kp.dim() != 3 or kp.shape[0] != 1 or kp.shape[1] != 3 or kp.shape[2] < 1:
+            raise ValueError("add_fragment_keypoints: expected kp [1,3,M'], got %s" % (tuple(kp.shape),))
+        kp = kp.to(self.device, torch.float32).contiguous()
+        count = torch.clamp(count.to(self.device, torch.int32).reshape(1), max=kp.shape[2])
+        desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
+        return self._store(fragment_id, kp[0], desc[0], count[0], cloud)
+
     def add_fragment_result(self, fragment_id, xyz, desc, cloud):
         xyz = torch.as_tensor(np.asarray(xyz, np.float32) if not isinstance(xyz, torch.Tensor) else xyz).to(self.device, torch.float32)
         desc = torch.as_tensor(np.asarray(desc, np.float32) if not isinstance(desc, torch.Tensor) else desc).to(self.device, torch.float32)

@@ -1876,3 +1876,50 @@ def overlap_ratio(rows, offsets, frag1, frag2, Rt, perm1, perm2, radius: float):
                                                      _ptr(perm2), P, Lmax, float(radius), _ptr(hits), _ptr(ratio),
                                                      _stream(rows)), "usip_overlap_ratio_f32")
     return ratio, hits
+
+
+# ------------------------------------------------------------------------------------------------ f-11 baseline keypoints
+def _need_frames(pc, count, perm):
+    _need(pc, "pc", torch.float32)
+    if pc.dim() != 3 or pc.shape[1] != 3:
+        raise RuntimeError("iss: expected pc f32 [B,3,N]")
+    B, _, N = pc.shape
+    if not (1 <= N <= 1 << 20 and 1 <= B <= 65535):
+        raise RuntimeError("iss: N must be in 1..2^20 and B in 1..65535 (got B = %d, N = %d)" % (B, N))
+    _need_on(count, "count", torch.int32, (B,), pc.device)
+    _need_on(perm, "perm", torch.int32, (B, N), pc.device)
+    if perm is None:
+        raise RuntimeError("iss: perm is required")
+    return B, N
+
+
+def iss_saliency(pc, count, perm, salient_radius: float, gamma_21: float, gamma_32: float, min_neighbors: int,
+                 want_visits: bool = False):
+    """f-11: pc f32 [B,3,N], count i32 [B] or None, perm i32 [B,N] (every frame's live points ascending along x, stable)
+    -> (saliency f64 [B,N], neighbours i32 [B,N]); with want_visits also the 256-point tiles each workgroup walked, i32
+    [B, ceil(N/256)]."""
+    B, N = _need_frames(pc, count, perm)
+    if not (float(salient_radius) > 0.0 and int(min_neighbors) >= 1):
+        raise RuntimeError("iss: salient_radius must be positive and min_neighbors at least 1")
+    sal = torch.empty((B, N), dtype=torch.float64, device=pc.device)
+    nb = torch.empty((B, N), dtype=torch.int32, device=pc.device)
+    visits = torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=pc.device) if want_visits else None
+    with torch.cuda.device(pc.device), prof.kernel("iss_saliency", 28.0 * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_iss_saliency_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), B, N, float(salient_radius),
+                                                    float(gamma_21), float(gamma_32), int(min_neighbors), _ptr(sal),
+                                                    _ptr(nb), _opt_ptr(visits), _stream(pc)), "usip_iss_saliency_f32")
+    return (sal, nb, visits) if want_visits else (sal, nb)
+
+
+def iss_nms(pc, count, perm, saliency, non_max_radius: float, min_neighbors: int):
+    """f-11: saliency f64 [B,N] -> keypoint u8 [B,N]: salient, enough neighbours within non_max_radius, none of them larger."""
+    B, N = _need_frames(pc, count, perm)
+    _need_on(saliency, "saliency", torch.float64, (B, N), pc.device)
+    if saliency is None or not (float(non_max_radius) > 0.0 and int(min_neighbors) >= 1):
+        raise RuntimeError("iss: saliency is required, non_max_radius must be positive and min_neighbors at least 1")
+    kp = torch.empty((B, N), dtype=torch.uint8, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("iss_nms", 25.0 * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_iss_nms_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), _ptr(saliency), B, N,
+                                               float(non_max_radius), int(min_neighbors), _ptr(kp), _stream(pc)),
+                   "usip_iss_nms_f32")
+    return kp
