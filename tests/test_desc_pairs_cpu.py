@@ -8,9 +8,11 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from test_pairs_cpu import check_parent_bits, cs
 
 CLOUD_KEYS = ("anc_pc", "anc_sn", "anc_node", "pos_pc", "pos_sn", "pos_node")
 CASES = ["c4_train_end", "c1_train_far", "c5_train_pert", "c4_test_mine2", "c5_test", "c1_test_mine"]
+DESCRIPTOR_PINS = [i for i in cs.IDS if cs.is_desc(i[0])]
 
 
 def fixture_bank(g):
@@ -200,3 +202,10 @@ def test_c_entry_refuses_a_broken_sequence_table_and_short_scans():
     assert call([0, 4, 7], 1100) < 0           # does not end at num_scans
     assert call([1, 4, 8], 1100) < 0           # does not start at 0
     assert call([0, 4, 8], 1023) < 0           # min_rows < N
+
+
+@pytest.mark.parametrize("name,mode", DESCRIPTOR_PINS)
+def test_host_twin_gives_the_bits_pinned_before_the_cloud_stage_was_merged(name, mode):
+    """tests/golden/cloud_stage_parent_bits.npz: what the f-8 twin computed before its per-cloud loop became
+    csrc/cloud_stage_host.h's -- the clouds, rows and node slots, and the positive and negatives chosen on the way."""
+    check_parent_bits(name, mode, cs.host_twin(name, mode), "host twin")

@@ -13,7 +13,8 @@ import pytest
 import torch
 
 from conftest import ROOT, load_golden
-from test_desc_pairs_cpu import CASES, CLOUD_KEYS, _case, check_against_fixture, fixture_bank
+from test_desc_pairs_cpu import CASES, CLOUD_KEYS, DESCRIPTOR_PINS, _case, check_against_fixture, fixture_bank
+from test_pairs_cpu import check_device_against_twin, cs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -71,6 +72,13 @@ def test_philox_mode_matches_host_twin_at_the_reference_shape():
     for k in CLOUD_KEYS:
         assert got[k].shape == want[k].shape and got[k].dtype == np.float32
         assert _within_ulp(got[k], want[k]), (k, np.abs(got[k] - want[k]).max())
+
+
+@pytest.mark.parametrize("name,mode", DESCRIPTOR_PINS)
+def test_device_matches_host_twin_at_the_pinned_cases(name, mode):
+    """The descriptor case of tests/golden/cloud_stage_parent_bits.npz (N = 300: two point workgroups, the second partial,
+    M = 7) through the merged cloud stage's kernels: pos_id, neg_idx, rows and node slots equal, floats within one ulp."""
+    check_device_against_twin(name, mode, cs.device(name, mode, DEV), cs.host_twin(name, mode), _within_ulp)
 
 
 def test_nodes_are_fps_of_the_built_candidates():

@@ -4,15 +4,20 @@ KittiLoader / OxfordLoader run on recorded draws (tests/golden/pairs_cases.npz, 
 import ctypes
 import os
 import subprocess
+import sys
 import types
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
+from conftest import GOLDEN, ROOT, load_golden
+
+sys.path.insert(0, GOLDEN)
+import make_cloud_stage_golden as cs  # noqa: E402   (the cases of tests/golden/cloud_stage_parent_bits.npz and how they are stored)
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KEYS = ("src_pc", "src_sn", "src_node", "dst_pc", "dst_sn", "dst_node", "R", "scale", "shift")
+DETECTOR_PINS = [i for i in cs.IDS if not cs.is_desc(i[0])]
 
 
 @pytest.fixture(scope="module")
@@ -159,3 +164,38 @@ def test_presets_and_refusals():
     assert not np.array_equal(order, pairs.epoch_order(10, 1, 1))
     b = list(pairs.epoch_batches(10, 2, 1, 0, rank=1, world=2))
     assert len(b) == 2 and np.array_equal(b[0], order[2:4]) and np.array_equal(b[1], order[6:8])
+
+
+def check_parent_bits(name, mode, got, what):
+    """Every stored output of (case, mode), bit for bit; the inputs' digest first (nothing is skipped when it moves)."""
+    want = load_golden(os.path.basename(cs.PATH))
+    assert bytes(want["%s_sha256" % name]).hex() == cs.digest(name), "the generators no longer give the fixture's inputs"
+    stored = {k[len(cs.key(name, mode, "")):]: want[k] for k in want if k.startswith(cs.key(name, mode, ""))}
+    assert set(stored) == set(got) and {"rows", "node_slots"} <= set(stored), (sorted(stored), sorted(got))
+    differ = {k: int((got[k] != e).sum()) if got[k].shape == e.shape else -1 for k, e in stored.items()}
+    print("%s, %s %s: entries that differ from the pinned bits %s" % (what, name, mode, differ))
+    for k, e in stored.items():
+        assert got[k].dtype == e.dtype and got[k].shape == e.shape, k
+        assert np.array_equal(got[k], e), (what, name, mode, k, differ[k])
+
+
+@pytest.mark.parametrize("name,mode", DETECTOR_PINS)
+def test_host_twin_gives_the_bits_pinned_before_the_cloud_stage_was_merged(name, mode):
+    """Twin and device are held together everywhere else; this holds the twin to what the f-5 twin computed before its
+    per-cloud loop became csrc/cloud_stage_host.h's (the fix_idx layout, Oxford's height scaling and ENU -> cam, sn_last)."""
+    check_parent_bits(name, mode, cs.host_twin(name, mode), "host twin")
+
+
+def check_device_against_twin(name, mode, got, want, within_ulp):
+    """A case of the fixture through build(..., with_indices=True): integer outputs equal the twin's, float outputs (stored
+    as their bit patterns) lie within the GPU files' _within_ulp of it."""
+    assert set(got) == set(want)
+    differ = {k: int((got[k] != w).sum()) if got[k].shape == w.shape else -1 for k, w in want.items()}
+    print("device, %s %s: entries that differ from the twin's %s" % (name, mode, differ))
+    for k, w in want.items():
+        assert got[k].dtype == w.dtype and got[k].shape == w.shape, k
+        if w.dtype == np.uint32:
+            g, w = got[k].view(np.float32), w.view(np.float32)
+            assert within_ulp(g, w), (name, mode, k, np.abs(g - w).max())
+        else:
+            assert np.array_equal(got[k], w), (name, mode, k)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from conftest import load_golden
-from test_pairs_cpu import CASES, KEYS, _case, check_against_fixture
+from test_pairs_cpu import CASES, DETECTOR_PINS, KEYS, _case, check_against_fixture, check_device_against_twin, cs
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -62,6 +62,13 @@ def test_philox_mode_matches_host_twin_at_kitti_shape(preset):
     for k in KEYS:
         assert got[k].shape == want[k].shape and got[k].dtype == np.float32
         assert _within_ulp(got[k], want[k]), (k, np.abs(got[k] - want[k]).max())
+
+
+@pytest.mark.parametrize("name,mode", DETECTOR_PINS)
+def test_device_matches_host_twin_at_the_pinned_cases(name, mode):
+    """The cases of tests/golden/cloud_stage_parent_bits.npz (N = 300: two point workgroups, the second partial; the
+    fix_idx layout, Oxford's height scaling and ENU -> cam, sn_last) through the merged cloud stage's kernels."""
+    check_device_against_twin(name, mode, cs.device(name, mode, DEV), cs.host_twin(name, mode), _within_ulp)
 
 
 def test_nodes_are_fps_of_the_built_candidates():

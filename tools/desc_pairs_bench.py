@@ -9,8 +9,8 @@ builder_ms            HIP events around one build (P pairs), median of --runs, a
 detector_builder_ms   the detector builder (usip_amd.pairs, tools/pair_builder_bench.py's own measurement) at equal
                       (P, N, M, n_sub) on the same bank: the yardstick, since the per-slot and FPS work per cloud are its own
 fps_ms                usip_fps_f32 alone on the same candidates (its share of the builder)
-points_us             desc_points_kernel from a rocprofv3 --stats run (average), with algorithmic bytes and the fraction
-                      of 8 TB/s those bytes would take; select_mine_us: desc_select_kernel + desc_mine_kernel
+points_us             cloud_points_kernel<..., CloudView> from a rocprofv3 --stats run (average), with algorithmic bytes and
+                      the fraction of 8 TB/s those bytes would take; select_mine_us: desc_select_kernel + desc_mine_kernel
 detector_forward_ms   the frozen detector's eval-mode forward on cat(anchor, positive)
 descriptor_step_ms    DescriptorStep alone (graph replay, Adam) on a static batch
 step_ms               one training step = frozen-detector forward + DescriptorStep: on a pre-built batch, with the builder
@@ -67,11 +67,13 @@ def kernels_from_stats(path):
         with open(f) as fh:
             for row in csv.DictReader(fh):
                 name = row.get("Name") or row.get("KernelName") or ""
-                for k in ("desc_points_kernel", "desc_select_kernel", "desc_mine_kernel", "desc_nodes_kernel"):
+                if "cloud_" in name and "CloudView" not in name:         # the detector builder's instantiation
+                    continue
+                for k in ("cloud_points_kernel", "desc_select_kernel", "desc_mine_kernel", "cloud_nodes_kernel"):
                     if k in name:
                         out[k] = float(row["AverageNs"]) / 1e3
-    if "desc_points_kernel" not in out:
-        raise RuntimeError("no desc_points_kernel row in %s" % path)
+    if "cloud_points_kernel" not in out:
+        raise RuntimeError("no cloud_points_kernel<..., CloudView> row in %s" % path)
     return out
 
 
@@ -146,10 +148,10 @@ def main():
     line["points_bytes"] = nbytes
     if args.kernel_stats:
         k = kernels_from_stats(args.kernel_stats)
-        line["points_us"] = round(k["desc_points_kernel"], 2)
-        line["points_frac_8TBps"] = round(nbytes / 8e12 / (k["desc_points_kernel"] * 1e-6), 3)
+        line["points_us"] = round(k["cloud_points_kernel"], 2)
+        line["points_frac_8TBps"] = round(nbytes / 8e12 / (k["cloud_points_kernel"] * 1e-6), 3)
         line["select_mine_us"] = round(k.get("desc_select_kernel", 0.0) + k.get("desc_mine_kernel", 0.0), 2)
-        line["nodes_us"] = round(k.get("desc_nodes_kernel", 0.0), 2)
+        line["nodes_us"] = round(k.get("cloud_nodes_kernel", 0.0), 2)
     else:
         line["points_us"] = line["select_mine_us"] = "not measured (no --kernel-stats)"
     torch.cuda.synchronize()

@@ -3,12 +3,12 @@
 
     python tools/pair_builder_bench.py                       # builder, FPS share, step legs, CPU recipe cost
     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python tools/pair_builder_bench.py --quick
-    python tools/pair_builder_bench.py --kernel-stats DIR    # + pairs_points_kernel us from that trace
+    python tools/pair_builder_bench.py --kernel-stats DIR    # + cloud_points_kernel us from that trace
 
 builder_ms      HIP events around one build (P pairs), median of --runs
 fps_ms          usip_fps_f32 alone on the same candidates, median of --runs (its share of the builder)
-points_us       pairs_points_kernel from a rocprofv3 --stats run (average), with algorithmic bytes and the fraction of
-                8 TB/s those bytes would take
+points_us       cloud_points_kernel<..., PairView> from a rocprofv3 --stats run (average), with algorithmic bytes and the
+                fraction of 8 TB/s those bytes would take
 step_ms         DetectorStep (graph replay, Adam) per step: on a pre-built batch, with the builder run before each step on
                 the same stream, and prefetched (built on a side stream while the previous step replays); the three legs
                 alternate --rounds times in one process, medians reported
@@ -94,9 +94,9 @@ def points_from_stats(path):
         with open(f) as fh:
             for row in csv.DictReader(fh):
                 name = row.get("Name") or row.get("KernelName") or ""
-                if "pairs_points_kernel" in name:
+                if "cloud_points_kernel" in name and "PairView" in name:
                     return float(row["AverageNs"]) / 1e3, f
-    raise RuntimeError("no pairs_points_kernel row in %s" % path)
+    raise RuntimeError("no cloud_points_kernel<..., PairView> row in %s" % path)
 
 
 def main():

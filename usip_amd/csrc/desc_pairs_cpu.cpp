@@ -1,49 +1,29 @@
 // usip_amd/csrc/desc_pairs_cpu.cpp -- host twin of csrc/desc_pairs.hip: the same draws and arithmetic
-// (csrc/desc_pairs_math.h) on host pointers, in the same order, with a float64 farthest-point sampling loop in numpy's
-// order (FarthestSampler.sample, data/kitti_descriptor_loader.py:70-84).  Never reached from the device entry points.
-#include <cmath>
-#include <vector>
+// (csrc/desc_pairs_math.h) on host pointers, in the same order, the per-cloud stage through csrc/cloud_stage_host.h.
+// Never reached from the device entry points.
+#include "cloud_stage_host.h"
 #include "desc_pairs_math.h"
 
 using namespace usip_desc_pairs;
 
 namespace {
 
-// out[0] = first, then k-1 times the first arg-max of the running minimum of (dx*dx + dy*dy) + dz*dz in float64
-// (the loop of csrc/pairs_cpu.cpp, which keeps its own copy private)
-void fps_host(const float* pts, int n, int first, int k, int32_t* out)
-{
-    std::vector<double> dist((size_t)n, INFINITY);
-    int cur = first;
-    out[0] = cur;
-    for (int it = 1; it < k; ++it) {
-        const double cx = pts[cur], cy = pts[n + cur], cz = pts[2 * n + cur];
-        double best = -1.0;
-        int bi = 0;
-        for (int j = 0; j < n; ++j) {
-            const double dx = cx - (double)pts[j], dy = cy - (double)pts[n + j], dz = cz - (double)pts[2 * n + j];
-            const double d = (dx * dx + dy * dy) + dz * dz;
-            dist[j] = d < dist[j] ? d : dist[j];
-            if (dist[j] > best) { best = dist[j]; bi = j; }
-        }
-        out[it] = cur = bi;
-    }
-}
-
 template <class Src>
 void build_host(const usip_desc_pairs_recipe& rd, const Src& src, const usip_desc_pairs_bank& b, const int32_t* scan_ids,
                 int P, const usip_desc_pairs_out& out)
 {
     const usip_pairs_recipe& r = rd.cloud;
-    const int N = r.N, M = r.M, ns = r.n_sub, Cs = r.Cs;
     const PosedBank bank{b.rows, b.offsets, b.poses, b.seq_of, b.seq_start, b.num_scans, b.num_seq};
-    std::vector<double> T((size_t)T_SIZE);
-    std::vector<float> cand((size_t)3 * ns);
-    std::vector<int32_t> fps((size_t)M);
+    std::vector<double> T((size_t)2 * P * T_SIZE);
+    std::vector<int32_t> cloud_scan((size_t)2 * P);
+    const CloudView v{T.data(), b.offsets, cloud_scan.data(), b.num_scans};
+    const CloudOut o{{out.pc[0], out.pc[1]}, {out.sn[0], out.sn[1]}, {out.node[0], out.node[1]}, out.rows, out.node_slots};
     int fails = 0;
     for (int p = 0; p < P; ++p) {
         const int a = bank.scan(scan_ids[p]);
         const int pos = select_positive(bank, rd.positive_radius, src, p, a);
+        cloud_scan[p] = a;
+        cloud_scan[P + p] = pos;
         out.pos_id[p] = pos;
         out.anc_seq[p] = bank.seq(a);
         for (int i = 0; i < 16; ++i) {
@@ -57,46 +37,10 @@ void build_host(const usip_desc_pairs_recipe& rd, const Src& src, const usip_des
         }
         const double us = src.scale_u(p);
         for (int c = 0; c < 2; ++c) {
-            const int q = c * P + p, s = c == 0 ? a : pos;
-            const long long o0 = bank.offsets[s], n = bank.offsets[s + 1] - o0;
             double u[CLOUD_U];
             src.cloud_params(p, c, u);
-            cloud_table(r, us, u, T.data());
-            float* pc = out.pc[c] + (long long)p * 3 * N;
-            float* sn = out.sn[c] + (long long)p * Cs * N;
-            for (int j = 0; j < N; ++j) {
-                const long long row = src.row(p, c, n, N, j);
-                const float* rp = bank.rows + (o0 + row) * r.row_len;
-                float xyz[3], sv[MAX_CS], o[3];
-                load_row(r, rp, xyz, sv);
-                double zp[4] = {0, 0, 0, 0}, zs[MAX_CS] = {0, 0, 0, 0, 0, 0, 0, 0};
-                if (r.train) {
-                    src.jit_pc(p, c, N, j, zp);
-                    src.jit_sn(p, c, N, Cs, j, zs);
-                }
-                finish_xyz(r, T.data(), 0, xyz, zp, r.pc_sigma, r.pc_clip, true, o);
-                finish_sn(r, T.data(), 0, sv, zs);
-                for (int k = 0; k < 3; ++k) pc[(long long)k * N + j] = o[k];
-                for (int k = 0; k < Cs; ++k) sn[(long long)k * N + j] = sv[k];
-                if (out.rows) out.rows[(long long)q * N + j] = (int32_t)row;
-            }
-            for (int i = 0; i < ns; ++i) {
-                const long long row = src.row(p, c, n, N, src.cand(p, c, N, i));
-                const float* cp = bank.rows + (o0 + row) * r.row_len;
-                for (int k = 0; k < 3; ++k) cand[(size_t)k * ns + i] = cp[k];
-            }
-            fps_host(cand.data(), ns, src.first(p, c, ns), M, fps.data());
-            float* node = out.node[c] + (long long)p * 3 * M;
-            for (int m = 0; m < M; ++m) {
-                const int ci = fps[m];
-                const float xyz[3] = {cand[ci], cand[ns + ci], cand[2 * ns + ci]};
-                double z[4] = {0, 0, 0, 0};
-                if (r.train) src.jit_node(p, c, M, m, z);
-                float o[3];
-                finish_xyz(r, T.data(), 0, xyz, z, r.node_sigma, r.node_clip, false, o);
-                for (int k = 0; k < 3; ++k) node[(long long)k * M + m] = o[k];
-                if (out.node_slots) out.node_slots[(long long)q * M + m] = src.cand(p, c, N, ci);
-            }
+            cloud_table(r, us, u, T.data() + (size_t)(c * P + p) * T_SIZE);
+            cloud_host(r, src, v, b.rows, P, c * P + p, o);
         }
     }
     if (rd.mine) out.neg_fail[0] = fails;
@@ -122,7 +66,7 @@ extern "C" int usip_desc_pairs_build_f32_cpu(const usip_desc_pairs_recipe* recip
                                     draws->neg_pick, draws->T};
         build_host(*recipe, src, *bank, scan_ids, P, *out);
     } else {
-        const PhiloxDescDraws src{seed, step, pair_base};
+        const PhiloxDescDraws src{{seed, step, pair_base}};
         build_host(*recipe, src, *bank, scan_ids, P, *out);
     }
     return USIP_OK;

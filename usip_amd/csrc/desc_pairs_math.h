@@ -1,7 +1,7 @@
 // usip_amd/csrc/desc_pairs_math.h -- the arithmetic of one descriptor training pair, shared by the kernels of
-// csrc/desc_pairs.hip and the host twin of csrc/desc_pairs_cpu.cpp.  The per-slot work is csrc/pairs_math.h's (load_row,
-// raw_xyz, finish_xyz, finish_sn with cloud 0: no transform); what is new here is the choice of the positive scan, the
-// mining of negatives, a table per CLOUD, and the two sources of draws with their own stream tags.
+// csrc/desc_pairs.hip and the host twin of csrc/desc_pairs_cpu.cpp.  The per-slot work is csrc/pairs_math.h's cloud stage
+// (cloud_point, cloud_node) seen through CloudView: no transform; what is new here is the choice of the positive scan, the
+// mining of negatives, a table per CLOUD, and the parameter draws, with stream tags of their own.
 //
 // Reference semantics (data/kitti_descriptor_loader.py):
 //   get_nearby_instance_unagumented_np   :154-203, the narrowing rejection search (select_positive)
@@ -15,14 +15,9 @@ namespace usip_desc_pairs {
 
 using namespace usip_pairs;
 
-// Stream tags (counter word 1 = tag << 8 | cloud); f-5 uses 1-8.
+// Stream tags (counter word 1 = tag << 8 | cloud); f-5 uses 1-8, the per-slot streams here are f-5's + DTAG0 (17-22).
 enum : uint32_t {
-    DTAG_CHOICE = 17,
-    DTAG_CAND = 18,
-    DTAG_FIRST = 19,
-    DTAG_JIT_PC = 20,     // element = slot
-    DTAG_JIT_SN = 21,     // element = 2 * slot + channel / 4
-    DTAG_JIT_NODE = 22,   // element = node
+    DTAG0 = 16,
     DTAG_PARAM_U = 23,    // cloud c, elements 0, 1: that cloud's uniforms; cloud 0, element 2: the pair's scale
     DTAG_PARAM_N = 24,    // cloud c, element 0: that cloud's perturbation normals
     DTAG_TRY = 25,        // element = try number of the positive search: word 0
@@ -30,28 +25,32 @@ enum : uint32_t {
 };
 constexpr int CLOUD_U = 10;       // params per cloud, from index 1 + CLOUD_U * c
 
-USIP_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// One cloud's table (pairs_math.h's layout; the transform's entries stay zero and are never read with cloud 0).
+// One cloud's table (pairs_math.h's layout; no height scale, and the transform's entries stay zero: CloudView::dst is 0).
 USIP_HD void cloud_table(const usip_pairs_recipe& r, double u_scale, const double* u, double* T)
 {
-    const double pi = 3.141592653589793;
-    int ns = 0;
-    if (r.train) {
-        if (r.rot_horizontal) rotation(0.0, u[0] * 2 * pi, 0.0, T + 9 * ns++);
-        if (r.rot_3d) rotation(u[1] * pi * 2, u[2] * pi * 2, u[3] * pi * 2, T + 9 * ns++);
-        if (r.rot_perturbation)
-            rotation(clip(r.pert_sigma * u[4], r.pert_clip), clip(r.pert_sigma * u[5], r.pert_clip),
-                     clip(r.pert_sigma * u[6], r.pert_clip), T + 9 * ns++);
-    }
-    for (int i = 9 * ns; i < 27; ++i) T[i] = 0.0;
-    T[T_NSTAGE] = ns;
-    T[T_SCALE] = r.train ? uniform(r.aug_scale_lo, r.aug_scale_hi, u_scale) : 1.0;
-    for (int k = 0; k < 3; ++k)
-        T[T_SHIFT + k] = (r.train && r.translation_perturbation) ? uniform(-r.shift_range, r.shift_range, u[7 + k]) : 0.0;
+    augment_table(r, u, u_scale, u + 7, T);
     T[T_HEIGHT] = 1.0;
     for (int i = T_HEIGHT_ON; i < T_SIZE; ++i) T[i] = 0.0;
 }
+
+// The descriptor's pair: one table per cloud, the scan chosen on the device (anchor or positive), no transform, and no
+// fix_idx layout (a scan shorter than N is refused).
+struct CloudView {
+    const double* tab;          // [2P][T_SIZE]
+    const int64_t* offsets;
+    const int32_t* cloud_scan;  // [2P]
+    int num_scans;
+
+    USIP_HD const double* table(int q, int) const { return tab + (long long)q * T_SIZE; }
+    USIP_HD void scan(int q, int, long long& o0, long long& n) const
+    {
+        const int s = clampi(cloud_scan[q], 0, num_scans - 1);
+        o0 = offsets[s];
+        n = offsets[s + 1] - o0;
+    }
+    USIP_HD static int dst(int) { return 0; }
+    USIP_HD static bool usable(long long n, int N) { return n >= N; }
+};
 
 struct PosedBank {
     const float* rows;
@@ -115,11 +114,7 @@ USIP_HD long long mine_negative(const PosedBank& b, double thr, const Src& src, 
 }
 
 // ----------------------------------------------------------------------------------------------- sources of draws
-struct PhiloxDescDraws {
-    uint64_t seed, step;
-    long long base;
-
-    USIP_HD uint64_t gp(int p) const { return (uint64_t)(base + p); }
+struct PhiloxDescDraws : PhiloxSlots<DTAG0> {
     // word 0 of (DTAG_PARAM_U, cloud 0, element 2): the pair's scale uniform
     USIP_HD double scale_u(int p) const
     {
@@ -140,42 +135,6 @@ struct PhiloxDescDraws {
         u[4] = z[0]; u[5] = z[1]; u[6] = z[2];
         pairs_block(seed, step, gp(p), DTAG_PARAM_U, c, 1, b);
         u[7] = u53(b[0]); u[8] = u53(b[1]); u[9] = u53(b[2]);
-    }
-    USIP_HD PairsPerm perm(int p, int c, uint32_t tag, uint64_t n) const
-    {
-        uint64_t b[4];
-        pairs_block(seed, step, gp(p), tag, c, 0, b);
-        PairsPerm q;
-        q.init(b, n);
-        return q;
-    }
-    USIP_HD long long row(int p, int c, long long n, int, int j) const    // n >= N: no fix_idx layout
-    {
-        return (long long)perm(p, c, DTAG_CHOICE, (uint64_t)n)((uint64_t)j);
-    }
-    USIP_HD int cand(int p, int c, int N, int i) const { return (int)perm(p, c, DTAG_CAND, (uint64_t)N)((uint64_t)i); }
-    USIP_HD int first(int p, int c, int n_sub) const { return (int)perm(p, c, DTAG_FIRST, (uint64_t)n_sub)(0); }
-    USIP_HD void jit_pc(int p, int c, int, int j, double* z) const
-    {
-        uint64_t b[4];
-        pairs_block(seed, step, gp(p), DTAG_JIT_PC, c, (uint64_t)j, b);
-        normal4(b, z);
-    }
-    USIP_HD void jit_sn(int p, int c, int, int Cs, int j, double* z) const
-    {
-        uint64_t b[4];
-        double t[4];
-        for (int e = 0; 4 * e < Cs; ++e) {
-            pairs_block(seed, step, gp(p), DTAG_JIT_SN, c, 2 * (uint64_t)j + e, b);
-            normal4(b, t);
-            for (int k = 0; k < 4 && 4 * e + k < Cs; ++k) z[4 * e + k] = t[k];
-        }
-    }
-    USIP_HD void jit_node(int p, int c, int, int m, double* z) const
-    {
-        uint64_t b[4];
-        pairs_block(seed, step, gp(p), DTAG_JIT_NODE, c, (uint64_t)m, b);
-        normal4(b, z);
     }
     USIP_HD int try_index(int p, int counter, int lo, int hi, int) const
     {

@@ -1,6 +1,8 @@
 // usip_amd/csrc/pairs_math.h -- the arithmetic of one training pair, shared by the kernels of csrc/pairs.hip
 // and the host twin of csrc/pairs_cpu.cpp.  Two sources of draws feed it through the same interface: PhiloxDraws (training)
 // and ExplicitDraws (the reference's recorded draws, tests/golden/pairs_cases.npz), so the fixtures test the code that trains.
+// cloud_point / cloud_node are the per-cloud stage of BOTH builders (f-5 and the descriptor's f-8, csrc/desc_pairs_math.h):
+// one thread of csrc/cloud_stage.h's kernels or one iteration of csrc/cloud_stage_host.h's loops, told apart by a View.
 //
 // Reference semantics (data/kitti_detector_loader.py, data/oxford_detector_loader.py, data/augmentation.py):
 //   angles2rotation_matrix  R = Rz (Ry Rx), float64
@@ -61,28 +63,41 @@ USIP_HD void rotation(double ax, double ay, double az, double R[9])
 }
 
 USIP_HD double clip(double v, double c) { return v < -c ? -c : (v > c ? c : v); }
+USIP_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 USIP_HD double uniform(double lo, double hi, double u) { return lo + (hi - lo) * u; }    // numpy: low + (high - low) * u
 
-// u: the pair's USIP_PAIRS_NPARAM raw draws (layout in include/usip_hip.h) -> T
-USIP_HD void pair_table(const usip_pairs_recipe& r, const double* u, double* T)
+// augment's part of a table, T[0 .. T_SHIFT + 3): rot = the yaw uniform, rand(3), randn(3); one scale and three shift uniforms
+USIP_HD void augment_table(const usip_pairs_recipe& r, const double* rot, double u_scale, const double* u_shift, double* T)
 {
     const double pi = 3.141592653589793;
     int ns = 0;
     if (r.train) {
-        if (r.rot_horizontal) rotation(0.0, u[0] * 2 * pi, 0.0, T + 9 * ns++);             // np.random.uniform() * 2 * np.pi
-        if (r.rot_3d) rotation(u[1] * pi * 2, u[2] * pi * 2, u[3] * pi * 2, T + 9 * ns++); // np.random.rand(3) * np.pi * 2
+        if (r.rot_horizontal) rotation(0.0, rot[0] * 2 * pi, 0.0, T + 9 * ns++);           // np.random.uniform() * 2 * np.pi
+        if (r.rot_3d) rotation(rot[1] * pi * 2, rot[2] * pi * 2, rot[3] * pi * 2, T + 9 * ns++);   // np.random.rand(3) * np.pi * 2
         if (r.rot_perturbation)
-            rotation(clip(r.pert_sigma * u[4], r.pert_clip), clip(r.pert_sigma * u[5], r.pert_clip),
-                     clip(r.pert_sigma * u[6], r.pert_clip), T + 9 * ns++);
+            rotation(clip(r.pert_sigma * rot[4], r.pert_clip), clip(r.pert_sigma * rot[5], r.pert_clip),
+                     clip(r.pert_sigma * rot[6], r.pert_clip), T + 9 * ns++);
     }
     for (int i = 9 * ns; i < 27; ++i) T[i] = 0.0;
     T[T_NSTAGE] = ns;
-    T[T_SCALE] = r.train ? uniform(r.aug_scale_lo, r.aug_scale_hi, u[7]) : 1.0;
+    T[T_SCALE] = r.train ? uniform(r.aug_scale_lo, r.aug_scale_hi, u_scale) : 1.0;
     for (int k = 0; k < 3; ++k)
-        T[T_SHIFT + k] = (r.train && r.translation_perturbation) ? uniform(-r.shift_range, r.shift_range, u[8 + k]) : 0.0;
+        T[T_SHIFT + k] = (r.train && r.translation_perturbation) ? uniform(-r.shift_range, r.shift_range, u_shift[k]) : 0.0;
+}
+
+// Pair p's USIP_PAIRS_NPARAM raw draws u (layout in include/usip_hip.h) -> T.  The draws come in two halves, each where it
+// is used and every index a constant, so that on the device u stays in registers and the halves share them.
+template <class Src>
+USIP_HD void pair_table(const usip_pairs_recipe& r, const Src& src, int p, double* T)
+{
+    const double pi = 3.141592653589793;
+    double u[USIP_PAIRS_NPARAM];
+    src.params(p, 0, u);                                   // u[0 .. 12): augment and height scale
+    augment_table(r, u, u[7], u + 8, T);
     const bool height = r.train && r.height_scaling;
     T[T_HEIGHT] = height ? (double)(float)uniform(r.height_lo, r.height_hi, u[11]) : 1.0;
     T[T_HEIGHT_ON] = height ? 1.0 : 0.0;
+    src.params(p, 1, u);                                   // u[12 .. 24): the dst transform
     double ax = 0, ay = 0, az = 0;
     if (r.dst_rot_type == 2) {
         ay = u[12] * 2 * pi;
@@ -192,30 +207,18 @@ USIP_HD long long fix_copies(long long n, int N)
 }
 
 // ----------------------------------------------------------------------------------------------- sources of draws
-struct PhiloxDraws {
+// The per-slot Philox draws of one cloud, streams TAG0 + TAG_CHOICE .. TAG0 + TAG_JIT_NODE: TAG0 = 0 for the detector's
+// pairs, 16 for the descriptor's (csrc/desc_pairs_math.h), so the two builders share no draw.
+template <uint32_t TAG0>
+struct PhiloxSlots {
     uint64_t seed, step;
     long long base;
 
     USIP_HD uint64_t gp(int p) const { return (uint64_t)(base + p); }
-    USIP_HD void params(int p, double* u) const
-    {
-        uint64_t b[4];
-        for (int e = 0; e < USIP_PAIRS_NPARAM / 4; ++e) {
-            pairs_block(seed, step, gp(p), TAG_PARAM_U, 0, e, b);
-            for (int i = 0; i < 4; ++i) u[4 * e + i] = u53(b[i]);
-        }
-        double z[4];
-        pairs_block(seed, step, gp(p), TAG_PARAM_N, 0, 0, b);
-        normal4(b, z);
-        u[4] = z[0]; u[5] = z[1]; u[6] = z[2];
-        pairs_block(seed, step, gp(p), TAG_PARAM_N, 0, 1, b);
-        normal4(b, z);
-        u[15] = z[0]; u[16] = z[1]; u[17] = z[2];
-    }
     USIP_HD PairsPerm perm(int p, int c, uint32_t tag, uint64_t n) const
     {
         uint64_t b[4];
-        pairs_block(seed, step, gp(p), tag, c, 0, b);
+        pairs_block(seed, step, gp(p), TAG0 + tag, c, 0, b);
         PairsPerm q;
         q.init(b, n);
         return q;
@@ -232,7 +235,7 @@ struct PhiloxDraws {
     USIP_HD void jit_pc(int p, int c, int, int j, double* z) const
     {
         uint64_t b[4];
-        pairs_block(seed, step, gp(p), TAG_JIT_PC, c, (uint64_t)j, b);
+        pairs_block(seed, step, gp(p), TAG0 + TAG_JIT_PC, c, (uint64_t)j, b);
         normal4(b, z);
     }
     USIP_HD void jit_sn(int p, int c, int, int Cs, int j, double* z) const
@@ -240,7 +243,7 @@ struct PhiloxDraws {
         uint64_t b[4];
         double t[4];
         for (int e = 0; 4 * e < Cs; ++e) {
-            pairs_block(seed, step, gp(p), TAG_JIT_SN, c, 2 * (uint64_t)j + e, b);
+            pairs_block(seed, step, gp(p), TAG0 + TAG_JIT_SN, c, 2 * (uint64_t)j + e, b);
             normal4(b, t);
             for (int k = 0; k < 4 && 4 * e + k < Cs; ++k) z[4 * e + k] = t[k];
         }
@@ -248,8 +251,27 @@ struct PhiloxDraws {
     USIP_HD void jit_node(int p, int c, int, int m, double* z) const
     {
         uint64_t b[4];
-        pairs_block(seed, step, gp(p), TAG_JIT_NODE, c, (uint64_t)m, b);
+        pairs_block(seed, step, gp(p), TAG0 + TAG_JIT_NODE, c, (uint64_t)m, b);
         normal4(b, z);
+    }
+};
+
+struct PhiloxDraws : PhiloxSlots<0> {
+    // half h of the pair's draws, u[12 h .. 12 h + 12): uniforms, then the perturbation normals over u[4..6] / u[15..17]
+    USIP_HD void params(int p, int h, double* u) const
+    {
+        uint64_t b[4];
+#pragma unroll
+        for (int e = 3 * h; e < 3 * h + 3; ++e) {
+            pairs_block(seed, step, gp(p), TAG_PARAM_U, 0, e, b);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) u[4 * e + i] = u53(b[i]);
+        }
+        double z[4];
+        pairs_block(seed, step, gp(p), TAG_PARAM_N, 0, h, b);
+        normal4(b, z);
+        double* n = u + (h ? 15 : 4);
+        n[0] = z[0]; n[1] = z[1]; n[2] = z[2];
     }
 };
 
@@ -259,9 +281,10 @@ struct ExplicitDraws {
     usip_pairs_draws d;
     int N, n_sub, M, Cs;
 
-    USIP_HD void params(int p, double* u) const
+    USIP_HD void params(int p, int h, double* u) const
     {
-        for (int i = 0; i < USIP_PAIRS_NPARAM; ++i) u[i] = d.params[(long long)p * USIP_PAIRS_NPARAM + i];
+#pragma unroll
+        for (int i = 12 * h; i < 12 * h + 12; ++i) u[i] = d.params[(long long)p * USIP_PAIRS_NPARAM + i];
     }
     USIP_HD long long row(int p, int c, long long n, int, int j) const
     {
@@ -270,13 +293,11 @@ struct ExplicitDraws {
     }
     USIP_HD int cand(int p, int c, int, int i) const
     {
-        const int v = d.cand[((long long)p * 2 + c) * n_sub + i];
-        return v < 0 ? 0 : (v >= N ? N - 1 : v);
+        return clampi(d.cand[((long long)p * 2 + c) * n_sub + i], 0, N - 1);
     }
     USIP_HD int first(int p, int c, int) const
     {
-        const int v = d.first[p * 2 + c];
-        return v < 0 ? 0 : (v >= n_sub ? n_sub - 1 : v);
+        return clampi(d.first[p * 2 + c], 0, n_sub - 1);
     }
     USIP_HD void jit_pc(int p, int c, int, int j, double* z) const
     {
@@ -291,6 +312,95 @@ struct ExplicitDraws {
         for (int k = 0; k < 3; ++k) z[k] = d.jit_node[(((long long)p * 2 + c) * M + m) * 3 + k];
     }
 };
+
+// ------------------------------------------------------------------------------------------------ the cloud stage
+// Cloud q = c * P + p is cloud c (0 or 1) of pair p.  A View tells the two builders apart:
+//   table(q, p)           the cloud's float64 table
+//   scan(q, p, o0, n)     its scan's first bank row and row count
+//   dst(c)                1 where the cloud takes the table's transform
+//   usable(n, N)          false for a scan the entry points refuse on the host (min_rows)
+struct CloudOut {
+    float* pc[2];           // [P][3][N] per cloud of the pair
+    float* sn[2];           // [P][Cs][N]
+    float* node[2];         // [P][3][M]
+    int32_t* rows;          // [2P][N] or null
+    int32_t* node_slots;    // [2P][M] or null
+};
+
+// The detector's pair: one table per pair, the scan from the call's ids, cloud 1 takes the dst transform.
+struct PairView {
+    const double* tab;      // [P][T_SIZE]
+    const int64_t* offsets;
+    const int32_t* scan_ids;
+    int num_scans;
+
+    USIP_HD const double* table(int, int p) const { return tab + (long long)p * T_SIZE; }
+    USIP_HD void scan(int, int p, long long& o0, long long& n) const
+    {
+        const int s = clampi(scan_ids[p], 0, num_scans - 1);
+        o0 = offsets[s];
+        n = offsets[s + 1] - o0;
+    }
+    USIP_HD static int dst(int c) { return c; }
+    USIP_HD static bool usable(long long n, int) { return n >= 1; }
+};
+
+// Slot j of cloud q: slot -> scan row through the keyed bijection (or the fix_idx layout), one row load, augment and
+// transform, pc / sn written transposed; slots j < n_sub first write the un-augmented FPS candidate j of cd [3][n_sub]
+// (first: written after the slot's own work, the Philox kernel holds enough across it to spill scalar registers).
+template <class Src, class View>
+USIP_HD void cloud_point(const usip_pairs_recipe& r, const Src& src, const View& v, const float* bank, int P, int q, int j,
+                         const CloudOut& out, float* cd)
+{
+    const int N = r.N, c = q / P, p = q - c * P;
+    long long o0, n;
+    v.scan(q, p, o0, n);
+    if (!v.usable(n, N)) return;
+    const double* T = v.table(q, p);
+    if (j < r.n_sub) {
+        const long long crow = src.row(p, c, n, N, src.cand(p, c, N, j));
+        float cx[3];
+        raw_xyz(T, bank + (o0 + crow) * r.row_len, cx);
+        for (int k = 0; k < 3; ++k) cd[(long long)k * r.n_sub + j] = cx[k];
+    }
+    const long long row = src.row(p, c, n, N, j);
+    const float* rp = bank + (o0 + row) * r.row_len;
+    float xyz[3], s[MAX_CS];
+    load_row(r, rp, xyz, s);
+    raw_xyz(T, rp, xyz);
+    double zp[4] = {0, 0, 0, 0}, zs[MAX_CS];
+    for (int k = 0; k < MAX_CS; ++k) zs[k] = 0.0;
+    if (r.train) {
+        src.jit_pc(p, c, N, j, zp);
+        src.jit_sn(p, c, N, r.Cs, j, zs);
+    }
+    float o[3];
+    finish_xyz(r, T, v.dst(c), xyz, zp, r.pc_sigma, r.pc_clip, true, o);
+    finish_sn(r, T, v.dst(c), s, zs);
+    float* pc = out.pc[c] + (long long)p * 3 * N;
+    float* sn = out.sn[c] + (long long)p * r.Cs * N;
+    for (int k = 0; k < 3; ++k) pc[(long long)k * N + j] = o[k];
+    for (int k = 0; k < r.Cs; ++k) sn[(long long)k * N + j] = s[k];
+    if (out.rows) out.rows[(long long)q * N + j] = (int32_t)row;
+}
+
+// Node m of cloud q: the candidate FPS chose (fps [M], indices into cd), augment with its own jitter, transform.
+template <class Src, class View>
+USIP_HD void cloud_node(const usip_pairs_recipe& r, const Src& src, const View& v, int P, int q, int m, const float* cd,
+                        const int32_t* fps, const CloudOut& out)
+{
+    const int M = r.M, ns = r.n_sub, c = q / P, p = q - c * P;
+    const double* T = v.table(q, p);
+    const int ci = clampi(fps[m], 0, ns - 1);
+    const float xyz[3] = {cd[ci], cd[ns + ci], cd[2 * ns + ci]};
+    double z[4] = {0, 0, 0, 0};
+    if (r.train) src.jit_node(p, c, M, m, z);
+    float o[3];
+    finish_xyz(r, T, v.dst(c), xyz, z, r.node_sigma, r.node_clip, false, o);
+    float* node = out.node[c] + (long long)p * 3 * M;
+    for (int k = 0; k < 3; ++k) node[(long long)k * M + m] = o[k];
+    if (out.node_slots) out.node_slots[(long long)q * M + m] = src.cand(p, c, r.N, ci);
+}
 
 // Shape rules shared by the device and host entry points.
 inline bool recipe_ok(const usip_pairs_recipe* r)

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .pairs import PairBuilder, ScanBank, epoch_batches, epoch_order            # noqa: F401  (re-exported)
+from .pairs import ScanBank, _CloudBuilder, epoch_batches, epoch_order          # noqa: F401  (re-exported)
 
 KEYS = ops.DESC_PAIRS_KEYS
 
@@ -218,7 +218,7 @@ def empty_batch(c: ops.DescPairsRecipeC, pairs: int, device) -> Dict[str, torch.
             for k, (shape, dt) in ops.desc_pairs_shapes(c, pairs).items()}
 
 
-class DescriptorPairBuilder:
+class DescriptorPairBuilder(_CloudBuilder):
     """P (anchor, positive) pairs per call, with the negatives mined among the call's own P anchors.
 
     Negatives are mined within the rank's own P pairs: data parallel shards the pairs, as everywhere in this project,
@@ -231,37 +231,29 @@ class DescriptorPairBuilder:
     prefetch(schedule): double-buffered, batch k+1 built on a side stream while the consumer runs batch k.
     build / apply use one workspace, each prefetch buffer one of its own."""
 
+    _workspace_bytes = staticmethod(ops.desc_pairs_workspace_bytes)
+    _workspace_offset = staticmethod(ops.desc_pairs_workspace_offset)
+
     def __init__(self, bank: PosedScanBank, recipe: DescriptorPairRecipe, pairs: int, device=None, seed: int = 0,
                  rank: int = 0, mode: str = "train"):
-        if mode not in ("train", "test"):
-            raise ValueError("DescriptorPairBuilder: mode is 'train' or 'test'")
-        self.bank, self.recipe, self.pairs = bank, recipe, int(pairs)
-        self.device = torch.device(device) if device is not None else bank.device
-        self.seed, self.rank, self.mode = int(seed), int(rank), mode
-        self.c = recipe.c_struct(mode == "train")
-        if bank.min_rows < recipe.N:
-            raise ValueError("DescriptorPairBuilder: every scan needs at least N = %d rows; the bank's shortest has %d"
-                             % (recipe.N, bank.min_rows))
-        if recipe.mine and self.pairs < 2:
-            raise ValueError("DescriptorPairBuilder: mining negatives needs at least 2 pairs per call")
-        # [0]: build / apply, [1], [2]: the two prefetch buffers
-        self._ws = [torch.empty(ops.desc_pairs_workspace_bytes(self.c, self.pairs), dtype=torch.uint8, device=self.device)
-                    for _ in range(3)]
+        super().__init__(bank, recipe, pairs, device, seed, rank, mode)
         self._bank = bank.c_dict()
-        self.last_rows = self.last_node_slots = None
 
-    _ids = PairBuilder._ids                                   # the same checks of the scan ids, the same pinned upload
+    def _check(self):
+        if self.bank.min_rows < self.recipe.N:
+            raise ValueError("DescriptorPairBuilder: every scan needs at least N = %d rows; the bank's shortest has %d"
+                             % (self.recipe.N, self.bank.min_rows))
+        if self.recipe.mine and self.pairs < 2:
+            raise ValueError("DescriptorPairBuilder: mining negatives needs at least 2 pairs per call")
+
+    def _empty_batch(self):
+        return empty_batch(self.c, self.pairs, self.device)
 
     def _out(self, out, with_indices):
-        full = empty_batch(self.c, self.pairs, self.device) if out is None or any(k not in out for k in KEYS) else {}
+        full = self._empty_batch() if out is None or any(k not in out for k in KEYS) else {}
         if out is not None:
             full.update({k: out[k] for k in KEYS if k in out})
-        rows = nodes = None
-        if with_indices:
-            rows = torch.empty((2, self.pairs, self.recipe.N), dtype=torch.int32, device=self.device)
-            nodes = torch.empty((2, self.pairs, self.recipe.M), dtype=torch.int32, device=self.device)
-        self.last_rows, self.last_node_slots = rows, nodes
-        return full, rows, nodes
+        return (full,) + self._index_out(with_indices)
 
     def build(self, scan_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
               _ws: int = 0) -> Dict[str, torch.Tensor]:
@@ -277,26 +269,16 @@ class DescriptorPairBuilder:
         ops.desc_pairs_apply(self.c, d, self._bank, self._ids(scan_ids), out, self._ws[0], rows, nodes)
         return out
 
-    def workspace_candidates(self, which: int = 0):
-        """The un-augmented FPS candidates [2P, 3, n_sub] and first indices [2P] in workspace `which` (0: the last build
-        or apply), at the offsets the library reports (usip_desc_pairs_workspace_offset)."""
-        P, ns = self.pairs, self.recipe.n_sub
-        ws = self._ws[which]
-        o_c, o_f = ops.desc_pairs_workspace_offset(self.c, P, 1), ops.desc_pairs_workspace_offset(self.c, P, 2)
-        cand = ws[o_c:o_c + 2 * P * 3 * ns * 4].view(torch.float32).view(2 * P, 3, ns)
-        first = ws[o_f:o_f + 2 * P * 4].view(torch.int32)
-        return cand, first
-
     def prefetch(self, schedule: Iterable, outs=None):
-        """schedule: iterable of (scan_ids, step).  PairBuilder.prefetch's own loop drives this builder (the same two
+        """schedule: iterable of (scan_ids, step).  The shared prefetch loop drives this builder (the same two
         buffers, 'built' / 'consumed' events and side stream): the consumer's stream waits for 'built', the side stream
         for 'consumed', the host never waits, and leaving the loop early (break, an exception, closing the generator)
         makes the current stream wait for every build still in flight, so reusing `outs` or the memory afterwards is
         ordered after the last write.  The two buffers allocated here live until the generator is gone, i.e. past that
         wait, and go back to the current stream's pool.  A yielded batch is valid until the next iteration."""
         if outs is None:
-            outs = [empty_batch(self.c, self.pairs, self.device) for _ in range(2)]
-        yield from PairBuilder.prefetch(self, schedule, outs)
+            outs = [self._empty_batch() for _ in range(2)]
+        yield from super().prefetch(schedule, outs)
 
 
 _DRAW_NP = {k: (np.int32 if dt == torch.int32 else np.float64) for k, dt in ops.DESC_PAIRS_DRAWS.items()}

@@ -1297,14 +1297,44 @@ class PairsOutC(ctypes.Structure):
 PAIRS_KEYS = ("src_pc", "src_sn", "src_node", "dst_pc", "dst_sn", "dst_node", "R", "scale", "shift")
 
 
-def _pairs_out(out: dict, rows, node_slots) -> PairsOutC:
-    o = PairsOutC()
-    for i, side in enumerate(("src", "dst")):
-        o.pc[i], o.sn[i], o.node[i] = (out[side + "_" + k].data_ptr() for k in ("pc", "sn", "node"))
-    o.R, o.scale, o.shift = out["R"].data_ptr(), out["scale"].data_ptr(), out["shift"].data_ptr()
-    o.rows = rows.data_ptr() if rows is not None else None
-    o.node_slots = node_slots.data_ptr() if node_slots is not None else None
+def _data_ptr(t):
+    return t.data_ptr()
+
+
+def _clouds_out(o, ptr, out: dict, sides, rest, rows, node_slots):
+    """Fill an out struct of either builder: the two clouds' pc / sn / node, the fields `rest`, the optional indices.
+    ptr: tensor or array -> address (device tensors here, numpy arrays for the host twins)."""
+    for i, side in enumerate(sides):
+        o.pc[i], o.sn[i], o.node[i] = (ptr(out[side + "_" + k]) for k in ("pc", "sn", "node"))
+    for k in rest:
+        setattr(o, k, ptr(out[k]))
+    o.rows = ptr(rows) if rows is not None else None
+    o.node_slots = ptr(node_slots) if node_slots is not None else None
     return o
+
+
+def _pairs_out(ptr, out: dict, rows, node_slots) -> PairsOutC:
+    return _clouds_out(PairsOutC(), ptr, out, ("src", "dst"), PAIRS_KEYS[6:], rows, node_slots)
+
+
+def _check_workspace_and_indices(tag: str, cloud: PairsRecipeC, P: int, device, workspace, need: int, rows, node_slots):
+    """What the two builders check alike: the workspace's size and the optional index outputs, all on `device`."""
+    if workspace.device != device or workspace.numel() * workspace.element_size() < need:
+        raise RuntimeError("%s: the workspace must hold usip_%s_workspace_bytes() bytes on %s" % (tag, tag, device))
+    for name, t, n in (("rows", rows, cloud.N), ("node_slots", node_slots, cloud.M)):
+        if t is not None:
+            _need(t, name, torch.int32)
+            if tuple(t.shape) != (2, P, n) or t.device != device:
+                raise RuntimeError("%s: %s must be i32 (2, %d, %d) on %s" % (tag, name, P, n, device))
+
+
+def _workspace_query(symbol: str, recipe, P: int, part=None) -> int:
+    """usip_*_workspace_bytes, or with `part` usip_*_workspace_offset."""
+    args = (ctypes.addressof(recipe), int(P)) + (() if part is None else (int(part),))
+    n = int(getattr(_lib.lib(), symbol)(*args))
+    if n < 0:
+        raise RuntimeError("usip_amd: %s: invalid recipe%s (USIP_EINVAL)" % (symbol, "" if part is None else " or part"))
+    return n
 
 
 def _pairs_check_out(recipe: PairsRecipeC, out: dict, P: int, device, scan_ids, rows, node_slots, workspace):
@@ -1319,13 +1349,7 @@ def _pairs_check_out(recipe: PairsRecipeC, out: dict, P: int, device, scan_ids, 
             raise RuntimeError("pairs: %s must be f32 %s on %s" % (k, shapes[k.replace("dst_", "src_")], device))
     if scan_ids.device != device:
         raise RuntimeError("pairs: scan_ids on %s, the bank on %s" % (scan_ids.device, device))
-    if workspace.device != device or workspace.numel() * workspace.element_size() < pairs_workspace_bytes(recipe, P):
-        raise RuntimeError("pairs: the workspace must hold usip_pairs_workspace_bytes() bytes on %s" % device)
-    for name, t, n in (("rows", rows, recipe.N), ("node_slots", node_slots, recipe.M)):
-        if t is not None:
-            _need(t, name, torch.int32)
-            if tuple(t.shape) != (2, P, n) or t.device != device:
-                raise RuntimeError("pairs: %s must be i32 (2, %d, %d) on %s" % (name, P, n, device))
+    _check_workspace_and_indices("pairs", recipe, P, device, workspace, pairs_workspace_bytes(recipe, P), rows, node_slots)
 
 
 def pairs_build(recipe: PairsRecipeC, bank: torch.Tensor, offsets: torch.Tensor, scan_ids: torch.Tensor, min_rows: int,
@@ -1336,7 +1360,7 @@ def pairs_build(recipe: PairsRecipeC, bank: torch.Tensor, offsets: torch.Tensor,
     _need(scan_ids, "scan_ids", torch.int32)
     P = scan_ids.numel()
     _pairs_check_out(recipe, out, P, bank.device, scan_ids, rows, node_slots, workspace)
-    o = _pairs_out(out, rows, node_slots)
+    o = _pairs_out(_data_ptr, out, rows, node_slots)
     with torch.cuda.device(bank.device), prof.kernel("pairs_build", 2.0 * P * recipe.N * (32 + 4 * (3 + recipe.Cs))):
         _lib.check(_lib.lib().usip_pairs_build_f32(
             ctypes.addressof(recipe), _ptr(bank), _ptr(offsets), offsets.numel() - 1, _ptr(scan_ids), P, int(min_rows),
@@ -1362,7 +1386,7 @@ def pairs_apply(recipe: PairsRecipeC, draws: dict, bank: torch.Tensor, offsets: 
             if t.device != bank.device:
                 raise RuntimeError("pairs: draw %s on %s, the bank on %s" % (k[0], t.device, bank.device))
             setattr(d, k[0], t.data_ptr())
-    o = _pairs_out(out, rows, node_slots)
+    o = _pairs_out(_data_ptr, out, rows, node_slots)
     with torch.cuda.device(bank.device), prof.kernel("pairs_apply", 2.0 * P * recipe.N * (32 + 4 * (3 + recipe.Cs))):
         _lib.check(_lib.lib().usip_pairs_apply_f32(
             ctypes.addressof(recipe), ctypes.addressof(d), _ptr(bank), _ptr(offsets), offsets.numel() - 1,
@@ -1372,17 +1396,11 @@ def pairs_apply(recipe: PairsRecipeC, draws: dict, bank: torch.Tensor, offsets: 
 
 def pairs_workspace_offset(recipe: PairsRecipeC, P: int, part: int) -> int:
     """Byte offset of workspace part 0 table, 1 candidates, 2 first indices, 3 FPS picks, 4 total (include/usip_hip.h)."""
-    n = int(_lib.lib().usip_pairs_workspace_offset(ctypes.addressof(recipe), int(P), int(part)))
-    if n < 0:
-        raise RuntimeError("usip_amd: usip_pairs_workspace_offset: invalid recipe or part (USIP_EINVAL)")
-    return n
+    return _workspace_query("usip_pairs_workspace_offset", recipe, P, part)
 
 
 def pairs_workspace_bytes(recipe: PairsRecipeC, P: int) -> int:
-    n = int(_lib.lib().usip_pairs_workspace_bytes(ctypes.addressof(recipe), int(P)))
-    if n < 0:
-        raise RuntimeError("usip_amd: usip_pairs_workspace_bytes: invalid recipe (USIP_EINVAL)")
-    return n
+    return _workspace_query("usip_pairs_workspace_bytes", recipe, P)
 
 
 # ------------------------------------------------------------------------------- f-8 descriptor batches from posed scans
@@ -1427,14 +1445,7 @@ def desc_pairs_shapes(recipe: DescPairsRecipeC, P: int) -> dict:
 
 def desc_pairs_out_struct(ptr, out: dict, rows, node_slots) -> DescPairsOutC:
     """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
-    o = DescPairsOutC()
-    for i, side in enumerate(("anc", "pos")):
-        o.pc[i], o.sn[i], o.node[i] = (ptr(out[side + "_" + k]) for k in ("pc", "sn", "node"))
-    for k in DESC_PAIRS_KEYS[6:]:
-        setattr(o, k, ptr(out[k]))
-    o.rows = ptr(rows) if rows is not None else None
-    o.node_slots = ptr(node_slots) if node_slots is not None else None
-    return o
+    return _clouds_out(DescPairsOutC(), ptr, out, ("anc", "pos"), DESC_PAIRS_KEYS[6:], rows, node_slots)
 
 
 def _desc_pairs_check(recipe: DescPairsRecipeC, bank: dict, scan_ids, out: dict, rows, node_slots, workspace):
@@ -1461,13 +1472,8 @@ def _desc_pairs_check(recipe: DescPairsRecipeC, bank: dict, scan_ids, out: dict,
         _need(out[k], k, dt)
         if tuple(out[k].shape) != shape or out[k].device != dev:
             raise RuntimeError("desc_pairs: %s must be %s %s on %s" % (k, dt, shape, dev))
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < desc_pairs_workspace_bytes(recipe, P):
-        raise RuntimeError("desc_pairs: the workspace must hold usip_desc_pairs_workspace_bytes() bytes on %s" % dev)
-    for name, t, n in (("rows", rows, recipe.cloud.N), ("node_slots", node_slots, recipe.cloud.M)):
-        if t is not None:
-            _need(t, name, torch.int32)
-            if tuple(t.shape) != (2, P, n) or t.device != dev:
-                raise RuntimeError("desc_pairs: %s must be i32 (2, %d, %d) on %s" % (name, P, n, dev))
+    _check_workspace_and_indices("desc_pairs", recipe.cloud, P, dev, workspace, desc_pairs_workspace_bytes(recipe, P), rows,
+                                 node_slots)
     b = DescPairsBankC()
     for k in ("rows", "offsets", "poses", "seq_of", "seq_start"):
         setattr(b, k, bank[k].data_ptr())
@@ -1485,7 +1491,7 @@ def desc_pairs_build(recipe: DescPairsRecipeC, bank: dict, scan_ids: torch.Tenso
     """f-8: P descriptor pairs with Philox draws (usip_desc_pairs_build_f32) into `out` (DESC_PAIRS_KEYS -> tensors).
     bank: rows, offsets, poses, seq_of, seq_start (device tensors), seq_start_host (int32 numpy), min_rows."""
     P, b = _desc_pairs_check(recipe, bank, scan_ids, out, rows, node_slots, workspace)
-    o = desc_pairs_out_struct(lambda t: t.data_ptr(), out, rows, node_slots)
+    o = desc_pairs_out_struct(_data_ptr, out, rows, node_slots)
     dev = bank["rows"].device
     with torch.cuda.device(dev), prof.kernel("desc_pairs_build", _desc_pairs_bytes(recipe, P)):
         _lib.check(_lib.lib().usip_desc_pairs_build_f32(
@@ -1519,8 +1525,8 @@ def desc_pairs_apply(recipe: DescPairsRecipeC, draws: dict, bank: dict, scan_ids
     tries = draws.get("tries")
     if tries is None or tries.dim() != 2 or tries.shape[0] != P:
         raise RuntimeError("desc_pairs: draw tries must be i32 (%d, T)" % P)
-    d = desc_pairs_draws_struct(lambda t: t.data_ptr(), draws, tries.shape[1])
-    o = desc_pairs_out_struct(lambda t: t.data_ptr(), out, rows, node_slots)
+    d = desc_pairs_draws_struct(_data_ptr, draws, tries.shape[1])
+    o = desc_pairs_out_struct(_data_ptr, out, rows, node_slots)
     with torch.cuda.device(dev), prof.kernel("desc_pairs_apply", _desc_pairs_bytes(recipe, P)):
         _lib.check(_lib.lib().usip_desc_pairs_apply_f32(
             ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(scan_ids), P, ctypes.addressof(o),
@@ -1530,17 +1536,11 @@ def desc_pairs_apply(recipe: DescPairsRecipeC, draws: dict, bank: dict, scan_ids
 
 def desc_pairs_workspace_offset(recipe: DescPairsRecipeC, P: int, part: int) -> int:
     """Byte offset of workspace part 0 tables, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud scan ids, 5 total."""
-    n = int(_lib.lib().usip_desc_pairs_workspace_offset(ctypes.addressof(recipe), int(P), int(part)))
-    if n < 0:
-        raise RuntimeError("usip_amd: usip_desc_pairs_workspace_offset: invalid recipe or part (USIP_EINVAL)")
-    return n
+    return _workspace_query("usip_desc_pairs_workspace_offset", recipe, P, part)
 
 
 def desc_pairs_workspace_bytes(recipe: DescPairsRecipeC, P: int) -> int:
-    n = int(_lib.lib().usip_desc_pairs_workspace_bytes(ctypes.addressof(recipe), int(P)))
-    if n < 0:
-        raise RuntimeError("usip_amd: usip_desc_pairs_workspace_bytes: invalid recipe (USIP_EINVAL)")
-    return n
+    return _workspace_query("usip_desc_pairs_workspace_bytes", recipe, P)
 
 
 # ------------------------------------------------------------------------------------------------ f-6 evaluation

@@ -200,30 +200,22 @@ def empty_batch(recipe: PairRecipe, pairs: int, device) -> Dict[str, torch.Tenso
     return {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in KEYS}
 
 
-class PairBuilder:
-    """P pairs per call, written as DetectorStep.step consumes them (synth.make_pair_batch's shapes and dtypes).
+class _CloudBuilder:
+    """What PairBuilder and desc_pairs.DescriptorPairBuilder share: the bookkeeping, the upload of the scan ids, the
+    optional index outputs, three workspaces ([0]: build / apply, [1], [2]: the two prefetch buffers) and prefetch.
+    A builder supplies its library's workspace functions, _check (its refusals), _empty_batch and build."""
 
-    build(scan_ids, step, out=None): Philox draws; `out` (e.g. st.static_batch(batch)) is written in place.
-    apply(scan_ids, draws, out=None): the recorded draws of the reference (tests).
-    prefetch(schedule): double-buffered, batch k+1 built on a side stream while the consumer runs batch k.
-    build / apply use one workspace, each prefetch buffer one of its own, so a build on the current stream never races
-    a live prefetch; two builds on two different streams at once are the caller's to order."""
+    _workspace_bytes = _workspace_offset = None              # ops functions of (recipe struct, P[, part])
 
-    epoch_order = staticmethod(epoch_order)
-
-    def __init__(self, bank: ScanBank, recipe: PairRecipe, pairs: int, device=None, seed: int = 0, rank: int = 0,
-                 mode: str = "train"):
+    def __init__(self, bank, recipe, pairs: int, device=None, seed: int = 0, rank: int = 0, mode: str = "train"):
         if mode not in ("train", "test"):
-            raise ValueError("PairBuilder: mode is 'train' or 'test'")
+            raise ValueError("%s: mode is 'train' or 'test'" % type(self).__name__)
         self.bank, self.recipe, self.pairs = bank, recipe, int(pairs)
         self.device = torch.device(device) if device is not None else bank.device
         self.seed, self.rank, self.mode = int(seed), int(rank), mode
         self.c = recipe.c_struct(mode == "train")
-        if recipe.require_full and bank.min_rows < recipe.N:
-            raise ValueError("PairBuilder: this recipe needs scans of at least N = %d rows; the bank's shortest has %d"
-                             % (recipe.N, bank.min_rows))
-        # [0]: build / apply, [1], [2]: the two prefetch buffers
-        self._ws = [torch.empty(ops.pairs_workspace_bytes(self.c, self.pairs), dtype=torch.uint8, device=self.device)
+        self._check()
+        self._ws = [torch.empty(self._workspace_bytes(self.c, self.pairs), dtype=torch.uint8, device=self.device)
                     for _ in range(3)]
         self.last_rows = self.last_node_slots = None
 
@@ -241,35 +233,20 @@ class PairBuilder:
             raise ValueError("PairBuilder: %d scan ids for %d pairs" % (ids.numel(), self.pairs))
         return ids
 
-    def _out(self, out, with_indices):
-        out = out if out is not None else empty_batch(self.recipe, self.pairs, self.device)
+    def _index_out(self, with_indices):
         rows = nodes = None
         if with_indices:
             rows = torch.empty((2, self.pairs, self.recipe.N), dtype=torch.int32, device=self.device)
             nodes = torch.empty((2, self.pairs, self.recipe.M), dtype=torch.int32, device=self.device)
         self.last_rows, self.last_node_slots = rows, nodes
-        return out, rows, nodes
-
-    def build(self, scan_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
-              _ws: int = 0) -> Dict[str, torch.Tensor]:
-        out, rows, nodes = self._out(out, with_indices)
-        ops.pairs_build(self.c, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, self.seed,
-                        int(step), self.rank * self.pairs, out, self._ws[_ws], rows, nodes)
-        return out
-
-    def apply(self, scan_ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
-        out, rows, nodes = self._out(out, with_indices)
-        d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in draws.items() if v is not None}
-        ops.pairs_apply(self.c, d, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, out,
-                        self._ws[0], rows, nodes)
-        return out
+        return rows, nodes
 
     def workspace_candidates(self, which: int = 0):
         """The un-augmented FPS candidates [2P, 3, n_sub] and first indices [2P] in workspace `which` (0: the last build
-        or apply), at the offsets the library reports (usip_pairs_workspace_offset)."""
+        or apply), at the offsets the library reports (usip_pairs_workspace_offset, usip_desc_pairs_workspace_offset)."""
         P, ns = self.pairs, self.recipe.n_sub
         ws = self._ws[which]
-        o_c, o_f = ops.pairs_workspace_offset(self.c, P, 1), ops.pairs_workspace_offset(self.c, P, 2)
+        o_c, o_f = self._workspace_offset(self.c, P, 1), self._workspace_offset(self.c, P, 2)
         cand = ws[o_c:o_c + 2 * P * 3 * ns * 4].view(torch.float32).view(2 * P, 3, ns)
         first = ws[o_f:o_f + 2 * P * 4].view(torch.int32)
         return cand, first
@@ -287,7 +264,7 @@ class PairBuilder:
         cur = torch.cuda.current_stream(self.device)
         side = torch.cuda.Stream(self.device)
         if outs is None:
-            bufs = [empty_batch(self.recipe, self.pairs, self.device) for _ in range(2)]
+            bufs = [self._empty_batch() for _ in range(2)]
             for b in bufs:
                 for t in b.values():
                     t.record_stream(side)
@@ -328,6 +305,45 @@ class PairBuilder:
             cur.wait_stream(side)
 
 
+class PairBuilder(_CloudBuilder):
+    """P pairs per call, written as DetectorStep.step consumes them (synth.make_pair_batch's shapes and dtypes).
+
+    build(scan_ids, step, out=None): Philox draws; `out` (e.g. st.static_batch(batch)) is written in place.
+    apply(scan_ids, draws, out=None): the recorded draws of the reference (tests).
+    prefetch(schedule): double-buffered, batch k+1 built on a side stream while the consumer runs batch k.
+    build / apply use one workspace, each prefetch buffer one of its own, so a build on the current stream never races
+    a live prefetch; two builds on two different streams at once are the caller's to order."""
+
+    epoch_order = staticmethod(epoch_order)
+    _workspace_bytes = staticmethod(ops.pairs_workspace_bytes)
+    _workspace_offset = staticmethod(ops.pairs_workspace_offset)
+
+    def _check(self):
+        if self.recipe.require_full and self.bank.min_rows < self.recipe.N:
+            raise ValueError("PairBuilder: this recipe needs scans of at least N = %d rows; the bank's shortest has %d"
+                             % (self.recipe.N, self.bank.min_rows))
+
+    def _empty_batch(self):
+        return empty_batch(self.recipe, self.pairs, self.device)
+
+    def _out(self, out, with_indices):
+        return (out if out is not None else self._empty_batch(),) + self._index_out(with_indices)
+
+    def build(self, scan_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
+              _ws: int = 0) -> Dict[str, torch.Tensor]:
+        out, rows, nodes = self._out(out, with_indices)
+        ops.pairs_build(self.c, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, self.seed,
+                        int(step), self.rank * self.pairs, out, self._ws[_ws], rows, nodes)
+        return out
+
+    def apply(self, scan_ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
+        out, rows, nodes = self._out(out, with_indices)
+        d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in draws.items() if v is not None}
+        ops.pairs_apply(self.c, d, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, out,
+                        self._ws[0], rows, nodes)
+        return out
+
+
 def build_cpu(recipe: PairRecipe, scans: Sequence[np.ndarray], scan_ids, pairs: int, seed: int = 0, step: int = 0,
               rank: int = 0, mode: str = "train", draws: Optional[Dict[str, np.ndarray]] = None):
     """The host twin (usip_pairs_build_f32_cpu) on numpy scans: Philox draws, or `draws` (the layouts of
@@ -342,11 +358,7 @@ def build_cpu(recipe: PairRecipe, scans: Sequence[np.ndarray], scan_ids, pairs: 
         R=(P, 3, 3), scale=(P,), shift=(P, 3, 1)).items()}
     rows = np.zeros((2, P, N), dtype=np.int32)
     nodes = np.zeros((2, P, M), dtype=np.int32)
-    o = ops.PairsOutC()
-    for i, side in enumerate(("src", "dst")):
-        o.pc[i], o.sn[i], o.node[i] = (out[side + "_" + k].ctypes.data for k in ("pc", "sn", "node"))
-    o.R, o.scale, o.shift = out["R"].ctypes.data, out["scale"].ctypes.data, out["shift"].ctypes.data
-    o.rows, o.node_slots = rows.ctypes.data, nodes.ctypes.data
+    o = ops._pairs_out(lambda a: a.ctypes.data, out, rows, nodes)
     keep = []
     d = None
     if draws is not None:
