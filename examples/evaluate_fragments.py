@@ -12,7 +12,10 @@
         evaluates data laid out as the reference's scripts expect: <scenes>/<scene>/<i>.npy, <results>/<scene>/<i>.bin,
         <gt>/<scene>-evaluation/gt.log and gt.info.
 
-Prints ONE JSON line (what evaluate.m prints, per scene and as means) and writes <results>/<scene>.log as writeLog.m does;
+--registration ransac (default: register2Fragments.m) or fgr (eval_indoor/fgr/register2FragmentsFGR.m: Fast Global
+Registration on the mutual nearest descriptors, at most 1024 keypoints per fragment; --k and --trials are not used).
+
+Prints ONE JSON line (what evaluate.m prints, per scene and as means, and the registrator) and writes <results>/<scene>.log as writeLog.m does;
 with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
 import argparse
 import glob
@@ -48,7 +51,7 @@ def evaluate_scene(name, scenes, results, gt_root, args):
     rows = [fr.read_descriptors_bin(os.path.join(results, name, "%d.bin" % i), args.dim) for i in range(len(clouds))]
     top = max(len(x) for x, _ in rows)
     ev = fr.FragmentEvaluator(None, None, None, args.device, top=top, k=args.k, max_trials=args.trials, seed=args.seed,
-                              batch_pairs=args.batch_pairs)
+                              batch_pairs=args.batch_pairs, registrator=args.registration)
     for i, path in enumerate(clouds):
         ev.add_fragment_result(i, rows[i][0], rows[i][1], np.load(path))
     gt = fr.read_log(os.path.join(gt_root, "%s-evaluation" % name, "gt.log"))
@@ -79,6 +82,7 @@ def main():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--k", type=int, default=fr.K_MATCH)
     ap.add_argument("--trials", type=int, default=fr.MAX_TRIALS)
+    ap.add_argument("--registration", choices=("ransac", "fgr"), default="ransac")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch-pairs", type=int, default=32)
     ap.add_argument("--pair-files", action="store_true")
@@ -92,7 +96,7 @@ def main():
     else:
         ap.error("give --make-synthetic DIR, or --scenes, --results and --gt")
     per_scene = {n: evaluate_scene(n, scenes, results, gt, args) for n in names}
-    out = {"scenes": per_scene}
+    out = {"scenes": per_scene, "registration": args.registration}
     for k in ("recall", "precision", "inlier_num_mean", "inlier_ratio_mean"):          # evaluate.m's last line: means
         out[k] = float(np.mean([s[k] for s in per_scene.values()]))
     for k in ("pairs", "written"):

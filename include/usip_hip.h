@@ -966,6 +966,79 @@ int usip_iss_saliency_f32_cpu(const float* pc, const int32_t* count, int B, int 
 int usip_iss_nms_f32_cpu(const float* pc, const int32_t* count, const double* saliency, int B, int N, double non_max_radius,
                          int min_neighbors, uint8_t* keypoint, int num_threads);
 
+/* ------------------------------------------------------------------ f-12  Fast Global Registration of fragment pairs
+ * The second registrator of the reference's indoor evaluation (evaluation/matlab/eval_indoor/fgr/register2FragmentsFGR.m,
+ * computeAndVisualizeFGR.m): Fast Global Registration (Zhou, Park, Koltun, ECCV 2016).  The reference's
+ * fgr/fast_global_registration.cpp wraps an app.h it does not ship, so the definition below is this project's own, written
+ * from the paper and its published constants.  Float64 arithmetic on float32 inputs, never contracted, no floating-point
+ * atomics, every sum in the order stated here; csrc/fgr_math.h is the arithmetic.  The estimate maps fragment 2 into
+ * fragment 1, x1 = R x2 + t, as f-9's.
+ *
+ * Per pair: kp1, kp2 f32 [3][M] (finite values) with counts n1, n2 i32 (a count above M or below 0 behaves as M or 0);
+ * nn12 i32 [M]: for keypoint i of fragment 1 its nearest descriptor of fragment 2 (usip_knn_nd_counted_f32 with k = 1), nn21
+ * i32 [M] the converse.  1 <= M <= 1024, P <= 65535.
+ *
+ * usip_fgr_tuples_f32 / usip_fgr_tuples_explicit_f32:
+ *  1 mutual i32 [P][M][2]: the rows (i, nn12[i]) for ascending i < n1 with 0 <= nn12[i] < n2 and nn21[nn12[i]] == i, zeros
+ *    beyond mutual_count i32 [P] = nc <= M.  (FGR's two lazy lists followed by its cross-check reduce to exactly this set.)
+ *  2 norm f64 [P][8] = mean1[3], mean2[3], scale, 0.  A mean is over ALL n keypoints of its fragment, matched or not: lane l
+ *    of 256 adds its points l, l + 256, ... in ascending order, the 256 partial sums go through the binary tree part[l] +=
+ *    part[l + stride], stride = 128 .. 1, and the total is divided by n (0 for an empty fragment).  scale = the largest
+ *    sqrt((x x + y y) + z z) over both centred sets; u = (x - mean) / scale.  A scale that is 0 or not finite makes the pair
+ *    invalid: no trial is walked.
+ *  3 T = 100 nc trials.  Trial t takes three rows of the mutual list: perm(0), perm(1), perm(2) of a PairsPerm bijection on
+ *    [0, nc) keyed from the Philox4x64-10 block with key (seed, 0) and counter (t, 10 << 8, g, 0), g = pair_ids[p] (NULL: p)
+ *    -- f-6's keying under stream tag 10; a triple depends on (seed, g, t) only.  The explicit form reads triples i32
+ *    [P][T][3], clamped into [0, nc), and walks min(100 nc, T) trials.  The trial is accepted iff li 0.95 < lj && lj < li /
+ *    0.95 for each of the edges (0,1), (0,2), (1,2), li and lj the edge's lengths in normalised fragment 1 and 2 (a repeated
+ *    row gives li = lj = 0 and is refused).  The first 1000 accepted trials, in ascending t, each contribute their three rows
+ *    in draw order, duplicates stay: rows i32 [P][3000] (indices into the mutual list, zeros beyond row_count i32 [P]);
+ *    trials_walked i32 [P] = t + 1 of the trial that filled the cap, else the number of trials.  triples_out i32
+ *    [P][T_out][3], optional (NULL): the triples of the walked trials t < T_out; other entries are left untouched.
+ *
+ * usip_fgr_optimize_f32: the pair is invalid with a bad scale or fewer than 10 rows.  Otherwise graduated non-convexity:
+ * par = 1, (R, t) = (I, 0); iteration k = 0 .. 63: if k % 4 == 0 && par > 0.025 then par = par / 1.4; per row q = R u2 + t from
+ * the ORIGINAL normalised u2 and the accumulated transform, r = u1 - q, e = (r0 r0 + r1 r1) + r2 r2, w = par / (e + par), s =
+ * w w, Jacobian rows [0, -q2, q1, -1, 0, 0], [q2, 0, -q0, 0, -1, 0], [-q1, q0, 0, 0, 0, -1].  The 21 upper entries of A = sum s J'J
+ * and the 6 of b = sum s J'r are 27 sums, each taken as the means are (lane l of 256 its rows l, l + 256, ..., then the tree);
+ * six of them are sums of exact zeros and two repeat a third, so 19 are carried (csrc/fgr_math.h: sums_of_row has the
+ * expressions).  A = L L' column by column, inner sums subtracted in ascending index; a pivot that is not finite and positive
+ * makes the pair invalid.  x = -A^-1 b by forward and backward substitution; a component of x that is not finite, or |x0..2| >
+ * pi, makes the pair invalid.  Rd = Rz(x2) Ry(x1) Rx(x0) with the header's own fgr_sincos (a reduction by multiples of pi/2
+ * with rint, then fixed polynomials: host and device return the same bits, which libm's sin and the device's do not); R <- Rd
+ * R, t <- Rd t + x3..5.  Finally t_out = (t scale - R mean2) + mean1.  Rt f64 [P][3][4], valid u8 [P]; an invalid pair gets
+ * [I | 0], valid 0, an empty mask and 0 inliers, as f-9's RANSAC.  inlier_mask u8 [P][M] over the MUTUAL rows (not the tuple
+ * rows): f-6's euc3Ddist under the estimate < threshold (0.2 in the evaluation), zeros beyond nc; inliers i32 [P] its count.
+ *
+ * USIP_EINVAL: a shape outside the limits, T or T_out < 1 with its array given, a NULL among the required pointers. */
+int usip_fgr_tuples_f32(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* nn12,
+                        const int32_t* nn21, int P, int M, uint64_t seed, const int64_t* pair_ids, int32_t* mutual,
+                        int32_t* mutual_count, double* norm, int32_t* rows, int32_t* row_count, int32_t* trials_walked,
+                        int32_t* triples_out, int T_out, void* stream);
+int usip_fgr_tuples_explicit_f32(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2,
+                                 const int32_t* nn12, const int32_t* nn21, int P, int M, const int32_t* triples, int T,
+                                 int32_t* mutual, int32_t* mutual_count, double* norm, int32_t* rows, int32_t* row_count,
+                                 int32_t* trials_walked, void* stream);
+int usip_fgr_optimize_f32(const float* kp1, const float* kp2, const int32_t* mutual, const int32_t* mutual_count,
+                          const double* norm, const int32_t* rows, const int32_t* row_count, int P, int M, double threshold,
+                          double* Rt, uint8_t* valid, uint8_t* inlier_mask, int32_t* inliers, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order, the trials as the sequential loop;
+ * num_threads splits the pairs.  usip_fgr_tuples_f32_cpu takes either source of draws (triples NULL: Philox). */
+int usip_fgr_tuples_f32_cpu(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2, const int32_t* nn12,
+                            const int32_t* nn21, int P, int M, uint64_t seed, const int64_t* pair_ids, const int32_t* triples,
+                            int T, int32_t* mutual, int32_t* mutual_count, double* norm, int32_t* rows, int32_t* row_count,
+                            int32_t* trials_walked, int32_t* triples_out, int T_out, int num_threads);
+int usip_fgr_tuples_explicit_f32_cpu(const float* kp1, const float* kp2, const int32_t* n1, const int32_t* n2,
+                                     const int32_t* nn12, const int32_t* nn21, int P, int M, const int32_t* triples, int T,
+                                     int32_t* mutual, int32_t* mutual_count, double* norm, int32_t* rows, int32_t* row_count,
+                                     int32_t* trials_walked, int num_threads);
+int usip_fgr_optimize_f32_cpu(const float* kp1, const float* kp2, const int32_t* mutual, const int32_t* mutual_count,
+                              const double* norm, const int32_t* rows, const int32_t* row_count, int P, int M,
+                              double threshold, double* Rt, uint8_t* valid, uint8_t* inlier_mask, int32_t* inliers,
+                              int num_threads);
+/* The contract's sine and cosine of n HOST doubles, |x| <= pi (csrc/fgr_math.h: fgr_sincos), for tests of its accuracy. */
+int usip_fgr_sincos_f64_cpu(const double* x, int n, double* sin_out, double* cos_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,20 @@ SIGNATURES = {
     "usip_iss_nms_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _stream], _int),
     "usip_iss_saliency_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, _dbl, _dbl, _int, ctypes.c_void_p, _i32p, _int], _int),
     "usip_iss_nms_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _int], _int),
+    # f-12 Fast Global Registration: mutual rows, normalisation, tuple test; the optimisation (usip_amd/fragments.py)
+    "usip_fgr_tuples_f32": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, ctypes.c_uint64, ctypes.c_void_p, _i32p, _i32p,
+                            ctypes.c_void_p, _i32p, _i32p, _i32p, _i32p, _int, _stream], _int),
+    "usip_fgr_tuples_explicit_f32": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, _i32p, _int, _i32p, _i32p, ctypes.c_void_p,
+                                     _i32p, _i32p, _i32p, _stream], _int),
+    "usip_fgr_optimize_f32": ([_f32p, _f32p, _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _dbl]
+                              + [ctypes.c_void_p] * 3 + [_i32p, _stream], _int),
+    "usip_fgr_tuples_f32_cpu": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, ctypes.c_uint64, ctypes.c_void_p, _i32p, _int,
+                                _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _i32p, _i32p, _int, _int], _int),
+    "usip_fgr_tuples_explicit_f32_cpu": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, _i32p, _int, _i32p, _i32p,
+                                         ctypes.c_void_p, _i32p, _i32p, _i32p, _int], _int),
+    "usip_fgr_optimize_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _dbl]
+                                  + [ctypes.c_void_p] * 3 + [_i32p, _int], _int),
+    "usip_fgr_sincos_f64_cpu": ([ctypes.c_void_p, _int, ctypes.c_void_p, ctypes.c_void_p], _int),
 }
 
 

@@ -6,6 +6,8 @@ mrEvaluateRegistrationMy.m).
   match_descriptors_topk   pdist2(b, a, 'euclidean', 'smallest', k) on ragged batches
   match_union              union([i, nn12(i, :)], [nn21(q, :), q], 'rows')
   fragment_registration    ransacfitRt on up to 10240 correspondences (threshold 0.2, ransac.m's default 30000 trials)
+  fgr_registration         Fast Global Registration (eval_indoor/fgr/register2FragmentsFGR.m; Zhou, Park, Koltun 2016) on the
+                           mutual nearest descriptors: tuple test, 64 Gauss-Newton steps (csrc/fgr.hip)
   information_matrix       the 6 x 6 sum of A'A over the inliers' fragment-1 keypoints
   overlap_ratio            ratioAligned: the share of each full fragment with a point of the other closer than 0.2 m
   *_cpu                    the same on numpy arrays over the library's host twins (csrc/fragments_cpu.cpp; RANSAC:
@@ -32,6 +34,8 @@ FragmentResult = namedtuple("FragmentResult",
                             "Rt inliers inlier_mask trialcount valid delta_t delta_deg chosen counts inlier_ratio")
 LogEntry = namedtuple("LogEntry", "info trans")                               # gt.log: (i, j, n), 4 x 4
 InfoEntry = namedtuple("InfoEntry", "info mat")                               # gt.info: (i, j, n), 6 x 6
+FgrResult = namedtuple("FgrResult", "Rt inliers inlier_mask valid delta_t delta_deg counts inlier_ratio mutual rows row_count "
+                                    "trials_walked")
 ResultEntry = namedtuple("ResultEntry", "info trans inlier_num inlier_ratio information")
 PairFile = namedtuple("PairFile", "fragment1 fragment2 inlier_num inlier_ratio ratio_aligned trans information")
 
@@ -72,6 +76,26 @@ def fragment_registration(x1, x2, count, threshold: float = INLIER_THRESHOLD, ma
     o = ops.ransac_select_large(x1, x2, count, counts, min(int(max_trials), T - 1), threshold, seed, pair_ids, triplets)
     eye = torch.eye(3, 4, dtype=torch.float64, device=x1.device)
     return _finish(o, count.to(torch.float64), counts, eye)
+
+
+def _finish_fgr(t, o, lib_np):
+    count = t["mutual_count"]
+    ratio = o["inliers"] / (np.maximum(count, 1) if lib_np else torch.clamp(count, min=1).to(torch.float64))
+    return FgrResult(o["Rt"], o["inliers"], o["inlier_mask"], o["valid"], None, None, count, ratio, t["mutual"], t["rows"],
+                     t["row_count"], t["trials_walked"])
+
+
+def fgr_registration(kp1, kp2, n1, n2, nn12, nn21, threshold: float = INLIER_THRESHOLD, seed: int = 0, pair_ids=None,
+                     triples=None) -> FgrResult:
+    """x1 = R x2 + t by Fast Global Registration from the keypoints kp1, kp2 f32 [P,3,M] (M <= 1024) with counts n1, n2 i32
+    [P] and the nearest descriptors nn12, nn21 i32 [P,M] of match_descriptors_topk(k = 1) in both directions.  The fields of
+    fragment_registration without trialcount and chosen, plus mutual i32 [P,M,2] (the mutual nearest rows, `counts` of them
+    per pair), rows i32 [P,3000] with row_count (the tuple test's rows, indices into mutual) and trials_walked.  inlier_mask
+    u8 [P,M] and inlier_ratio = inliers / counts are over the mutual rows.  An invalid pair (no scale, fewer than 10 rows, a
+    failed solve) gets [I | 0], 0 inliers and an empty mask.  Device tensors, no host synchronisation."""
+    t = ops.fgr_tuples(kp1, kp2, n1, n2, nn12, nn21, seed, pair_ids, triples)
+    o = ops.fgr_optimize(kp1, kp2, t["mutual"], t["mutual_count"], t["norm"], t["rows"], t["row_count"], threshold)
+    return _finish_fgr(t, o, False)
 
 
 def information_matrix(x1, inlier_mask):
@@ -167,6 +191,62 @@ def fragment_registration_cpu(x1, x2, count, threshold: float = INLIER_THRESHOLD
     return _finish(o, np.asarray(count, np.float64), counts, np.eye(3, 4))
 
 
+def fgr_tuples_cpu(kp1, kp2, n1, n2, nn12, nn21, seed: int = 0, pair_ids=None, triples=None, want_triples: int = 0,
+                   num_threads: int = 1) -> Dict[str, np.ndarray]:
+    """ops.fgr_tuples on numpy arrays over the host twin."""
+    a, b = _np(kp1, np.float32, "kp1"), _np(kp2, np.float32, "kp2")
+    if a.ndim != 3 or a.shape[1] != 3 or b.shape != a.shape:
+        raise ValueError("expected kp1, kp2 [P,3,M]")
+    P, _, M = a.shape
+    if not (1 <= M <= ops.FGR_MMAX and P <= 65535):                        # the device entries' rule and error
+        raise RuntimeError("fgr: M must be in 1..%d and P at most 65535 (got P = %d, M = %d)" % (ops.FGR_MMAX, P, M))
+    c1, c2 = _np(n1, np.int32, "n1", (P,)), _np(n2, np.int32, "n2", (P,))
+    f12 = _np(np.reshape(nn12, (P, -1)), np.int32, "nn12", (P, M))
+    f21 = _np(np.reshape(nn21, (P, -1)), np.int32, "nn21", (P, M))
+    ids = None if pair_ids is None else _np(pair_ids, np.int64, "pair_ids", (P,))
+    tr = None if triples is None else _np(triples, np.int32, "triples")
+    if tr is not None and (tr.ndim != 3 or tr.shape[0] != P or tr.shape[1] < 1 or tr.shape[2] != 3):
+        raise ValueError("triples must be i32 [P,T,3]")
+    out = {"mutual": np.zeros((P, M, 2), np.int32), "mutual_count": np.zeros(P, np.int32), "norm": np.zeros((P, 8)),
+           "rows": np.zeros((P, ops.FGR_ROWS_MAX), np.int32), "row_count": np.zeros(P, np.int32),
+           "trials_walked": np.zeros(P, np.int32),
+           "triples": np.zeros((P, int(want_triples), 3), np.int32) if want_triples and tr is None else None}
+    _lib.check(_lib.lib().usip_fgr_tuples_f32_cpu(
+        _p(a), _p(b), _p(c1), _p(c2), _p(f12), _p(f21), P, M, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(ids), _p(tr),
+        tr.shape[1] if tr is not None else 0, _p(out["mutual"]), _p(out["mutual_count"]), _p(out["norm"]), _p(out["rows"]),
+        _p(out["row_count"]), _p(out["trials_walked"]), _p(out["triples"]), int(want_triples), int(num_threads)),
+        "usip_fgr_tuples_f32_cpu")
+    return out
+
+
+def fgr_optimize_cpu(kp1, kp2, mutual, mutual_count, norm, rows, row_count, threshold: float = INLIER_THRESHOLD,
+                     num_threads: int = 1) -> Dict[str, np.ndarray]:
+    """ops.fgr_optimize on numpy arrays over the host twin."""
+    a, b = _np(kp1, np.float32, "kp1"), _np(kp2, np.float32, "kp2")
+    if a.ndim != 3 or a.shape[1] != 3 or b.shape != a.shape:
+        raise ValueError("expected kp1, kp2 [P,3,M]")
+    P, _, M = a.shape
+    if not (1 <= M <= ops.FGR_MMAX and P <= 65535):
+        raise RuntimeError("fgr: M must be in 1..%d and P at most 65535 (got P = %d, M = %d)" % (ops.FGR_MMAX, P, M))
+    mu, mc = _np(mutual, np.int32, "mutual", (P, M, 2)), _np(mutual_count, np.int32, "mutual_count", (P,))
+    nm, rw = _np(norm, np.float64, "norm", (P, 8)), _np(rows, np.int32, "rows", (P, ops.FGR_ROWS_MAX))
+    rc = _np(row_count, np.int32, "row_count", (P,))
+    out = {"Rt": np.zeros((P, 3, 4)), "valid": np.zeros(P, np.uint8), "inlier_mask": np.zeros((P, M), np.uint8),
+           "inliers": np.zeros(P, np.int32)}
+    _lib.check(_lib.lib().usip_fgr_optimize_f32_cpu(
+        _p(a), _p(b), _p(mu), _p(mc), _p(nm), _p(rw), _p(rc), P, M, float(threshold), _p(out["Rt"]), _p(out["valid"]),
+        _p(out["inlier_mask"]), _p(out["inliers"]), int(num_threads)), "usip_fgr_optimize_f32_cpu")
+    return out
+
+
+def fgr_registration_cpu(kp1, kp2, n1, n2, nn12, nn21, threshold: float = INLIER_THRESHOLD, seed: int = 0, pair_ids=None,
+                         triples=None, num_threads: int = 1) -> FgrResult:
+    t = fgr_tuples_cpu(kp1, kp2, n1, n2, nn12, nn21, seed, pair_ids, triples, 0, num_threads)
+    o = fgr_optimize_cpu(kp1, kp2, t["mutual"], t["mutual_count"], t["norm"], t["rows"], t["row_count"], threshold,
+                         num_threads)
+    return _finish_fgr(t, o, True)
+
+
 def information_matrix_cpu(x1, inlier_mask):
     x = _np(x1, np.float32, "x1")
     P, _, Nmax = x.shape
@@ -198,9 +278,28 @@ def overlap_ratio_cpu(bank: HostBank, frag1, frag2, Rt, radius: float = OVERLAP_
 # ------------------------------------------------------------------------------------------------ the per-pair pipeline
 def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                    threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
-                   seed: int = 0) -> Dict[str, torch.Tensor]:
+                   seed: int = 0, registrator: str = "ransac") -> Dict[str, torch.Tensor]:
     """register2Fragments.m for a batch of pairs, on the device: kp f32 [P,3,M], desc f32 [P,D,M], n i32 [P] of either
-    fragment; frag1, frag2 i32 [P] into the bank; pair_ids i64 [P] key the draws.  No host synchronisation."""
+    fragment; frag1, frag2 i32 [P] into the bank; pair_ids i64 [P] key the draws.  No host synchronisation.
+
+    registrator "fgr" is register2FragmentsFGR.m instead: the nearest descriptor in both directions (k = 1; `k` and
+    `max_trials` are not used) -> fgr_registration -> the information matrix over the mutual inliers -> the same overlap
+    walk and gate.  The reference's FGR wrapper hard-codes ratioAligned = 0.8 and inlierRatio = 0.99 and so writes every
+    pair to its log; here the gate sees the measured values, as for RANSAC.  Its keys: RANSAC's without trialcount and
+    chosen, plus row_count and trials_walked; matches counts the mutual rows."""
+    if registrator == "fgr":
+        nn12, _ = match_descriptors_topk(desc1, desc2, n1, n2, 1)
+        nn21, _ = match_descriptors_topk(desc2, desc1, n2, n1, 1)
+        reg = fgr_registration(kp1, kp2, n1, n2, nn12, nn21, threshold, seed, pair_ids)
+        x1 = torch.gather(kp1, 2, reg.mutual[:, :, 0].long().unsqueeze(1).expand(-1, 3, -1)).contiguous()
+        info = information_matrix(x1, reg.inlier_mask)
+        ratio, hits = overlap_ratio(bank, frag1, frag2, reg.Rt, radius)
+        gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
+        return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, valid=reg.valid, matches=reg.counts,
+                    row_count=reg.row_count, trials_walked=reg.trials_walked, information=info, ratio_aligned=ratio,
+                    overlap_hits=hits, gate=gate, frag1=frag1, frag2=frag2)
+    if registrator != "ransac":
+        raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
     nn12, _ = match_descriptors_topk(desc1, desc2, n1, n2, k)
     nn21, _ = match_descriptors_topk(desc2, desc1, n2, n1, k)
     pairs, count = match_union(nn12, nn21, n1, n2)
@@ -218,8 +317,22 @@ def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, fr
 
 def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                        threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
-                       seed: int = 0, num_threads: int = 1) -> Dict[str, np.ndarray]:
+                       seed: int = 0, num_threads: int = 1, registrator: str = "ransac") -> Dict[str, np.ndarray]:
     """register_pairs assembled from the host twins, on numpy arrays."""
+    if registrator == "fgr":
+        nn12, _ = match_descriptors_topk_cpu(desc1, desc2, n1, n2, 1, num_threads)
+        nn21, _ = match_descriptors_topk_cpu(desc2, desc1, n2, n1, 1, num_threads)
+        kp1, kp2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
+        reg = fgr_registration_cpu(kp1, kp2, n1, n2, nn12, nn21, threshold, seed, pair_ids, None, num_threads)
+        x1 = np.ascontiguousarray(np.take_along_axis(kp1, np.broadcast_to(reg.mutual[:, None, :, 0], kp1.shape), 2))
+        info = information_matrix_cpu(x1, reg.inlier_mask)
+        ratio, hits = overlap_ratio_cpu(bank, frag1, frag2, reg.Rt, radius, True, num_threads)
+        gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
+        return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, valid=reg.valid, matches=reg.counts,
+                    row_count=reg.row_count, trials_walked=reg.trials_walked, information=info, ratio_aligned=ratio,
+                    overlap_hits=hits, gate=gate, frag1=np.asarray(frag1, np.int32), frag2=np.asarray(frag2, np.int32))
+    if registrator != "ransac":
+        raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
     nn12, _ = match_descriptors_topk_cpu(desc1, desc2, n1, n2, k, num_threads)
     nn21, _ = match_descriptors_topk_cpu(desc2, desc1, n2, n1, k, num_threads)
     pairs, count = match_union_cpu(nn12, nn21, n1, n2)
@@ -413,7 +526,12 @@ class FragmentEvaluator:
 
     def __init__(self, detector, descriptor, opt, device, nms_radius: float = 0.1, top: int = 512, k: int = K_MATCH,
                  inlier_threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,
-                 overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32):
+                 overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32, registrator: str = "ransac"):
+        if registrator not in ("ransac", "fgr"):
+            raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
+        if registrator == "fgr" and int(top) > ops.FGR_MMAX:
+            raise ValueError("FragmentEvaluator: registrator 'fgr' takes at most %d keypoints per fragment" % ops.FGR_MMAX)
+        self.registrator = registrator
         self.detector, self.descriptor, self.opt = detector, descriptor, opt
         self.device = torch.device(device)
         self.nms_radius, self.top, self.k = float(nms_radius), int(top), int(k)
@@ -495,7 +613,7 @@ class FragmentEvaluator:
             a, b = f1.long(), f2.long()
             parts.append(register_pairs(kp[a], desc[a], cnt[a].contiguous(), kp[b], desc[b], cnt[b].contiguous(), bank, f1,
                                         f2, ids, self.k, self.inlier_threshold, self.max_trials, self.overlap_radius,
-                                        self.seed))
+                                        self.seed, self.registrator))
         if not parts:
             return {}
         return {key: torch.cat([p[key] for p in parts]) for key in parts[0]}

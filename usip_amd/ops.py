@@ -1923,3 +1923,82 @@ def iss_nms(pc, count, perm, saliency, non_max_radius: float, min_neighbors: int
                                                float(non_max_radius), int(min_neighbors), _ptr(kp), _stream(pc)),
                    "usip_iss_nms_f32")
     return kp
+
+
+# ------------------------------------------------------------------------------------------------ f-12 fast global registration
+FGR_MMAX, FGR_ROWS_MAX = 1024, 3000
+
+
+def _need_fgr(kp1, kp2, n1, n2):
+    _need(kp1, "kp1", torch.float32)
+    _need(kp2, "kp2", torch.float32)
+    if kp1.dim() != 3 or kp1.shape[1] != 3 or kp2.shape != kp1.shape or kp2.device != kp1.device:
+        raise RuntimeError("fgr: expected kp1, kp2 f32 [P,3,M] on one device")
+    P, _, M = kp1.shape
+    if not (1 <= M <= FGR_MMAX and P <= 65535):
+        raise RuntimeError("fgr: M must be in 1..%d and P at most 65535 (got P = %d, M = %d)" % (FGR_MMAX, P, M))
+    for t, name in ((n1, "n1"), (n2, "n2")):
+        if t is None:
+            raise RuntimeError("fgr: %s is required" % name)
+        _need_on(t, name, torch.int32, (P,), kp1.device)
+    return P, M
+
+
+def fgr_tuples(kp1, kp2, n1, n2, nn12, nn21, seed: int = 0, pair_ids=None, triples=None, want_triples: int = 0):
+    """f-12: kp1, kp2 f32 [P,3,M], n1, n2 i32 [P], nn12, nn21 i32 [P,M] (or [P,M,1]) -> dict(mutual i32 [P,M,2], mutual_count
+    i32 [P], norm f64 [P,8], rows i32 [P,3000], row_count, trials_walked i32 [P], triples i32 [P,want_triples,3] or None).
+    triples i32 [P,T,3]: explicit draws; otherwise Philox draws of (seed, pair_ids)."""
+    P, M = _need_fgr(kp1, kp2, n1, n2)
+    dev = kp1.device
+    nn12, nn21 = nn12.reshape(P, -1), nn21.reshape(P, -1)
+    _need_on(nn12, "nn12", torch.int32, (P, M), dev)
+    _need_on(nn21, "nn21", torch.int32, (P, M), dev)
+    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
+    if triples is not None:
+        _need(triples, "triples", torch.int32)
+        if triples.dim() != 3 or triples.shape[0] != P or triples.shape[1] < 1 or triples.shape[2] != 3 or triples.device != dev:
+            raise RuntimeError("fgr: triples must be i32 [P,T,3] on %s" % dev)
+    out = {"mutual": torch.empty((P, M, 2), dtype=torch.int32, device=dev),
+           "mutual_count": torch.empty((P,), dtype=torch.int32, device=dev),
+           "norm": torch.empty((P, 8), dtype=torch.float64, device=dev),
+           "rows": torch.empty((P, FGR_ROWS_MAX), dtype=torch.int32, device=dev),
+           "row_count": torch.empty((P,), dtype=torch.int32, device=dev),
+           "trials_walked": torch.empty((P,), dtype=torch.int32, device=dev),
+           "triples": torch.zeros((P, int(want_triples), 3), dtype=torch.int32, device=dev)
+           if want_triples and triples is None else None}
+    with torch.cuda.device(dev), prof.kernel("fgr_tuples", 32.0 * P * M + 4.0 * P * FGR_ROWS_MAX):
+        if triples is None:
+            _lib.check(_lib.lib().usip_fgr_tuples_f32(
+                _ptr(kp1), _ptr(kp2), _ptr(n1), _ptr(n2), _ptr(nn12), _ptr(nn21), P, M, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                _opt_ptr(pair_ids), _ptr(out["mutual"]), _ptr(out["mutual_count"]), _ptr(out["norm"]), _ptr(out["rows"]),
+                _ptr(out["row_count"]), _ptr(out["trials_walked"]), _opt_ptr(out["triples"]), int(want_triples),
+                _stream(kp1)), "usip_fgr_tuples_f32")
+        else:
+            _lib.check(_lib.lib().usip_fgr_tuples_explicit_f32(
+                _ptr(kp1), _ptr(kp2), _ptr(n1), _ptr(n2), _ptr(nn12), _ptr(nn21), P, M, _ptr(triples), triples.shape[1],
+                _ptr(out["mutual"]), _ptr(out["mutual_count"]), _ptr(out["norm"]), _ptr(out["rows"]), _ptr(out["row_count"]),
+                _ptr(out["trials_walked"]), _stream(kp1)), "usip_fgr_tuples_explicit_f32")
+    return out
+
+
+def fgr_optimize(kp1, kp2, mutual, mutual_count, norm, rows, row_count, threshold: float):
+    """f-12: the 64 Gauss-Newton steps over the tuple rows and the inliers over the mutual rows -> dict(Rt f64 [P,3,4], valid u8
+    [P], inlier_mask u8 [P,M], inliers i32 [P])."""
+    P, M = _need_fgr(kp1, kp2, mutual_count, row_count)
+    dev = kp1.device
+    for t, name, dt, shape in ((mutual, "mutual", torch.int32, (P, M, 2)), (norm, "norm", torch.float64, (P, 8)),
+                               (rows, "rows", torch.int32, (P, FGR_ROWS_MAX))):
+        if t is None:
+            raise RuntimeError("fgr: %s is required" % name)
+        _need_on(t, name, dt, shape, dev)
+    out = {"Rt": torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
+           "valid": torch.empty((P,), dtype=torch.uint8, device=dev),
+           "inlier_mask": torch.empty((P, M), dtype=torch.uint8, device=dev),
+           "inliers": torch.empty((P,), dtype=torch.int32, device=dev)}
+    with torch.cuda.device(dev), prof.kernel("fgr_optimize", 32.0 * P * M + 12.0 * P * FGR_ROWS_MAX,
+                                             64.0 * 90.0 * P * FGR_ROWS_MAX):
+        _lib.check(_lib.lib().usip_fgr_optimize_f32(
+            _ptr(kp1), _ptr(kp2), _ptr(mutual), _ptr(mutual_count), _ptr(norm), _ptr(rows), _ptr(row_count), P, M,
+            float(threshold), _ptr(out["Rt"]), _ptr(out["valid"]), _ptr(out["inlier_mask"]), _ptr(out["inliers"]),
+            _stream(kp1)), "usip_fgr_optimize_f32")
+    return out
