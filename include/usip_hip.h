@@ -1039,6 +1039,87 @@ int usip_fgr_optimize_f32_cpu(const float* kp1, const float* kp2, const int32_t*
 /* The contract's sine and cosine of n HOST doubles, |x| <= pi (csrc/fgr_math.h: fgr_sincos), for tests of its accuracy. */
 int usip_fgr_sincos_f64_cpu(const double* x, int n, double* sin_out, double* cos_out);
 
+/* ------------------------------------------------------------------ f-13  trimmed ICP refinement of fragment registrations
+ * The reference's second log writer (evaluation/matlab/eval_indoor/3dmatch/writeLogReconputeAlign.m) downsamples both
+ * fragments on a 0.04 m grid (f-7's grid average), refines the pair's estimate with pcregrigid (point to point, InlierRatio
+ * 0.3) and counts the moved fragment-2 points within 0.05 m of fragment 1.  pcregrigid is a MATLAB built-in whose source is not
+ * part of the reference, so the definition below is this project's own, written from the function's documented behaviour and
+ * defaults (20 iterations, Tolerance [0.01 0.009] on the mean of the last three iterations).  f-9's conventions: float32
+ * inputs, float64 arithmetic, never contracted, sums in a fixed order, no floating-point atomics, no launch synchronises the
+ * host, every index read from memory is clamped before use.  csrc/icp_math.h is the arithmetic.
+ *
+ * The bank is f-9's: rows f32 [total_rows][row_len >= 3] (x y z first; here the DOWNSAMPLED fragments), offsets i64
+ * [num_frags + 1], perm1 i32 [total_rows] (per fragment, at its offset, its local row indices ascending along x).  Per pair:
+ * frag1, frag2 i32 [P] (clamped into the bank), Rt0 f64 [P][3][4] mapping fragment 2 into fragment 1, mask u8 [P] (NULL:
+ * all ones).  A = fragment 1 with n1 rows, B = fragment 2 with n2 rows.  Lmax must be at least the length of every fragment a pair
+ * names: a longer fragment is cut to its first Lmax rows only so that nothing is read or written outside an array, perm1 then
+ * names rows that are gone and the result is unspecified (the device's walk and the twin's loop need not agree).  order2 i32
+ * [P][Lmax] (NULL: the identity): slot s < n2 of the pair names the row of B that the s-th query is; the first n2 slots must
+ * hold a permutation of 0 .. n2 - 1 (values are clamped; a row no slot names keeps idx = 0, d2 = 0).  The order decides only
+ * which queries share a workgroup -- usip_overlap_keys_f32's moved x under Rt0, sorted, keeps them close -- never a result.
+ *
+ * usip_icp_nearest_f32: one pass under the poses Rt f64 [P][3][4].  For row i of B: q = R b_i + t (f-9's xform), idx[p][i] =
+ * the row j of A with the least d2 = sqdist3(q, a_j), the LOWEST row index among equal distances; d2[p][i] that distance.
+ * The search is exact: it equals the loop over all rows of A, which is what the host twin runs.  idx i32 [P][Lmax], d2 f64
+ * [P][Lmax]; zeros beyond n2 and for a pair with mask 0, n1 = 0 or n2 = 0.  visits u64 [P], optional (NULL): the (query, row)
+ * distances the lanes evaluated (a lane whose bound is met skips a staged tile and does not count it) -- against n1 n2 the
+ * share of the all-pairs work that the walk did.
+ *
+ * usip_icp_refine_f32: (R, t) = Rt0; iteration k = 1 .. max_iterations:
+ *  1 the nearest pass under (R, t);
+ *  2 m = max(1, floor(inlier_ratio n2)) (at most n2); kept are the m smallest rows under the lexicographic order (d2_i, i),
+ *    stated as the cut (d2*, i*): row i is kept iff d2_i < d2* or (d2_i == d2* and i <= i*);
+ *  3 the rigid fit of the kept ORIGINAL b_i onto a_idx[i] (MATLAB composes increments of a moved copy; the absolute pose from
+ *    the original rows is the same optimum without accumulated rounding): lane l of 256 adds its kept rows among l, l + 256,
+ *    ... in ascending i, the 256 partial sums go through f-6's binary tree -- first the six centroid sums, each divided by m,
+ *    then f-6's accumulate over the centred rows (x = a, y = b), then transform_from (8 Jacobi sweeps, never a NaN from
+ *    coincident rows: B = 0 gives R = I);
+ *  4 a fit with an entry that is not finite ends the pair: the last finite pose stays, converged = 0, iterations = k - 1;
+ *  5 dt_k = |t_k - t_{k-1}|, dc_k = |R_k - R_{k-1}|_F (nine squared differences added in row-major order, then sqrt).  The
+ *    pair stops after iteration k with converged = 1 when mean(dt) <= tol_t and mean(dc) <= tol_c, the means over the last
+ *    min(k, 3) values: ((v_{k-2} + v_{k-1}) + v_k) / 3, (v_1 + v_2) / 2, v_1.  (The documented rotation test is on the angle
+ *    in radians; acos rounds differently on host and device, so the caller passes the chordal bound tol_c = 2 sqrt(2)
+ *    sin(tol_r / 2) of the same angle and the library takes square roots only.)
+ * The final pass: 1 and 2 under the final pose; hits = #{i : sqrt(d2_i) < align_radius} (f-9's within); ratio f64 [P][2] =
+ * hits / n1, hits / n2 (the reference's one count over both lengths); rmse = sqrt(sum of the kept d2 / m), the sum taken as
+ * in 3.  Rt f64 [P][3][4], iterations i32 [P] (fits done), converged u8 [P], hits i32 [P].  A pair with mask 0, n1 = 0 or
+ * n2 = 0 is not refined: Rt = Rt0, every other output 0.  The reference passes R through rotm2eul / eul2rotm to satisfy
+ * affine3d; the estimate is taken as it is.  cut_d2 f64 [P][max_iterations + 1] with cut_i i32 of the same shape, optional
+ * (both or neither): the cut (d2*, i*) of every pass that ran, iteration k at column k - 1, the final pass at column
+ * max_iterations, zeros elsewhere.  workspace: usip_icp_workspace_bytes(P, Lmax) bytes of device memory.  visits as
+ * above, summed over every pass.  stage_ms HOST f64 [4], optional (NULL) and a measurement only: HIP-event milliseconds of the
+ * nearest, trim and fit launches of the loop and of the final pass's three; giving it makes the call wait for its launches, and
+ * an event that cannot be created, recorded or read is returned as the call's HIP error (stage_ms is then incomplete).
+ *
+ * Limits: P <= 65535, Lmax in 1 .. 2^24, 0 < inlier_ratio <= 1, 0 <= max_iterations <= 64, tolerances >= 0, align_radius > 0;
+ * anything else, a NULL among the required pointers or a workspace too small is USIP_EINVAL.  The loop is 3 launches per
+ * iteration for the whole batch; every workgroup reads its pair's state in device memory first and leaves when the pair has
+ * stopped. */
+long long usip_icp_workspace_bytes(int P, int Lmax);
+int usip_icp_nearest_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                         const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt,
+                         const uint8_t* mask, const int32_t* order2, int P, int Lmax, int32_t* idx, double* d2,
+                         unsigned long long* visits, void* stream);
+int usip_icp_refine_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                        const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt0,
+                        const uint8_t* mask, const int32_t* order2, int P, int Lmax, double inlier_ratio, int max_iterations,
+                        double tol_t, double tol_c, double align_radius, void* workspace, long long workspace_bytes,
+                        double* Rt, int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
+                        double* cut_d2, int32_t* cut_i, unsigned long long* visits, double* stage_ms, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; the search is the loop over all rows of A
+ * in ascending row order, the trim a selection on (bit pattern, row).  num_threads splits the pairs.  idx_out i32 [P][Lmax],
+ * d2_out f64 [P][Lmax], optional (NULL): the final pass's neighbours and distances. */
+int usip_icp_nearest_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                             const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt,
+                             const uint8_t* mask, const int32_t* order2, int P, int Lmax, int32_t* idx, double* d2,
+                             int num_threads);
+int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                            const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt0,
+                            const uint8_t* mask, const int32_t* order2, int P, int Lmax, double inlier_ratio,
+                            int max_iterations, double tol_t, double tol_c, double align_radius, double* Rt,
+                            int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
+                            double* cut_d2, int32_t* cut_i, int32_t* idx_out, double* d2_out, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

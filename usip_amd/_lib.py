@@ -229,6 +229,22 @@ SIGNATURES = {
     "usip_fgr_optimize_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _dbl]
                                   + [ctypes.c_void_p] * 3 + [_i32p, _int], _int),
     "usip_fgr_sincos_f64_cpu": ([ctypes.c_void_p, _int, ctypes.c_void_p, ctypes.c_void_p], _int),
+    # f-13 trimmed ICP between downsampled fragments: the nearest pass, the whole loop (usip_amd/fragments.py)
+    "usip_icp_workspace_bytes": ([_int, _int], ctypes.c_longlong),
+    "usip_icp_nearest_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
+                             + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _i32p, ctypes.c_void_p, ctypes.c_void_p, _stream],
+                             _int),
+    "usip_icp_refine_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
+                            + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _dbl, _int, _dbl, _dbl, _dbl, ctypes.c_void_p,
+                                                       ctypes.c_longlong, ctypes.c_void_p, _i32p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, _i32p, ctypes.c_void_p, ctypes.c_void_p, _i32p,
+                                                       ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
+    "usip_icp_nearest_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
+                                 + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _i32p, ctypes.c_void_p, _int], _int),
+    "usip_icp_refine_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
+                                + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _dbl, _int, _dbl, _dbl, _dbl, ctypes.c_void_p,
+                                                           _i32p, ctypes.c_void_p, ctypes.c_void_p, _i32p, ctypes.c_void_p,
+                                                           ctypes.c_void_p, _i32p, _i32p, ctypes.c_void_p, _int], _int),
 }
 
 

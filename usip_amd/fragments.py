@@ -10,6 +10,9 @@ mrEvaluateRegistrationMy.m).
                            mutual nearest descriptors: tuple test, 64 Gauss-Newton steps (csrc/fgr.hip)
   information_matrix       the 6 x 6 sum of A'A over the inliers' fragment-1 keypoints
   overlap_ratio            ratioAligned: the share of each full fragment with a point of the other closer than 0.2 m
+  RefineBank / icp_refine  writeLogReconputeAlign.m: both fragments voxel-averaged at 0.04 m, the estimate refined by trimmed
+                           point-to-point ICP (pcregrigid's InlierRatio 0.3), the share of moved points within 0.05 m and
+                           the second gate, `> 0.15` (csrc/icp.hip)
   *_cpu                    the same on numpy arrays over the library's host twins (csrc/fragments_cpu.cpp; RANSAC:
                            evaluation.ransac_*_cpu with the limit at 10240)
   transformation_error     mrComputeTransformationError with the file's own dcm2quat
@@ -22,12 +25,13 @@ mrEvaluateRegistrationMy.m).
 RANSAC draws are f-6's (usip_amd/evaluation.py): the reference's algorithm on Philox draws keyed by (seed, pair id, trial).
 """
 from collections import namedtuple
+import math
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
-from . import _lib, inference, ops
+from . import _lib, inference, ops, prepare
 from .evaluation import _np, _p, ransac_select_cpu, ransac_trials_cpu, select_keypoints_device
 
 FragmentResult = namedtuple("FragmentResult",
@@ -41,6 +45,10 @@ PairFile = namedtuple("PairFile", "fragment1 fragment2 inlier_num inlier_ratio r
 
 INLIER_THRESHOLD, MAX_TRIALS, OVERLAP_RADIUS, K_MATCH = 0.2, 30000, 0.2, 5
 GATE_ALIGNED, GATE_INLIER_RATIO = 0.23, 0.025                                # writeLog.m
+GATE_REFINED, REFINE_LEAF, REFINE_RADIUS, REFINE_INLIER_RATIO = 0.15, 0.04, 0.05, 0.3      # writeLogReconputeAlign.m
+REFINE_ITERATIONS, REFINE_TOLERANCE = 20, (0.01, 0.009)                      # pcregrigid's documented defaults
+IcpResult = namedtuple("IcpResult", "Rt iterations converged rmse hits ratio")
+REFINE_KEYS = ("refined_Rt", "refine_iterations", "refine_converged", "refined_ratio_aligned", "refined_hits", "gate_refined")
 
 
 # ------------------------------------------------------------------------------------------------ device
@@ -143,6 +151,86 @@ def overlap_ratio(bank: FragmentBank, frag1, frag2, Rt, radius: float = OVERLAP_
     keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
     perm2 = torch.argsort(keys, dim=1, stable=True).to(torch.int32)
     return ops.overlap_ratio(bank.rows, bank.offsets, frag1, frag2, Rt, bank.perm, perm2, radius)
+
+
+def chordal_tolerance(tol_r: float) -> float:
+    """|R - R'|_F of two rotations tol_r radians apart, 2 sqrt(2) sin(tol_r / 2): the bound the library compares with."""
+    return 2.0 * math.sqrt(2.0) * math.sin(0.5 * float(tol_r))
+
+
+class RefineBank:
+    """The fragments' clouds voxel-averaged at `leaf` (pcdownsample 'gridAverage', f-7's kernels; positions only: a zero
+    reflectance column and zero normals go in), in ONE float32 device buffer [rows, 3] with offsets and the x-order of every
+    fragment, as FragmentBank holds the full clouds.  Built once per scene: every fragment's cell count is read from the
+    device here, nothing is read after."""
+
+    def __init__(self, clouds: Sequence, device, leaf: float = REFINE_LEAF):
+        self.device, self.leaf = torch.device(device), float(leaf)
+        if not self.leaf > 0.0:
+            raise ValueError("RefineBank: leaf must be positive")
+        parts = []
+        for c in clouds:
+            c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32))
+            parts.append(self._downsample(c.to(self.device, torch.float32)[:, :3]))
+        if not parts:
+            raise ValueError("RefineBank: no fragments")
+        self.lengths = [int(p.shape[0]) for p in parts]
+        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.rows = torch.cat(parts).contiguous()
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.perm = torch.cat([torch.argsort(p[:, 0], stable=True).to(torch.int32) for p in parts]).contiguous()
+        self.lmax = max(max(self.lengths), 1)
+
+    def _downsample(self, xyz):
+        n = xyz.shape[0]
+        if n == 0:
+            return xyz.new_zeros((0, 3))
+        pts = torch.cat((xyz, xyz.new_zeros((n, 1))), 1).contiguous()
+        lo, hi = torch.aminmax(xyz, dim=0)
+        keys = ops.scan_voxel_keys(pts, torch.cat((lo, hi)).contiguous(), self.leaf)
+        skeys, order = torch.sort(keys, stable=True)
+        _, counts = torch.unique_consecutive(skeys, return_counts=True)
+        start = torch.zeros(counts.shape[0] + 1, dtype=torch.int32, device=pts.device)
+        start[1:] = torch.cumsum(counts, 0)
+        nrm = torch.zeros((n, 4), dtype=torch.float64, device=pts.device)
+        return ops.scan_voxel_average(pts, nrm, order.to(torch.int32), start)[:, :3].contiguous()
+
+    def host(self):
+        return HostBank(self.rows.cpu().numpy(), self.offsets_host.copy(), self.perm.cpu().numpy(), self.lmax)
+
+
+def _refine_args(inlier_ratio, max_iterations, tolerance, align_radius):
+    if len(tolerance) != 2:
+        raise ValueError("icp_refine: tolerance is (translation, rotation in radians)")
+    return float(inlier_ratio), int(max_iterations), float(tolerance[0]), chordal_tolerance(tolerance[1]), float(align_radius)
+
+
+def icp_refine(bank: RefineBank, frag1, frag2, Rt, mask=None, inlier_ratio: float = REFINE_INLIER_RATIO,
+               max_iterations: int = REFINE_ITERATIONS, tolerance=REFINE_TOLERANCE,
+               align_radius: float = REFINE_RADIUS, want_cuts: bool = False) -> IcpResult:
+    """writeLogReconputeAlign.m's refinement for a batch of pairs, on the device: frag1, frag2 i32 [P] into the bank, Rt f64
+    [P,3,4] the estimate (fragment 2 into fragment 1), mask bool or u8 [P] (pairs with 0 are not refined: Rt stays, the rest
+    is 0).  tolerance = (translation, rotation in radians) on the mean change of the last three iterations, pcregrigid's.
+    -> IcpResult(Rt, iterations, converged, rmse, hits, ratio f64 [P,2] = hits over either fragment's downsampled length).
+    Fragment 2's rows are sorted along their moved x here, by the keys the library computes.  No host synchronisation.
+    want_cuts: -> (IcpResult, cut_d2 f64, cut_i i32 [P,max_iterations+1]), the trim's cut of every pass, the final pass last."""
+    ir, it, tt, tc, ar = _refine_args(inlier_ratio, max_iterations, tolerance, align_radius)
+    Rt = Rt.contiguous()
+    keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
+    order2 = torch.argsort(keys, dim=1, stable=True).to(torch.int32)
+    m = None if mask is None else mask.to(torch.uint8).contiguous()
+    o = ops.icp_refine(bank.rows, bank.offsets, bank.perm, frag1, frag2, Rt, bank.lmax, m, order2, ir, it, tt, tc, ar,
+                       want_cuts=want_cuts)
+    res = IcpResult(o["Rt"], o["iterations"], o["converged"], o["rmse"], o["hits"], o["ratio"])
+    return (res, o["cut_d2"], o["cut_i"]) if want_cuts else res
+
+
+def _refined(out, res: IcpResult, lib_np):
+    both = np.logical_and if lib_np else torch.logical_and
+    out.update(refined_Rt=res.Rt, refine_iterations=res.iterations, refine_converged=res.converged,
+               refined_ratio_aligned=res.ratio, refined_hits=res.hits,
+               gate_refined=both(res.ratio[:, 0] > GATE_REFINED, out["inlier_ratio"] > GATE_INLIER_RATIO))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
@@ -275,10 +363,83 @@ def overlap_ratio_cpu(bank: HostBank, frag1, frag2, Rt, radius: float = OVERLAP_
     return ratio, hits
 
 
+def refine_bank_cpu(clouds: Sequence, leaf: float = REFINE_LEAF) -> HostBank:
+    """RefineBank on the host: every cloud through the grid average's host twin -> HostBank of the downsampled rows [rows, 3]."""
+    parts = []
+    for c in clouds:
+        a = np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32)
+        if a.shape[0] == 0:
+            parts.append(a)
+            continue
+        xyzi = np.ascontiguousarray(np.concatenate((a, np.zeros((a.shape[0], 1), np.float32)), 1))
+        parts.append(np.ascontiguousarray(prepare.grid_cpu(xyzi, np.zeros((a.shape[0], 4)), float(leaf))[0][:, :3]))
+    if not parts:
+        raise ValueError("refine_bank_cpu: no fragments")
+    return host_bank(parts)
+
+
+def _icp_host(bank: HostBank, frag1, frag2, Rt, mask, order2):
+    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
+    perm1 = _np(bank.perm, np.int32, "perm", (rows.shape[0],))
+    f2 = _np(frag2, np.int32, "frag2")
+    P = f2.shape[0]
+    if P > 65535:
+        raise RuntimeError("icp: at most 65535 pairs per call (got %d)" % P)
+    f1, G = _np(frag1, np.int32, "frag1", (P,)), _np(Rt, np.float64, "Rt", (P, 3, 4))
+    L = int(bank.lmax)
+    m = None if mask is None else _np(np.asarray(mask).astype(np.uint8), np.uint8, "mask", (P,))
+    o2 = None if order2 is None else _np(order2, np.int32, "order2", (P, L))
+    return rows, offsets, perm1, f1, f2, G, m, o2, P, L
+
+
+def moved_x_order_cpu(bank: HostBank, frag2, Rt):
+    """-> i32 [P,lmax]: every pair's fragment-2 rows ascending along their moved x (usip_overlap_keys_f32_cpu, stable)."""
+    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
+    f2 = _np(frag2, np.int32, "frag2")
+    P, L = f2.shape[0], int(bank.lmax)
+    G = _np(Rt, np.float64, "Rt", (P, 3, 4))
+    keys = np.zeros((P, L))
+    _lib.check(_lib.lib().usip_overlap_keys_f32_cpu(_p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0],
+                                                    _p(f2), _p(G), P, L, _p(keys)), "usip_overlap_keys_f32_cpu")
+    return np.ascontiguousarray(np.argsort(keys, axis=1, kind="stable").astype(np.int32))
+
+
+def icp_nearest_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, order2=None, num_threads: int = 1):
+    """ops.icp_nearest on numpy arrays over the host twin (the loop over all rows) -> (idx i32 [P,lmax], d2 f64 [P,lmax])."""
+    rows, offsets, perm1, f1, f2, G, m, o2, P, L = _icp_host(bank, frag1, frag2, Rt, mask, order2)
+    idx, d2 = np.zeros((P, L), np.int32), np.zeros((P, L))
+    _lib.check(_lib.lib().usip_icp_nearest_f32_cpu(_p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0],
+                                                   _p(perm1), _p(f1), _p(f2), _p(G), _p(m), _p(o2), P, L, _p(idx), _p(d2),
+                                                   int(num_threads)), "usip_icp_nearest_f32_cpu")
+    return idx, d2
+
+
+def icp_refine_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, inlier_ratio: float = REFINE_INLIER_RATIO,
+                   max_iterations: int = REFINE_ITERATIONS, tolerance=REFINE_TOLERANCE, align_radius: float = REFINE_RADIUS,
+                   num_threads: int = 1, want_neighbours: bool = False, order2="moved_x", want_cuts: bool = False):
+    """icp_refine on numpy arrays over the host twin -> IcpResult; with want_neighbours also the final pass's (idx, d2); with
+    want_cuts also (cut_d2 f64, cut_i i32) [P,max_iterations+1]: the trim's cut (d2*, i*) of every pass, the final pass last."""
+    ir, it, tt, tc, ar = _refine_args(inlier_ratio, max_iterations, tolerance, align_radius)
+    if isinstance(order2, str):
+        order2 = moved_x_order_cpu(bank, frag2, Rt)
+    rows, offsets, perm1, f1, f2, G, m, o2, P, L = _icp_host(bank, frag1, frag2, Rt, mask, order2)
+    out = IcpResult(np.zeros((P, 3, 4)), np.zeros(P, np.int32), np.zeros(P, np.uint8), np.zeros(P), np.zeros(P, np.int32),
+                    np.zeros((P, 2)))
+    idx, d2 = (np.zeros((P, L), np.int32), np.zeros((P, L))) if want_neighbours else (None, None)
+    cd, ci = (np.zeros((P, it + 1)), np.zeros((P, it + 1), np.int32)) if want_cuts else (None, None)
+    _lib.check(_lib.lib().usip_icp_refine_f32_cpu(
+        _p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0], _p(perm1), _p(f1), _p(f2), _p(G), _p(m),
+        _p(o2), P, L, ir, it, tt, tc, ar, _p(out.Rt), _p(out.iterations), _p(out.converged), _p(out.rmse), _p(out.hits),
+        _p(out.ratio), _p(cd), _p(ci), _p(idx), _p(d2), int(num_threads)), "usip_icp_refine_f32_cpu")
+    extra = ((idx, d2) if want_neighbours else ()) + ((cd, ci) if want_cuts else ())
+    return (out,) + extra if extra else out
+
+
 # ------------------------------------------------------------------------------------------------ the per-pair pipeline
 def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                    threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
-                   seed: int = 0, registrator: str = "ransac") -> Dict[str, torch.Tensor]:
+                   seed: int = 0, registrator: str = "ransac", refine: Optional[RefineBank] = None,
+                   refine_args: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
     """register2Fragments.m for a batch of pairs, on the device: kp f32 [P,3,M], desc f32 [P,D,M], n i32 [P] of either
     fragment; frag1, frag2 i32 [P] into the bank; pair_ids i64 [P] key the draws.  No host synchronisation.
 
@@ -286,7 +447,22 @@ def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, fr
     `max_trials` are not used) -> fgr_registration -> the information matrix over the mutual inliers -> the same overlap
     walk and gate.  The reference's FGR wrapper hard-codes ratioAligned = 0.8 and inlierRatio = 0.99 and so writes every
     pair to its log; here the gate sees the measured values, as for RANSAC.  Its keys: RANSAC's without trialcount and
-    chosen, plus row_count and trials_walked; matches counts the mutual rows."""
+    chosen, plus row_count and trials_walked; matches counts the mutual rows.
+
+    refine: the scene's RefineBank (its fragments in the bank's order) adds writeLogReconputeAlign.m to either registrator:
+    icp_refine(refine, frag1, frag2, Rt, mask = valid & inlier_ratio > 0.025, **refine_args) and the keys refined_Rt,
+    refine_iterations, refine_converged, refined_ratio_aligned, refined_hits and gate_refined = refined ratio(1) > 0.15 &
+    inlier_ratio > 0.025.  A pair outside the mask fails that gate whatever ICP would find.  Every other key is unchanged."""
+    out = _register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
+                          seed, registrator)
+    if refine is not None:
+        mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
+        _refined(out, icp_refine(refine, frag1, frag2, out["Rt"], mask, **(refine_args or {})), False)
+    return out
+
+
+def _register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius, seed,
+                    registrator):
     if registrator == "fgr":
         nn12, _ = match_descriptors_topk(desc1, desc2, n1, n2, 1)
         nn21, _ = match_descriptors_topk(desc2, desc1, n2, n1, 1)
@@ -317,8 +493,21 @@ def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, fr
 
 def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                        threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
-                       seed: int = 0, num_threads: int = 1, registrator: str = "ransac") -> Dict[str, np.ndarray]:
-    """register_pairs assembled from the host twins, on numpy arrays."""
+                       seed: int = 0, num_threads: int = 1, registrator: str = "ransac", refine: Optional[HostBank] = None,
+                       refine_args: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+    """register_pairs assembled from the host twins, on numpy arrays; refine: the HostBank of the downsampled fragments
+    (refine_bank_cpu, or RefineBank.host())."""
+    out = _register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
+                              seed, num_threads, registrator)
+    if refine is not None:
+        mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
+        _refined(out, icp_refine_cpu(refine, out["frag1"], out["frag2"], out["Rt"], mask, num_threads=num_threads,
+                                     **(refine_args or {})), True)
+    return out
+
+
+def _register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius, seed,
+                        num_threads, registrator):
     if registrator == "fgr":
         nn12, _ = match_descriptors_topk_cpu(desc1, desc2, n1, n2, 1, num_threads)
         nn21, _ = match_descriptors_topk_cpu(desc2, desc1, n2, n1, 1, num_threads)
@@ -503,12 +692,15 @@ def to4x4(Rt):
     return np.concatenate((np.asarray(Rt, np.float64).reshape(3, 4), [[0.0, 0.0, 0.0, 1.0]]))
 
 
-def result_entries(per_pair: Dict[str, np.ndarray], fragment_ids: Sequence[int], num_fragments: int) -> List[ResultEntry]:
-    """writeLog.m: the pairs that pass `ratioAligned(1) > 0.23 && inlierRatio > 0.025`, in the order they were run."""
+def result_entries(per_pair: Dict[str, np.ndarray], fragment_ids: Sequence[int], num_fragments: int, gate: str = "gate",
+                   transform: str = "Rt") -> List[ResultEntry]:
+    """writeLog.m: the pairs that pass `ratioAligned(1) > 0.23 && inlierRatio > 0.025`, in the order they were run.
+    gate "gate_refined", the recomputed `> 0.15`, is writeLogReconputeAlign.m, which still writes the unrefined estimate
+    (transform "Rt"); transform "refined_Rt" writes the refined one."""
     out = []
-    for p in np.nonzero(per_pair["gate"])[0]:
+    for p in np.nonzero(per_pair[gate])[0]:
         out.append(ResultEntry((int(fragment_ids[per_pair["frag1"][p]]), int(fragment_ids[per_pair["frag2"][p]]),
-                                int(num_fragments)), to4x4(per_pair["Rt"][p]), int(per_pair["inliers"][p]),
+                                int(num_fragments)), to4x4(per_pair[transform][p]), int(per_pair["inliers"][p]),
                                float(per_pair["inlier_ratio"][p]), per_pair["information"][p]))
     return out
 
@@ -526,7 +718,16 @@ class FragmentEvaluator:
 
     def __init__(self, detector, descriptor, opt, device, nms_radius: float = 0.1, top: int = 512, k: int = K_MATCH,
                  inlier_threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,
-                 overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32, registrator: str = "ransac"):
+                 overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32, registrator: str = "ransac",
+                 refine: bool = False, refine_leaf: float = REFINE_LEAF, refine_args: Optional[Dict] = None,
+                 log_transform: str = "estimate"):
+        if log_transform not in ("estimate", "refined"):
+            raise ValueError("log_transform must be 'estimate' or 'refined' (got %r)" % (log_transform,))
+        if log_transform == "refined" and not refine:
+            raise ValueError("FragmentEvaluator: log_transform 'refined' needs refine=True")
+        self.refine, self.refine_leaf, self.refine_args = bool(refine), float(refine_leaf), dict(refine_args or {})
+        self.log_transform = log_transform
+        self._refine_bank = None
         if registrator not in ("ransac", "fgr"):
             raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
         if registrator == "fgr" and int(top) > ops.FGR_MMAX:
@@ -550,7 +751,7 @@ class FragmentEvaluator:
         cloud = cloud if isinstance(cloud, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cloud)[:, :3], dtype=np.float32))
         self.fragments[int(fragment_id)] = (kp.contiguous(), desc.contiguous(), count,
                                             cloud.to(self.device, torch.float32)[:, :3].contiguous())
-        self._bank = None
+        self._bank = self._refine_bank = None
         return self.fragments[int(fragment_id)]
 
     def add_fragment(self, fragment_id, pc, sn, node, cloud):
@@ -589,6 +790,12 @@ class FragmentEvaluator:
             self._bank = FragmentBank([self.fragments[i][3] for i in self.ids()], self.device)
         return self._bank
 
+    def refine_bank(self) -> Optional[RefineBank]:
+        """The downsampled fragments beside bank(), when refine is on; built once (it reads every fragment's row count)."""
+        if self.refine and self._refine_bank is None:
+            self._refine_bank = RefineBank([self.fragments[i][3] for i in self.ids()], self.device, self.refine_leaf)
+        return self._refine_bank
+
     def all_pairs(self):
         ids = self.ids()
         return [(a, b) for x, a in enumerate(ids) for b in ids[x + 1:]]
@@ -602,7 +809,7 @@ class FragmentEvaluator:
         """Every pair through register_pairs, batch by batch -> per-pair device tensors; nothing synchronises."""
         pairs = self.all_pairs() if pairs is None else list(pairs)
         slot = {i: s for s, i in enumerate(self.ids())}
-        bank = self.bank()
+        bank, fine = self.bank(), self.refine_bank()
         kp, desc, cnt = self.stacked()
         parts = []
         for base in range(0, len(pairs), self.batch_pairs):
@@ -613,7 +820,7 @@ class FragmentEvaluator:
             a, b = f1.long(), f2.long()
             parts.append(register_pairs(kp[a], desc[a], cnt[a].contiguous(), kp[b], desc[b], cnt[b].contiguous(), bank, f1,
                                         f2, ids, self.k, self.inlier_threshold, self.max_trials, self.overlap_radius,
-                                        self.seed, self.registrator))
+                                        self.seed, self.registrator, fine, self.refine_args))
         if not parts:
             return {}
         return {key: torch.cat([p[key] for p in parts]) for key in parts[0]}
@@ -622,15 +829,16 @@ class FragmentEvaluator:
                  gt_info: Optional[Sequence] = None) -> Dict:
         dev = self.evaluate_device(pairs)
         host = {k: v.cpu().numpy() for k, v in dev.items()}                # the one read
-        return summarize(host, self.ids(), gt, gt_info)
+        return summarize(host, self.ids(), gt, gt_info, None, "gate_refined" if self.refine else "gate",
+                         "refined_Rt" if self.log_transform == "refined" else "Rt")
 
 
 def summarize(per_pair: Dict[str, np.ndarray], fragment_ids: Sequence[int], gt=None, gt_info=None,
-              num_fragments: Optional[int] = None) -> Dict:
+              num_fragments: Optional[int] = None, gate: str = "gate", transform: str = "Rt") -> Dict:
     """What evaluate.m prints (when gt and gt_info are given) plus the result log's entries and the per-pair arrays."""
     n = int(num_fragments if num_fragments is not None else (gt[0].info[2] if gt else len(fragment_ids)))
-    entries = result_entries(per_pair, fragment_ids, n) if per_pair else []
-    out = {"pairs": int(len(per_pair["gate"])) if per_pair else 0, "written": len(entries), "entries": entries,
+    entries = result_entries(per_pair, fragment_ids, n, gate, transform) if per_pair else []
+    out = {"pairs": int(len(per_pair[gate])) if per_pair else 0, "written": len(entries), "entries": entries,
            "per_pair": per_pair}
     if gt is not None and gt_info is not None:
         out.update(evaluate_log(entries, gt, gt_info))

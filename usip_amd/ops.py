@@ -6,6 +6,7 @@ returns without synchronising.  Host tensors raise RuntimeError: there is no CPU
 """
 import ctypes
 import functools
+import math
 import os
 from typing import Optional
 
@@ -2001,4 +2002,105 @@ def fgr_optimize(kp1, kp2, mutual, mutual_count, norm, rows, row_count, threshol
             _ptr(kp1), _ptr(kp2), _ptr(mutual), _ptr(mutual_count), _ptr(norm), _ptr(rows), _ptr(row_count), P, M,
             float(threshold), _ptr(out["Rt"]), _ptr(out["valid"]), _ptr(out["inlier_mask"]), _ptr(out["inliers"]),
             _stream(kp1)), "usip_fgr_optimize_f32")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ f-13 trimmed ICP refinement
+ICP_MAX_ITERATIONS = 64
+ICP_TOL_C = 2.0 * 2.0 ** 0.5 * math.sin(0.5 * 0.009)     # |R - R'|_F of rotations 0.009 rad apart: pcregrigid's default, chordal
+
+
+def _need_icp(rows, offsets, perm1, frag1, frag2, Rt, mask, order2):
+    P = _need_bank(rows, offsets, frag1, frag2, Rt)
+    if frag1 is None or Rt is None:
+        raise RuntimeError("icp: frag1 and Rt are required")
+    dev = rows.device
+    _need_on(perm1, "perm1", torch.int32, (rows.shape[0],), dev)
+    if perm1 is None:
+        raise RuntimeError("icp: perm1 is required")
+    _need_on(mask, "mask", torch.uint8, (P,), dev)
+    if order2 is not None:
+        _need(order2, "order2", torch.int32)
+        if order2.dim() != 2 or order2.shape[0] != P or order2.shape[1] < 1 or order2.device != dev:
+            raise RuntimeError("icp: order2 must be i32 [P,Lmax] on %s" % dev)
+    if P > 65535:
+        raise RuntimeError("icp: at most 65535 pairs per call (got %d)" % P)
+    return P
+
+
+def icp_nearest(rows, offsets, perm1, frag1, frag2, Rt, Lmax: int, mask=None, order2=None, want_visits: bool = False):
+    """f-13: for every row of fragment 2 moved by Rt f64 [P,3,4] the nearest row of fragment 1 in a CSR bank (rows f32
+    [total,>=3], offsets i64 [F+1], perm1 i32 [total]: every fragment's local rows ascending along x) -> (idx i32 [P,Lmax],
+    d2 f64 [P,Lmax]): the lowest row index among equal distances, zeros beyond the fragment and where mask u8 [P] is 0.
+    order2 i32 [P,Lmax]: which row of fragment 2 each query slot is (a permutation per pair; it never changes a result).
+    want_visits: also u64 [P] (as int64), the (query, row) pairs the walk evaluated."""
+    P = _need_icp(rows, offsets, perm1, frag1, frag2, Rt, mask, order2)
+    Lmax = int(Lmax) if order2 is None else order2.shape[1]
+    if not 1 <= Lmax <= 1 << 24:
+        raise RuntimeError("icp: Lmax must be in 1..2^24 (got %d)" % Lmax)
+    dev = rows.device
+    idx = torch.empty((P, Lmax), dtype=torch.int32, device=dev)
+    d2 = torch.empty((P, Lmax), dtype=torch.float64, device=dev)
+    visits = torch.empty((P,), dtype=torch.int64, device=dev) if want_visits else None
+    with torch.cuda.device(dev), prof.kernel("icp_nearest", 28.0 * P * Lmax):
+        _lib.check(_lib.lib().usip_icp_nearest_f32(
+            _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0], _ptr(perm1), _ptr(frag1),
+            _ptr(frag2), _ptr(Rt), _opt_ptr(mask), _opt_ptr(order2), P, Lmax, _ptr(idx), _ptr(d2), _opt_ptr(visits),
+            _stream(rows)), "usip_icp_nearest_f32")
+    return (idx, d2, visits) if want_visits else (idx, d2)
+
+
+def icp_workspace_bytes(P: int, Lmax: int) -> int:
+    need = int(_lib.lib().usip_icp_workspace_bytes(int(P), int(Lmax)))
+    if need < 0:
+        raise RuntimeError("usip_amd: usip_icp_workspace_bytes: invalid argument (USIP_EINVAL)")
+    return need
+
+
+def icp_refine(rows, offsets, perm1, frag1, frag2, Rt0, Lmax: int, mask=None, order2=None, inlier_ratio: float = 0.3,
+               max_iterations: int = 20, tol_t: float = 0.01, tol_c: float = ICP_TOL_C, align_radius: float = 0.05,
+               want_visits: bool = False, workspace=None, want_stage_ms: bool = False, want_cuts: bool = False):
+    """f-13: trimmed point-to-point ICP from Rt0 f64 [P,3,4] on the bank of icp_nearest -> dict(Rt f64 [P,3,4], iterations
+    i32 [P], converged u8 [P], rmse f64 [P], hits i32 [P], ratio f64 [P,2]; visits i64 [P] with want_visits; cut_d2 f64 and
+    cut_i i32 [P,max_iterations+1] with want_cuts: the trim's cut (d2*, i*) of every pass, the final pass last).  tol_c bounds
+    the Frobenius norm of the change of R (include/usip_hip.h f-13).  No host synchronisation -- unless want_stage_ms asks for
+    the measurement stage_ms (host f64 [4]: nearest, trim, fit, the final pass), which waits for the launches."""
+    P = _need_icp(rows, offsets, perm1, frag1, frag2, Rt0, mask, order2)
+    Lmax = int(Lmax) if order2 is None else order2.shape[1]
+    if not 1 <= Lmax <= 1 << 24:
+        raise RuntimeError("icp: Lmax must be in 1..2^24 (got %d)" % Lmax)
+    if not (0.0 < float(inlier_ratio) <= 1.0 and 0 <= int(max_iterations) <= ICP_MAX_ITERATIONS and float(tol_t) >= 0.0
+            and float(tol_c) >= 0.0 and float(align_radius) > 0.0):
+        raise RuntimeError("icp: inlier_ratio in (0, 1], max_iterations in 0..%d, tolerances >= 0 and align_radius > 0 "
+                           "(got %r, %r, %r, %r, %r)" % (ICP_MAX_ITERATIONS, inlier_ratio, max_iterations, tol_t, tol_c,
+                                                        align_radius))
+    dev = rows.device
+    need = icp_workspace_bytes(P, Lmax)
+    if workspace is None:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError("icp: workspace must be contiguous u8 [>= %d] on %s" % (need, dev))
+    out = {"Rt": torch.empty((P, 3, 4), dtype=torch.float64, device=dev),
+           "iterations": torch.empty((P,), dtype=torch.int32, device=dev),
+           "converged": torch.empty((P,), dtype=torch.uint8, device=dev),
+           "rmse": torch.empty((P,), dtype=torch.float64, device=dev),
+           "hits": torch.empty((P,), dtype=torch.int32, device=dev),
+           "ratio": torch.empty((P, 2), dtype=torch.float64, device=dev)}
+    visits = torch.empty((P,), dtype=torch.int64, device=dev) if want_visits else None
+    stage_ms = (ctypes.c_double * 4)() if want_stage_ms else None
+    cut_d2 = torch.empty((P, int(max_iterations) + 1), dtype=torch.float64, device=dev) if want_cuts else None
+    cut_i = torch.empty((P, int(max_iterations) + 1), dtype=torch.int32, device=dev) if want_cuts else None
+    with torch.cuda.device(dev), prof.kernel("icp_refine", 28.0 * P * Lmax * (int(max_iterations) + 1)):
+        _lib.check(_lib.lib().usip_icp_refine_f32(
+            _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0], _ptr(perm1), _ptr(frag1),
+            _ptr(frag2), _ptr(Rt0), _opt_ptr(mask), _opt_ptr(order2), P, Lmax, float(inlier_ratio), int(max_iterations),
+            float(tol_t), float(tol_c), float(align_radius), _ptr(workspace), workspace.numel(), _ptr(out["Rt"]),
+            _ptr(out["iterations"]), _ptr(out["converged"]), _ptr(out["rmse"]), _ptr(out["hits"]), _ptr(out["ratio"]),
+            _opt_ptr(cut_d2), _opt_ptr(cut_i), _opt_ptr(visits), ctypes.addressof(stage_ms) if want_stage_ms else None, _stream(rows)), "usip_icp_refine_f32")
+    if want_visits:
+        out["visits"] = visits
+    if want_stage_ms:
+        out["stage_ms"] = list(stage_ms)
+    if want_cuts:
+        out["cut_d2"], out["cut_i"] = cut_d2, cut_i
     return out
