@@ -20,6 +20,13 @@ point-to-point ICP (pcregrigid's InlierRatio 0.3; --refine-iterations N, default
 0.009 rad), the share of moved points within 0.05 m recomputed and the log gated by `> 0.15` instead of `> 0.23`.  The log
 holds the unrefined estimate, as the reference's does; --log-transform refined writes the refined pose instead.
 
+--optimize (needs --refine icp) adds split_txt_compute_G.m and the robust pose-graph optimisation behind it: the dense
+information matrix of every pair under its refined pose, the log's pairs as a pose graph, the loop closures the graph does
+not support pruned (--optimize-tau2 X, default 0.04; --optimize-fill gt|estimate: what stands in for an odometry pair the log
+lacks, default gt; --optimize-transform edge|graph: what the refined log holds, default edge).  The JSON line then also
+carries loop_recall, loop_precision, loops_in and loops_kept, and <scene>_odom.log/.info, <scene>_loop.log/.info and
+<scene>_reg_refine_all.log are written beside <scene>.log.
+
 Prints ONE JSON line (what evaluate.m prints, per scene and as means, and the registrator) and writes <results>/<scene>.log as writeLog.m does;
 with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
 import argparse
@@ -33,6 +40,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from usip_amd import fragments as fr            # noqa: E402
+from usip_amd import posegraph as pg            # noqa: E402
+
+LOOP_KEYS = ("loop_recall", "loop_precision", "loops_in", "loops_kept")
 
 
 def make_synthetic(root, fragments, points, dim, seed):
@@ -58,7 +68,9 @@ def evaluate_scene(name, scenes, results, gt_root, args):
     ev = fr.FragmentEvaluator(None, None, None, args.device, top=top, k=args.k, max_trials=args.trials, seed=args.seed,
                               batch_pairs=args.batch_pairs, registrator=args.registration, refine=args.refine == "icp",
                               refine_args=dict(max_iterations=args.refine_iterations, tolerance=tuple(args.refine_tolerance)),
-                              log_transform=args.log_transform)
+                              log_transform=args.log_transform, optimize=args.optimize,
+                              optimize_args=dict(tau2=args.optimize_tau2, fill=args.optimize_fill,
+                                                 transform=args.optimize_transform) if args.optimize else None)
     for i, path in enumerate(clouds):
         ev.add_fragment_result(i, rows[i][0], rows[i][1], np.load(path))
     gt = fr.read_log(os.path.join(gt_root, "%s-evaluation" % name, "gt.log"))
@@ -73,8 +85,11 @@ def evaluate_scene(name, scenes, results, gt_root, args):
             fr.write_pair_file(os.path.join(results, name, "registration-results", "%d-%d.rt.txt" % (a, b)),
                                fr.PairFile(a, b, int(pp["inliers"][p]), float(pp["inlier_ratio"][p]),
                                            tuple(pp["ratio_aligned"][p]), fr.to4x4(pp["Rt"][p]), pp["information"][p]))
+    if args.optimize:
+        pg.write_split(results, name, *out["split"])
+        pg.write_refined(results, name, out["refined_entries"])
     return {k: out[k] for k in ("pairs", "written", "recall", "precision", "inlier_num_mean", "inlier_ratio_mean", "good",
-                                "bad", "false_pos", "gt_num", "rs_num")}
+                                "bad", "false_pos", "gt_num", "rs_num") + (LOOP_KEYS if args.optimize else ())}
 
 
 def main():
@@ -94,6 +109,10 @@ def main():
     ap.add_argument("--log-transform", choices=("estimate", "refined"), default="estimate")
     ap.add_argument("--refine-tolerance", type=float, nargs=2, metavar=("T", "R"), default=list(fr.REFINE_TOLERANCE))
     ap.add_argument("--refine-iterations", type=int, default=fr.REFINE_ITERATIONS)
+    ap.add_argument("--optimize", action="store_true")
+    ap.add_argument("--optimize-tau2", type=float, default=pg.TAU2)
+    ap.add_argument("--optimize-fill", choices=("gt", "estimate"), default="gt")
+    ap.add_argument("--optimize-transform", choices=("edge", "graph"), default="edge")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--batch-pairs", type=int, default=32)
     ap.add_argument("--pair-files", action="store_true")
@@ -101,6 +120,8 @@ def main():
     args = ap.parse_args()
     if args.log_transform == "refined" and args.refine != "icp":
         ap.error("--log-transform refined needs --refine icp")
+    if args.optimize and args.refine != "icp":
+        ap.error("--optimize needs --refine icp")
     if args.make_synthetic:
         scenes, results, gt = make_synthetic(args.make_synthetic, args.fragments, args.points, args.dim, args.seed)
         names = ["synthetic"]
@@ -116,6 +137,12 @@ def main():
         out[k] = float(np.mean([s[k] for s in per_scene.values()]))
     for k in ("pairs", "written"):
         out[k] = int(sum(s[k] for s in per_scene.values()))
+    if args.optimize:
+        out["optimize"] = dict(tau2=args.optimize_tau2, fill=args.optimize_fill, transform=args.optimize_transform)
+        for k in LOOP_KEYS[:2]:
+            out[k] = float(np.mean([s[k] for s in per_scene.values()]))
+        for k in LOOP_KEYS[2:]:
+            out[k] = int(sum(s[k] for s in per_scene.values()))
     print(json.dumps(out))
 
 

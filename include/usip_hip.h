@@ -1120,6 +1120,80 @@ int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int64_t* offse
                             int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
                             double* cut_d2, int32_t* cut_i, int32_t* idx_out, double* d2_out, int num_threads);
 
+/* ------------------------------------------------------------------ f-14  loop closures pruned by pose-graph optimisation
+ * The reference's last indoor number is not per pair: eval_indoor/split_txt_compute_G.m splits <scene>.log into odometry
+ * (j - i == 1) and loop-closure edges with a dense 6 x 6 information matrix each (computeInformation, method 'point'), a
+ * robust global optimisation (Choi, Zhou, Koltun, CVPR 2015) prunes the loop closures that disagree with the rest of the
+ * graph, and loop_evaluation/ scores what is left.  The optimiser is a tool the reference does not ship, so the definition
+ * below is this project's own, written from the paper.  f-9's and f-13's conventions: float64 arithmetic, never contracted,
+ * every sum in a stated order, no floating-point atomics, no launch synchronises the host, every index read from memory is
+ * checked or clamped before use.  csrc/posegraph_math.h is the arithmetic.
+ *
+ * usip_icp_information_f32: f-13's bank (perm1 is not needed) and pairs; idx i32 [P][Lmax], d2 f64 [P][Lmax] as
+ * usip_icp_nearest_f32 wrote them under the pose in question; mask u8 [P] (NULL: all ones).  count i32 [P] = the rows i < n2
+ * with sqrt(d2_i) < radius (f-9's within, strict); info f64 [P][6][6] = the sum over those rows, with multiplicity, of A'A at
+ * s = a_idx[i] (idx clamped into fragment 1), A as usip_information_f32's: lane l of 256 adds its rows among l, l + 256, ...
+ * in ascending i, the 256 partial sums of the nine distinct terms go through f-6's binary tree, the matrix is assigned entry
+ * by entry and so exactly symmetric.  A pair with mask 0, n1 = 0, n2 = 0 or no row within the radius gets zeros, never a NaN.
+ * USIP_EINVAL: the bank's and P's limits of f-13, a radius that is not positive, a NULL among the required pointers.
+ *
+ * usip_posegraph_optimize_f64: S scenes in one call.  Per scene: n i32 [S] fragments, ecount i32 [S] edges sorted by (i, j)
+ * with 0 <= i < j < n and at most one edge per pair: edge_i, edge_j i32 [S][Emax], X f64 [S][Emax][3][4] mapping fragment j
+ * into fragment i's frame (a .log entry), info f64 [S][Emax][6][6] (symmetric; info[0][0] is the number of aligned points);
+ * T0 f64 [S][Nmax][3][4], the start poses mapping fragment k into fragment 0's frame.  An edge with j == i + 1 is an odometry
+ * edge: its weight is 1 and it is never pruned.  Fragment 0 is fixed.  The unknowns of a step are d_k = (rho_k, phi_k), k = 1
+ * .. n - 1, translation first.  One iteration:
+ *  1 per edge E = T_i^-1 T_j (the rigid inverse R', -(R' t); every 3-sum from the left), D = E X^-1, e = [t(D); qv(D)] with
+ *    qv the vector part of the quaternion of R(D) by Shepperd's rule: the branch is the largest of (trace, R00, R11, R22),
+ *    the lowest index on ties, the sign such that w >= 0 -- finite at a half turn, which a wrong loop closure can be.
+ *  2 f = sum_r e_r (sum_c L_rc e_c), both ascending, L the edge's info; mu = L_00 tau2; the weight l = 1 for an odometry
+ *    edge, else (mu / (mu + f))^2, or 0 when mu + f is not finite and positive; in stage 2 a loop edge with kept = 0 has l = 0.
+ *    An edge with l = 0 contributes nothing.
+ *  3 J_i = -S, J_j = S Ad_E, S = diag(1, 1, 1, 1/2, 1/2, 1/2), Ad_E (rho, phi) = (R_E rho + t_E x (R_E phi), R_E phi): the
+ *    small-residual Jacobians of the right perturbations T_k <- T_k exp(d_k).
+ *  4 H's block (j, i) is l J_j' L J_i of its one edge; block (a, a) is the sum of l J_a' L J_a over the edges incident to a in
+ *    ascending edge index, g_a the sum of l J_a' L e over the same edges (csrc/posegraph_math.h: edge_blocks has the
+ *    expressions); the incidence lists are built inside the call.
+ *  5 H = L L' over the 6 (n - 1) unknowns: every entry is H_rc minus its inner sum in ascending k, divided by the pivot's
+ *    square root; x = H^-1 g by forward substitution in ascending and backward substitution in descending order; d = -x.
+ *  6 Rd = Rz(phi2) Ry(phi1) Rx(phi0) with f-12's fgr_sincos; t <- R rho + t with the old R, then R <- R Rd.  step = the largest
+ *    |component| of d.
+ *  7 A pivot that is not finite and positive (status 1), a component of d that is not finite (2) or an angle |phi| > pi (3)
+ *    ends the scene: the last good poses stay, iterations_done counts the steps that succeeded.
+ * Stage 1 runs iterations1 steps (no stopping rule); a weight pass under its final poses gives weight1, and kept = odometry ||
+ * weight1 >= prune.  Stage 2 runs iterations2 steps from stage 1's poses over the kept edges, the line process still on; a
+ * final weight pass gives weight2 (0 for an edge that was not kept) and energy = f (-1 where f is not finite).  A scene that
+ * ended early skips the remaining steps, not the weight passes.
+ * T f64 [S][Nmax][3][4]; weight1, weight2, energy f64 [S][Emax]; kept u8 [S][Emax]; iterations_done i32 [S][2]; last_step f64
+ * [S][2] (the last successful step of either stage, 0 without one); status i32 [S]; zeros beyond n and ecount; no NaN leaves
+ * the call.  workspace: usip_posegraph_workspace_bytes(S, Nmax, Emax) bytes of device memory.
+ *
+ * Limits: S <= 65535, 2 <= n <= Nmax <= 128, 1 <= Emax <= Nmax (Nmax - 1) / 2, iterations in 0 .. 256, tau2 > 0 and finite,
+ * 0 <= prune <= 1; anything else, a NULL among the required pointers or a workspace too small is USIP_EINVAL.  A scene whose n
+ * or ecount is outside its range, or whose edges are unsorted, repeated or have i >= j or j >= n, is USIP_EINVAL in the host
+ * twin; the device entry cannot read its arrays without waiting for the device, so there such a scene gets status 4 and zeros
+ * in every other output, and nothing of it is indexed. */
+int usip_icp_information_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                             const int32_t* frag1, const int32_t* frag2, const int32_t* idx, const double* d2,
+                             const uint8_t* mask, int P, int Lmax, double radius, double* info, int32_t* count, void* stream);
+long long usip_posegraph_workspace_bytes(int S, int Nmax, int Emax);
+int usip_posegraph_optimize_f64(const int32_t* n, const int32_t* ecount, const int32_t* edge_i, const int32_t* edge_j,
+                                const double* X, const double* info, const double* T0, int S, int Nmax, int Emax, double tau2,
+                                double prune, int iterations1, int iterations2, void* workspace, long long workspace_bytes,
+                                double* T, double* weight1, double* weight2, double* energy, uint8_t* kept,
+                                int32_t* iterations_done, double* last_step, int32_t* status, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order, as plain loops; num_threads splits the
+ * pairs or the scenes. */
+int usip_icp_information_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                                 const int32_t* frag1, const int32_t* frag2, const int32_t* idx, const double* d2,
+                                 const uint8_t* mask, int P, int Lmax, double radius, double* info, int32_t* count,
+                                 int num_threads);
+int usip_posegraph_optimize_f64_cpu(const int32_t* n, const int32_t* ecount, const int32_t* edge_i, const int32_t* edge_j,
+                                    const double* X, const double* info, const double* T0, int S, int Nmax, int Emax,
+                                    double tau2, double prune, int iterations1, int iterations2, double* T, double* weight1,
+                                    double* weight2, double* energy, uint8_t* kept, int32_t* iterations_done,
+                                    double* last_step, int32_t* status, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

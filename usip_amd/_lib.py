@@ -245,6 +245,17 @@ SIGNATURES = {
                                 + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _dbl, _int, _dbl, _dbl, _dbl, ctypes.c_void_p,
                                                            _i32p, ctypes.c_void_p, ctypes.c_void_p, _i32p, ctypes.c_void_p,
                                                            ctypes.c_void_p, _i32p, _i32p, ctypes.c_void_p, _int], _int),
+    # f-14 loop closures pruned by pose-graph optimisation: dense information, the optimiser (usip_amd/posegraph.py)
+    "usip_icp_information_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
+                                 + [ctypes.c_void_p] * 2 + [_int, _int, _dbl, ctypes.c_void_p, _i32p, _stream], _int),
+    "usip_posegraph_workspace_bytes": ([_int, _int, _int], ctypes.c_longlong),
+    "usip_posegraph_optimize_f64": ([_i32p] * 4 + [ctypes.c_void_p] * 3 + [_int, _int, _int, _dbl, _dbl, _int, _int,
+                                                                           ctypes.c_void_p, ctypes.c_longlong]
+                                    + [ctypes.c_void_p] * 5 + [_i32p, ctypes.c_void_p, _i32p, _stream], _int),
+    "usip_icp_information_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
+                                     + [ctypes.c_void_p] * 2 + [_int, _int, _dbl, ctypes.c_void_p, _i32p, _int], _int),
+    "usip_posegraph_optimize_f64_cpu": ([_i32p] * 4 + [ctypes.c_void_p] * 3 + [_int, _int, _int, _dbl, _dbl, _int, _int]
+                                        + [ctypes.c_void_p] * 5 + [_i32p, ctypes.c_void_p, _i32p, _int], _int),
 }
 
 

@@ -182,16 +182,23 @@ USIP_HD bool solve6(const double S[NSUM], double x[6])
     return ok && fabs(x[0]) <= PI && fabs(x[1]) <= PI && fabs(x[2]) <= PI;
 }
 
-// Rd = Rz(x2) Ry(x1) Rx(x0); R <- Rd R, t <- Rd t + x3..5
-USIP_HD void apply_step(Pose& p, const double x[6])
+// D = Rz(x2) Ry(x1) Rx(x0), row-major, |x| <= pi (csrc/posegraph_math.h takes its step's rotation from here too)
+USIP_HD void rotation_zyx(const double x[3], double D[9])
 {
     double sa, ca, sb, cb, sg, cg;
     fgr_sincos(x[0], &sa, &ca);
     fgr_sincos(x[1], &sb, &cb);
     fgr_sincos(x[2], &sg, &cg);
-    const double D[9] = {cg * cb, (cg * sb) * sa - sg * ca, (cg * sb) * ca + sg * sa,
-                         sg * cb, (sg * sb) * sa + cg * ca, (sg * sb) * ca - cg * sa,
-                         -sb,     cb * sa,                  cb * ca};
+    D[0] = cg * cb; D[1] = (cg * sb) * sa - sg * ca; D[2] = (cg * sb) * ca + sg * sa;
+    D[3] = sg * cb; D[4] = (sg * sb) * sa + cg * ca; D[5] = (sg * sb) * ca - cg * sa;
+    D[6] = -sb;     D[7] = cb * sa;                  D[8] = cb * ca;
+}
+
+// Rd = Rz(x2) Ry(x1) Rx(x0); R <- Rd R, t <- Rd t + x3..5
+USIP_HD void apply_step(Pose& p, const double x[6])
+{
+    double D[9];
+    rotation_zyx(x, D);
     Pose n;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {

@@ -13,6 +13,9 @@ mrEvaluateRegistrationMy.m).
   RefineBank / icp_refine  writeLogReconputeAlign.m: both fragments voxel-averaged at 0.04 m, the estimate refined by trimmed
                            point-to-point ICP (pcregrigid's InlierRatio 0.3), the share of moved points within 0.05 m and
                            the second gate, `> 0.15` (csrc/icp.hip)
+  optimize                 split_txt_compute_G.m and the robust pose-graph optimisation behind it: the dense information of
+                           every pair under its refined pose, the loop closures the graph does not support pruned, recall
+                           and precision after pruning (usip_amd/posegraph.py, csrc/posegraph.hip)
   *_cpu                    the same on numpy arrays over the library's host twins (csrc/fragments_cpu.cpp; RANSAC:
                            evaluation.ransac_*_cpu with the limit at 10240)
   transformation_error     mrComputeTransformationError with the file's own dcm2quat
@@ -439,7 +442,7 @@ def icp_refine_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, inlier_ratio: fl
 def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                    threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
                    seed: int = 0, registrator: str = "ransac", refine: Optional[RefineBank] = None,
-                   refine_args: Optional[Dict] = None) -> Dict[str, torch.Tensor]:
+                   refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """register2Fragments.m for a batch of pairs, on the device: kp f32 [P,3,M], desc f32 [P,D,M], n i32 [P] of either
     fragment; frag1, frag2 i32 [P] into the bank; pair_ids i64 [P] key the draws.  No host synchronisation.
 
@@ -452,12 +455,21 @@ def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, fr
     refine: the scene's RefineBank (its fragments in the bank's order) adds writeLogReconputeAlign.m to either registrator:
     icp_refine(refine, frag1, frag2, Rt, mask = valid & inlier_ratio > 0.025, **refine_args) and the keys refined_Rt,
     refine_iterations, refine_converged, refined_ratio_aligned, refined_hits and gate_refined = refined ratio(1) > 0.15 &
-    inlier_ratio > 0.025.  A pair outside the mask fails that gate whatever ICP would find.  Every other key is unchanged."""
+    inlier_ratio > 0.025.  A pair outside the mask fails that gate whatever ICP would find.  Every other key is unchanged.
+
+    dense_radius (with refine): split_txt_compute_G.m's computeInformation 'point' under refined_Rt, over the same mask:
+    the keys dense_information f64 [P,6,6] and dense_count i32 [P] (posegraph.dense_information)."""
     out = _register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
                           seed, registrator)
+    if dense_radius is not None and refine is None:
+        raise ValueError("register_pairs: dense_radius needs refine")
     if refine is not None:
         mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
         _refined(out, icp_refine(refine, frag1, frag2, out["Rt"], mask, **(refine_args or {})), False)
+        if dense_radius is not None:
+            from . import posegraph
+            out["dense_information"], out["dense_count"] = posegraph.dense_information(refine, frag1, frag2, out["refined_Rt"],
+                                                                                       mask, dense_radius)
     return out
 
 
@@ -494,7 +506,7 @@ def _register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids
 def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                        threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
                        seed: int = 0, num_threads: int = 1, registrator: str = "ransac", refine: Optional[HostBank] = None,
-                       refine_args: Optional[Dict] = None) -> Dict[str, np.ndarray]:
+                       refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None) -> Dict[str, np.ndarray]:
     """register_pairs assembled from the host twins, on numpy arrays; refine: the HostBank of the downsampled fragments
     (refine_bank_cpu, or RefineBank.host())."""
     out = _register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
@@ -503,6 +515,12 @@ def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, fr
         mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
         _refined(out, icp_refine_cpu(refine, out["frag1"], out["frag2"], out["Rt"], mask, num_threads=num_threads,
                                      **(refine_args or {})), True)
+        if dense_radius is not None:
+            from . import posegraph
+            out["dense_information"], out["dense_count"] = posegraph.dense_information_cpu(
+                refine, out["frag1"], out["frag2"], out["refined_Rt"], mask, dense_radius, num_threads)
+    elif dense_radius is not None:
+        raise ValueError("register_pairs_cpu: dense_radius needs refine")
     return out
 
 
@@ -714,13 +732,21 @@ class FragmentEvaluator:
     [1,3,M] device tensors) and caches keypoints, descriptors and count beside the fragment's full cloud ([rows, >= 3]);
     add_fragment_result(id, xyz, desc, cloud) takes precomputed [xyz, descriptor] rows, what the .bin files hold.  Ids
     are the fragments' integer indices in the scene.  evaluate(pairs, gt, gt_info) runs the pairs (default: all i < j) in
-    batches through register_pairs, reads the host once, applies writeLog.m's gate and scores with evaluate_log."""
+    batches through register_pairs, reads the host once, applies writeLog.m's gate and scores with evaluate_log.
+
+    optimize (needs refine): split_txt_compute_G.m and the optimisation behind it.  Every pair's dense information is taken
+    under refined_Rt; the pairs that pass the log's gate are the graph's edges, with the log's transform (log_transform);
+    the graph is built and optimised on the device before the one read (posegraph.prune_pairs).  optimize_args: tau2,
+    prune, iterations1, iterations2 (include/usip_hip.h f-14), fill ("gt": a missing odometry pair comes from gt.log and
+    gt.info, the default when evaluate() is given them; "estimate": from the pair's ungated estimate; None), transform
+    ("edge" or "graph": what the refined log's entries hold), radius.  summarize() then also returns loop_recall,
+    loop_precision, loops_in, loops_kept, and per pair dense_information, dense_count, loop_weight, loop_kept, loop_Rt."""
 
     def __init__(self, detector, descriptor, opt, device, nms_radius: float = 0.1, top: int = 512, k: int = K_MATCH,
                  inlier_threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,
                  overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32, registrator: str = "ransac",
                  refine: bool = False, refine_leaf: float = REFINE_LEAF, refine_args: Optional[Dict] = None,
-                 log_transform: str = "estimate"):
+                 log_transform: str = "estimate", optimize: bool = False, optimize_args: Optional[Dict] = None):
         if log_transform not in ("estimate", "refined"):
             raise ValueError("log_transform must be 'estimate' or 'refined' (got %r)" % (log_transform,))
         if log_transform == "refined" and not refine:
@@ -728,6 +754,13 @@ class FragmentEvaluator:
         self.refine, self.refine_leaf, self.refine_args = bool(refine), float(refine_leaf), dict(refine_args or {})
         self.log_transform = log_transform
         self._refine_bank = None
+        if optimize and not refine:
+            raise ValueError("FragmentEvaluator: optimize=True needs refine=True (the dense information is taken under the "
+                             "refined pose)")
+        self.optimize, self.optimize_args = bool(optimize), dict(optimize_args or {})
+        if self.optimize:
+            from . import posegraph
+            posegraph.split_optimize_args(self.optimize_args)              # an unknown key is refused here
         if registrator not in ("ransac", "fgr"):
             raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
         if registrator == "fgr" and int(top) > ops.FGR_MMAX:
@@ -805,9 +838,16 @@ class FragmentEvaluator:
         fr = [self.fragments[i] for i in self.ids()]
         return torch.stack([f[0] for f in fr]), torch.stack([f[1] for f in fr]), torch.stack([f[2] for f in fr])
 
-    def evaluate_device(self, pairs: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
-        """Every pair through register_pairs, batch by batch -> per-pair device tensors; nothing synchronises."""
+    def evaluate_device(self, pairs: Optional[Sequence] = None, gt: Optional[Sequence] = None,
+                        gt_info: Optional[Sequence] = None) -> Dict[str, torch.Tensor]:
+        """Every pair through register_pairs, batch by batch -> per-pair device tensors; nothing synchronises.  With
+        optimize the scene's graph is built from them and optimised here too (gt, gt_info: what fill "gt" fills from)."""
         pairs = self.all_pairs() if pairs is None else list(pairs)
+        dense = None
+        if self.optimize:
+            from . import posegraph
+            dense = float(self.optimize_args.get("radius", posegraph.INFORMATION_RADIUS))
+            plan = posegraph.plan_for(pairs, self.ids(), gt, gt_info, self.optimize_args)   # a chain that cannot close: here
         slot = {i: s for s, i in enumerate(self.ids())}
         bank, fine = self.bank(), self.refine_bank()
         kp, desc, cnt = self.stacked()
@@ -820,28 +860,42 @@ class FragmentEvaluator:
             a, b = f1.long(), f2.long()
             parts.append(register_pairs(kp[a], desc[a], cnt[a].contiguous(), kp[b], desc[b], cnt[b].contiguous(), bank, f1,
                                         f2, ids, self.k, self.inlier_threshold, self.max_trials, self.overlap_radius,
-                                        self.seed, self.registrator, fine, self.refine_args))
+                                        self.seed, self.registrator, fine, self.refine_args, dense))
         if not parts:
             return {}
-        return {key: torch.cat([p[key] for p in parts]) for key in parts[0]}
+        out = {key: torch.cat([p[key] for p in parts]) for key in parts[0]}
+        if self.optimize:
+            out.update(posegraph.prune_pairs(plan, out["gate_refined"], out[self._log_key()], out["dense_information"],
+                                             self.optimize_args))
+        return out
+
+    def _log_key(self):
+        return "refined_Rt" if self.log_transform == "refined" else "Rt"
 
     def evaluate(self, pairs: Optional[Sequence] = None, gt: Optional[Sequence] = None,
                  gt_info: Optional[Sequence] = None) -> Dict:
-        dev = self.evaluate_device(pairs)
+        dev = self.evaluate_device(pairs, gt, gt_info)
         host = {k: v.cpu().numpy() for k, v in dev.items()}                # the one read
-        return summarize(host, self.ids(), gt, gt_info, None, "gate_refined" if self.refine else "gate",
-                         "refined_Rt" if self.log_transform == "refined" else "Rt")
+        return summarize(host, self.ids(), gt, gt_info, None, "gate_refined" if self.refine else "gate", self._log_key(),
+                         self.optimize_args if self.optimize else None)
 
 
 def summarize(per_pair: Dict[str, np.ndarray], fragment_ids: Sequence[int], gt=None, gt_info=None,
-              num_fragments: Optional[int] = None, gate: str = "gate", transform: str = "Rt") -> Dict:
-    """What evaluate.m prints (when gt and gt_info are given) plus the result log's entries and the per-pair arrays."""
+              num_fragments: Optional[int] = None, gate: str = "gate", transform: str = "Rt",
+              optimize_args: Optional[Dict] = None) -> Dict:
+    """What evaluate.m prints (when gt and gt_info are given) plus the result log's entries and the per-pair arrays.
+    optimize_args (a dict, possibly empty; per_pair must hold dense_information): the result log's pairs as a pose graph,
+    its loop closures pruned (posegraph.summarize_loops; run on the host twins here unless per_pair already holds
+    loop_kept) -> also loop_recall, loop_precision, loops_in, loops_kept, refined_entries and split."""
     n = int(num_fragments if num_fragments is not None else (gt[0].info[2] if gt else len(fragment_ids)))
     entries = result_entries(per_pair, fragment_ids, n, gate, transform) if per_pair else []
     out = {"pairs": int(len(per_pair[gate])) if per_pair else 0, "written": len(entries), "entries": entries,
            "per_pair": per_pair}
     if gt is not None and gt_info is not None:
         out.update(evaluate_log(entries, gt, gt_info))
+    if optimize_args is not None and per_pair:
+        from . import posegraph
+        out.update(posegraph.summarize_loops(per_pair, fragment_ids, gt, gt_info, gate, transform, optimize_args))
     return out
 
 

@@ -2104,3 +2104,91 @@ def icp_refine(rows, offsets, perm1, frag1, frag2, Rt0, Lmax: int, mask=None, or
     if want_cuts:
         out["cut_d2"], out["cut_i"] = cut_d2, cut_i
     return out
+
+
+# ------------------------------------------------------------------------------------------------ f-14 pose-graph pruning
+POSEGRAPH_NMAX, POSEGRAPH_MAX_ITERATIONS = 128, 256
+
+
+def icp_information(rows, offsets, frag1, frag2, idx, d2, mask=None, radius: float = 0.05):
+    """f-14: the dense information matrix of computeInformation 'point' over the rows icp_nearest found within `radius`:
+    idx i32 [P,Lmax], d2 f64 [P,Lmax] of icp_nearest on the same bank and pairs -> (info f64 [P,6,6], count i32 [P]); zeros
+    where mask u8 [P] is 0, a fragment is empty or no row is within the radius."""
+    P = _need_bank(rows, offsets, frag1, frag2, None)
+    if frag1 is None or idx is None or d2 is None:
+        raise RuntimeError("icp_information: frag1, idx and d2 are required")
+    dev = rows.device
+    _need(idx, "idx", torch.int32)
+    if idx.dim() != 2 or idx.shape[0] != P or not 1 <= idx.shape[1] <= 1 << 24 or idx.device != dev:
+        raise RuntimeError("icp_information: idx must be i32 [P,Lmax] on %s" % dev)
+    Lmax = idx.shape[1]
+    _need_on(d2, "d2", torch.float64, (P, Lmax), dev)
+    _need_on(mask, "mask", torch.uint8, (P,), dev)
+    if P > 65535 or not float(radius) > 0.0:
+        raise RuntimeError("icp_information: at most 65535 pairs per call and a positive radius (got %d, %r)" % (P, radius))
+    info = torch.empty((P, 6, 6), dtype=torch.float64, device=dev)
+    count = torch.empty((P,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev), prof.kernel("icp_information", 12.0 * P * Lmax):
+        _lib.check(_lib.lib().usip_icp_information_f32(
+            _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0], _ptr(frag1), _ptr(frag2),
+            _ptr(idx), _ptr(d2), _opt_ptr(mask), P, Lmax, float(radius), _ptr(info), _ptr(count), _stream(rows)),
+            "usip_icp_information_f32")
+    return info, count
+
+
+def posegraph_workspace_bytes(S: int, Nmax: int, Emax: int) -> int:
+    need = int(_lib.lib().usip_posegraph_workspace_bytes(int(S), int(Nmax), int(Emax)))
+    if need < 0:
+        raise RuntimeError("usip_amd: usip_posegraph_workspace_bytes: invalid argument (USIP_EINVAL)")
+    return need
+
+
+def posegraph_optimize(n, ecount, edge_i, edge_j, X, info, T0, tau2: float = 0.04, prune: float = 0.25,
+                       iterations1: int = 32, iterations2: int = 32, workspace=None):
+    """f-14: the robust pose-graph optimisation of S scenes in one launch.  n, ecount i32 [S]; edge_i, edge_j i32 [S,Emax]
+    sorted by (i, j); X f64 [S,Emax,3,4]; info f64 [S,Emax,6,6]; T0 f64 [S,Nmax,3,4] -> dict(T, weight1, weight2, energy,
+    kept u8 [S,Emax], iterations_done i32 [S,2], last_step f64 [S,2], status i32 [S]: 0 done, 1 pivot, 2 a step that is not
+    finite, 3 an angle beyond pi, 4 a graph out of shape).  No host synchronisation."""
+    _need(T0, "T0", torch.float64)
+    if T0.dim() != 4 or tuple(T0.shape[2:]) != (3, 4):
+        raise RuntimeError("posegraph: expected T0 f64 [S,Nmax,3,4]")
+    S, Nmax = T0.shape[0], T0.shape[1]
+    _need(edge_i, "edge_i", torch.int32)
+    if edge_i.dim() != 2 or edge_i.shape[0] != S:
+        raise RuntimeError("posegraph: expected edge_i i32 [S,Emax]")
+    Emax, dev = edge_i.shape[1], T0.device
+    if not (S <= 65535 and 2 <= Nmax <= POSEGRAPH_NMAX and 1 <= Emax <= Nmax * (Nmax - 1) // 2):
+        raise RuntimeError("posegraph: S <= 65535, 2 <= Nmax <= %d and 1 <= Emax <= Nmax (Nmax - 1) / 2 (got %d, %d, %d)"
+                           % (POSEGRAPH_NMAX, S, Nmax, Emax))
+    for t, name, dt, shape in ((n, "n", torch.int32, (S,)), (ecount, "ecount", torch.int32, (S,)),
+                               (edge_i, "edge_i", torch.int32, (S, Emax)), (edge_j, "edge_j", torch.int32, (S, Emax)),
+                               (X, "X", torch.float64, (S, Emax, 3, 4)), (info, "info", torch.float64, (S, Emax, 6, 6))):
+        if t is None:
+            raise RuntimeError("posegraph: %s is required" % name)
+        _need_on(t, name, dt, shape, dev)
+    if not (float(tau2) > 0.0 and math.isfinite(float(tau2)) and 0.0 <= float(prune) <= 1.0
+            and 0 <= int(iterations1) <= POSEGRAPH_MAX_ITERATIONS and 0 <= int(iterations2) <= POSEGRAPH_MAX_ITERATIONS):
+        raise RuntimeError("posegraph: tau2 > 0, prune in [0, 1] and iterations in 0..%d (got %r, %r, %r, %r)"
+                           % (POSEGRAPH_MAX_ITERATIONS, tau2, prune, iterations1, iterations2))
+    need = posegraph_workspace_bytes(S, Nmax, Emax)
+    if workspace is None:
+        workspace = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need or not workspace.is_contiguous():
+        raise RuntimeError("posegraph: workspace must be contiguous u8 [>= %d] on %s" % (need, dev))
+    out = {"T": torch.empty((S, Nmax, 3, 4), dtype=torch.float64, device=dev),
+           "weight1": torch.empty((S, Emax), dtype=torch.float64, device=dev),
+           "weight2": torch.empty((S, Emax), dtype=torch.float64, device=dev),
+           "energy": torch.empty((S, Emax), dtype=torch.float64, device=dev),
+           "kept": torch.empty((S, Emax), dtype=torch.uint8, device=dev),
+           "iterations_done": torch.empty((S, 2), dtype=torch.int32, device=dev),
+           "last_step": torch.empty((S, 2), dtype=torch.float64, device=dev),
+           "status": torch.empty((S,), dtype=torch.int32, device=dev)}
+    M = 6.0 * (Nmax - 1)
+    steps = int(iterations1) + int(iterations2)
+    with torch.cuda.device(dev), prof.kernel("posegraph_optimize", 8.0 * S * steps * M * M, S * steps * M * M * M / 3.0):
+        _lib.check(_lib.lib().usip_posegraph_optimize_f64(
+            _ptr(n), _ptr(ecount), _ptr(edge_i), _ptr(edge_j), _ptr(X), _ptr(info), _ptr(T0), S, Nmax, Emax, float(tau2),
+            float(prune), int(iterations1), int(iterations2), _ptr(workspace), workspace.numel(), _ptr(out["T"]),
+            _ptr(out["weight1"]), _ptr(out["weight2"]), _ptr(out["energy"]), _ptr(out["kept"]), _ptr(out["iterations_done"]),
+            _ptr(out["last_step"]), _ptr(out["status"]), _stream(T0)), "usip_posegraph_optimize_f64")
+    return out
