@@ -6,6 +6,7 @@ The RANSAC bars are f-6's (tests/test_registration_cpu.py, derived there): 1e-9 
 oracle's eigen-gap is below 1e-5 lambda_max or an oracle residual lies within 1e-7 m of the threshold, at most 1 % left out
 -- and the fixtures here leave out none, which is asserted."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -15,6 +16,9 @@ import fragments_oracle as fo
 from conftest import GOLDEN
 from usip_amd import evaluation as ev
 from usip_amd import fragments as fr
+
+sys.path.insert(0, GOLDEN)
+import make_tile_walk_golden as tw  # noqa: E402   (the cases of tests/golden/tile_walk_parent_bits.npz and how they are stored)
 
 TOL_R, TOL_T = 1e-9, 1e-7
 GAP, NEAR = 1e-5, 1e-7
@@ -480,3 +484,16 @@ def test_synthetic_scene_scores_one_through_the_host_twins():
                               np.arange(len(pairs)), num_threads=8)
     s = fr.summarize(o, list(range(F)), sc["gt"], sc["gt_info"])
     assert s["gt_num"] >= 6 and s["recall"] == 1.0 and s["precision"] == 1.0
+
+
+# ------------------------------------------------------------------------------------------------ the pinned bits
+@pytest.mark.parametrize("name", tw.OVERLAP)
+def test_overlap_gives_the_bits_pinned_before_the_tile_walk_was_shared(name):
+    """tests/golden/tile_walk_parent_bits.npz: (ratio, hits) of the twin before csrc/bank.h and csrc/host_split.h."""
+    tw.check("overlap-" + name, tw.overlap_host(name), "host twin")
+
+
+@pytest.mark.parametrize("registrator", tw.REGISTRATORS)
+def test_register_pairs_cpu_gives_the_bits_pinned_before_it_ran_over_a_backend(registrator):
+    """Every key of register_pairs_cpu with refine and dense_radius set, as the two copies of the pipeline returned them."""
+    tw.check("pairs-" + registrator, tw.pairs_host(registrator), "host twins")

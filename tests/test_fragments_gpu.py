@@ -437,3 +437,15 @@ def test_example_scores_recall_one_on_the_synthetic_scene(tmp_path):
     assert res["recall"] == 1.0 and res["precision"] == 1.0 and res["pairs"] == 15
     log = fr.read_result_log(str(tmp_path / "scene" / "results" / "synthetic.log"))
     assert len(log) == res["written"] and os.path.exists(str(tmp_path / "scene" / "results" / "synthetic" / "0.bin"))
+
+
+@pytest.mark.parametrize("name", tc.tw.OVERLAP)
+def test_overlap_on_the_device_gives_the_pinned_parent_bits(name):
+    """tests/golden/tile_walk_parent_bits.npz through overlap_kernel<XQ> over csrc/tile_walk.h: a partial last tile, the
+    binary search at lo == nd with the start tile clamped, constant-x runs of 65 tiles, an empty fragment."""
+    tc.tw.check("overlap-" + name, tc.tw.overlap_device(name, DEV), "device")
+
+
+@pytest.mark.parametrize("registrator", tc.tw.REGISTRATORS)
+def test_register_pairs_on_the_device_gives_the_pinned_parent_bits(registrator):
+    tc.tw.check("pairs-" + registrator, tc.tw.pairs_device(registrator, DEV), "device")

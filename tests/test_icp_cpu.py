@@ -16,13 +16,17 @@ Those three tests run the emulation only, no library code: icp_oracle.walk must 
 import os
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import icp_oracle as io
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 from usip_amd import fragments as fr
+
+sys.path.insert(0, GOLDEN)
+import make_tile_walk_golden as tw  # noqa: E402   (the cases of tests/golden/tile_walk_parent_bits.npz and how they are stored)
 
 MARGIN = 1e-9
 POSE_IS_FREE = ("one_row_a",)       # every rotation about the one row fits equally well: the pose is not compared
@@ -290,3 +294,10 @@ def test_twin_runs_clean_under_address_and_undefined_behaviour_sanitizers(tmp_pa
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     print(r.stdout.decode()[-2000:])
     assert r.returncode == 0 and b"runtime error" not in r.stdout and b"AddressSanitizer" not in r.stdout
+
+
+@pytest.mark.parametrize("name", io.NAMES)
+def test_twin_gives_the_bits_pinned_before_the_tile_walk_was_shared(name):
+    """tests/golden/tile_walk_parent_bits.npz: one nearest pass (idx, d2) and every output of the loop, the cuts included,
+    as the twin computed them before csrc/bank.h and csrc/host_split.h."""
+    tw.check("icp-" + name, tw.icp_host(name), "host twin")

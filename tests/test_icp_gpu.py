@@ -205,3 +205,10 @@ def test_limits_are_refused():
     with pytest.raises(RuntimeError):
         ops.icp_nearest(d.rows.cpu(), d.offsets, d.perm, dev(f1), dev(f2), dev(Rt0), bank.lmax)
     assert ops.icp_workspace_bytes(3, 1000) >= 3 * 1000 * 12
+
+
+@pytest.mark.parametrize("name", io.NAMES)
+def test_device_gives_the_pinned_parent_bits(name):
+    """tests/golden/tile_walk_parent_bits.npz through icp_nearest_kernel over csrc/tile_walk.h: n = 1 and 0, a partial last
+    tile, lo == n1 with the start tile clamped, constant-x runs longer than a tile."""
+    host.tw.check("icp-" + name, host.tw.icp_device(name, DEV), "device")

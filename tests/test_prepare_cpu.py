@@ -13,11 +13,17 @@ to 1e-13, 3x the larger of the two.  Curvature: 1e-12 absolute (an eigenvalue's 
 3.5e-16 and 4.4e-16).  A point is left out when the oracle's gap ratio is below 1e-3, its flip product below 1e-9 in
 magnitude or its two largest |normal| components within 1e-9;
 at most 1 % may be (0 of 20 000 are)."""
+import sys
+
 import numpy as np
 import pytest
 
 import prepare_oracle as po
+from conftest import GOLDEN
 from usip_amd import pairs, prepare
+
+sys.path.insert(0, GOLDEN)
+import make_tile_walk_golden as tw  # noqa: E402   (the cases of tests/golden/tile_walk_parent_bits.npz and how they are stored)
 
 K = 9
 VIEW = (0.0, 0.0, 1.0)
@@ -174,3 +180,9 @@ def test_bin_files_round_trip(tmp_path, scan):
     rows = prepare.prepare_cpu(scan[:2000], K)
     prepare.save_test_bin(tmp_path / "out.bin", rows)
     assert np.array_equal(np.fromfile(tmp_path / "out.bin", np.float32).reshape(-1, 6), rows[:, :6])
+
+
+@pytest.mark.parametrize("name", tw.SCANS)
+def test_neighbours_give_the_bits_pinned_before_the_thread_split_was_shared(name):
+    """tests/golden/tile_walk_parent_bits.npz: K = 1, 9, 16 on 255, 256, 257 and 515 rows and on a constant-x run."""
+    tw.check("knn-" + name, {"idx%d" % k: tw.knn_host(name, k) for k in tw.KNN_K}, "host twin")

@@ -182,3 +182,9 @@ def test_prepare_example_feeds_the_training_example(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     losses = [float(ln.split()[3]) for ln in r.stdout.splitlines() if ln.startswith("step")]
     assert losses and all(math.isfinite(v) for v in losses)
+
+
+@pytest.mark.parametrize("name", host.tw.SCANS)
+def test_neighbours_on_the_device_give_the_pinned_parent_bits(name):
+    """tests/golden/tile_walk_parent_bits.npz through scan_knn_kernel<K> over csrc/tile_walk.h's tiles and reduction."""
+    host.tw.check("knn-" + name, {"idx%d" % k: host.tw.knn_device(name, k, DEV) for k in host.tw.KNN_K}, "device")

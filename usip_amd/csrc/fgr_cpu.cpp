@@ -3,9 +3,9 @@
 // strided partial sums, then the binary tree).  num_threads splits the pairs.  Never reached from the device entry points.
 #include <cmath>
 #include <cstring>
-#include <thread>
 #include <vector>
 #include "fgr_math.h"
+#include "host_split.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_fgr;
@@ -13,22 +13,6 @@ using namespace usip_fgr;
 namespace {
 
 bool shape_ok(int P, int M) { return P >= 0 && P <= 65535 && M >= 1 && M <= MMAX; }
-
-template <class F>
-void over_pairs(int P, int num_threads, const F& f)
-{
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || P < 2) {
-        f(0, P);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-        const int lo = (int)((long long)P * w / nt), hi = (int)((long long)P * (w + 1) / nt);
-        if (lo < hi) pool.emplace_back([=, &f] { f(lo, hi); });
-    }
-    for (auto& th : pool) th.join();
-}
 
 struct TuplesOut {
     int32_t* mutual;
@@ -197,10 +181,10 @@ extern "C" int usip_fgr_tuples_f32_cpu(const float* kp1, const float* kp2, const
     const TuplesOut out{mutual, mutual_count, norm, rows, row_count, trials_walked, triples_out, triples_out ? T_out : 0};
     if (triples) {
         const ExplicitTriples src{triples, T};
-        over_pairs(P, num_threads, [&](int lo, int hi) { tuples_range(kp1, kp2, n1, n2, nn12, nn21, M, src, out, lo, hi); });
+        usip_host::split(P, num_threads, [&](int lo, int hi) { tuples_range(kp1, kp2, n1, n2, nn12, nn21, M, src, out, lo, hi); });
     } else {
         const PhiloxTriples src{seed, pair_ids};
-        over_pairs(P, num_threads, [&](int lo, int hi) { tuples_range(kp1, kp2, n1, n2, nn12, nn21, M, src, out, lo, hi); });
+        usip_host::split(P, num_threads, [&](int lo, int hi) { tuples_range(kp1, kp2, n1, n2, nn12, nn21, M, src, out, lo, hi); });
     }
     return USIP_OK;
 }
@@ -224,7 +208,7 @@ extern "C" int usip_fgr_optimize_f32_cpu(const float* kp1, const float* kp2, con
     if (P == 0) return USIP_OK;
     if (!kp1 || !kp2 || !mutual || !mutual_count || !norm || !rows || !row_count || !Rt || !valid || !inlier_mask || !inliers)
         return USIP_EINVAL;
-    over_pairs(P, num_threads, [&](int lo, int hi) {
+    usip_host::split(P, num_threads, [&](int lo, int hi) {
         optimize_range(kp1, kp2, mutual, mutual_count, norm, rows, row_count, M, threshold, Rt, valid, inlier_mask, inliers,
                        lo, hi);
     });

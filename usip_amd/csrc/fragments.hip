@@ -18,13 +18,18 @@
 //                                the radius (fragments_math.h beyond()); a lane stops testing at its first hit, the
 //                                workgroup ends when no lane is left.
 #include "common.h"
+#include "bank.h"
 #include "fragments_math.h"
+#include "tile_walk.h"
 
 using namespace usip_reg;
 using namespace usip_frag;
+using namespace usip_bank;
+using namespace usip_walk;
 
 namespace {
 
+static_assert(OTILE == WALK_TILE, "overlap_kernel walks tile_walk.h's tiles");
 constexpr int UT = 1024;    // lanes of the union's workgroup
 
 // ------------------------------------------------------------------------------------------------ top-k matching
@@ -214,26 +219,6 @@ __global__ __launch_bounds__(REFIT_LANES) void information_kernel(const float* _
 }
 
 // ------------------------------------------------------------------------------------------------ overlap
-struct Bank {
-    const float* rows;
-    const int64_t* offsets;
-    int row_len, num_frags;
-    long long total;
-};
-
-// fragment f of the bank -> (first row, rows), never outside the buffer and never more than lmax rows
-__device__ __forceinline__ void fragment_range(const Bank& bank, int f, int lmax, long long* first, int* n)
-{
-    f = clamp_index(f, bank.num_frags);
-    long long lo = bank.offsets[f], hi = bank.offsets[f + 1];
-    lo = lo < 0 ? 0 : (lo > bank.total ? bank.total : lo);
-    hi = hi < lo ? lo : (hi > bank.total ? bank.total : hi);
-    *first = lo;
-    *n = (int)(hi - lo > (long long)lmax ? (long long)lmax : hi - lo);
-}
-
-__device__ __forceinline__ int safe_index(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }
-
 // the point at sorted position s of a fragment, moved by Rt when `moved`
 __device__ __forceinline__ void sorted_point(const float* base, int row_len, const int32_t* perm, int s, int n, bool moved,
                                              const double* Rt, double* x, double* y, double* z)
@@ -244,12 +229,6 @@ __device__ __forceinline__ void sorted_point(const float* base, int row_len, con
     *y = moved ? xform(Rt, 1, b0, b1, b2) : b1;
     *z = moved ? xform(Rt, 2, b0, b1, b2) : b2;
 }
-__device__ __forceinline__ double sorted_x(const float* base, int row_len, const int32_t* perm, int s, int n, bool moved,
-                                           const double* Rt)
-{
-    const float* r = base + (long long)safe_index(perm[s], n) * row_len;
-    return moved ? xform(Rt, 0, (double)r[0], (double)r[1], (double)r[2]) : (double)r[0];
-}
 
 __global__ __launch_bounds__(256) void overlap_keys_kernel(Bank bank, const int32_t* __restrict__ frag2,
                                                            const double* __restrict__ Rt, int Lmax,
@@ -257,37 +236,13 @@ __global__ __launch_bounds__(256) void overlap_keys_kernel(Bank bank, const int3
 {
     const int p = blockIdx.y, s = blockIdx.x * 256 + threadIdx.x;
     if (s >= Lmax) return;
-    long long first;
-    int n;
-    fragment_range(bank, frag2[p], Lmax, &first, &n);
+    const Range f = bank.range(frag2[p], Lmax);
     double v = (double)__builtin_inff();                               // padding sorts last
-    if (s < n) {
-        const float* r = bank.rows + (first + s) * bank.row_len;
+    if (s < f.n) {
+        const float* r = bank.rows + (f.first + s) * bank.row_len;
         v = xform(Rt + (long long)p * 12, 0, (double)r[0], (double)r[1], (double)r[2]);
     }
     keys[(long long)p * Lmax + s] = v;
-}
-
-// the smallest and the largest v of the workgroup (4 waves), in every lane
-__device__ __forceinline__ void block_minmax(double lo, double hi, double (*slots)[2], double* out_lo, double* out_hi)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double a = __shfl_xor(lo, off), b = __shfl_xor(hi, off);
-        lo = a < lo ? a : lo;
-        hi = b > hi ? b : hi;
-    }
-    if ((threadIdx.x & 63) == 0) { slots[threadIdx.x >> 6][0] = lo; slots[threadIdx.x >> 6][1] = hi; }
-    __syncthreads();
-    lo = slots[0][0];
-    hi = slots[0][1];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-        lo = slots[w][0] < lo ? slots[w][0] : lo;
-        hi = slots[w][1] > hi ? slots[w][1] : hi;
-    }
-    *out_lo = lo;
-    *out_hi = hi;
 }
 
 // XQ false: the queries are fragment 1's points, the database fragment 2's moved by Rt (ratio[p][0]); XQ true: the
@@ -301,23 +256,20 @@ __global__ __launch_bounds__(OTILE) void overlap_kernel(Bank bank, const int32_t
 {
     __shared__ double tile[2][3][OTILE];
     __shared__ double sRt[12];
-    __shared__ double slots[4][2];
+    __shared__ double slots[2 * WALK_WAVES];
     const int p = blockIdx.y, l = threadIdx.x;
-    long long o1, o2;
-    int n1, n2;
-    fragment_range(bank, frag1[p], Lmax, &o1, &n1);
-    fragment_range(bank, frag2[p], Lmax, &o2, &n2);
-    const int nq = XQ ? n2 : n1, nd = XQ ? n1 : n2;
+    const Range r1 = bank.range(frag1[p], Lmax), r2 = bank.range(frag2[p], Lmax);
+    const int nq = XQ ? r2.n : r1.n, nd = XQ ? r1.n : r2.n;
     if (blockIdx.x * OTILE >= nq || nd < 1) return;                    // workgroup-uniform
     if (l < 12) sRt[l] = Rt_all[(long long)p * 12 + l];
     __syncthreads();
     double Rt[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Rt[k] = sRt[k];
-    const int32_t* pa = perm1 + o1;
+    const int32_t* pa = perm1 + r1.first;
     const int32_t* pb = perm2 + (long long)p * Lmax;
-    const float* ra = bank.rows + o1 * bank.row_len;
-    const float* rb = bank.rows + o2 * bank.row_len;
+    const float* ra = bank.rows + r1.first * bank.row_len;
+    const float* rb = bank.rows + r2.first * bank.row_len;
     const float* qrows = XQ ? rb : ra;
     const float* drows = XQ ? ra : rb;
     const int32_t* qperm = XQ ? pb : pa;
@@ -328,55 +280,37 @@ __global__ __launch_bounds__(OTILE) void overlap_kernel(Bank bank, const int32_t
     const bool live = q < nq;
     double xi, yi, zi;
     sorted_point(qrows, row_len, qperm, live ? q : nq - 1, nq, XQ, Rt, &xi, &yi, &zi);
-    double xlo, xhi;
-    block_minmax(xi, xi, slots, &xlo, &xhi);                           // the x range of this workgroup's queries
+    double xlo = xi, xhi = xi;
+    block_minmax<true, true>(xlo, xhi, slots);                         // the x range of this workgroup's queries
 
-    // the first sorted database position whose x is not below xlo (workgroup-uniform)
-    int lo = 0, hi = nd;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sorted_x(drows, row_len, dperm, mid, nd, !XQ, Rt) < xlo) lo = mid + 1; else hi = mid;
-    }
-    const int tiles = (nd + OTILE - 1) / OTILE;
-    int right = min(lo / OTILE, tiles - 1), left = right - 1;
+    const auto x_at = [&](int s) {                                     // x of the database row at sorted position s
+        const float* r = drows + (long long)safe_index(dperm[s], nd) * row_len;
+        return !XQ ? xform(Rt, 0, (double)r[0], (double)r[1], (double)r[2]) : (double)r[0];
+    };
+    const Tiles<decltype(x_at)> tiles(nd, x_at);
+    const int start = tiles.start(xlo);
     bool hit = false;
-    while (true) {
-        if (!__syncthreads_or(live && !hit)) break;                    // (also: every lane is done with the tiles)
-        if (left >= 0 && beyond(xlo - sorted_x(drows, row_len, dperm, min(left * OTILE + OTILE - 1, nd - 1), nd, !XQ, Rt),
-                                radius))
-            left = -1;
-        if (right < tiles && beyond(sorted_x(drows, row_len, dperm, right * OTILE, nd, !XQ, Rt) - xhi, radius))
-            right = tiles;
-        if (left < 0 && right >= tiles) break;                         // workgroup-uniform
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int t = side == 0 ? left : right;
-            if (side == 0 ? left >= 0 : right < tiles) {
-                const int s = t * OTILE + l;
-                double x, y, z;
-                sorted_point(drows, row_len, dperm, s < nd ? s : nd - 1, nd, !XQ, Rt, &x, &y, &z);
-                tile[side][0][l] = x;
-                tile[side][1][l] = y;
-                tile[side][2][l] = z;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int t = side == 0 ? left : right;
-            if (side == 0 ? left >= 0 : right < tiles) {
-                const int m = min(OTILE, nd - t * OTILE);
-                if (live && !hit)
-                    for (int c = 0; c < m; ++c)
-                        if (within(sqdist3(xi, yi, zi, tile[side][0][c], tile[side][1][c], tile[side][2][c]), radius, r2hi)) {
-                            hit = true;
-                            break;
-                        }
-            }
-        }
-        if (left >= 0) --left;
-        if (right < tiles) ++right;
-    }
+    walk_outward(
+        tiles, start - 1, start,
+        [&](int left, int right) {
+            if (!__syncthreads_or(live && !hit)) return END_LEFT | END_RIGHT;  // (also: every lane is done with the tiles)
+            return (left >= 0 && beyond(xlo - tiles.near_x(0, left), radius) ? END_LEFT : 0) |
+                   (right < tiles.tiles && beyond(tiles.near_x(1, right) - xhi, radius) ? END_RIGHT : 0);
+        },
+        [&](int side, int t) {
+            const int s = t * OTILE + l;
+            double x, y, z;
+            sorted_point(drows, row_len, dperm, s < nd ? s : nd - 1, nd, !XQ, Rt, &x, &y, &z);
+            tile[side][0][l] = x;
+            tile[side][1][l] = y;
+            tile[side][2][l] = z;
+        },
+        [&](int side, int, int m) {
+            bool found = hit || !live;                                 // (a local: the flag stays a lane mask in the loop)
+            for (int c = 0; c < m && !found; ++c)
+                found = within(sqdist3(xi, yi, zi, tile[side][0][c], tile[side][1][c], tile[side][2][c]), radius, r2hi);
+            hit = found && live;
+        });
     const int found = __syncthreads_count(live && hit);
     if (l == 0 && found) atomicAdd(&hits[2 * p + (XQ ? 1 : 0)], found);
 }
@@ -387,18 +321,9 @@ __global__ __launch_bounds__(64) void overlap_ratio_kernel(Bank bank, const int3
 {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= P) return;
-    long long o;
-    int n1, n2;
-    fragment_range(bank, frag1[p], Lmax, &o, &n1);
-    fragment_range(bank, frag2[p], Lmax, &o, &n2);
+    const int n1 = bank.range(frag1[p], Lmax).n, n2 = bank.range(frag2[p], Lmax).n;
     ratio[2 * p] = n1 > 0 ? (double)hits[2 * p] / (double)n1 : 0.0;
     ratio[2 * p + 1] = n2 > 0 ? (double)hits[2 * p + 1] / (double)n2 : 0.0;
-}
-
-bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, int P, int Lmax)
-{
-    return rows && offsets && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
-           Lmax <= (1 << 24);
 }
 
 }  // namespace

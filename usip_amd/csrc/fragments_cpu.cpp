@@ -5,31 +5,18 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <thread>
 #include <vector>
+#include "bank.h"
 #include "fragments_math.h"
+#include "host_split.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_reg;
 using namespace usip_frag;
+using namespace usip_bank;
+using namespace usip_host;
 
 namespace {
-
-template <class F>
-void split(long long total, int num_threads, const F& body)
-{
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || total < 2 * nt) {
-        body(0, total);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-        const long long lo = total * w / nt, hi = total * (w + 1) / nt;
-        pool.emplace_back([=, &body] { body(lo, hi); });
-    }
-    for (auto& th : pool) th.join();
-}
 
 template <int K>
 void knn_host(const float* a, const float* b, const int32_t* a_count, const int32_t* b_count, float* dist, int32_t* idx,
@@ -65,39 +52,16 @@ void knn_host(const float* a, const float* b, const int32_t* a_count, const int3
     });
 }
 
-struct Range {
-    long long first;
-    int n;
-};
-
-Range fragment_range(const int64_t* offsets, int num_frags, long long total, int f, int lmax)
-{
-    f = clamp_index(f, num_frags);
-    long long lo = offsets[f], hi = offsets[f + 1];
-    lo = lo < 0 ? 0 : (lo > total ? total : lo);
-    hi = hi < lo ? lo : (hi > total ? total : hi);
-    return {lo, (int)(hi - lo > (long long)lmax ? (long long)lmax : hi - lo)};
-}
-
-int safe_index(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }
-
-bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, int P, int Lmax)
-{
-    return rows && offsets && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
-           Lmax <= (1 << 24);
-}
-
 // queries q[3][nq] against the database d[3][nd] sorted along x: the number of queries with a point within the radius
 int count_hits(const std::vector<double>& q, int nq, const std::vector<double>& d, int nd, double radius, bool prune,
                int num_threads)
 {
     const double r2hi = radius_sq_hi(radius);
-    std::vector<int> found((size_t)64, 0);
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
+    std::vector<int> found((size_t)clamp_threads(num_threads), 0);     // a slot per range
     const double* dx = d.data();
     const double* dy = dx + nd;
     const double* dz = dy + nd;
-    auto body = [&](int w, long long lo, long long hi) {
+    split_numbered(nq, num_threads, [&](long long lo, long long hi, int w) {
         int mine = 0;
         for (long long i = lo; i < hi; ++i) {
             const double xi = q[i], yi = q[(size_t)nq + i], zi = q[(size_t)2 * nq + i];
@@ -118,16 +82,9 @@ int count_hits(const std::vector<double>& q, int nq, const std::vector<double>& 
             mine += hit ? 1 : 0;
         }
         found[w] = mine;
-    };
-    if (nt == 1 || nq < 2 * nt) {
-        body(0, 0, nq);
-    } else {
-        std::vector<std::thread> pool;
-        for (int w = 0; w < nt; ++w) pool.emplace_back(body, w, (long long)nq * w / nt, (long long)nq * (w + 1) / nt);
-        for (auto& th : pool) th.join();
-    }
+    });
     int total = 0;
-    for (int w = 0; w < 64; ++w) total += found[w];
+    for (int mine : found) total += mine;
     return total;
 }
 

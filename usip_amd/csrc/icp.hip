@@ -19,22 +19,25 @@
 //   icp_final_kernel     one workgroup per pair: the hits within the radius, the root mean kept d2.
 #include <vector>
 #include "common.h"
+#include "bank.h"
 #include "icp_math.h"
+#include "tile_walk.h"
 
 using namespace usip_reg;
 using namespace usip_frag;
 using namespace usip_icp;
+using namespace usip_bank;
+using usip_walk::block_minmax;
+using usip_walk::walk_outward;
 
 namespace {
 
-constexpr int WAVES = LANES / USIP_WAVE;
+static_assert(LANES == usip_walk::WALK_TILE && TILE == usip_walk::WALK_TILE, "icp_nearest_kernel walks tile_walk.h's tiles");
+constexpr int WAVES = usip_walk::WALK_WAVES;
 
-struct Bank {
-    const float* rows;
-    const int64_t* offsets;
+// the bank and, per fragment at its offset, the local row indices ascending along x
+struct SortedBank : Bank {
     const int32_t* perm1;
-    int row_len, num_frags;
-    long long total;
 };
 
 struct Pairs {
@@ -45,23 +48,7 @@ struct Pairs {
 
 __device__ __forceinline__ Range range_of(const Bank& bank, const int32_t* frag, int p, int lmax)
 {
-    return fragment_range(bank.offsets, bank.num_frags, bank.total, frag[p], lmax);
-}
-
-// the smallest v of the workgroup, in every lane
-__device__ __forceinline__ double block_min(double lo, double* slots)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double a = __shfl_xor(lo, off);
-        lo = a < lo ? a : lo;
-    }
-    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = lo;
-    __syncthreads();
-    lo = slots[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) lo = slots[w] < lo ? slots[w] : lo;
-    return lo;
+    return bank.range(frag[p], lmax);
 }
 
 // Exclusive scan of one flag per lane over the workgroup; the caller puts a barrier between two calls.
@@ -105,15 +92,9 @@ __global__ __launch_bounds__(64) void icp_init_kernel(Bank bank, Pairs pr, const
     ratio[2 * p + 1] = 0.0;
 }
 
-// x of fragment 1's row at sorted position s
-__device__ __forceinline__ double sorted_x(const float* rows1, int row_len, const int32_t* perm, int s, int n1)
-{
-    return (double)rows1[(long long)safe_index(perm[s], n1) * row_len];
-}
-
 // state NULL: every pair with mask[p] != 0 (mask NULL: every pair); otherwise the running pairs, or, in the final pass,
 // the refined ones.
-__global__ __launch_bounds__(LANES) void icp_nearest_kernel(Bank bank, Pairs pr, const double* __restrict__ Rt_all,
+__global__ __launch_bounds__(LANES) void icp_nearest_kernel(SortedBank bank, Pairs pr, const double* __restrict__ Rt_all,
                                                             const uint8_t* __restrict__ mask,
                                                             const int32_t* __restrict__ order2,
                                                             const int32_t* __restrict__ state, int final_pass,
@@ -150,59 +131,41 @@ __global__ __launch_bounds__(LANES) void icp_nearest_kernel(Bank bank, Pairs pr,
     const double b0 = (double)b[0], b1 = (double)b[1], b2 = (double)b[2];
     const double qx = xform(Rt, 0, b0, b1, b2), qy = xform(Rt, 1, b0, b1, b2), qz = xform(Rt, 2, b0, b1, b2);
     const double inf = (double)__builtin_inff();
-    const double xlo = block_min(live ? qx : inf, slots);
+    double xlo = live ? qx : inf, unused = 0.0;
+    block_minmax<true, false>(xlo, unused, slots);
 
-    // the first sorted position of fragment 1 whose x is not below xlo
-    int lo = 0, hi = n1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sorted_x(rows1, row_len, perm, mid, n1) < xlo) lo = mid + 1; else hi = mid;
-    }
-    const int tiles = (n1 + TILE - 1) / TILE;
-    int right = min(lo / TILE, tiles - 1), left = right - 1;
+    const auto x_at = [&](int at) { return (double)rows1[(long long)safe_index(perm[at], n1) * row_len]; };
+    const usip_walk::Tiles<decltype(x_at)> tiles(n1, x_at);
+    const int start = tiles.start(xlo);
     double best = inf;
     int brow = 0x7fffffff;
     unsigned long long evaluated = 0;
-    while (true) {
-        bool need[2] = {false, false};
-        if (left >= 0)
-            need[0] = live && !bound_met(qx - sorted_x(rows1, row_len, perm, min(left * TILE + TILE - 1, n1 - 1), n1), best);
-        if (right < tiles) need[1] = live && !bound_met(sorted_x(rows1, row_len, perm, right * TILE, n1) - qx, best);
-        if (!__syncthreads_or(need[0])) left = -1;                     // (also: every lane is done with the tiles)
-        if (!__syncthreads_or(need[1])) right = tiles;
-        if (left < 0 && right >= tiles) break;
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int t = side == 0 ? left : right;
-            if (side == 0 ? left >= 0 : right < tiles) {
-                const int at = min(t * TILE + l, n1 - 1);
-                const int row = safe_index(perm[at], n1);
-                const float* a = rows1 + (long long)row * row_len;
-                tile[side][0][l] = (double)a[0];
-                tile[side][1][l] = (double)a[1];
-                tile[side][2][l] = (double)a[2];
-                trow[side][l] = row;
+    bool need[2];
+    walk_outward(
+        tiles, start - 1, start,
+        [&](int left, int right) {
+            need[0] = left >= 0 && live && !bound_met(qx - tiles.near_x(0, left), best);
+            need[1] = right < tiles.tiles && live && !bound_met(tiles.near_x(1, right) - qx, best);
+            const int end_left = __syncthreads_or(need[0]) ? 0 : usip_walk::END_LEFT;  // (also: every lane is done with the tiles)
+            return end_left | (__syncthreads_or(need[1]) ? 0 : usip_walk::END_RIGHT);
+        },
+        [&](int side, int t) {
+            const int row = safe_index(perm[min(t * TILE + l, n1 - 1)], n1);
+            const float* a = rows1 + (long long)row * row_len;
+            tile[side][0][l] = (double)a[0];
+            tile[side][1][l] = (double)a[1];
+            tile[side][2][l] = (double)a[2];
+            trow[side][l] = row;
+        },
+        [&](int side, int, int m) {
+            if (!need[side]) return;
+            evaluated += (unsigned long long)m;
+            for (int c = 0; c < m; ++c) {
+                const double d2 = sqdist3(qx, qy, qz, tile[side][0][c], tile[side][1][c], tile[side][2][c]);
+                const int row = trow[side][c];
+                if (better(d2, row, best, brow)) { best = d2; brow = row; }
             }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int side = 0; side < 2; ++side) {
-            const int t = side == 0 ? left : right;
-            if (side == 0 ? left >= 0 : right < tiles) {
-                const int m = min(TILE, n1 - t * TILE);
-                if (need[side]) {
-                    evaluated += (unsigned long long)m;
-                    for (int c = 0; c < m; ++c) {
-                        const double d2 = sqdist3(qx, qy, qz, tile[side][0][c], tile[side][1][c], tile[side][2][c]);
-                        const int row = trow[side][c];
-                        if (better(d2, row, best, brow)) { best = d2; brow = row; }
-                    }
-                }
-            }
-        }
-        if (left >= 0) --left;
-        if (right < tiles) ++right;
-    }
+        });
     if (live) {
         idx[(long long)p * pr.Lmax + i] = brow;
         d2out[(long long)p * pr.Lmax + i] = best;
@@ -381,13 +344,6 @@ __global__ __launch_bounds__(LANES) void icp_final_kernel(Bank bank, Pairs pr, c
     rmse[p] = sqrt(total / (double)trim_count(inlier_ratio, n2));
 }
 
-bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, const int32_t* perm1,
-             int P, int Lmax)
-{
-    return rows && offsets && perm1 && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
-           Lmax <= (1 << 24);
-}
-
 long long align256(long long v) { return (v + 255) / 256 * 256; }
 
 struct Workspace {
@@ -418,7 +374,7 @@ extern "C" int usip_icp_nearest_f32(const float* rows, int row_len, const int64_
                                     const double* Rt, const uint8_t* mask, const int32_t* order2, int P, int Lmax,
                                     int32_t* idx, double* d2, unsigned long long* visits, void* stream)
 {
-    if (!bank_ok(rows, row_len, offsets, num_frags, total_rows, perm1, P, Lmax)) return USIP_EINVAL;
+    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1)) return USIP_EINVAL;
     if (P == 0) return USIP_OK;
     if (!frag1 || !frag2 || !Rt || !idx || !d2) return USIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -426,7 +382,7 @@ extern "C" int usip_icp_nearest_f32(const float* rows, int row_len, const int64_
     if (e == hipSuccess) e = hipMemsetAsync(d2, 0, (size_t)P * Lmax * sizeof(double), st);
     if (e == hipSuccess && visits) e = hipMemsetAsync(visits, 0, (size_t)P * sizeof(unsigned long long), st);
     if (e != hipSuccess) return (int)e;
-    const Bank bank{rows, offsets, perm1, row_len, num_frags, total_rows};
+    const SortedBank bank{{rows, offsets, row_len, num_frags, total_rows}, perm1};
     const Pairs pr{frag1, frag2, Lmax};
     USIP_LAUNCH(icp_nearest_kernel, dim3(usip_ceil_div(Lmax, TILE), P), dim3(LANES), 0, st, bank, pr, Rt, mask, order2,
                 (const int32_t*)nullptr, 0, idx, d2, visits);
@@ -443,7 +399,7 @@ extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t
                                    double* cut_d2, int32_t* cut_i_out, unsigned long long* visits, double* stage_ms,
                                    void* stream)
 {
-    if (!bank_ok(rows, row_len, offsets, num_frags, total_rows, perm1, P, Lmax)) return USIP_EINVAL;
+    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1)) return USIP_EINVAL;
     if (!(inlier_ratio > 0.0 && inlier_ratio <= 1.0) || max_iterations < 0 || max_iterations > MAX_ITERATIONS ||
         !(tol_t >= 0.0) || !(tol_c >= 0.0) || !(align_radius > 0.0))
         return USIP_EINVAL;
@@ -468,7 +424,7 @@ extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t
     if (e == hipSuccess && cut_d2) e = hipMemsetAsync(cut_d2, 0, (size_t)P * slots * sizeof(double), st);
     if (e == hipSuccess && cut_d2) e = hipMemsetAsync(cut_i_out, 0, (size_t)P * slots * sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
-    const Bank bank{rows, offsets, perm1, row_len, num_frags, total_rows};
+    const SortedBank bank{{rows, offsets, row_len, num_frags, total_rows}, perm1};
     const Pairs pr{frag1, frag2, Lmax};
     const dim3 grid(usip_ceil_div(Lmax, TILE), P);
     USIP_LAUNCH(icp_init_kernel, dim3(usip_ceil_div(P, 64)), dim3(64), 0, st, bank, pr, Rt0, mask, P, Rt, state, hist,

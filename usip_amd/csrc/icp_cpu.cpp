@@ -6,46 +6,18 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <thread>
 #include <vector>
+#include "bank.h"
+#include "host_split.h"
 #include "icp_math.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_reg;
 using namespace usip_frag;
 using namespace usip_icp;
+using namespace usip_bank;
 
 namespace {
-
-bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, const int32_t* perm1,
-             int P, int Lmax)
-{
-    return rows && offsets && perm1 && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
-           Lmax <= (1 << 24);
-}
-
-template <class F>
-void over_pairs(int P, int num_threads, const F& f)
-{
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || P < 2) {
-        f(0, P);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-        const int lo = (int)((long long)P * w / nt), hi = (int)((long long)P * (w + 1) / nt);
-        if (lo < hi) pool.emplace_back([=, &f] { f(lo, hi); });
-    }
-    for (auto& th : pool) th.join();
-}
-
-struct Bank {
-    const float* rows;
-    const int64_t* offsets;
-    int row_len, num_frags;
-    long long total;
-};
 
 struct Pair {
     const float* rows1;
@@ -55,8 +27,8 @@ struct Pair {
 
 Pair pair_of(const Bank& bank, const int32_t* frag1, const int32_t* frag2, int p, int Lmax)
 {
-    const Range r1 = fragment_range(bank.offsets, bank.num_frags, bank.total, frag1[p], Lmax);
-    const Range r2 = fragment_range(bank.offsets, bank.num_frags, bank.total, frag2[p], Lmax);
+    const Range r1 = bank.range(frag1[p], Lmax);
+    const Range r2 = bank.range(frag2[p], Lmax);
     return {bank.rows + r1.first * bank.row_len, bank.rows + r2.first * bank.row_len, r1.n, r2.n};
 }
 
@@ -143,13 +115,13 @@ extern "C" int usip_icp_nearest_f32_cpu(const float* rows, int row_len, const in
                                         const int32_t* frag2, const double* Rt, const uint8_t* mask, const int32_t* order2,
                                         int P, int Lmax, int32_t* idx, double* d2, int num_threads)
 {
-    if (!bank_ok(rows, row_len, offsets, num_frags, total_rows, perm1, P, Lmax)) return USIP_EINVAL;
+    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1)) return USIP_EINVAL;
     if (P == 0) return USIP_OK;
     if (!frag1 || !frag2 || !Rt || !idx || !d2) return USIP_EINVAL;
     const Bank bank{rows, offsets, row_len, num_frags, total_rows};
     std::memset(idx, 0, sizeof(int32_t) * (size_t)P * (size_t)Lmax);
     std::memset(d2, 0, sizeof(double) * (size_t)P * (size_t)Lmax);
-    over_pairs(P, num_threads, [&](int lo, int hi) {
+    usip_host::split(P, num_threads, [&](int lo, int hi) {
         for (int p = lo; p < hi; ++p) {
             if (mask && mask[p] == 0) continue;
             const Pair pr = pair_of(bank, frag1, frag2, p, Lmax);
@@ -169,7 +141,7 @@ extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int
                                        double* rmse, int32_t* hits, double* ratio, double* cut_d2, int32_t* cut_i_out,
                                        int32_t* idx_out, double* d2_out, int num_threads)
 {
-    if (!bank_ok(rows, row_len, offsets, num_frags, total_rows, perm1, P, Lmax)) return USIP_EINVAL;
+    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1)) return USIP_EINVAL;
     if (!(inlier_ratio > 0.0 && inlier_ratio <= 1.0) || max_iterations < 0 || max_iterations > MAX_ITERATIONS ||
         !(tol_t >= 0.0) || !(tol_c >= 0.0) || !(align_radius > 0.0))
         return USIP_EINVAL;
@@ -186,7 +158,7 @@ extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int
     const double r2hi = radius_sq_hi(align_radius);
     if (idx_out) std::memset(idx_out, 0, sizeof(int32_t) * (size_t)P * (size_t)Lmax);
     if (d2_out) std::memset(d2_out, 0, sizeof(double) * (size_t)P * (size_t)Lmax);
-    over_pairs(P, num_threads, [&](int lo, int hi) {
+    usip_host::split(P, num_threads, [&](int lo, int hi) {
         Scratch sc;
         std::vector<int32_t> idx;
         std::vector<double> d2;

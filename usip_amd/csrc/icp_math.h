@@ -21,23 +21,6 @@ constexpr int MAX_ITERATIONS = 64;
 constexpr int RUNNING = 0, STOPPED = 1, NOT_REFINED = 2;               // a pair's state between the launches
 static_assert(LANES == usip_reg::REFIT_LANES, "the fit's sums go through registration_math.h's tree");
 
-struct Range {
-    long long first;
-    int n;
-};
-
-// fragment f of the bank -> (first row, rows), never outside the buffer and never more than lmax rows
-USIP_HD Range fragment_range(const int64_t* offsets, int num_frags, long long total, int f, int lmax)
-{
-    f = usip_reg::clamp_index(f, num_frags);
-    long long lo = offsets[f], hi = offsets[f + 1];
-    lo = lo < 0 ? 0 : (lo > total ? total : lo);
-    hi = hi < lo ? lo : (hi > total ? total : hi);
-    return {lo, (int)(hi - lo > (long long)lmax ? (long long)lmax : hi - lo)};
-}
-
-USIP_HD int safe_index(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }
-
 // A non-negative float64 orders as its bit pattern does.
 USIP_HD unsigned long long bits_of(double v)
 {

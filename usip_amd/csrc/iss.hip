@@ -21,13 +21,13 @@
 // Slots beyond count[b] get saliency 0, neighbours 0, keypoint 0.  An entry of perm outside [0, count) reads point 0: a
 // wrong permutation gives wrong values, never a wild read.
 #include "common.h"
+#include "bank.h"
 #include "iss_math.h"
 
 using namespace usip_iss;
+using usip_bank::safe_index;
 
 namespace {
-
-__device__ __forceinline__ int safe_index(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }
 
 // One frame as a workgroup sees it
 struct Frame {

@@ -5,12 +5,13 @@
 // original one.  Threads split the queries, nothing else.  Never reached from the device entry points.
 #include <algorithm>
 #include <cmath>
-#include <thread>
 #include <vector>
+#include "host_split.h"
 #include "iss_math.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_iss;
+using usip_host::split;
 
 namespace {
 
@@ -18,20 +19,6 @@ int live_points(const int32_t* count, int f, int N)
 {
     const int c = count ? count[f] : N;
     return c < 0 ? 0 : (c > N ? N : c);
-}
-
-// fn(lo, hi) over [0, total) on nt threads
-template <class Fn>
-void split(long long total, int num_threads, Fn fn)
-{
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || total < 2 * nt) {
-        fn(0LL, total);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) pool.emplace_back(fn, total * w / nt, total * (w + 1) / nt);
-    for (auto& th : pool) th.join();
 }
 
 bool bad_shape(int B, int N, double r, int min_neighbors)

@@ -14,6 +14,7 @@
 //                            running values in registers), the two substitutions with the solution in LDS, the update.
 //                            __syncthreads() orders the workgroup's global writes between the phases.
 #include "common.h"
+#include "bank.h"
 #include "posegraph_math.h"
 
 using namespace usip_pg;
@@ -21,8 +22,9 @@ using usip_frag::info_fill;
 using usip_frag::info_terms;
 using usip_frag::radius_sq_hi;
 using usip_frag::within;
-using usip_icp::fragment_range;
-using usip_icp::Range;
+using usip_bank::bank_ok;
+using usip_bank::fragment_range;
+using usip_bank::Range;
 using usip_reg::tree_sum;
 
 namespace {
@@ -388,12 +390,6 @@ __global__ __launch_bounds__(LANES) void posegraph_kernel(Graph g, Result o, dou
         __syncthreads();
     }
     if (first_lane()) *sc.status = status;
-}
-
-bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, int P, int Lmax)
-{
-    return rows && offsets && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
-           Lmax <= (1 << 24);
 }
 
 }  // namespace

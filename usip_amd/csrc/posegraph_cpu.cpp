@@ -4,8 +4,9 @@
 // pairs or the scenes.  Never reached from the device entry points.
 #include <cmath>
 #include <cstring>
-#include <thread>
 #include <vector>
+#include "bank.h"
+#include "host_split.h"
 #include "posegraph_math.h"
 #include "../../include/usip_hip.h"
 
@@ -14,27 +15,13 @@ using usip_frag::info_fill;
 using usip_frag::info_terms;
 using usip_frag::radius_sq_hi;
 using usip_frag::within;
-using usip_icp::fragment_range;
-using usip_icp::Range;
+using usip_bank::bank_ok;
+using usip_bank::fragment_range;
+using usip_bank::Range;
+using usip_host::split;
 using usip_reg::tree_sum;
 
 namespace {
-
-template <class F>
-void over(int P, int num_threads, const F& f)
-{
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || P < 2) {
-        f(0, P);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-        const int lo = (int)((long long)P * w / nt), hi = (int)((long long)P * (w + 1) / nt);
-        if (lo < hi) pool.emplace_back([=, &f] { f(lo, hi); });
-    }
-    for (auto& th : pool) th.join();
-}
 
 struct Scene {
     const int32_t* ei;
@@ -133,12 +120,6 @@ int solve(Scene& sc)
     return inf ? ST_NOT_FINITE : (far ? ST_ANGLE : ST_OK);
 }
 
-bool bank_ok(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total, int P, int Lmax)
-{
-    return rows && offsets && row_len >= 3 && num_frags >= 1 && total >= 0 && P >= 0 && P <= 65535 && Lmax >= 1 &&
-           Lmax <= (1 << 24);
-}
-
 }  // namespace
 
 extern "C" int usip_icp_information_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
@@ -150,7 +131,7 @@ extern "C" int usip_icp_information_f32_cpu(const float* rows, int row_len, cons
     if (P == 0) return USIP_OK;
     if (!frag1 || !frag2 || !idx || !d2 || !info || !count) return USIP_EINVAL;
     const double r2hi = radius_sq_hi(radius);
-    over(P, num_threads, [&](int lo, int hi) {
+    split(P, num_threads, [&](int lo, int hi) {
         std::vector<double> buf((size_t)LANES * 10);
         double (*part)[10] = reinterpret_cast<double (*)[10]>(buf.data());
         for (int p = lo; p < hi; ++p) {
@@ -212,7 +193,7 @@ extern "C" int usip_posegraph_optimize_f64_cpu(const int32_t* n, const int32_t* 
     std::memset(iterations_done, 0, sizeof(int32_t) * (size_t)S * 2);
     std::memset(last_step, 0, sizeof(double) * (size_t)S * 2);
     std::memset(status, 0, sizeof(int32_t) * (size_t)S);
-    over(S, num_threads, [&](int lo, int hi) {
+    split(S, num_threads, [&](int lo, int hi) {
         Scene sc;
         for (int s = lo; s < hi; ++s) {
             sc.ei = edge_i + (long long)s * Emax;

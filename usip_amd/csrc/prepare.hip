@@ -18,29 +18,18 @@
 //   scan_voxel_average_kernel  one lane per occupied cell: its members in ascending original index, float64 sums in that
 //                              order (no atomics: bit-reproducible and the host twin's order).
 #include "common.h"
+#include "bank.h"
 #include "prepare_math.h"
+#include "tile_walk.h"
 
 using namespace usip_prep;
+using usip_bank::safe_index;
+using usip_walk::block_minmax;
+using usip_walk::Tiles;
+
+static_assert(usip_prep::TILE == usip_walk::WALK_TILE, "scan_knn_kernel walks tile_walk.h's tiles");
 
 namespace {
-
-__device__ __forceinline__ int safe_index(int j, int n) { return (unsigned)j < (unsigned)n ? j : 0; }
-
-// the largest v of the workgroup (4 waves), in every lane
-__device__ __forceinline__ double block_max(double v, double* slots)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off);
-        v = o > v ? o : v;
-    }
-    __syncthreads();                                                   // the previous round's reads are done
-    if ((threadIdx.x & 63) == 0) slots[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double a = slots[0] > slots[1] ? slots[0] : slots[1];
-    const double b = slots[2] > slots[3] ? slots[2] : slots[3];
-    return a > b ? a : b;
-}
 
 template <int K>
 __global__ __launch_bounds__(TILE) void scan_knn_kernel(const float4* __restrict__ pts, const int32_t* __restrict__ perm,
@@ -50,15 +39,14 @@ __global__ __launch_bounds__(TILE) void scan_knn_kernel(const float4* __restrict
     __shared__ int32_t orig[2][TILE];
     __shared__ double slots[4];
     const int l = threadIdx.x, b = blockIdx.x;
-    const int tiles = (n + TILE - 1) / TILE;
     const int q = b * TILE + l;                                        // position in the sorted order
     const bool live = q < n;
     const int me = safe_index(perm[live ? q : n - 1], n);
     const float4 p = pts[me];
     const double xi = (double)p.x, yi = (double)p.y, zi = (double)p.z;
-    // the x range of this workgroup's queries
-    const double xlo = (double)pts[safe_index(perm[b * TILE], n)].x;
-    const double xhi = (double)pts[safe_index(perm[min(b * TILE + TILE - 1, n - 1)], n)].x;
+    const auto x_at = [&](int s) { return (double)pts[safe_index(perm[s], n)].x; };
+    const Tiles<decltype(x_at)> tiles(n, x_at);
+    const double xlo = tiles.near_x(1, b), xhi = tiles.near_x(0, b);   // the x range of this workgroup's queries
 
     KList<K> list;
     list.clear();
@@ -75,8 +63,7 @@ __global__ __launch_bounds__(TILE) void scan_knn_kernel(const float4* __restrict
             if (j != me && list.admits(d, j)) list.insert(d, j);
         }
     };
-    auto walk = [&](int slot, int t) {
-        const int count = min(TILE, n - t * TILE);
+    auto walk = [&](int slot, int t, int count) {
         int c = 0;
         for (; c + 4 <= count; c += 4) {                               // four rows in flight: the LDS latency overlaps
             const float4 o0 = tile[slot][c], o1 = tile[slot][c + 1], o2 = tile[slot][c + 2], o3 = tile[slot][c + 3];
@@ -98,29 +85,31 @@ __global__ __launch_bounds__(TILE) void scan_knn_kernel(const float4* __restrict
 
     stage(0, b);
     __syncthreads();
-    if (live) walk(0, b);
+    if (live) walk(0, b, tiles.rows(b));
     int left = b - 1, right = b + 1, seen = 1;
     while (true) {
-        const double bound = block_max(live ? list.worst() : -1.0, slots);     // (also: every lane is done with the tiles)
+        double unused = 0.0, bound = live ? list.worst() : -1.0;
+        __syncthreads();                                               // the previous round's reads are done
+        block_minmax<false, true>(unused, bound, slots);               // (also: every lane is done with the tiles)
         if (left >= 0) {
-            const double gap = xlo - (double)pts[safe_index(perm[left * TILE + TILE - 1], n)].x;
+            const double gap = xlo - tiles.near_x(0, left);
             if (gap * gap > bound) left = -1;
         }
-        if (right < tiles) {
-            const double gap = (double)pts[safe_index(perm[right * TILE], n)].x - xhi;
-            if (gap * gap > bound) right = tiles;
+        if (right < tiles.tiles) {
+            const double gap = tiles.near_x(1, right) - xhi;
+            if (gap * gap > bound) right = tiles.tiles;
         }
-        if (left < 0 && right >= tiles) break;                         // workgroup-uniform
+        if (left < 0 && right >= tiles.tiles) break;                   // workgroup-uniform
         if (left >= 0) stage(0, left);
-        if (right < tiles) stage(1, right);
+        if (right < tiles.tiles) stage(1, right);
         __syncthreads();
         if (left >= 0) {
-            if (live) walk(0, left);
+            if (live) walk(0, left, tiles.rows(left));
             --left;
             ++seen;
         }
-        if (right < tiles) {
-            if (live) walk(1, right);
+        if (right < tiles.tiles) {
+            if (live) walk(1, right, tiles.rows(right));
             ++right;
             ++seen;
         }

@@ -3,8 +3,8 @@
 // (d2, index) order do not depend on the order candidates are offered in, so it is what the device's pruned walk over the
 // x-sorted scan must reproduce; threads split the queries, nothing else.  Never reached from the device entry points.
 #include <cmath>
-#include <thread>
 #include <vector>
+#include "host_split.h"
 #include "prepare_math.h"
 #include "../../include/usip_hip.h"
 
@@ -30,17 +30,7 @@ void knn_range(const float* xyzi, int n, int32_t* idx, int lo, int hi)
 template <int K>
 int knn_host(const float* xyzi, int n, int32_t* idx, int num_threads)
 {
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || n < 2 * nt) {
-        knn_range<K>(xyzi, n, idx, 0, n);
-        return USIP_OK;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-        const int lo = (int)((long long)n * w / nt), hi = (int)((long long)n * (w + 1) / nt);
-        pool.emplace_back([=] { knn_range<K>(xyzi, n, idx, lo, hi); });
-    }
-    for (auto& th : pool) th.join();
+    usip_host::split(n, num_threads, [=](int lo, int hi) { knn_range<K>(xyzi, n, idx, lo, hi); });
     return USIP_OK;
 }
 

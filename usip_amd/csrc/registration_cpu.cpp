@@ -4,8 +4,8 @@
 // fragment evaluation's RANSAC: Nmax <= 10240.  Never reached from the device entry points.
 #include <cmath>
 #include <cstring>
-#include <thread>
 #include <vector>
+#include "host_split.h"
 #include "registration_math.h"
 #include "../../include/usip_hip.h"
 
@@ -62,18 +62,9 @@ template <class Src>
 void trials_host(const float* x1, const float* x2, const int32_t* count, int P, int Nmax, int T, double threshold,
                  const Src& src, int32_t* counts, double* hyp, int32_t* drawn, int num_threads)
 {
-    const long long total = (long long)P * T;
-    const int nt = num_threads < 1 ? 1 : (num_threads > 64 ? 64 : num_threads);
-    if (nt == 1 || total < 2 * nt) {
-        trials_range(x1, x2, count, Nmax, T, threshold, src, counts, hyp, drawn, 0, total);
-        return;
-    }
-    std::vector<std::thread> pool;
-    for (int w = 0; w < nt; ++w) {
-        const long long lo = total * w / nt, hi = total * (w + 1) / nt;
-        pool.emplace_back([=, &src] { trials_range(x1, x2, count, Nmax, T, threshold, src, counts, hyp, drawn, lo, hi); });
-    }
-    for (auto& th : pool) th.join();
+    usip_host::split((long long)P * T, num_threads, [&](long long lo, long long hi) {
+        trials_range(x1, x2, count, Nmax, T, threshold, src, counts, hyp, drawn, lo, hi);
+    });
 }
 
 template <class Src>

@@ -114,23 +114,32 @@ def information_matrix(x1, inlier_mask):
     return ops.information(x1, inlier_mask)
 
 
+def _pack(parts, device):
+    """Fragments' rows [n,3] on the device -> the fields of a bank: lengths, offsets (host and device), rows in ONE buffer,
+    every fragment's local row indices ascending along x, lmax."""
+    lengths = [int(p.shape[0]) for p in parts]
+    offsets_host = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    return dict(lengths=lengths, offsets_host=offsets_host, rows=torch.cat(parts).contiguous(),
+                offsets=torch.from_numpy(offsets_host).to(device),
+                perm=torch.cat([torch.argsort(p[:, 0], stable=True).to(torch.int32) for p in parts]).contiguous(),
+                lmax=max(max(lengths), 1))
+
+
+def _rows3(c, device):
+    c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32))
+    return c.to(device, torch.float32)[:, :3]
+
+
 class FragmentBank:
     """The fragments' full clouds in ONE float32 device buffer [rows, 3] with int64 offsets (CSR, as pairs.ScanBank holds
     scans), plus, per fragment, its local row indices ascending along x."""
 
     def __init__(self, clouds: Sequence, device):
         self.device = torch.device(device)
-        parts = [c.to(self.device, torch.float32)[:, :3] if isinstance(c, torch.Tensor)
-                 else torch.from_numpy(np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32)).to(self.device)
-                 for c in clouds]
+        parts = [_rows3(c, self.device) for c in clouds]
         if not parts:
-            raise ValueError("FragmentBank: no fragments")
-        self.lengths = [int(p.shape[0]) for p in parts]
-        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        self.rows = torch.cat(parts).contiguous()
-        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
-        self.perm = torch.cat([torch.argsort(p[:, 0], stable=True).to(torch.int32) for p in parts]).contiguous()
-        self.lmax = max(max(self.lengths), 1)
+            raise ValueError("%s: no fragments" % type(self).__name__)
+        self.__dict__.update(_pack(parts, self.device))
 
     def host(self):
         return HostBank(self.rows.cpu().numpy(), self.offsets_host.copy(), self.perm.cpu().numpy(), self.lmax)
@@ -146,14 +155,19 @@ def host_bank(clouds: Sequence) -> HostBank:
     return HostBank(np.concatenate(parts), offsets, perm, max(max(p.shape[0] for p in parts), 1))
 
 
+def moved_x_order(bank, frag2, Rt):
+    """-> i32 [P,lmax]: every pair's fragment-2 rows ascending along their moved x, sorted on the device by the keys the
+    library computes (stable; padding last).  Rt contiguous f64 [P,3,4]."""
+    keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
+    return torch.argsort(keys, dim=1, stable=True).to(torch.int32)
+
+
 def overlap_ratio(bank: FragmentBank, frag1, frag2, Rt, radius: float = OVERLAP_RADIUS):
     """frag1, frag2 i32 [P] (fragments of the bank), Rt f64 [P,3,4] moving fragment 2 into fragment 1's frame ->
     (ratio f64 [P,2], hits i32 [P,2]): register2Fragments.m's ratioAligned.  The moved fragment is sorted along x here,
     on the device, by the keys the library computes."""
     Rt = Rt.contiguous()
-    keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
-    perm2 = torch.argsort(keys, dim=1, stable=True).to(torch.int32)
-    return ops.overlap_ratio(bank.rows, bank.offsets, frag1, frag2, Rt, bank.perm, perm2, radius)
+    return ops.overlap_ratio(bank.rows, bank.offsets, frag1, frag2, Rt, bank.perm, moved_x_order(bank, frag2, Rt), radius)
 
 
 def chordal_tolerance(tol_r: float) -> float:
@@ -161,28 +175,17 @@ def chordal_tolerance(tol_r: float) -> float:
     return 2.0 * math.sqrt(2.0) * math.sin(0.5 * float(tol_r))
 
 
-class RefineBank:
+class RefineBank(FragmentBank):
     """The fragments' clouds voxel-averaged at `leaf` (pcdownsample 'gridAverage', f-7's kernels; positions only: a zero
     reflectance column and zero normals go in), in ONE float32 device buffer [rows, 3] with offsets and the x-order of every
     fragment, as FragmentBank holds the full clouds.  Built once per scene: every fragment's cell count is read from the
     device here, nothing is read after."""
 
     def __init__(self, clouds: Sequence, device, leaf: float = REFINE_LEAF):
-        self.device, self.leaf = torch.device(device), float(leaf)
+        self.leaf = float(leaf)
         if not self.leaf > 0.0:
             raise ValueError("RefineBank: leaf must be positive")
-        parts = []
-        for c in clouds:
-            c = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32))
-            parts.append(self._downsample(c.to(self.device, torch.float32)[:, :3]))
-        if not parts:
-            raise ValueError("RefineBank: no fragments")
-        self.lengths = [int(p.shape[0]) for p in parts]
-        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
-        self.rows = torch.cat(parts).contiguous()
-        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
-        self.perm = torch.cat([torch.argsort(p[:, 0], stable=True).to(torch.int32) for p in parts]).contiguous()
-        self.lmax = max(max(self.lengths), 1)
+        FragmentBank.__init__(self, [self._downsample(_rows3(c, torch.device(device))) for c in clouds], device)
 
     def _downsample(self, xyz):
         n = xyz.shape[0]
@@ -197,9 +200,6 @@ class RefineBank:
         start[1:] = torch.cumsum(counts, 0)
         nrm = torch.zeros((n, 4), dtype=torch.float64, device=pts.device)
         return ops.scan_voxel_average(pts, nrm, order.to(torch.int32), start)[:, :3].contiguous()
-
-    def host(self):
-        return HostBank(self.rows.cpu().numpy(), self.offsets_host.copy(), self.perm.cpu().numpy(), self.lmax)
 
 
 def _refine_args(inlier_ratio, max_iterations, tolerance, align_radius):
@@ -219,20 +219,17 @@ def icp_refine(bank: RefineBank, frag1, frag2, Rt, mask=None, inlier_ratio: floa
     want_cuts: -> (IcpResult, cut_d2 f64, cut_i i32 [P,max_iterations+1]), the trim's cut of every pass, the final pass last."""
     ir, it, tt, tc, ar = _refine_args(inlier_ratio, max_iterations, tolerance, align_radius)
     Rt = Rt.contiguous()
-    keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
-    order2 = torch.argsort(keys, dim=1, stable=True).to(torch.int32)
     m = None if mask is None else mask.to(torch.uint8).contiguous()
-    o = ops.icp_refine(bank.rows, bank.offsets, bank.perm, frag1, frag2, Rt, bank.lmax, m, order2, ir, it, tt, tc, ar,
-                       want_cuts=want_cuts)
+    o = ops.icp_refine(bank.rows, bank.offsets, bank.perm, frag1, frag2, Rt, bank.lmax, m, moved_x_order(bank, frag2, Rt),
+                       ir, it, tt, tc, ar, want_cuts=want_cuts)
     res = IcpResult(o["Rt"], o["iterations"], o["converged"], o["rmse"], o["hits"], o["ratio"])
     return (res, o["cut_d2"], o["cut_i"]) if want_cuts else res
 
 
-def _refined(out, res: IcpResult, lib_np):
-    both = np.logical_and if lib_np else torch.logical_and
+def _refined(out, res: IcpResult):
     out.update(refined_Rt=res.Rt, refine_iterations=res.iterations, refine_converged=res.converged,
                refined_ratio_aligned=res.ratio, refined_hits=res.hits,
-               gate_refined=both(res.ratio[:, 0] > GATE_REFINED, out["inlier_ratio"] > GATE_INLIER_RATIO))
+               gate_refined=(res.ratio[:, 0] > GATE_REFINED) & (out["inlier_ratio"] > GATE_INLIER_RATIO))
     return out
 
 
@@ -347,22 +344,25 @@ def information_matrix_cpu(x1, inlier_mask):
     return info
 
 
+def _host_bank_args(bank: HostBank):
+    """-> (the C argument run rows, row_len, offsets, num_frags, total_rows of a HostBank, the arrays it points into: the
+    caller keeps them until the call has returned)"""
+    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
+    return (_p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0]), (rows, offsets)
+
+
 def overlap_ratio_cpu(bank: HostBank, frag1, frag2, Rt, radius: float = OVERLAP_RADIUS, prune: bool = True,
                       num_threads: int = 1):
-    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
-    perm1 = _np(bank.perm, np.int32, "perm", (rows.shape[0],))
+    args, alive = _host_bank_args(bank)
+    perm1 = _np(bank.perm, np.int32, "perm", (args[-1],))
     f2 = _np(frag2, np.int32, "frag2")
     P = f2.shape[0]
     f1, G = _np(frag1, np.int32, "frag1", (P,)), _np(Rt, np.float64, "Rt", (P, 3, 4))
-    L, nf = int(bank.lmax), offsets.shape[0] - 1
-    keys = np.zeros((P, L))
-    _lib.check(_lib.lib().usip_overlap_keys_f32_cpu(_p(rows), rows.shape[1], _p(offsets), nf, rows.shape[0], _p(f2), _p(G),
-                                                    P, L, _p(keys)), "usip_overlap_keys_f32_cpu")
-    perm2 = np.ascontiguousarray(np.argsort(keys, axis=1, kind="stable").astype(np.int32))
+    perm2 = moved_x_order_cpu(bank, f2, G)
     hits, ratio = np.zeros((P, 2), np.int32), np.zeros((P, 2))
-    _lib.check(_lib.lib().usip_overlap_ratio_f32_cpu(_p(rows), rows.shape[1], _p(offsets), nf, rows.shape[0], _p(f1), _p(f2),
-                                                     _p(G), _p(perm1), _p(perm2), P, L, float(radius), 1 if prune else 0,
-                                                     _p(hits), _p(ratio), int(num_threads)), "usip_overlap_ratio_f32_cpu")
+    _lib.check(_lib.lib().usip_overlap_ratio_f32_cpu(*args, _p(f1), _p(f2), _p(G), _p(perm1), _p(perm2), P, int(bank.lmax),
+                                                     float(radius), 1 if prune else 0, _p(hits), _p(ratio),
+                                                     int(num_threads)), "usip_overlap_ratio_f32_cpu")
     return ratio, hits
 
 
@@ -382,8 +382,8 @@ def refine_bank_cpu(clouds: Sequence, leaf: float = REFINE_LEAF) -> HostBank:
 
 
 def _icp_host(bank: HostBank, frag1, frag2, Rt, mask, order2):
-    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
-    perm1 = _np(bank.perm, np.int32, "perm", (rows.shape[0],))
+    args, alive = _host_bank_args(bank)
+    perm1 = _np(bank.perm, np.int32, "perm", (args[-1],))
     f2 = _np(frag2, np.int32, "frag2")
     P = f2.shape[0]
     if P > 65535:
@@ -392,28 +392,26 @@ def _icp_host(bank: HostBank, frag1, frag2, Rt, mask, order2):
     L = int(bank.lmax)
     m = None if mask is None else _np(np.asarray(mask).astype(np.uint8), np.uint8, "mask", (P,))
     o2 = None if order2 is None else _np(order2, np.int32, "order2", (P, L))
-    return rows, offsets, perm1, f1, f2, G, m, o2, P, L
+    return args + (_p(perm1), _p(f1), _p(f2), _p(G), _p(m), _p(o2), P, L), alive + (perm1, f1, f2, G, m, o2)
 
 
 def moved_x_order_cpu(bank: HostBank, frag2, Rt):
     """-> i32 [P,lmax]: every pair's fragment-2 rows ascending along their moved x (usip_overlap_keys_f32_cpu, stable)."""
-    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
+    args, alive = _host_bank_args(bank)
     f2 = _np(frag2, np.int32, "frag2")
     P, L = f2.shape[0], int(bank.lmax)
     G = _np(Rt, np.float64, "Rt", (P, 3, 4))
     keys = np.zeros((P, L))
-    _lib.check(_lib.lib().usip_overlap_keys_f32_cpu(_p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0],
-                                                    _p(f2), _p(G), P, L, _p(keys)), "usip_overlap_keys_f32_cpu")
+    _lib.check(_lib.lib().usip_overlap_keys_f32_cpu(*args, _p(f2), _p(G), P, L, _p(keys)), "usip_overlap_keys_f32_cpu")
     return np.ascontiguousarray(np.argsort(keys, axis=1, kind="stable").astype(np.int32))
 
 
 def icp_nearest_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, order2=None, num_threads: int = 1):
     """ops.icp_nearest on numpy arrays over the host twin (the loop over all rows) -> (idx i32 [P,lmax], d2 f64 [P,lmax])."""
-    rows, offsets, perm1, f1, f2, G, m, o2, P, L = _icp_host(bank, frag1, frag2, Rt, mask, order2)
+    args, alive = _icp_host(bank, frag1, frag2, Rt, mask, order2)
+    P, L = args[-2:]
     idx, d2 = np.zeros((P, L), np.int32), np.zeros((P, L))
-    _lib.check(_lib.lib().usip_icp_nearest_f32_cpu(_p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0],
-                                                   _p(perm1), _p(f1), _p(f2), _p(G), _p(m), _p(o2), P, L, _p(idx), _p(d2),
-                                                   int(num_threads)), "usip_icp_nearest_f32_cpu")
+    _lib.check(_lib.lib().usip_icp_nearest_f32_cpu(*args, _p(idx), _p(d2), int(num_threads)), "usip_icp_nearest_f32_cpu")
     return idx, d2
 
 
@@ -425,20 +423,82 @@ def icp_refine_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, inlier_ratio: fl
     ir, it, tt, tc, ar = _refine_args(inlier_ratio, max_iterations, tolerance, align_radius)
     if isinstance(order2, str):
         order2 = moved_x_order_cpu(bank, frag2, Rt)
-    rows, offsets, perm1, f1, f2, G, m, o2, P, L = _icp_host(bank, frag1, frag2, Rt, mask, order2)
+    args, alive = _icp_host(bank, frag1, frag2, Rt, mask, order2)
+    P, L = args[-2:]
     out = IcpResult(np.zeros((P, 3, 4)), np.zeros(P, np.int32), np.zeros(P, np.uint8), np.zeros(P), np.zeros(P, np.int32),
                     np.zeros((P, 2)))
     idx, d2 = (np.zeros((P, L), np.int32), np.zeros((P, L))) if want_neighbours else (None, None)
     cd, ci = (np.zeros((P, it + 1)), np.zeros((P, it + 1), np.int32)) if want_cuts else (None, None)
     _lib.check(_lib.lib().usip_icp_refine_f32_cpu(
-        _p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0], _p(perm1), _p(f1), _p(f2), _p(G), _p(m),
-        _p(o2), P, L, ir, it, tt, tc, ar, _p(out.Rt), _p(out.iterations), _p(out.converged), _p(out.rmse), _p(out.hits),
+        *args, ir, it, tt, tc, ar, _p(out.Rt), _p(out.iterations), _p(out.converged), _p(out.rmse), _p(out.hits),
         _p(out.ratio), _p(cd), _p(ci), _p(idx), _p(d2), int(num_threads)), "usip_icp_refine_f32_cpu")
     extra = ((idx, d2) if want_neighbours else ()) + ((cd, ci) if want_cuts else ())
     return (out,) + extra if extra else out
 
 
 # ------------------------------------------------------------------------------------------------ the per-pair pipeline
+# what _register_pairs runs over: the library's steps on device tensors, or on numpy arrays over the host twins
+_Backend = namedtuple("_Backend", "match union gather ransac fgr information overlap refine dense points index")
+
+
+def _dense(name):
+    def call(*args):
+        from . import posegraph
+        return getattr(posegraph, name)(*args)
+    return call
+
+
+_DEVICE = _Backend(match_descriptors_topk, match_union,
+                   lambda kp, rows: torch.gather(kp, 2, rows.long().unsqueeze(1).expand(-1, 3, -1)).contiguous(),
+                   fragment_registration, fgr_registration, information_matrix, overlap_ratio, icp_refine,
+                   _dense("dense_information"), lambda kp: kp, lambda frag: frag)
+
+
+def _host(nt: int) -> _Backend:
+    return _Backend(
+        lambda a, b, na, nb, k: match_descriptors_topk_cpu(a, b, na, nb, k, nt), match_union_cpu,
+        lambda kp, rows: np.ascontiguousarray(np.take_along_axis(kp, np.broadcast_to(rows[:, None, :],
+                                                                                     (len(kp), 3, rows.shape[1])), 2)),
+        lambda *a: fragment_registration_cpu(*a, None, nt), lambda *a: fgr_registration_cpu(*a, None, nt),
+        information_matrix_cpu, lambda *a: overlap_ratio_cpu(*a, True, nt),
+        lambda *a, **kw: icp_refine_cpu(*a, num_threads=nt, **kw), lambda *a: _dense("dense_information_cpu")(*a, nt),
+        lambda kp: np.asarray(kp, np.float32), lambda frag: np.asarray(frag, np.int32))
+
+
+def _register_pairs(be, name, kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
+                    seed, registrator, refine, refine_args, dense_radius):
+    """register_pairs over the backend `be` (_DEVICE, or _host(num_threads))."""
+    if registrator not in ("ransac", "fgr"):
+        raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
+    if dense_radius is not None and refine is None:
+        raise ValueError("%s: dense_radius needs refine" % name)
+    k = 1 if registrator == "fgr" else k
+    nn12, _ = be.match(desc1, desc2, n1, n2, k)
+    nn21, _ = be.match(desc2, desc1, n2, n1, k)
+    kp1, kp2 = be.points(kp1), be.points(kp2)
+    if registrator == "fgr":
+        reg = be.fgr(kp1, kp2, n1, n2, nn12, nn21, threshold, seed, pair_ids)
+        x1 = be.gather(kp1, reg.mutual[:, :, 0])
+        out = dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, valid=reg.valid, matches=reg.counts,
+                   row_count=reg.row_count, trials_walked=reg.trials_walked)
+    else:
+        pairs, count = be.union(nn12, nn21, n1, n2)
+        x1, x2 = be.gather(kp1, pairs[:, :, 0]), be.gather(kp2, pairs[:, :, 1])
+        reg = be.ransac(x1, x2, count, threshold, max_trials, seed, pair_ids)
+        out = dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, trialcount=reg.trialcount, valid=reg.valid,
+                   chosen=reg.chosen, matches=count)
+    frag1, frag2 = be.index(frag1), be.index(frag2)
+    ratio, hits = be.overlap(bank, frag1, frag2, reg.Rt, radius)
+    out.update(information=be.information(x1, reg.inlier_mask), ratio_aligned=ratio, overlap_hits=hits,
+               gate=(ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO), frag1=frag1, frag2=frag2)
+    if refine is not None:
+        mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
+        _refined(out, be.refine(refine, frag1, frag2, out["Rt"], mask, **(refine_args or {})))
+        if dense_radius is not None:
+            out["dense_information"], out["dense_count"] = be.dense(refine, frag1, frag2, out["refined_Rt"], mask, dense_radius)
+    return out
+
+
 def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                    threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
                    seed: int = 0, registrator: str = "ransac", refine: Optional[RefineBank] = None,
@@ -459,48 +519,8 @@ def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, fr
 
     dense_radius (with refine): split_txt_compute_G.m's computeInformation 'point' under refined_Rt, over the same mask:
     the keys dense_information f64 [P,6,6] and dense_count i32 [P] (posegraph.dense_information)."""
-    out = _register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
-                          seed, registrator)
-    if dense_radius is not None and refine is None:
-        raise ValueError("register_pairs: dense_radius needs refine")
-    if refine is not None:
-        mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
-        _refined(out, icp_refine(refine, frag1, frag2, out["Rt"], mask, **(refine_args or {})), False)
-        if dense_radius is not None:
-            from . import posegraph
-            out["dense_information"], out["dense_count"] = posegraph.dense_information(refine, frag1, frag2, out["refined_Rt"],
-                                                                                       mask, dense_radius)
-    return out
-
-
-def _register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius, seed,
-                    registrator):
-    if registrator == "fgr":
-        nn12, _ = match_descriptors_topk(desc1, desc2, n1, n2, 1)
-        nn21, _ = match_descriptors_topk(desc2, desc1, n2, n1, 1)
-        reg = fgr_registration(kp1, kp2, n1, n2, nn12, nn21, threshold, seed, pair_ids)
-        x1 = torch.gather(kp1, 2, reg.mutual[:, :, 0].long().unsqueeze(1).expand(-1, 3, -1)).contiguous()
-        info = information_matrix(x1, reg.inlier_mask)
-        ratio, hits = overlap_ratio(bank, frag1, frag2, reg.Rt, radius)
-        gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
-        return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, valid=reg.valid, matches=reg.counts,
-                    row_count=reg.row_count, trials_walked=reg.trials_walked, information=info, ratio_aligned=ratio,
-                    overlap_hits=hits, gate=gate, frag1=frag1, frag2=frag2)
-    if registrator != "ransac":
-        raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
-    nn12, _ = match_descriptors_topk(desc1, desc2, n1, n2, k)
-    nn21, _ = match_descriptors_topk(desc2, desc1, n2, n1, k)
-    pairs, count = match_union(nn12, nn21, n1, n2)
-    i1 = pairs[:, :, 0].long().unsqueeze(1).expand(-1, 3, -1)
-    i2 = pairs[:, :, 1].long().unsqueeze(1).expand(-1, 3, -1)
-    x1, x2 = torch.gather(kp1, 2, i1).contiguous(), torch.gather(kp2, 2, i2).contiguous()
-    reg = fragment_registration(x1, x2, count, threshold, max_trials, seed, pair_ids)
-    info = information_matrix(x1, reg.inlier_mask)
-    ratio, hits = overlap_ratio(bank, frag1, frag2, reg.Rt, radius)
-    gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
-    return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, trialcount=reg.trialcount, valid=reg.valid,
-                chosen=reg.chosen, matches=count, information=info, ratio_aligned=ratio, overlap_hits=hits, gate=gate,
-                frag1=frag1, frag2=frag2)
+    return _register_pairs(_DEVICE, "register_pairs", kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k,
+                           threshold, max_trials, radius, seed, registrator, refine, refine_args, dense_radius)
 
 
 def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, frag2, pair_ids, k: int = K_MATCH,
@@ -509,50 +529,8 @@ def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, fr
                        refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None) -> Dict[str, np.ndarray]:
     """register_pairs assembled from the host twins, on numpy arrays; refine: the HostBank of the downsampled fragments
     (refine_bank_cpu, or RefineBank.host())."""
-    out = _register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
-                              seed, num_threads, registrator)
-    if refine is not None:
-        mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
-        _refined(out, icp_refine_cpu(refine, out["frag1"], out["frag2"], out["Rt"], mask, num_threads=num_threads,
-                                     **(refine_args or {})), True)
-        if dense_radius is not None:
-            from . import posegraph
-            out["dense_information"], out["dense_count"] = posegraph.dense_information_cpu(
-                refine, out["frag1"], out["frag2"], out["refined_Rt"], mask, dense_radius, num_threads)
-    elif dense_radius is not None:
-        raise ValueError("register_pairs_cpu: dense_radius needs refine")
-    return out
-
-
-def _register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius, seed,
-                        num_threads, registrator):
-    if registrator == "fgr":
-        nn12, _ = match_descriptors_topk_cpu(desc1, desc2, n1, n2, 1, num_threads)
-        nn21, _ = match_descriptors_topk_cpu(desc2, desc1, n2, n1, 1, num_threads)
-        kp1, kp2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
-        reg = fgr_registration_cpu(kp1, kp2, n1, n2, nn12, nn21, threshold, seed, pair_ids, None, num_threads)
-        x1 = np.ascontiguousarray(np.take_along_axis(kp1, np.broadcast_to(reg.mutual[:, None, :, 0], kp1.shape), 2))
-        info = information_matrix_cpu(x1, reg.inlier_mask)
-        ratio, hits = overlap_ratio_cpu(bank, frag1, frag2, reg.Rt, radius, True, num_threads)
-        gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
-        return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, valid=reg.valid, matches=reg.counts,
-                    row_count=reg.row_count, trials_walked=reg.trials_walked, information=info, ratio_aligned=ratio,
-                    overlap_hits=hits, gate=gate, frag1=np.asarray(frag1, np.int32), frag2=np.asarray(frag2, np.int32))
-    if registrator != "ransac":
-        raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
-    nn12, _ = match_descriptors_topk_cpu(desc1, desc2, n1, n2, k, num_threads)
-    nn21, _ = match_descriptors_topk_cpu(desc2, desc1, n2, n1, k, num_threads)
-    pairs, count = match_union_cpu(nn12, nn21, n1, n2)
-    kp1, kp2 = np.asarray(kp1, np.float32), np.asarray(kp2, np.float32)
-    x1 = np.ascontiguousarray(np.take_along_axis(kp1, np.broadcast_to(pairs[:, None, :, 0], (len(kp1), 3, pairs.shape[1])), 2))
-    x2 = np.ascontiguousarray(np.take_along_axis(kp2, np.broadcast_to(pairs[:, None, :, 1], (len(kp2), 3, pairs.shape[1])), 2))
-    reg = fragment_registration_cpu(x1, x2, count, threshold, max_trials, seed, pair_ids, None, num_threads)
-    info = information_matrix_cpu(x1, reg.inlier_mask)
-    ratio, hits = overlap_ratio_cpu(bank, frag1, frag2, reg.Rt, radius, True, num_threads)
-    gate = (ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO)
-    return dict(Rt=reg.Rt, inliers=reg.inliers, inlier_ratio=reg.inlier_ratio, trialcount=reg.trialcount, valid=reg.valid,
-                chosen=reg.chosen, matches=count, information=info, ratio_aligned=ratio, overlap_hits=hits, gate=gate,
-                frag1=np.asarray(frag1, np.int32), frag2=np.asarray(frag2, np.int32))
+    return _register_pairs(_host(int(num_threads)), "register_pairs_cpu", kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2,
+                           pair_ids, k, threshold, max_trials, radius, seed, registrator, refine, refine_args, dense_radius)
 
 
 # ------------------------------------------------------------------------------------------------ the score

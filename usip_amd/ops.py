@@ -1849,14 +1849,18 @@ def _need_bank(rows, offsets, frag1, frag2, Rt):
     return P
 
 
+def _bank_args(rows, offsets):
+    """the C argument run rows, row_len, offsets, num_frags, total_rows of a CSR bank"""
+    return _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0]
+
+
 def overlap_keys(rows, offsets, frag2, Rt, Lmax: int):
     """f-9: x of every fragment-2 point moved by Rt -> keys f64 [P,Lmax] (+inf beyond the fragment), to sort by."""
     P = _need_bank(rows, offsets, None, frag2, Rt)
     keys = torch.empty((P, int(Lmax)), dtype=torch.float64, device=rows.device)
     with torch.cuda.device(rows.device), prof.kernel("overlap_keys", 20.0 * P * Lmax):
-        _lib.check(_lib.lib().usip_overlap_keys_f32(_ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1,
-                                                    rows.shape[0], _ptr(frag2), _ptr(Rt), P, int(Lmax), _ptr(keys),
-                                                    _stream(rows)), "usip_overlap_keys_f32")
+        _lib.check(_lib.lib().usip_overlap_keys_f32(*_bank_args(rows, offsets), _ptr(frag2), _ptr(Rt), P, int(Lmax),
+                                                    _ptr(keys), _stream(rows)), "usip_overlap_keys_f32")
     return keys
 
 
@@ -1872,10 +1876,9 @@ def overlap_ratio(rows, offsets, frag1, frag2, Rt, perm1, perm2, radius: float):
     hits = torch.empty((P, 2), dtype=torch.int32, device=rows.device)
     ratio = torch.empty((P, 2), dtype=torch.float64, device=rows.device)
     with torch.cuda.device(rows.device), prof.kernel("overlap_ratio", 32.0 * P * Lmax):
-        _lib.check(_lib.lib().usip_overlap_ratio_f32(_ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1,
-                                                     rows.shape[0], _ptr(frag1), _ptr(frag2), _ptr(Rt), _ptr(perm1),
-                                                     _ptr(perm2), P, Lmax, float(radius), _ptr(hits), _ptr(ratio),
-                                                     _stream(rows)), "usip_overlap_ratio_f32")
+        _lib.check(_lib.lib().usip_overlap_ratio_f32(*_bank_args(rows, offsets), _ptr(frag1), _ptr(frag2), _ptr(Rt),
+                                                     _ptr(perm1), _ptr(perm2), P, Lmax, float(radius), _ptr(hits),
+                                                     _ptr(ratio), _stream(rows)), "usip_overlap_ratio_f32")
     return ratio, hits
 
 
@@ -2044,9 +2047,8 @@ def icp_nearest(rows, offsets, perm1, frag1, frag2, Rt, Lmax: int, mask=None, or
     visits = torch.empty((P,), dtype=torch.int64, device=dev) if want_visits else None
     with torch.cuda.device(dev), prof.kernel("icp_nearest", 28.0 * P * Lmax):
         _lib.check(_lib.lib().usip_icp_nearest_f32(
-            _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0], _ptr(perm1), _ptr(frag1),
-            _ptr(frag2), _ptr(Rt), _opt_ptr(mask), _opt_ptr(order2), P, Lmax, _ptr(idx), _ptr(d2), _opt_ptr(visits),
-            _stream(rows)), "usip_icp_nearest_f32")
+            *_bank_args(rows, offsets), _ptr(perm1), _ptr(frag1), _ptr(frag2), _ptr(Rt), _opt_ptr(mask), _opt_ptr(order2), P,
+            Lmax, _ptr(idx), _ptr(d2), _opt_ptr(visits), _stream(rows)), "usip_icp_nearest_f32")
     return (idx, d2, visits) if want_visits else (idx, d2)
 
 
@@ -2092,9 +2094,9 @@ def icp_refine(rows, offsets, perm1, frag1, frag2, Rt0, Lmax: int, mask=None, or
     cut_i = torch.empty((P, int(max_iterations) + 1), dtype=torch.int32, device=dev) if want_cuts else None
     with torch.cuda.device(dev), prof.kernel("icp_refine", 28.0 * P * Lmax * (int(max_iterations) + 1)):
         _lib.check(_lib.lib().usip_icp_refine_f32(
-            _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0], _ptr(perm1), _ptr(frag1),
-            _ptr(frag2), _ptr(Rt0), _opt_ptr(mask), _opt_ptr(order2), P, Lmax, float(inlier_ratio), int(max_iterations),
-            float(tol_t), float(tol_c), float(align_radius), _ptr(workspace), workspace.numel(), _ptr(out["Rt"]),
+            *_bank_args(rows, offsets), _ptr(perm1), _ptr(frag1), _ptr(frag2), _ptr(Rt0), _opt_ptr(mask), _opt_ptr(order2), P,
+            Lmax, float(inlier_ratio), int(max_iterations), float(tol_t), float(tol_c), float(align_radius),
+            _ptr(workspace), workspace.numel(), _ptr(out["Rt"]),
             _ptr(out["iterations"]), _ptr(out["converged"]), _ptr(out["rmse"]), _ptr(out["hits"]), _ptr(out["ratio"]),
             _opt_ptr(cut_d2), _opt_ptr(cut_i), _opt_ptr(visits), ctypes.addressof(stage_ms) if want_stage_ms else None, _stream(rows)), "usip_icp_refine_f32")
     if want_visits:
@@ -2130,9 +2132,8 @@ def icp_information(rows, offsets, frag1, frag2, idx, d2, mask=None, radius: flo
     count = torch.empty((P,), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev), prof.kernel("icp_information", 12.0 * P * Lmax):
         _lib.check(_lib.lib().usip_icp_information_f32(
-            _ptr(rows), rows.shape[1], _ptr(offsets), offsets.shape[0] - 1, rows.shape[0], _ptr(frag1), _ptr(frag2),
-            _ptr(idx), _ptr(d2), _opt_ptr(mask), P, Lmax, float(radius), _ptr(info), _ptr(count), _stream(rows)),
-            "usip_icp_information_f32")
+            *_bank_args(rows, offsets), _ptr(frag1), _ptr(frag2), _ptr(idx), _ptr(d2), _opt_ptr(mask), P, Lmax, float(radius),
+            _ptr(info), _ptr(count), _stream(rows)), "usip_icp_information_f32")
     return info, count
 
 

@@ -89,16 +89,15 @@ def dense_information(bank, frag1, frag2, Rt, mask=None, radius: float = INFORMA
     or u8 [P] -> (info f64 [P,6,6], count i32 [P]); zeros where mask is 0.  One nearest pass, then the sums.  No host
     synchronisation."""
     Rt = Rt.contiguous()
-    keys = ops.overlap_keys(bank.rows, bank.offsets, frag2, Rt, bank.lmax)
-    order2 = torch.argsort(keys, dim=1, stable=True).to(torch.int32)
     m = None if mask is None else mask.to(torch.uint8).contiguous()
-    idx, d2 = ops.icp_nearest(bank.rows, bank.offsets, bank.perm, frag1, frag2, Rt, bank.lmax, m, order2)
+    idx, d2 = ops.icp_nearest(bank.rows, bank.offsets, bank.perm, frag1, frag2, Rt, bank.lmax, m,
+                              fragments.moved_x_order(bank, frag2, Rt))
     return ops.icp_information(bank.rows, bank.offsets, frag1, frag2, idx, d2, m, radius)
 
 
 def icp_information_cpu(bank, frag1, frag2, idx, d2, mask=None, radius: float = INFORMATION_RADIUS, num_threads: int = 1):
     """ops.icp_information on numpy arrays over the host twin."""
-    rows, offsets = _np(bank.rows, np.float32, "rows"), _np(bank.offsets, np.int64, "offsets")
+    args, alive = fragments._host_bank_args(bank)
     f2 = _np(frag2, np.int32, "frag2")
     P = f2.shape[0]
     f1 = _np(frag1, np.int32, "frag1", (P,))
@@ -111,8 +110,8 @@ def icp_information_cpu(bank, frag1, frag2, idx, d2, mask=None, radius: float = 
     m = None if mask is None else _np(np.asarray(mask).astype(np.uint8), np.uint8, "mask", (P,))
     info, count = np.zeros((P, 6, 6)), np.zeros(P, np.int32)
     _lib.check(_lib.lib().usip_icp_information_f32_cpu(
-        _p(rows), rows.shape[1], _p(offsets), offsets.shape[0] - 1, rows.shape[0], _p(f1), _p(f2), _p(ix), _p(dd), _p(m), P,
-        ix.shape[1], float(radius), _p(info), _p(count), int(num_threads)), "usip_icp_information_f32_cpu")
+        *args, _p(f1), _p(f2), _p(ix), _p(dd), _p(m), P, ix.shape[1], float(radius), _p(info), _p(count), int(num_threads)),
+        "usip_icp_information_f32_cpu")
     return info, count
 
 
