@@ -6,12 +6,12 @@ as ONE JSON line.
     python examples/evaluate_registration.py --make-synthetic /tmp/eval_data
     python examples/evaluate_registration.py --data /tmp/eval_data --detector det.pth --descriptor desc.pth \\
         --write-descriptors /tmp/descriptors
-    python examples/evaluate_registration.py --data /tmp/eval_data --method iss      # or random: the baselines' numbers
+    python examples/evaluate_registration.py --data /tmp/eval_data --method iss      # or harris, random: the baselines' numbers
 
 Data layout: <dir>/<id>.bin float32 rows [x y z nx ny nz curvature] and <dir>/pairs.txt with one pair per line,
 `anc_id pos_id tx ty tz qw qx qy qz`: the pose that moves the positive scan into the anchor's frame.  Without checkpoints
 the weights are the repository's seeded ones (usip_amd.synth.fill_parameters): the numbers then say nothing about USIP,
-only that the pipeline runs.  --method iss | random scores the reference's baseline detectors (evaluation/save_keypoints.py)
+only that the pipeline runs.  --method iss | harris | random scores the reference's baseline detectors (evaluation/save_keypoints.py)
 instead of the learned one: --top keypoints per frame from usip_amd.baselines, described by the same descriptor."""
 import argparse
 import json
@@ -116,10 +116,12 @@ def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, des
                                             max_trials=max_trials, seed=seed)
 
 
-def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None):
-    """method 'iss' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss: IssDetector's parameters)."""
+def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None):
+    """method 'iss' / 'harris' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss, harris:
+    IssDetector's / HarrisDetector's parameters)."""
     dev = evaluator.device
-    detect = baselines.IssDetector(num=evaluator.top, seed=seed, **(iss or {})) if method == "iss" else None
+    detect = baselines.IssDetector(num=evaluator.top, seed=seed, **(iss or {})) if method == "iss" else \
+        baselines.HarrisDetector(num=evaluator.top, seed=seed, **(harris or {})) if method == "harris" else None
     for fid, rows in scans:
         t = torch.from_numpy(np.ascontiguousarray(rows.T)).to(dev)
         pc, sn = t[:3].unsqueeze(0).contiguous(), t[3:].unsqueeze(0).contiguous()
@@ -127,7 +129,7 @@ def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None):
             first = torch.tensor([(seed + 7919 * int(fid)) % pc.shape[2]], dtype=torch.int32, device=dev)
             evaluator.add_frame(fid, pc, sn, inference.sample_nodes(pc, nodes, first))
         else:
-            kp, count = detect(pc, None, [int(fid)]) if method == "iss" else \
+            kp, count = detect(pc, None, [int(fid)]) if detect is not None else \
                 baselines.random_keypoints(pc, None, evaluator.top, seed, [int(fid)])
             evaluator.add_frame_keypoints(fid, pc, sn, kp, count)
 
@@ -147,13 +149,15 @@ def main():
     ap.add_argument("--max-trials", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there")
-    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "random"],
-                    help="tsf: the learned detector; iss, random: the baselines, --top keypoints per frame")
+    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "random"],
+                    help="tsf: the learned detector; iss, harris, random: the baselines, --top keypoints per frame")
     ap.add_argument("--salient-radius", type=float, default=2.0)
     ap.add_argument("--non-max-radius", type=float, default=2.0)
     ap.add_argument("--gamma-21", type=float, default=0.975)
     ap.add_argument("--gamma-32", type=float, default=0.975)
     ap.add_argument("--min-neighbors", type=int, default=5)
+    ap.add_argument("--harris-radius", type=float, default=1.0)
+    ap.add_argument("--harris-threshold", type=float, default=0.001)
     args = ap.parse_args()
     if args.make_synthetic:
         scans, pairs = make_synthetic(np.random.default_rng(args.seed), args.frames, args.points)
@@ -166,7 +170,8 @@ def main():
                                 args.seed, args.descriptor, method=args.method)
     add_scans(evaluator, scans, args.nodes, args.seed, args.method,
               dict(salient_radius=args.salient_radius, non_max_radius=args.non_max_radius, gamma_21=args.gamma_21,
-                   gamma_32=args.gamma_32, min_neighbors=args.min_neighbors))
+                   gamma_32=args.gamma_32, min_neighbors=args.min_neighbors),
+              dict(radius=args.harris_radius, threshold=args.harris_threshold))
     summary = evaluator.evaluate(pairs)
     summary.pop("per_pair")
     summary["seeded_weights"] = not ((args.detector or args.method != "tsf") and args.descriptor)

@@ -4,10 +4,10 @@
 survivors, at most --top of them).
 
     python examples/extract_keypoints.py --checkpoint /tmp/detector.pth --out /tmp/keypoints
-    python examples/extract_keypoints.py --method iss --out /tmp/keypoints_iss      # or random: the reference's baselines
+    python examples/extract_keypoints.py --method iss --out /tmp/keypoints_iss      # or harris, random: the reference's baselines
 
---method iss | random (save_keypoints.py's method switch) needs no checkpoint: exactly --top keypoints per frame from
-usip_amd.baselines, ISS keypoints first and random cloud points behind them where ISS finds fewer."""
+--method iss | harris | random (save_keypoints.py's method switch) needs no checkpoint: exactly --top keypoints per frame
+from usip_amd.baselines, the detector's keypoints first and random cloud points behind them where it finds fewer."""
 import argparse
 import os
 import sys
@@ -24,12 +24,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="ball", choices=["ball", "som"])
     ap.add_argument("--checkpoint", help="detector checkpoint; required for --method tsf")
-    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "random"])
+    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "random"])
     ap.add_argument("--salient-radius", type=float, default=2.0)
     ap.add_argument("--non-max-radius", type=float, default=2.0)
     ap.add_argument("--gamma-21", type=float, default=0.975)
     ap.add_argument("--gamma-32", type=float, default=0.975)
     ap.add_argument("--min-neighbors", type=int, default=5)
+    ap.add_argument("--harris-radius", type=float, default=1.0)
+    ap.add_argument("--harris-threshold", type=float, default=0.001)
     ap.add_argument("--seed", type=int, default=0, help="of the baselines' random picks")
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--n", type=int, default=16384)
@@ -47,9 +49,10 @@ def main():
     pc, sn = torch.from_numpy(clouds).to(dev), torch.from_numpy(normals).to(dev)
     os.makedirs(args.out, exist_ok=True)
     if args.method != "tsf":
-        if args.method == "iss":
+        if args.method in ("iss", "harris"):
             detect = baselines.IssDetector(args.top, True, args.seed, args.salient_radius, args.non_max_radius,
-                                           args.gamma_21, args.gamma_32, args.min_neighbors)
+                                           args.gamma_21, args.gamma_32, args.min_neighbors) if args.method == "iss" else \
+                baselines.HarrisDetector(args.top, True, args.seed, args.harris_radius, args.harris_threshold)
             kp, count = detect(pc, None, range(args.frames))
             found = detect.last[0].sum(1).tolist()
         else:
@@ -58,7 +61,7 @@ def main():
         for i, n in enumerate(count.tolist()):
             path = os.path.join(args.out, "%06d.bin" % i)
             inference.write_keypoints_bin(path, kp[i, :, :n].t().cpu().numpy())
-            print("%s  %d keypoints  (%s)" % (path, n, "random" if found is None else "iss found %d" % found[i]))
+            print("%s  %d keypoints  (%s)" % (path, n, "random" if found is None else "%s found %d" % (args.method, found[i])))
         return
     opt = DetectorOptions(surface_normal_len=4, node_knn_k_1=16)
     detector = build_detector(args.model, opt).to(dev)

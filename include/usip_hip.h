@@ -1194,6 +1194,48 @@ int usip_posegraph_optimize_f64_cpu(const int32_t* n, const int32_t* ecount, con
                                     double* weight2, double* energy, uint8_t* kept, int32_t* iterations_done,
                                     double* last_step, int32_t* status, int num_threads);
 
+/* ------------------------------------------------------------------ f-16  baseline keypoints: Harris3D
+ * The second hand-crafted detector the reference compares its learned one with (evaluation/save_keypoints.py:52-55, 303-313,
+ * method = 'harris': PCLKeypoint.keypointHarris(xyz, radius 1, nms_threshold 0.001, threads 0)).  The PCL binding is not part
+ * of the reference; the definition below is this project's own, written from PCL's HarrisKeypoint3D with method HARRIS, the
+ * normals from NormalEstimation at the search radius, refineCorners off.  Float64 arithmetic on float32 inputs, never
+ * contracted; every sum in ascending position of the frame's stable order along x; csrc/harris_math.h is the arithmetic.
+ * Frames, count, perm, membership (strict d2 < r * r, the point itself a member) and the limits are f-11's.
+ *
+ * usip_harris_normals_f32: neighbours i32 [B][N] = m = |N_r(i)|; normals f64 [B][3][N]: zeros (NO NORMAL) when m <
+ * min_neighbors; else, with d = p_j - p_i over N_r(i), s_a = sum d_a, s_ab = sum d_a d_b, c_ab = s_ab - (s_a * s_b) / m, the
+ * eigenvector of the smallest eigenvalue of c / m by f-7's 8 cyclic Jacobi sweeps (the first of equal ones; (0, 0, 1) for a
+ * zero trace), flipped towards the origin by f-7's rule (the first of the largest |components| c: negated when n[c] * p[c] >
+ * 0).  A normal with a non-finite component is replaced by zeros.
+ *
+ * usip_harris_response_f32: normals f64 [B][3][N] as above or supplied (float32 normals cast to float64, used as given, not
+ * renormalised).  A row HAS A NORMAL iff its three components are finite and not all zero.  A point without one: response 0,
+ * members 0.  Else members i32 [B][N] = k = the members of N_r(i) that have a normal (>= 1) and, with C = (sum over them of
+ * n_j n_j') / k, trace = (c00 + c11) + c22, det = ((((c00 c11) c22 + ((2 c01) c02) c12) - (c02 c02) c11) - (c01 c01) c22) -
+ * (c12 c12) c00, response f64 [B][N] by method:
+ *   0 HARRIS  (0.04 + det) - (0.04 * trace) * trace   (unit normals have trace 1, so this is det)
+ *   1 NOBLE   det / trace
+ *   2 LOWE    det / (trace * trace)
+ *   3 TOMASI  the smallest eigenvalue of C (8 Jacobi sweeps)
+ * a zero trace gives 0, a non-finite result gives 0.  tiles_visited as f-11's.
+ *
+ * Keypoints: i is one iff response[i] > 0, response[i] >= threshold (>= 0, the reference: 0.001) and no member of N_r(i) has a
+ * larger response (equal ones do not suppress each other) -- usip_iss_nms_f32 with min_neighbors 1 on the response with
+ * everything below the threshold set to 0.  Keypoints are cloud points: no refinement.
+ * Slots beyond count[b] get zeros.  USIP_EINVAL: a shape outside the limits, min_neighbors < 1, an unknown method, a radius
+ * that is not positive and finite, a NULL among the required pointers. */
+int usip_harris_normals_f32(const float* pc, const int32_t* count, const int32_t* perm, int B, int N, double radius,
+                            int min_neighbors, double* normals, int32_t* neighbours, void* stream);
+int usip_harris_response_f32(const float* pc, const int32_t* count, const int32_t* perm, const double* normals, int B, int N,
+                             double radius, int method, double* response, int32_t* members, int32_t* tiles_visited,
+                             void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; every query tests all live points of its
+ * frame, in the frame's own stable order along x (no perm); num_threads splits the queries. */
+int usip_harris_normals_f32_cpu(const float* pc, const int32_t* count, int B, int N, double radius, int min_neighbors,
+                                double* normals, int32_t* neighbours, int num_threads);
+int usip_harris_response_f32_cpu(const float* pc, const int32_t* count, const double* normals, int B, int N, double radius,
+                                 int method, double* response, int32_t* members, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

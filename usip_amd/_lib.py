@@ -256,6 +256,13 @@ SIGNATURES = {
                                      + [ctypes.c_void_p] * 2 + [_int, _int, _dbl, ctypes.c_void_p, _i32p, _int], _int),
     "usip_posegraph_optimize_f64_cpu": ([_i32p] * 4 + [ctypes.c_void_p] * 3 + [_int, _int, _int, _dbl, _dbl, _int, _int]
                                         + [ctypes.c_void_p] * 5 + [_i32p, ctypes.c_void_p, _i32p, _int], _int),
+    # f-16 baseline keypoints: Harris3D normals and response (usip_amd/baselines.py); the suppression is f-11's
+    "usip_harris_normals_f32": ([_f32p, _i32p, _i32p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _stream], _int),
+    "usip_harris_response_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _i32p,
+                                  _stream], _int),
+    "usip_harris_normals_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _int], _int),
+    "usip_harris_response_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _int],
+                                     _int),
 }
 
 

@@ -2,26 +2,30 @@
 
 evaluation/save_keypoints.py has method = 'tsf' | 'iss' | 'harris' | 'sift' | 'random'; the hand-crafted ones come from an
 external PCL binding that is not part of the reference.  Here ISS (Intrinsic Shape Signatures, the parameters
-save_keypoints.py:44-50 pins) runs as HIP kernels (csrc/iss.hip; the definition is in include/usip_hip.h and
-csrc/iss_math.h), `random` and the rule that brings every method to the same keypoint count (ensure_keypoint_number,
+save_keypoints.py:44-50 pins) and Harris3D (save_keypoints.py:52-55: radius 1, threshold 0.001) run as HIP kernels (csrc/iss.hip,
+csrc/harris.hip; the definitions are in include/usip_hip.h, csrc/iss_math.h and csrc/harris_math.h), `random` and the rule that brings every method to the same keypoint count (ensure_keypoint_number,
 save_keypoints.py:219-227, 326-331) are torch plumbing on the device:
 
     det = IssDetector(num=512, seed=0)                       # radii 2 / 2, gamma 0.975 / 0.975, min_neighbors 5
     kp, count = det(pc, count=None, frame_ids=[0, 1])        # pc f32 [B,3,N] on the device -> f32 [B,3,512], i32 [B]
     evaluator.add_frame_keypoints(fid, pc, sn, kp, count)    # evaluation.RegistrationEvaluator: score them
+    det = HarrisDetector(num=512, seed=0)                    # radius 1, threshold 0.001, response "harris"
 
   iss_saliency       saliency f64 [B,N] and the neighbour counts at the salient radius
   iss_keypoints      (mask u8 [B,N], saliency, neighbours)
+  harris_normals     normals f64 [B,3,N] over the radius and the neighbour counts; fewer than min_neighbors: no normal, zeros
+  harris_response    (response f64 [B,N], members i32 [B,N], normals f64 [B,3,N]) from estimated or supplied normals
+  harris_keypoints   (mask u8 [B,N], response, members, normals): at or above the threshold, no larger response in reach
   select_keypoints   mask -> exactly `num` keypoints per frame (or at most, with ensure=False)
   random_keypoints   `num` distinct points per frame
-  *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp)
+  *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp, csrc/harris_cpu.cpp)
 
 The selection is reproducible and free of host synchronisation: one CPU generator per frame, seeded from (seed, frame_id) the
 way prepare._keep_rows seeds its own, draws u in [0, 1) for every point; a live point's key is u when it is a keypoint and
 1 + u otherwise, a dead slot's +inf; the first `num` points in ascending key (ties towards the lower index) are the frame's
 keypoints.  With more than `num` keypoints that is a uniform subset, as the reference draws one; with fewer, every keypoint
 comes first and uniform random cloud points pad.  The padding never repeats a keypoint -- the reference's np.random.choice
-over the whole cloud could.  `random` gives every live point the key u.  Harris3D and SIFT3D are not built.
+over the whole cloud could.  `random` gives every live point the key u.  SIFT3D is not built.
 """
 import ctypes
 from typing import Optional, Sequence, Tuple
@@ -32,6 +36,7 @@ import torch
 from . import _lib, ops
 
 ISS_DEFAULTS = dict(salient_radius=2.0, non_max_radius=2.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5)
+HARRIS_DEFAULTS = dict(radius=1.0, threshold=0.001, response="harris", min_neighbors=3)
 
 
 def _check(salient_radius, non_max_radius, min_neighbors):
@@ -73,6 +78,53 @@ def iss_keypoints(pc, count=None, salient_radius: float = 2.0, non_max_radius: f
     perm = sort_along_x(pc, count)
     sal, nb = ops.iss_saliency(pc, count, perm, salient_radius, gamma_21, gamma_32, min_neighbors)
     return ops.iss_nms(pc, count, perm, sal, non_max_radius, min_neighbors), sal, nb
+
+
+# ------------------------------------------------------------------------------------------------ Harris3D
+def _check_harris(radius, threshold, response, min_neighbors):
+    if not (0.0 < float(radius) < float("inf") and float(threshold) >= 0.0 and int(min_neighbors) >= 1):
+        raise ValueError("harris: the radius must be positive and finite, the threshold at least 0 and min_neighbors at least 1")
+    if response not in ops.HARRIS_METHODS:
+        raise ValueError("harris: response must be one of %s, got %r" % (sorted(ops.HARRIS_METHODS), response))
+
+
+def _supplied(normals, pc):
+    """PCL's setNormals: f32 [B,3,N], used as given -- cast to float64, not renormalised"""
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.shape != pc.shape \
+            or normals.device != pc.device:
+        raise ValueError("harris: supplied normals must be f32 %s on %s" % (tuple(pc.shape), pc.device))
+    return normals.to(torch.float64).contiguous()
+
+
+def harris_normals(pc, count=None, radius: float = 1.0, min_neighbors: int = 3, perm=None):
+    """pc f32 [B,3,N], count i32 [B] -> (normals f64 [B,3,N], neighbours i32 [B,N])."""
+    _check_harris(radius, 0.0, "harris", min_neighbors)
+    pc, count = _frames(pc, count)
+    perm = sort_along_x(pc, count) if perm is None else perm
+    return ops.harris_normals(pc, count, perm, radius, min_neighbors)
+
+
+def harris_response(pc, count=None, radius: float = 1.0, normals=None, response: str = "harris", min_neighbors: int = 3,
+                    perm=None, want_visits: bool = False):
+    """pc f32 [B,3,N], count i32 [B], normals f32 [B,3,N] or None (estimated over the radius) -> (response f64 [B,N], members
+    i32 [B,N], normals f64 [B,3,N][, tiles_visited i32 [B,ceil(N/256)]])."""
+    _check_harris(radius, 0.0, response, min_neighbors)
+    pc, count = _frames(pc, count)
+    perm = sort_along_x(pc, count) if perm is None else perm
+    nrm = ops.harris_normals(pc, count, perm, radius, min_neighbors)[0] if normals is None else _supplied(normals, pc)
+    out = ops.harris_response(pc, count, perm, nrm, radius, response, want_visits)
+    return out[:2] + (nrm,) + out[2:]
+
+
+def harris_keypoints(pc, count=None, radius: float = 1.0, threshold: float = 0.001, normals=None, response: str = "harris",
+                     min_neighbors: int = 3):
+    """-> (mask u8 [B,N], response f64 [B,N], members i32 [B,N], normals f64 [B,3,N]).  One sort, no host synchronisation."""
+    _check_harris(radius, threshold, response, min_neighbors)
+    pc, count = _frames(pc, count)
+    perm = sort_along_x(pc, count)
+    res, members, nrm = harris_response(pc, count, radius, normals, response, min_neighbors, perm)
+    kept = torch.where(res >= float(threshold), res, torch.zeros_like(res))
+    return ops.iss_nms(pc, count, perm, kept, radius, 1), res, members, nrm
 
 
 # ------------------------------------------------------------------------------------------------ the selection rule
@@ -151,6 +203,22 @@ class IssDetector:
         return select_keypoints(pc, self.last[0], count, self.num, self.ensure, self.seed, frame_ids)
 
 
+class HarrisDetector:
+    """Harris3D with its parameters and the keypoint count bundled: __call__(pc, count, frame_ids) -> (kp f32 [B,3,num], count
+    i32 [B]); .last holds (mask, response, members, normals) of the latest call."""
+
+    def __init__(self, num: int = 512, ensure: bool = True, seed: int = 0, radius: float = 1.0, threshold: float = 0.001,
+                 response: str = "harris"):
+        _check_harris(radius, threshold, response, 3)
+        self.num, self.ensure, self.seed = int(num), bool(ensure), int(seed)
+        self.params = dict(radius=float(radius), threshold=float(threshold), response=response)
+        self.last = None
+
+    def __call__(self, pc, count=None, frame_ids=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        self.last = harris_keypoints(pc, count, **self.params)
+        return select_keypoints(pc, self.last[0], count, self.num, self.ensure, self.seed, frame_ids)
+
+
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
 def _p(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
@@ -187,6 +255,50 @@ def iss_keypoints_cpu(pc, count=None, salient_radius: float = 2.0, non_max_radiu
     _lib.check(_lib.lib().usip_iss_nms_f32_cpu(_p(a), _p(c), _p(sal), B, N, float(non_max_radius), int(min_neighbors),
                                                _p(mask), int(num_threads)), "usip_iss_nms_f32_cpu")
     return mask, sal, nb
+
+
+def harris_normals_cpu(pc, count=None, radius: float = 1.0, min_neighbors: int = 3, num_threads: int = 1):
+    """-> (normals f64 [B,3,N], neighbours i32 [B,N])"""
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    nrm, nb = np.zeros((B, 3, N), np.float64), np.zeros((B, N), np.int32)
+    _lib.check(_lib.lib().usip_harris_normals_f32_cpu(_p(a), _p(c), B, N, float(radius), int(min_neighbors), _p(nrm), _p(nb),
+                                                      int(num_threads)), "usip_harris_normals_f32_cpu")
+    return nrm, nb
+
+
+def harris_response_cpu(pc, count=None, radius: float = 1.0, normals=None, response: str = "harris", min_neighbors: int = 3,
+                        num_threads: int = 1):
+    """-> (response f64 [B,N], members i32 [B,N], normals f64 [B,3,N])"""
+    _check_harris(radius, 0.0, response, min_neighbors)
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    if normals is None:
+        nrm = harris_normals_cpu(a, c, radius, min_neighbors, num_threads)[0]
+    else:
+        nrm = np.asarray(normals)
+        if nrm.dtype != np.float32 or nrm.shape != a.shape:
+            raise ValueError("harris: supplied normals must be f32 %s" % (a.shape,))
+        nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    res, members = np.zeros((B, N), np.float64), np.zeros((B, N), np.int32)
+    _lib.check(_lib.lib().usip_harris_response_f32_cpu(_p(a), _p(c), _p(nrm), B, N, float(radius),
+                                                       ops.HARRIS_METHODS[response], _p(res), _p(members), int(num_threads)),
+               "usip_harris_response_f32_cpu")
+    return res, members, nrm
+
+
+def harris_keypoints_cpu(pc, count=None, radius: float = 1.0, threshold: float = 0.001, normals=None,
+                         response: str = "harris", min_neighbors: int = 3, num_threads: int = 1):
+    """-> (mask u8 [B,N], response f64 [B,N], members i32 [B,N], normals f64 [B,3,N])"""
+    _check_harris(radius, threshold, response, min_neighbors)
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    res, members, nrm = harris_response_cpu(a, c, radius, normals, response, min_neighbors, num_threads)
+    kept = np.where(res >= float(threshold), res, 0.0)
+    mask = np.zeros((B, N), np.uint8)
+    _lib.check(_lib.lib().usip_iss_nms_f32_cpu(_p(a), _p(c), _p(kept), B, N, float(radius), 1, _p(mask), int(num_threads)),
+               "usip_iss_nms_f32_cpu")
+    return mask, res, members, nrm
 
 
 def _select_cpu(pc, mask, count, num, ensure, seed, frame_ids, want_index):

@@ -20,65 +20,11 @@
 //                         queries is salient writes zeros and leaves.
 // Slots beyond count[b] get saliency 0, neighbours 0, keypoint 0.  An entry of perm outside [0, count) reads point 0: a
 // wrong permutation gives wrong values, never a wild read.
-#include "common.h"
-#include "bank.h"
-#include "iss_math.h"
+#include "iss_walk.h"                                                  // Frame and walk_tiles, shared with csrc/harris.hip
 
 using namespace usip_iss;
-using usip_bank::safe_index;
 
 namespace {
-
-// One frame as a workgroup sees it
-struct Frame {
-    const float *x, *y, *z;
-    const int32_t* perm;
-    int n;                                                             // live points
-    __device__ __forceinline__ Frame(const float* pc, const int32_t* count, const int32_t* perm_, int N, int f)
-    {
-        x = pc + 3LL * f * N;
-        y = x + N;
-        z = y + N;
-        perm = perm_ + (long long)f * N;
-        const int c = count ? count[f] : N;
-        n = c < 0 ? 0 : (c > N ? N : c);
-    }
-    __device__ __forceinline__ int at(int s) const { return safe_index(perm[s < n ? s : n - 1], n); }   // sorted -> original
-    __device__ __forceinline__ double xs(int s) const { return (double)x[at(s)]; }
-    // the first tile in [0, w] whose largest x is within r of xlo (tile w is: its gap is <= 0); workgroup-uniform
-    __device__ __forceinline__ int first_tile(int w, double xlo, double r) const
-    {
-        int lo = 0, hi = w;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (xlo - xs(mid * TILE + TILE - 1) < r) hi = mid; else lo = mid + 1;
-        }
-        return lo;
-    }
-};
-
-// The walk both kernels share.  stage(slot, t) copies tile t of the sorted order into LDS slot `slot`; first_x(slot) is
-// the x of that slot's first row; walk(slot, rows) offers its rows to the lane in ascending order.  Returns the tiles walked.
-template <class Stage, class FirstX, class Walk>
-__device__ __forceinline__ int walk_tiles(const Frame& F, int w, double r, bool live, Stage stage, FirstX first_x, Walk walk)
-{
-    const int tiles = (F.n + TILE - 1) / TILE;
-    const double xlo = F.xs(w * TILE), xhi = F.xs(min(w * TILE + TILE - 1, F.n - 1));
-    int seen = 0, slot = 0;
-    int t = F.first_tile(w, xlo, r);
-    stage(0, t);
-    __syncthreads();
-    while (true) {
-        if (t > w && first_x(slot) - xhi >= r) break;                  // this tile and all behind it: no member
-        if (t + 1 < tiles) stage(slot ^ 1, t + 1);                     // (in flight while this tile is walked)
-        if (live) walk(slot, min(TILE, F.n - t * TILE));
-        ++seen;
-        __syncthreads();
-        if (++t >= tiles) break;
-        slot ^= 1;
-    }
-    return seen;
-}
 
 __global__ __launch_bounds__(TILE) void iss_saliency_kernel(const float* __restrict__ pc, const int32_t* __restrict__ count,
                                                             const int32_t* __restrict__ perm, int N, double rs, double r2,

@@ -6,7 +6,8 @@
 // that tile out.  What a tile holds in LDS, the per-row test and the rule that ends a side are the kernel's own (its stage,
 // visit and prune); the order of the rounds, the start tile, the x at a tile's near edge with the partial last tile clamped,
 // and the workgroup's smallest / largest x are here.  Device only.
-// csrc/iss.hip's walk_tiles is not one of these: it walks ascending because the order of its sums is part of its contract.
+// csrc/iss_walk.h's walk_tiles (csrc/iss.hip, csrc/harris.hip) is not one of these: it walks ascending because the order of
+// its sums is part of those kernels' contracts.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1929,6 +1929,45 @@ def iss_nms(pc, count, perm, saliency, non_max_radius: float, min_neighbors: int
     return kp
 
 
+# ------------------------------------------------------------------------------------------------ f-16 baseline keypoints: Harris3D
+HARRIS_METHODS = {"harris": 0, "noble": 1, "lowe": 2, "tomasi": 3}
+
+
+def harris_normals(pc, count, perm, radius: float, min_neighbors: int = 3):
+    """f-16: pc f32 [B,3,N], count i32 [B] or None, perm i32 [B,N] (every frame's live points ascending along x, stable)
+    -> (normals f64 [B,3,N], neighbours i32 [B,N]); a point with fewer than min_neighbors members within radius has no
+    normal: zeros."""
+    B, N = _need_frames(pc, count, perm)
+    if not (float(radius) > 0.0 and int(min_neighbors) >= 1):
+        raise RuntimeError("harris: radius must be positive and min_neighbors at least 1")
+    normals = torch.empty((B, 3, N), dtype=torch.float64, device=pc.device)
+    nb = torch.empty((B, N), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("harris_normals", 40.0 * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_harris_normals_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), B, N, float(radius),
+                                                      int(min_neighbors), _ptr(normals), _ptr(nb), _stream(pc)),
+                   "usip_harris_normals_f32")
+    return normals, nb
+
+
+def harris_response(pc, count, perm, normals, radius: float, response: str = "harris", want_visits: bool = False):
+    """f-16: normals f64 [B,3,N] (a row that is not finite or all zero: no normal) -> (response f64 [B,N], members i32
+    [B,N]); with want_visits also the 256-point tiles each workgroup walked, i32 [B, ceil(N/256)]."""
+    B, N = _need_frames(pc, count, perm)
+    _need_on(normals, "normals", torch.float64, (B, 3, N), pc.device)
+    if normals is None or not float(radius) > 0.0:
+        raise RuntimeError("harris: normals are required and radius must be positive")
+    if response not in HARRIS_METHODS:
+        raise RuntimeError("harris: response must be one of %s, got %r" % (sorted(HARRIS_METHODS), response))
+    res = torch.empty((B, N), dtype=torch.float64, device=pc.device)
+    members = torch.empty((B, N), dtype=torch.int32, device=pc.device)
+    visits = torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=pc.device) if want_visits else None
+    with torch.cuda.device(pc.device), prof.kernel("harris_response", 64.0 * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_harris_response_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), _ptr(normals), B, N,
+                                                       float(radius), HARRIS_METHODS[response], _ptr(res), _ptr(members),
+                                                       _opt_ptr(visits), _stream(pc)), "usip_harris_response_f32")
+    return (res, members, visits) if want_visits else (res, members)
+
+
 # ------------------------------------------------------------------------------------------------ f-12 fast global registration
 FGR_MMAX, FGR_ROWS_MAX = 1024, 3000
 
