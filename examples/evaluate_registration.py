@@ -6,12 +6,12 @@ as ONE JSON line.
     python examples/evaluate_registration.py --make-synthetic /tmp/eval_data
     python examples/evaluate_registration.py --data /tmp/eval_data --detector det.pth --descriptor desc.pth \\
         --write-descriptors /tmp/descriptors
-    python examples/evaluate_registration.py --data /tmp/eval_data --method iss      # or harris, random: the baselines' numbers
+    python examples/evaluate_registration.py --data /tmp/eval_data --method iss      # or harris, sift, random: the baselines' numbers
 
 Data layout: <dir>/<id>.bin float32 rows [x y z nx ny nz curvature] and <dir>/pairs.txt with one pair per line,
 `anc_id pos_id tx ty tz qw qx qy qz`: the pose that moves the positive scan into the anchor's frame.  Without checkpoints
 the weights are the repository's seeded ones (usip_amd.synth.fill_parameters): the numbers then say nothing about USIP,
-only that the pipeline runs.  --method iss | harris | random scores the reference's baseline detectors (evaluation/save_keypoints.py)
+only that the pipeline runs.  --method iss | harris | sift | random scores the reference's baseline detectors (evaluation/save_keypoints.py)
 instead of the learned one: --top keypoints per frame from usip_amd.baselines, described by the same descriptor."""
 import argparse
 import json
@@ -116,12 +116,17 @@ def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, des
                                             max_trials=max_trials, seed=seed)
 
 
-def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None):
-    """method 'iss' / 'harris' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss, harris:
-    IssDetector's / HarrisDetector's parameters)."""
+def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None, sift=None):
+    """method 'iss' / 'harris' / 'sift' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss, harris,
+    sift: IssDetector's / HarrisDetector's / SiftDetector's parameters; sift's field may be "x" | "y" | "z" or "curvature",
+    the scans' seventh column)."""
     dev = evaluator.device
     detect = baselines.IssDetector(num=evaluator.top, seed=seed, **(iss or {})) if method == "iss" else \
         baselines.HarrisDetector(num=evaluator.top, seed=seed, **(harris or {})) if method == "harris" else None
+    sift = dict(sift or {})
+    curvature = sift.get("field") == "curvature"
+    if method == "sift":
+        detect = baselines.SiftDetector(num=evaluator.top, seed=seed, **dict(sift, field="z" if curvature else sift.get("field", "z")))
     for fid, rows in scans:
         t = torch.from_numpy(np.ascontiguousarray(rows.T)).to(dev)
         pc, sn = t[:3].unsqueeze(0).contiguous(), t[3:].unsqueeze(0).contiguous()
@@ -129,8 +134,11 @@ def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None
             first = torch.tensor([(seed + 7919 * int(fid)) % pc.shape[2]], dtype=torch.int32, device=dev)
             evaluator.add_frame(fid, pc, sn, inference.sample_nodes(pc, nodes, first))
         else:
-            kp, count = detect(pc, None, [int(fid)]) if detect is not None else \
-                baselines.random_keypoints(pc, None, evaluator.top, seed, [int(fid)])
+            if method == "sift" and curvature:
+                kp, count = detect(pc, None, [int(fid)], field=t[6].unsqueeze(0).contiguous())
+            else:
+                kp, count = detect(pc, None, [int(fid)]) if detect is not None else \
+                    baselines.random_keypoints(pc, None, evaluator.top, seed, [int(fid)])
             evaluator.add_frame_keypoints(fid, pc, sn, kp, count)
 
 
@@ -149,8 +157,8 @@ def main():
     ap.add_argument("--max-trials", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there")
-    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "random"],
-                    help="tsf: the learned detector; iss, harris, random: the baselines, --top keypoints per frame")
+    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "sift", "random"],
+                    help="tsf: the learned detector; iss, harris, sift, random: the baselines, --top keypoints per frame")
     ap.add_argument("--salient-radius", type=float, default=2.0)
     ap.add_argument("--non-max-radius", type=float, default=2.0)
     ap.add_argument("--gamma-21", type=float, default=0.975)
@@ -158,6 +166,11 @@ def main():
     ap.add_argument("--min-neighbors", type=int, default=5)
     ap.add_argument("--harris-radius", type=float, default=1.0)
     ap.add_argument("--harris-threshold", type=float, default=0.001)
+    ap.add_argument("--sift-min-scale", type=float, default=0.5)
+    ap.add_argument("--sift-octaves", type=int, default=4)
+    ap.add_argument("--sift-scales", type=int, default=8)
+    ap.add_argument("--sift-contrast", type=float, default=0.1)
+    ap.add_argument("--sift-field", default="z", choices=["x", "y", "z", "curvature"])
     args = ap.parse_args()
     if args.make_synthetic:
         scans, pairs = make_synthetic(np.random.default_rng(args.seed), args.frames, args.points)
@@ -171,7 +184,9 @@ def main():
     add_scans(evaluator, scans, args.nodes, args.seed, args.method,
               dict(salient_radius=args.salient_radius, non_max_radius=args.non_max_radius, gamma_21=args.gamma_21,
                    gamma_32=args.gamma_32, min_neighbors=args.min_neighbors),
-              dict(radius=args.harris_radius, threshold=args.harris_threshold))
+              dict(radius=args.harris_radius, threshold=args.harris_threshold),
+              dict(min_scale=args.sift_min_scale, n_octaves=args.sift_octaves, n_scales_per_octave=args.sift_scales,
+                   min_contrast=args.sift_contrast, field=args.sift_field))
     summary = evaluator.evaluate(pairs)
     summary.pop("per_pair")
     summary["seeded_weights"] = not ((args.detector or args.method != "tsf") and args.descriptor)

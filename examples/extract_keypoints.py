@@ -4,9 +4,9 @@
 survivors, at most --top of them).
 
     python examples/extract_keypoints.py --checkpoint /tmp/detector.pth --out /tmp/keypoints
-    python examples/extract_keypoints.py --method iss --out /tmp/keypoints_iss      # or harris, random: the reference's baselines
+    python examples/extract_keypoints.py --method iss --out /tmp/keypoints_iss      # or harris, sift, random: the reference's baselines
 
---method iss | harris | random (save_keypoints.py's method switch) needs no checkpoint: exactly --top keypoints per frame
+--method iss | harris | sift | random (save_keypoints.py's method switch) needs no checkpoint: exactly --top keypoints per frame
 from usip_amd.baselines, the detector's keypoints first and random cloud points behind them where it finds fewer."""
 import argparse
 import os
@@ -24,7 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="ball", choices=["ball", "som"])
     ap.add_argument("--checkpoint", help="detector checkpoint; required for --method tsf")
-    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "random"])
+    ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "sift", "random"])
     ap.add_argument("--salient-radius", type=float, default=2.0)
     ap.add_argument("--non-max-radius", type=float, default=2.0)
     ap.add_argument("--gamma-21", type=float, default=0.975)
@@ -32,6 +32,11 @@ def main():
     ap.add_argument("--min-neighbors", type=int, default=5)
     ap.add_argument("--harris-radius", type=float, default=1.0)
     ap.add_argument("--harris-threshold", type=float, default=0.001)
+    ap.add_argument("--sift-min-scale", type=float, default=0.5)
+    ap.add_argument("--sift-octaves", type=int, default=4)
+    ap.add_argument("--sift-scales", type=int, default=8)
+    ap.add_argument("--sift-contrast", type=float, default=0.1)
+    ap.add_argument("--sift-field", default="z", choices=["x", "y", "z", "curvature"])
     ap.add_argument("--seed", type=int, default=0, help="of the baselines' random picks")
     ap.add_argument("--frames", type=int, default=4)
     ap.add_argument("--n", type=int, default=16384)
@@ -49,7 +54,13 @@ def main():
     pc, sn = torch.from_numpy(clouds).to(dev), torch.from_numpy(normals).to(dev)
     os.makedirs(args.out, exist_ok=True)
     if args.method != "tsf":
-        if args.method in ("iss", "harris"):
+        if args.method == "sift":                                       # its keypoints are voxel-cell centroids
+            detect = baselines.SiftDetector(args.top, True, args.seed, args.sift_min_scale, args.sift_octaves, args.sift_scales,
+                                            args.sift_contrast, "z" if args.sift_field == "curvature" else args.sift_field)
+            kp, count = detect(pc, None, range(args.frames),
+                               field=sn[:, 3].contiguous() if args.sift_field == "curvature" else None)
+            found = detect.last[1].sum(1).tolist()
+        elif args.method in ("iss", "harris"):
             detect = baselines.IssDetector(args.top, True, args.seed, args.salient_radius, args.non_max_radius,
                                            args.gamma_21, args.gamma_32, args.min_neighbors) if args.method == "iss" else \
                 baselines.HarrisDetector(args.top, True, args.seed, args.harris_radius, args.harris_threshold)

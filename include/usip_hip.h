@@ -1236,6 +1236,65 @@ int usip_harris_normals_f32_cpu(const float* pc, const int32_t* count, int B, in
 int usip_harris_response_f32_cpu(const float* pc, const int32_t* count, const double* normals, int B, int N, double radius,
                                  int method, double* response, int32_t* members, int num_threads);
 
+/* ------------------------------------------------------------------ f-17  baseline keypoints: SIFT3D
+ * The third hand-crafted detector the reference compares its learned one with (evaluation/save_keypoints.py:57-61, 314-325,
+ * method = 'sift': PCLKeypoint.keypointSift(xyz, min_scale 0.5, n_octaves 4, n_scales_per_octave 8, min_contrast 0.1)).  The
+ * PCL binding is not part of the reference and receives nothing but xyz, so the field of the scale space can only be a
+ * function of a coordinate; here it is an axis of the cloud (z by default, PCL's selector for xyz-only clouds) or a float32
+ * scalar per point.  The definition below is this project's own, written from PCL's SIFTKeypoint.  Float64 arithmetic on
+ * float32 inputs, never contracted; every sum in the stated order; csrc/sift_math.h is the arithmetic.  Frames (pc f32
+ * [B][3][N], count i32 [B] or NULL) and the limits (N <= 2^20, B <= 65535) are f-11's.
+ *
+ * Octaves.  base_o = min_scale * 2^o, o < n_octaves <= 8.  Octave 0's cloud is the voxel average of the input at leaf base_0,
+ * octave o's the voxel average of octave o-1's cloud at leaf base_o (keypoints are cell centroids, not cloud points).
+ * usip_sift_voxel_keys_f32: keys i64 [B][N]; cell = floor(v / leaf) per axis in float64 (grid anchored at the origin); key =
+ * (cx + 2^20) << 42 | (cy + 2^20) << 21 | (cz + 2^20); a cell index outside [-2^20, 2^20), a non-finite coordinate or a slot
+ * beyond count[b] gives INT64_MAX, which drops the row.
+ * usip_sift_voxel_average_f32: sorted_keys i64 [B][N] = every frame's keys ascending and order i32 [B][N] = the input index of
+ * each (a STABLE sort: equal keys in ascending input index).  Row c of the output is the c-th distinct key: out_pc f32
+ * [B][3][N] = the float64 sum of its members in that order / their count, cast to float32; out_field f32 [B][N] = that row's
+ * own float32 coordinate `axis` (0, 1, 2) when field is NULL, else the members' float64 mean of field f32 [B][N] cast to
+ * float32; count_out i32 [B] = the distinct keys; rows beyond it are zeros.  No host read.
+ *
+ * Scales.  S = n_scales_per_octave + 3 in 4 .. 11; sigma_s = base_o * 2^((s - 1) / n_scales_per_octave).  sigma2 f64 [S] ON THE
+ * HOST holds sigma_s^2, computed once by the caller and handed to the kernel and the twin alike (positive, finite, ascending).
+ *
+ * A cloud with fewer than 25 points is EMPTY for the three entry points below: everything zero.  Counts only shrink from
+ * octave to octave, so this is PCL's `break` without a host read.
+ * usip_sift_dog_f32: perm i32 [B][N] = the frame's live rows ascending along x (stable), as f-11's.  The members of (i, s):
+ * d2(i, j) < 9 * sigma_s^2 with d2 f-7's sqdist (strict; the point itself is one); w = sift_exp(-((0.5 * d2) / sigma_s^2));
+ * num_s += f_j * w, den_s += w in ascending position of perm; G_s = num_s / den_s; dog f64 [B][S-1][N] = G_{s+1} - G_s at the
+ * cloud's own rows.  sift_exp is csrc/sift_math.h's float64 exponential (range reduction by ln 2, degree-13 Taylor in Horner's
+ * order, ldexp), the same operations on either side.  The walk's radius is the smallest r >= sqrt(9 sigma_{S-1}^2) with r * r
+ * >= 9 sigma_{S-1}^2; tiles_visited i32 [B][ceil(N/256)] or NULL as f-11's.
+ * usip_sift_nearest_f32: idx i32 [B][N][25] = the 25 nearest rows of row i, itself included, ascending (d2, row).
+ * usip_sift_extrema_f32: for s = 1 .. S-3 and v = dog[s][i]: extremal iff |v| >= min_contrast and (v == min_s and v < min_{s-1}
+ * and v < min_{s+1}) or (v == max_s and v > max_{s-1} and v > max_{s+1}), minima and maxima over the 25 rows of idx.  mask u8
+ * [B][N] = extremal at some s; scale_index i32 [B][N] = the lowest such s, 0 when there is none.
+ * USIP_EINVAL: a shape outside the limits, S outside 4 .. 11, a leaf or a sigma2 that is not positive and finite, sigma2 not
+ * ascending, axis outside 0 .. 2, min_contrast not >= 0, a NULL among the required pointers. */
+int usip_sift_voxel_keys_f32(const float* pc, const int32_t* count, int B, int N, double leaf, int64_t* keys, void* stream);
+int usip_sift_voxel_average_f32(const float* pc, const float* field, int axis, const int64_t* sorted_keys, const int32_t* order,
+                                int B, int N, float* out_pc, float* out_field, int32_t* count_out, void* stream);
+int usip_sift_dog_f32(const float* pc, const float* field, const int32_t* count, const int32_t* perm, int B, int N, int S,
+                      const double* sigma2, double* dog, int32_t* tiles_visited, void* stream);
+int usip_sift_nearest_f32(const float* pc, const int32_t* count, const int32_t* perm, int B, int N, int32_t* idx, void* stream);
+int usip_sift_extrema_f32(const double* dog, const int32_t* idx, const int32_t* count, int B, int N, int S, double min_contrast,
+                          uint8_t* mask, int32_t* scale_index, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order.  The voxel average takes the UNSORTED keys and
+ * sorts them itself; the scale space and the 25 nearest offer all live rows of the frame to every query in the frame's own
+ * stable order along x (no perm); num_threads splits the queries (the cells). */
+int usip_sift_voxel_keys_f32_cpu(const float* pc, const int32_t* count, int B, int N, double leaf, int64_t* keys);
+int usip_sift_voxel_average_f32_cpu(const float* pc, const float* field, int axis, const int64_t* keys, int B, int N,
+                                    float* out_pc, float* out_field, int32_t* count_out, int num_threads);
+int usip_sift_dog_f32_cpu(const float* pc, const float* field, const int32_t* count, int B, int N, int S, const double* sigma2,
+                          double* dog, int num_threads);
+/* out[i] = sift_exp(x[i]), i < n: the exponential as either side evaluates it, for measuring it against a libm */
+int usip_sift_exp_f64_cpu(const double* x, long long n, double* out);
+int usip_sift_nearest_f32_cpu(const float* pc, const int32_t* count, int B, int N, int32_t* idx, int num_threads);
+int usip_sift_extrema_f32_cpu(const double* dog, const int32_t* idx, const int32_t* count, int B, int N, int S,
+                              double min_contrast, uint8_t* mask, int32_t* scale_index, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -263,6 +263,20 @@ SIGNATURES = {
     "usip_harris_normals_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _int], _int),
     "usip_harris_response_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _int],
                                      _int),
+    # f-17 baseline keypoints: SIFT3D voxel average, scale space, 25 nearest and extrema (usip_amd/baselines.py)
+    "usip_sift_voxel_keys_f32": ([_f32p, _i32p, _int, _int, _dbl, ctypes.c_void_p, _stream], _int),
+    "usip_sift_voxel_average_f32": ([_f32p, _f32p, _int, ctypes.c_void_p, _i32p, _int, _int, _f32p, _f32p, _i32p, _stream],
+                                    _int),
+    "usip_sift_dog_f32": ([_f32p, _f32p, _i32p, _i32p, _int, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _i32p, _stream],
+                          _int),
+    "usip_sift_nearest_f32": ([_f32p, _i32p, _i32p, _int, _int, _i32p, _stream], _int),
+    "usip_sift_extrema_f32": ([ctypes.c_void_p, _i32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p, _stream], _int),
+    "usip_sift_voxel_keys_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, ctypes.c_void_p], _int),
+    "usip_sift_voxel_average_f32_cpu": ([_f32p, _f32p, _int, ctypes.c_void_p, _int, _int, _f32p, _f32p, _i32p, _int], _int),
+    "usip_sift_dog_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _int], _int),
+    "usip_sift_exp_f64_cpu": ([ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p], _int),
+    "usip_sift_nearest_f32_cpu": ([_f32p, _i32p, _int, _int, _i32p, _int], _int),
+    "usip_sift_extrema_f32_cpu": ([ctypes.c_void_p, _i32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p, _int], _int),
 }
 
 

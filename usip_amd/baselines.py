@@ -4,28 +4,39 @@ evaluation/save_keypoints.py has method = 'tsf' | 'iss' | 'harris' | 'sift' | 'r
 external PCL binding that is not part of the reference.  Here ISS (Intrinsic Shape Signatures, the parameters
 save_keypoints.py:44-50 pins) and Harris3D (save_keypoints.py:52-55: radius 1, threshold 0.001) run as HIP kernels (csrc/iss.hip,
 csrc/harris.hip; the definitions are in include/usip_hip.h, csrc/iss_math.h and csrc/harris_math.h), `random` and the rule that brings every method to the same keypoint count (ensure_keypoint_number,
-save_keypoints.py:219-227, 326-331) are torch plumbing on the device:
+save_keypoints.py:219-227, 326-331) are torch plumbing on the device.  SIFT3D (save_keypoints.py:57-61: min_scale 0.5, 4 octaves,
+8 scales per octave, min_contrast 0.1; csrc/sift.hip, csrc/sift_math.h) runs over a scalar field of the cloud -- the
+binding receives nothing but xyz, so the field is an axis ("z" by default, PCL's selector for xyz-only clouds) or an f32 [B,N]
+tensor of the caller's (curvature, reflectance); its keypoints are voxel-cell centroids, not cloud points:
 
     det = IssDetector(num=512, seed=0)                       # radii 2 / 2, gamma 0.975 / 0.975, min_neighbors 5
     kp, count = det(pc, count=None, frame_ids=[0, 1])        # pc f32 [B,3,N] on the device -> f32 [B,3,512], i32 [B]
     evaluator.add_frame_keypoints(fid, pc, sn, kp, count)    # evaluation.RegistrationEvaluator: score them
     det = HarrisDetector(num=512, seed=0)                    # radius 1, threshold 0.001, response "harris"
+    det = SiftDetector(num=512, seed=0)                      # min_scale 0.5, 4 octaves, 8 scales, min_contrast 0.1, field "z"
 
   iss_saliency       saliency f64 [B,N] and the neighbour counts at the salient radius
   iss_keypoints      (mask u8 [B,N], saliency, neighbours)
   harris_normals     normals f64 [B,3,N] over the radius and the neighbour counts; fewer than min_neighbors: no normal, zeros
   harris_response    (response f64 [B,N], members i32 [B,N], normals f64 [B,3,N]) from estimated or supplied normals
   harris_keypoints   (mask u8 [B,N], response, members, normals): at or above the threshold, no larger response in reach
+  sift_octave        the voxel average of a cloud and its field at a leaf: (cloud f32 [B,3,N], field f32 [B,N], count i32 [B])
+  sift_scale_space   dog f64 [B,S-1,N] of an octave cloud: differences of the Gaussian-smoothed field over S scales
+  sift_keypoints     (candidates f32 [B,3,O*N], mask u8 [B,O*N], scale f64 [B,O*N], octave_count i32 [B,O]) over all octaves
+  select_candidates  SIFT's candidates (and, with ensure, the cloud's points behind them) -> `num` keypoints per frame
   select_keypoints   mask -> exactly `num` keypoints per frame (or at most, with ensure=False)
   random_keypoints   `num` distinct points per frame
-  *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp, csrc/harris_cpu.cpp)
+  *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp, csrc/harris_cpu.cpp,
+                     csrc/sift_cpu.cpp)
 
 The selection is reproducible and free of host synchronisation: one CPU generator per frame, seeded from (seed, frame_id) the
 way prepare._keep_rows seeds its own, draws u in [0, 1) for every point; a live point's key is u when it is a keypoint and
 1 + u otherwise, a dead slot's +inf; the first `num` points in ascending key (ties towards the lower index) are the frame's
 keypoints.  With more than `num` keypoints that is a uniform subset, as the reference draws one; with fewer, every keypoint
 comes first and uniform random cloud points pad.  The padding never repeats a keypoint -- the reference's np.random.choice
-over the whole cloud could.  `random` gives every live point the key u.  SIFT3D is not built.
+over the whole cloud could.  `random` gives every live point the key u.  SIFT's candidates are not cloud points: select_candidates draws u for the O * N
+candidate slots and the N cloud points of a frame from the same generator; a candidate keypoint's key is u, with ensure a live
+cloud point's is 1 + u, everything else +inf.
 """
 import ctypes
 from typing import Optional, Sequence, Tuple
@@ -37,6 +48,7 @@ from . import _lib, ops
 
 ISS_DEFAULTS = dict(salient_radius=2.0, non_max_radius=2.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5)
 HARRIS_DEFAULTS = dict(radius=1.0, threshold=0.001, response="harris", min_neighbors=3)
+SIFT_DEFAULTS = dict(min_scale=0.5, n_octaves=4, n_scales_per_octave=8, min_contrast=0.1, field="z")
 
 
 def _check(salient_radius, non_max_radius, min_neighbors):
@@ -127,6 +139,98 @@ def harris_keypoints(pc, count=None, radius: float = 1.0, threshold: float = 0.0
     return ops.iss_nms(pc, count, perm, kept, radius, 1), res, members, nrm
 
 
+# ------------------------------------------------------------------------------------------------ SIFT3D
+_AXES = {"x": 0, "y": 1, "z": 2}
+
+
+def _check_sift(min_scale, n_octaves, n_scales_per_octave, min_contrast):
+    if not (0.0 < float(min_scale) < float("inf") and float(min_contrast) >= 0.0):
+        raise ValueError("sift: min_scale must be positive and finite and min_contrast at least 0")
+    if not (1 <= int(n_octaves) <= 8 and 1 <= int(n_scales_per_octave) <= 8):
+        raise ValueError("sift: n_octaves and n_scales_per_octave must be in 1..8")
+
+
+def _field(field, shape, like):
+    """-> (axis, None) for "x" | "y" | "z", (0, the tensor / array) for a supplied f32 [B,N] field"""
+    if isinstance(field, str):
+        if field not in _AXES:
+            raise ValueError("sift: field must be one of %s or f32 [B,N], got %r" % (sorted(_AXES), field))
+        return _AXES[field], None
+    if isinstance(like, torch.Tensor):
+        ok = isinstance(field, torch.Tensor) and field.dtype == torch.float32 and field.device == like.device
+    else:
+        ok = isinstance(field, np.ndarray) and field.dtype == np.float32
+    if not ok or tuple(field.shape) != tuple(shape):
+        raise ValueError("sift: a supplied field must be f32 %s beside the cloud" % (tuple(shape),))
+    return 0, field
+
+
+def sift_sigma2(base: float, n_scales_per_octave: int) -> np.ndarray:
+    """sigma_s^2 f64 [S] of the octave with base scale `base`: S = n_scales_per_octave + 3, sigma_s = base * 2^((s - 1) /
+    n_scales_per_octave).  Computed once on the host; the kernel and the twin are handed this array."""
+    k = int(n_scales_per_octave)
+    sigma = np.float64(base) * np.power(np.float64(2.0), (np.arange(k + 3, dtype=np.float64) - 1.0) / np.float64(k))
+    return sigma * sigma
+
+
+def sift_walk_radius(sigma2) -> float:
+    """the scale-space walk's radius: the smallest float64 r >= sqrt(9 sigma_{S-1}^2) with r * r >= 9 sigma_{S-1}^2"""
+    t = np.float64(9.0) * np.float64(sigma2[-1])
+    r = np.sqrt(t)
+    while r * r < t:
+        r = np.nextafter(r, np.inf)
+    return float(r)
+
+
+def sift_octave(pc, field="z", count=None, leaf: float = 0.5):
+    """pc f32 [B,3,N], field "x" | "y" | "z" or f32 [B,N], count i32 [B] -> (cloud f32 [B,3,N], field f32 [B,N], count i32 [B]):
+    one row per occupied cell of the grid of size `leaf` anchored at the origin, in ascending cell key; the row is the cell's
+    centroid, its field the centroid's own coordinate (axis field) or the members' mean.  No host synchronisation."""
+    pc, count = _frames(pc, count)
+    axis, supplied = _field(field, (pc.shape[0], pc.shape[2]), pc)
+    keys = ops.sift_voxel_keys(pc, count, leaf)
+    sorted_keys, order = torch.sort(keys, dim=1, stable=True)
+    return ops.sift_voxel_average(pc, None if supplied is None else supplied.contiguous(), axis, sorted_keys,
+                                  order.to(torch.int32))
+
+
+def sift_scale_space(cloud, field, count, base: float, n_scales_per_octave: int = 8, perm=None, want_visits: bool = False):
+    """An octave cloud (sift_octave's three results) and its base scale -> dog f64 [B,S-1,N][, tiles_visited].  A frame with
+    fewer than 25 points gets zeros."""
+    _check_sift(base, 1, n_scales_per_octave, 0.0)
+    cloud, count = _frames(cloud, count)
+    perm = sort_along_x(cloud, count) if perm is None else perm
+    return ops.sift_dog(cloud, field, count, perm, sift_sigma2(base, n_scales_per_octave), want_visits)
+
+
+def sift_keypoints(pc, count=None, min_scale: float = 0.5, n_octaves: int = 4, n_scales_per_octave: int = 8,
+                   min_contrast: float = 0.1, field="z", want_octaves: bool = False):
+    """-> (candidates f32 [B,3,O*N], mask u8 [B,O*N], scale f64 [B,O*N], octave_count i32 [B,O]): octave o's cloud in slots o *
+    N .. o * N + N, mask where a row is a keypoint, scale = sigma of the lowest scale at which it is extremal (0 elsewhere),
+    octave_count the rows of every octave cloud.  No host synchronisation.  want_octaves: also the per-octave (cloud, field,
+    count, dog, idx, mask, scale_index)."""
+    _check_sift(min_scale, n_octaves, n_scales_per_octave, min_contrast)
+    pc, count = _frames(pc, count)
+    cloud, fld, cnt = pc, field, count
+    clouds, masks, scales, counts, octaves = [], [], [], [], []
+    for o in range(int(n_octaves)):
+        base = float(min_scale) * 2.0 ** o
+        cloud, fld, cnt = sift_octave(cloud, field if isinstance(field, str) else fld, cnt, base)
+        perm = sort_along_x(cloud, cnt)
+        sigma2 = sift_sigma2(base, n_scales_per_octave)
+        dog = ops.sift_dog(cloud, fld, cnt, perm, sigma2)
+        idx = ops.sift_nearest(cloud, cnt, perm)
+        mask, sidx = ops.sift_extrema(dog, idx, cnt, min_contrast)
+        sigma = torch.from_numpy(np.sqrt(sigma2)).to(pc.device, non_blocking=True)
+        clouds.append(cloud)
+        masks.append(mask)
+        scales.append(torch.where(mask.to(torch.bool), sigma[sidx.long()], torch.zeros((), dtype=torch.float64, device=pc.device)))
+        counts.append(cnt)
+        octaves.append((cloud, fld, cnt, dog, idx, mask, sidx))
+    out = (torch.cat(clouds, 2), torch.cat(masks, 1), torch.cat(scales, 1), torch.stack(counts, 1))
+    return out + (octaves,) if want_octaves else out
+
+
 # ------------------------------------------------------------------------------------------------ the selection rule
 def _draws(B: int, N: int, seed: int, frame_ids: Optional[Sequence[int]]) -> torch.Tensor:
     """u f64 [B,N] on the host: frame b's row from a generator seeded by (seed, frame_ids[b])."""
@@ -186,6 +290,51 @@ def random_keypoints(pc, count, num: int, seed: int = 0, frame_ids=None, want_in
     return (kp, cnt, order) if want_index else (kp, cnt)
 
 
+def _select_candidates(pc, count, cand, mask, num, ensure, u):
+    """SIFT's rule on tensors of one device: the slots are the M candidate slots, then the N cloud points."""
+    B, _, N = pc.shape
+    M = cand.shape[2]
+    num = int(num)
+    if num < 1:
+        raise ValueError("num must be at least 1")
+    live = torch.ones((B, N), dtype=torch.bool, device=pc.device) if count is None else \
+        torch.arange(N, device=pc.device).unsqueeze(0) < count.unsqueeze(1)
+    is_kp = mask.to(torch.bool)
+    inf = torch.full((), float("inf"), dtype=torch.float64, device=pc.device)
+    key = torch.cat((torch.where(is_kp, u[:, :M], inf), torch.where(live, u[:, M:] + 1.0, inf) if ensure else
+                     inf.expand(B, N)), 1)
+    if not ensure:                                                      # save_keypoints.py:355-356: the frame's point 0
+        key[:, M] = torch.where(is_kp.any(1), key[:, M], torch.zeros((), dtype=torch.float64, device=pc.device))
+    order = torch.argsort(key, dim=1, stable=True)[:, :num]
+    found = is_kp.sum(1)
+    cnt = torch.clamp(found + live.sum(1), max=num) if ensure else \
+        torch.where(found == 0, torch.ones_like(found), torch.clamp(found, max=num))
+    if order.shape[1] < num:
+        order = torch.cat((order, order[:, :1].expand(-1, num - order.shape[1])), 1)
+    slot = torch.arange(num, device=pc.device).unsqueeze(0)
+    order = torch.where(slot < cnt.unsqueeze(1), order, order[:, :1])  # the slots beyond count hold the first pick
+    kp = torch.gather(torch.cat((cand, pc), 2), 2, order.unsqueeze(1).expand(-1, 3, -1)).contiguous()
+    return kp, cnt.to(torch.int32), order
+
+
+def select_candidates(pc, count, candidates, mask, num: int, ensure: bool = True, seed: int = 0, frame_ids=None,
+                      want_index: bool = False):
+    """pc f32 [B,3,N], count i32 [B] or None, candidates f32 [B,3,M] with mask u8 [B,M] (sift_keypoints' first two results) ->
+    (kp f32 [B,3,num], count i32 [B]).  One CPU generator per frame, seeded as select_keypoints seeds it, draws u for the M
+    candidate slots and then the N cloud points; a candidate keypoint's key is u, with ensure a live cloud point's is 1 + u,
+    everything else +inf; the first `num` in ascending key, ties towards the lower slot.  With ensure every keypoint comes
+    first and uniform random cloud points pad to min(num, keypoints + live points); without, min(num, keypoints) -- the
+    frame's point 0 with count 1 when none was found.  The slots beyond count hold the frame's first pick.  want_index: also
+    the picked slots i64 [B,num] (below M a candidate slot, M + i the cloud's point i)."""
+    pc, count = _frames(pc, count)
+    M = candidates.shape[2]
+    if candidates.shape[:2] != pc.shape[:2] or tuple(mask.shape) != (pc.shape[0], M):
+        raise ValueError("expected candidates f32 [B,3,M] and mask u8 [B,M]")
+    u = _draws(pc.shape[0], M + pc.shape[2], seed, frame_ids).to(pc.device, non_blocking=True)
+    kp, cnt, order = _select_candidates(pc, count, candidates, mask, num, ensure, u)
+    return (kp, cnt, order) if want_index else (kp, cnt)
+
+
 class IssDetector:
     """ISS with its parameters and the keypoint count bundled: __call__(pc, count, frame_ids) -> (kp f32 [B,3,num], count
     i32 [B]); .last holds (mask, saliency, neighbours) of the latest call."""
@@ -217,6 +366,27 @@ class HarrisDetector:
     def __call__(self, pc, count=None, frame_ids=None) -> Tuple[torch.Tensor, torch.Tensor]:
         self.last = harris_keypoints(pc, count, **self.params)
         return select_keypoints(pc, self.last[0], count, self.num, self.ensure, self.seed, frame_ids)
+
+
+class SiftDetector:
+    """SIFT3D with its parameters and the keypoint count bundled: __call__(pc, count, frame_ids) -> (kp f32 [B,3,num], count
+    i32 [B]); .last holds (candidates, mask, scale, octave_count) of the latest call.  field: "x" | "y" | "z"; a call may hand
+    in a scalar of its own for its frames instead, field f32 [B,N]."""
+
+    def __init__(self, num: int = 512, ensure: bool = True, seed: int = 0, min_scale: float = 0.5, n_octaves: int = 4,
+                 n_scales_per_octave: int = 8, min_contrast: float = 0.1, field="z"):
+        _check_sift(min_scale, n_octaves, n_scales_per_octave, min_contrast)
+        if not isinstance(field, str) or field not in _AXES:
+            raise ValueError("sift: field must be one of %s, got %r" % (sorted(_AXES), field))
+        self.num, self.ensure, self.seed = int(num), bool(ensure), int(seed)
+        self.params = dict(min_scale=float(min_scale), n_octaves=int(n_octaves), n_scales_per_octave=int(n_scales_per_octave),
+                           min_contrast=float(min_contrast))
+        self.field = field
+        self.last = None
+
+    def __call__(self, pc, count=None, frame_ids=None, field=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        self.last = sift_keypoints(pc, count, field=self.field if field is None else field, **self.params)
+        return select_candidates(pc, count, self.last[0], self.last[1], self.num, self.ensure, self.seed, frame_ids)
 
 
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
@@ -299,6 +469,103 @@ def harris_keypoints_cpu(pc, count=None, radius: float = 1.0, threshold: float =
     _lib.check(_lib.lib().usip_iss_nms_f32_cpu(_p(a), _p(c), _p(kept), B, N, float(radius), 1, _p(mask), int(num_threads)),
                "usip_iss_nms_f32_cpu")
     return mask, res, members, nrm
+
+
+def sift_exp_cpu(x):
+    """csrc/sift_math.h's float64 exponential, as the kernels and the twin evaluate it"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.zeros_like(a)
+    _lib.check(_lib.lib().usip_sift_exp_f64_cpu(_p(a), a.size, _p(out)), "usip_sift_exp_f64_cpu")
+    return out
+
+
+def sift_octave_cpu(pc, field="z", count=None, leaf: float = 0.5, num_threads: int = 1):
+    """-> (cloud f32 [B,3,N], field f32 [B,N], count i32 [B])"""
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    axis, supplied = _field(field, (B, N), a)
+    supplied = None if supplied is None else np.ascontiguousarray(supplied)
+    keys = np.zeros((B, N), np.int64)
+    _lib.check(_lib.lib().usip_sift_voxel_keys_f32_cpu(_p(a), _p(c), B, N, float(leaf), _p(keys)), "usip_sift_voxel_keys_f32_cpu")
+    cloud, fld, cnt = np.zeros((B, 3, N), np.float32), np.zeros((B, N), np.float32), np.zeros((B,), np.int32)
+    _lib.check(_lib.lib().usip_sift_voxel_average_f32_cpu(_p(a), _p(supplied), axis, _p(keys), B, N, _p(cloud), _p(fld), _p(cnt),
+                                                          int(num_threads)), "usip_sift_voxel_average_f32_cpu")
+    return cloud, fld, cnt
+
+
+def sift_dog_cpu(cloud, field, count, sigma2, num_threads: int = 1):
+    """-> dog f64 [B,S-1,N] from the S values sigma_s^2"""
+    a, c = _frames_np(cloud, count)
+    B, _, N = a.shape
+    f = np.ascontiguousarray(field, dtype=np.float32)
+    s2 = np.ascontiguousarray(sigma2, dtype=np.float64)
+    if f.shape != (B, N) or s2.ndim != 1:
+        raise ValueError("sift: expected field f32 [B,N] and sigma2 f64 [S]")
+    dog = np.zeros((B, max(s2.shape[0] - 1, 1), N), np.float64)
+    _lib.check(_lib.lib().usip_sift_dog_f32_cpu(_p(a), _p(f), _p(c), B, N, s2.shape[0], _p(s2), _p(dog), int(num_threads)),
+               "usip_sift_dog_f32_cpu")
+    return dog
+
+
+def sift_scale_space_cpu(cloud, field, count, base: float, n_scales_per_octave: int = 8, num_threads: int = 1):
+    _check_sift(base, 1, n_scales_per_octave, 0.0)
+    return sift_dog_cpu(cloud, field, count, sift_sigma2(base, n_scales_per_octave), num_threads)
+
+
+def sift_nearest_cpu(cloud, count, num_threads: int = 1):
+    """-> idx i32 [B,N,25]"""
+    a, c = _frames_np(cloud, count)
+    B, _, N = a.shape
+    idx = np.zeros((B, N, ops.SIFT_NEAREST), np.int32)
+    _lib.check(_lib.lib().usip_sift_nearest_f32_cpu(_p(a), _p(c), B, N, _p(idx), int(num_threads)), "usip_sift_nearest_f32_cpu")
+    return idx
+
+
+def sift_extrema_cpu(dog, idx, count, min_contrast: float, num_threads: int = 1):
+    """-> (mask u8 [B,N], scale_index i32 [B,N])"""
+    d = np.ascontiguousarray(dog, dtype=np.float64)
+    B, S1, N = d.shape
+    i = np.ascontiguousarray(idx, dtype=np.int32)
+    c = None if count is None else np.ascontiguousarray(count, dtype=np.int32)
+    if i.shape != (B, N, ops.SIFT_NEAREST):
+        raise ValueError("sift: expected idx i32 [B,N,25]")
+    mask, sidx = np.zeros((B, N), np.uint8), np.zeros((B, N), np.int32)
+    _lib.check(_lib.lib().usip_sift_extrema_f32_cpu(_p(d), _p(i), _p(c), B, N, S1 + 1, float(min_contrast), _p(mask), _p(sidx),
+                                                    int(num_threads)), "usip_sift_extrema_f32_cpu")
+    return mask, sidx
+
+
+def sift_keypoints_cpu(pc, count=None, min_scale: float = 0.5, n_octaves: int = 4, n_scales_per_octave: int = 8,
+                       min_contrast: float = 0.1, field="z", want_octaves: bool = False, num_threads: int = 1):
+    """-> (candidates f32 [B,3,O*N], mask u8 [B,O*N], scale f64 [B,O*N], octave_count i32 [B,O])[, octaves]"""
+    _check_sift(min_scale, n_octaves, n_scales_per_octave, min_contrast)
+    cloud, cnt = _frames_np(pc, count)
+    fld = field
+    clouds, masks, scales, counts, octaves = [], [], [], [], []
+    for o in range(int(n_octaves)):
+        base = float(min_scale) * 2.0 ** o
+        cloud, fld, cnt = sift_octave_cpu(cloud, field if isinstance(field, str) else fld, cnt, base, num_threads)
+        sigma2 = sift_sigma2(base, n_scales_per_octave)
+        dog = sift_dog_cpu(cloud, fld, cnt, sigma2, num_threads)
+        idx = sift_nearest_cpu(cloud, cnt, num_threads)
+        mask, sidx = sift_extrema_cpu(dog, idx, cnt, min_contrast, num_threads)
+        clouds.append(cloud)
+        masks.append(mask)
+        scales.append(np.where(mask != 0, np.sqrt(sigma2)[sidx], 0.0))
+        counts.append(cnt)
+        octaves.append((cloud, fld, cnt, dog, idx, mask, sidx))
+    out = (np.concatenate(clouds, 2), np.concatenate(masks, 1), np.concatenate(scales, 1), np.stack(counts, 1))
+    return out + (octaves,) if want_octaves else out
+
+
+def select_candidates_cpu(pc, count, candidates, mask, num: int, ensure: bool = True, seed: int = 0, frame_ids=None,
+                          want_index: bool = False):
+    a, c = _frames_np(pc, count)
+    cand = np.ascontiguousarray(candidates, dtype=np.float32)
+    u = _draws(a.shape[0], cand.shape[2] + a.shape[2], seed, frame_ids)
+    kp, cnt, order = _select_candidates(torch.from_numpy(a), None if c is None else torch.from_numpy(c), torch.from_numpy(cand),
+                                        torch.from_numpy(np.ascontiguousarray(mask)), num, ensure, u)
+    return (kp.numpy(), cnt.numpy(), order.numpy()) if want_index else (kp.numpy(), cnt.numpy())
 
 
 def _select_cpu(pc, mask, count, num, ensure, seed, frame_ids, want_index):

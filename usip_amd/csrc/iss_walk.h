@@ -1,8 +1,9 @@
 // usip_amd/csrc/iss_walk.h -- the ASCENDING tile walk of the x-sorted baseline detectors: iss_saliency_kernel and
-// iss_nms_kernel (csrc/iss.hip), harris_normals_kernel and harris_response_kernel (csrc/harris.hip).  A workgroup of TILE
-// lanes owns TILE consecutive queries of a frame sorted along x (the caller's permutation), the frame is cut into tiles of
-// TILE rows of that order, and the tiles that can hold a member are walked from low x to high x -- the order of the sums is
-// part of these kernels' contracts, which is why they do not use tile_walk.h's outward walk.  Device only.
+// iss_nms_kernel (csrc/iss.hip), harris_normals_kernel and harris_response_kernel (csrc/harris.hip), sift_dog_kernel
+// (csrc/sift.hip).  A workgroup of TILE lanes owns TILE consecutive queries of a frame sorted along x (the caller's
+// permutation), the frame is cut into tiles of TILE rows of that order, and the tiles that can hold a member are walked from
+// low x to high x -- the order of the sums is part of these kernels' contracts, which is why they do not use tile_walk.h's
+// outward walk.  Device only.
 #pragma once
 #include "common.h"
 #include "bank.h"

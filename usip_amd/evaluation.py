@@ -209,7 +209,7 @@ class RegistrationEvaluator:
         return self.frames[frame_id]
 
     def add_frame_keypoints(self, frame_id, pc, sn, kp, count):
-        """Keypoints from elsewhere (usip_amd.baselines: ISS, Harris3D, random) instead of the detector's: kp f32 [1,3,M'] with M' <=
+        """Keypoints from elsewhere (usip_amd.baselines: ISS, Harris3D, SIFT3D, random) instead of the detector's: kp f32 [1,3,M'] with M' <=
         top, count i32 [1] on the device.  Described and cached exactly as add_frame does."""
         if kp.dim() != 3 or kp.shape[0] != 1 or kp.shape[1] != 3 or not 1 <= kp.shape[2] <= self.top:
             raise ValueError("add_frame_keypoints: expected kp [1,3,M'] with 1 <= M' <= top = %d, got %s"

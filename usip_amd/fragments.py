@@ -772,7 +772,7 @@ class FragmentEvaluator:
         return self._store(fragment_id, kp[0], desc[0], count[0], cloud)
 
     def add_fragment_keypoints(self, fragment_id, pc, sn, kp, count, cloud):
-        """Keypoints from elsewhere (usip_amd.baselines: ISS, Harris3D, random) instead of the detector's: kp f32 [1,3,M'] with M' <=
+        """Keypoints from elsewhere (usip_amd.baselines: ISS, Harris3D, SIFT3D, random) instead of the detector's: kp f32 [1,3,M'] with M' <=
         top, count i32 [1] on the device.  Described and cached exactly as add_fragment does."""
         if kp.dim() != 3 or kp.shape[0] != 1 or kp.shape[1] != 3 or kp.shape[2] < 1:
             raise ValueError("add_fragment_keypoints: expected kp [1,3,M'], got %s" % (tuple(kp.shape),))

@@ -1968,6 +1968,109 @@ def harris_response(pc, count, perm, normals, radius: float, response: str = "ha
     return (res, members, visits) if want_visits else (res, members)
 
 
+# ------------------------------------------------------------------------------------------------ f-17 baseline keypoints: SIFT3D
+SIFT_NEAREST = 25
+
+
+def _need_cloud(pc, count):
+    _need(pc, "pc", torch.float32)
+    if pc.dim() != 3 or pc.shape[1] != 3:
+        raise RuntimeError("sift: expected pc f32 [B,3,N]")
+    B, _, N = pc.shape
+    if not (1 <= N <= 1 << 20 and 1 <= B <= 65535):
+        raise RuntimeError("sift: N must be in 1..2^20 and B in 1..65535 (got B = %d, N = %d)" % (B, N))
+    _need_on(count, "count", torch.int32, (B,), pc.device)
+    return B, N
+
+
+def sift_voxel_keys(pc, count, leaf: float):
+    """f-17: pc f32 [B,3,N], count i32 [B] or None -> keys i64 [B,N]: the cell of every live point at `leaf` (floor(v / leaf) per
+    axis, the grid anchored at the origin), INT64_MAX for a dead slot or a dropped row."""
+    B, N = _need_cloud(pc, count)
+    if not 0.0 < float(leaf) < float("inf"):
+        raise RuntimeError("sift: the leaf must be positive and finite")
+    keys = torch.empty((B, N), dtype=torch.int64, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("sift_voxel_keys", 20.0 * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_sift_voxel_keys_f32(_ptr(pc), _opt_ptr(count), B, N, float(leaf), _ptr(keys), _stream(pc)),
+                   "usip_sift_voxel_keys_f32")
+    return keys
+
+
+def sift_voxel_average(pc, field, axis: int, sorted_keys, order):
+    """f-17: sorted_keys i64 [B,N] ascending per frame, order i32 [B,N] the input index of each (a stable sort), field f32 [B,N]
+    or None (the centroid's coordinate `axis`) -> (cloud f32 [B,3,N], field f32 [B,N], count i32 [B]): one row per distinct
+    key, in key order; zeros behind them."""
+    B, N = _need_cloud(pc, None)
+    _need_on(field, "field", torch.float32, (B, N), pc.device)
+    _need_on(sorted_keys, "sorted_keys", torch.int64, (B, N), pc.device)
+    _need_on(order, "order", torch.int32, (B, N), pc.device)
+    if sorted_keys is None or order is None or int(axis) not in (0, 1, 2):
+        raise RuntimeError("sift: sorted_keys and order are required and axis must be 0, 1 or 2")
+    out = torch.empty((B, 3, N), dtype=torch.float32, device=pc.device)
+    out_field = torch.empty((B, N), dtype=torch.float32, device=pc.device)
+    cnt = torch.empty((B,), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("sift_voxel_average", 32.0 * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_sift_voxel_average_f32(_ptr(pc), _opt_ptr(field), int(axis), _ptr(sorted_keys), _ptr(order),
+                                                          B, N, _ptr(out), _ptr(out_field), _ptr(cnt), _stream(pc)),
+                   "usip_sift_voxel_average_f32")
+    return out, out_field, cnt
+
+
+def _sigma2(sigma2):
+    """the S host float64 values sigma_s^2, as the library reads them"""
+    import numpy as np
+    a = np.ascontiguousarray(sigma2, dtype=np.float64)
+    if a.ndim != 1 or not 4 <= a.shape[0] <= 11:
+        raise RuntimeError("sift: sigma2 must hold S = 4 .. 11 float64 values")
+    return a
+
+
+def sift_dog(pc, field, count, perm, sigma2, want_visits: bool = False):
+    """f-17: the octave cloud pc f32 [B,3,N] with field f32 [B,N], perm i32 [B,N] (its live rows ascending along x, stable),
+    sigma2 the S host float64 values sigma_s^2 -> dog f64 [B,S-1,N]; with want_visits also the 256-point tiles each workgroup
+    walked, i32 [B, ceil(N/256)]."""
+    B, N = _need_frames(pc, count, perm)
+    _need_on(field, "field", torch.float32, (B, N), pc.device)
+    if field is None:
+        raise RuntimeError("sift: field is required")
+    a = _sigma2(sigma2)
+    S = a.shape[0]
+    dog = torch.empty((B, S - 1, N), dtype=torch.float64, device=pc.device)
+    visits = torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=pc.device) if want_visits else None
+    with torch.cuda.device(pc.device), prof.kernel("sift_dog", 16.0 * B * N + 8.0 * B * (S - 1) * N, keyed=True):
+        _lib.check(_lib.lib().usip_sift_dog_f32(_ptr(pc), _ptr(field), _opt_ptr(count), _ptr(perm), B, N, S, a.ctypes.data,
+                                                _ptr(dog), _opt_ptr(visits), _stream(pc)), "usip_sift_dog_f32")
+    return (dog, visits) if want_visits else dog
+
+
+def sift_nearest(pc, count, perm):
+    """f-17: -> idx i32 [B,N,25]: every row's 25 nearest rows of its frame, itself included, ascending (d2, row)."""
+    B, N = _need_frames(pc, count, perm)
+    idx = torch.empty((B, N, SIFT_NEAREST), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("sift_nearest", (16.0 + 4.0 * SIFT_NEAREST) * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_sift_nearest_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), B, N, _ptr(idx), _stream(pc)),
+                   "usip_sift_nearest_f32")
+    return idx
+
+
+def sift_extrema(dog, idx, count, min_contrast: float):
+    """f-17: dog f64 [B,S-1,N], idx i32 [B,N,25] -> (mask u8 [B,N], scale_index i32 [B,N])."""
+    _need(dog, "dog", torch.float64)
+    if dog.dim() != 3 or not 3 <= dog.shape[1] <= 10:
+        raise RuntimeError("sift: expected dog f64 [B,S-1,N] with S in 4..11")
+    B, S1, N = dog.shape
+    _need_on(idx, "idx", torch.int32, (B, N, SIFT_NEAREST), dog.device)
+    _need_on(count, "count", torch.int32, (B,), dog.device)
+    if idx is None or not float(min_contrast) >= 0.0:
+        raise RuntimeError("sift: idx is required and min_contrast must be at least 0")
+    mask = torch.empty((B, N), dtype=torch.uint8, device=dog.device)
+    scale = torch.empty((B, N), dtype=torch.int32, device=dog.device)
+    with torch.cuda.device(dog.device), prof.kernel("sift_extrema", (8.0 * S1 + 4.0) * SIFT_NEAREST * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_sift_extrema_f32(_ptr(dog), _ptr(idx), _opt_ptr(count), B, N, S1 + 1, float(min_contrast),
+                                                    _ptr(mask), _ptr(scale), _stream(dog)), "usip_sift_extrema_f32")
+    return mask, scale
+
+
 # ------------------------------------------------------------------------------------------------ f-12 fast global registration
 FGR_MMAX, FGR_ROWS_MAX = 1024, 3000
 
