@@ -21,13 +21,17 @@ import functools
 import os
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import harris_oracle as ho
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 from usip_amd import baselines as bl
+
+sys.path.insert(0, GOLDEN)
+import make_baseline_walk_golden as golden  # noqa: E402
 
 TOL = 1e-12
 U = 1.1e-16
@@ -266,6 +270,15 @@ def test_bad_arguments_raise():
     with pytest.raises(ValueError):
         bl.HarrisDetector(response="moravec")
     assert bl.HARRIS_DEFAULTS == dict(radius=1.0, threshold=0.001, response="harris", min_neighbors=3)
+
+
+# ---------------------------------------------------------------------------------------------------- the bits pinned at one commit
+@pytest.mark.parametrize("num_threads", [1, 3])
+@pytest.mark.parametrize("name", sorted(golden.CASES))
+def test_twin_equals_the_bits_pinned_before_the_shared_frame_loop(name, num_threads):
+    """tests/golden/make_baseline_walk_golden.py: what this twin computed before csrc/frames_host.h and
+    csrc/ascending_walk.h, every entry =="""
+    golden.check("harris", name, golden.harris_host(name, num_threads), "host twin, %d threads" % num_threads)
 
 
 # ---------------------------------------------------------------------------------------------------- the sanitizer build

@@ -6,11 +6,17 @@ Bars against the oracle, valid where no decision sits on a threshold (both of th
 as a condition on the input): the keypoint index set and the neighbour counts identical; |saliency - oracle| <= 1e-12 *
 trace(C) -- float64 rounding of a few hundred reordered sums (each within 1.1e-16 of the trace per term) and the Jacobi's
 convergence after JACOBI_SWEEPS sweeps (far below that).  Measured on the four slab inputs: at most 2.2e-15 * trace."""
+import sys
+
 import numpy as np
 import pytest
 
 import iss_oracle as io
+from conftest import GOLDEN
 from usip_amd import baselines as bl
+
+sys.path.insert(0, GOLDEN)
+import make_baseline_walk_golden as golden  # noqa: E402
 
 TOL = 1e-12
 
@@ -174,6 +180,15 @@ def test_bad_arguments_raise():
         bl.select_keypoints_cpu(pc, np.zeros((1, 16), np.uint8), None, 0)
     with pytest.raises(ValueError):
         bl.select_keypoints_cpu(pc, np.zeros((1, 16), np.uint8), None, 4, frame_ids=[0, 1])
+
+
+# ---------------------------------------------------------------------------------------------------- the bits pinned at one commit
+@pytest.mark.parametrize("num_threads", [1, 3])
+@pytest.mark.parametrize("name", sorted(golden.CASES))
+def test_twin_equals_the_bits_pinned_before_the_shared_frame_loop(name, num_threads):
+    """tests/golden/make_baseline_walk_golden.py: what this twin computed before csrc/frames_host.h and
+    csrc/ascending_walk.h, every entry =="""
+    golden.check("iss", name, golden.iss_host(name, num_threads), "host twin, %d threads" % num_threads)
 
 
 # ---------------------------------------------------------------------------------------------------- the keypoint count

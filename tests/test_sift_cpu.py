@@ -16,13 +16,17 @@ import functools
 import os
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import sift_oracle as so
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 from usip_amd import baselines as bl
+
+sys.path.insert(0, GOLDEN)
+import make_baseline_walk_golden as golden  # noqa: E402
 
 U = so.U
 SMALL = dict(min_scale=0.5, n_octaves=2, n_scales_per_octave=3, min_contrast=0.02)
@@ -332,6 +336,15 @@ def test_walk_radius_covers_the_widest_scale():
             s2 = bl.sift_sigma2(base, k)
             r = bl.sift_walk_radius(s2)
             assert r * r >= 9.0 * s2[-1] and np.nextafter(r, 0.0) ** 2 < 9.0 * s2[-1] * (1 + 1e-15) and len(s2) == k + 3
+
+
+# ---------------------------------------------------------------------------------------------------- the bits pinned at one commit
+@pytest.mark.parametrize("num_threads", [1, 3])
+@pytest.mark.parametrize("name", sorted(golden.CASES))
+def test_twin_equals_the_bits_pinned_before_the_shared_frame_loop(name, num_threads):
+    """tests/golden/make_baseline_walk_golden.py: what this twin computed before csrc/frames_host.h and
+    csrc/ascending_walk.h, every entry =="""
+    golden.check("sift", name, golden.sift_host(name, num_threads), "host twin, %d threads" % num_threads)
 
 
 # ---------------------------------------------------------------------------------------------------- the selection

@@ -57,6 +57,13 @@ def same_as_twin(pc, count=None, field="z", **par):
     return d
 
 
+@pytest.mark.parametrize("name", sorted(host.golden.CASES))
+def test_device_equals_the_bits_pinned_before_the_shared_walk(name):
+    """tests/golden/make_baseline_walk_golden.py: what the host twin computed before csrc/ascending_walk.h held the kernels'
+    body, every entry ==; on the five-tile case at radius 0.5 also the tiles each workgroup walked (the pruning still prunes)"""
+    host.golden.check("sift", name, host.golden.sift_device(name, DEV), "device")
+
+
 def test_ragged_batch_equals_the_host_twin():
     pc, count = host.ragged_batch()
     out = same_as_twin(pc, count, **host.SMALL)

@@ -245,6 +245,17 @@ def _draws(B: int, N: int, seed: int, frame_ids: Optional[Sequence[int]]) -> tor
     return u
 
 
+def _take(points, order, cnt, num):
+    """The tail of either rule: order i64 [B, <= num] padded to num, the slots beyond cnt hold the first pick -> (points f32
+    [B,3,num] at order, cnt i32 [B], order)."""
+    if order.shape[1] < num:
+        order = torch.cat((order, order[:, :1].expand(-1, num - order.shape[1])), 1)
+    slot = torch.arange(num, device=points.device).unsqueeze(0)
+    order = torch.where(slot < cnt.unsqueeze(1), order, order[:, :1])
+    kp = torch.gather(points, 2, order.unsqueeze(1).expand(-1, 3, -1)).contiguous()
+    return kp, cnt.to(torch.int32), order
+
+
 def _select(pc, mask, count, num, ensure, u):
     """The rule on tensors of one device (the device path and, on host tensors, the twin)."""
     B, _, N = pc.shape
@@ -264,12 +275,7 @@ def _select(pc, mask, count, num, ensure, u):
         none = found == 0                                              # save_keypoints.py:355-356: the frame's point 0
         order = torch.cat((torch.where(none.unsqueeze(1), torch.zeros_like(order[:, :1]), order[:, :1]), order[:, 1:]), 1)
         cnt = torch.where(none, torch.ones_like(found), torch.clamp(found, max=num))
-    if order.shape[1] < num:
-        order = torch.cat((order, order[:, :1].expand(-1, num - order.shape[1])), 1)
-    slot = torch.arange(num, device=pc.device).unsqueeze(0)
-    order = torch.where(slot < cnt.unsqueeze(1), order, order[:, :1])  # the slots beyond count hold the first pick
-    kp = torch.gather(pc, 2, order.unsqueeze(1).expand(-1, 3, -1)).contiguous()
-    return kp, cnt.to(torch.int32), order
+    return _take(pc, order, cnt, num)
 
 
 def select_keypoints(pc, mask, count, num: int, ensure: bool = True, seed: int = 0, frame_ids=None, want_index: bool = False):
@@ -309,12 +315,7 @@ def _select_candidates(pc, count, cand, mask, num, ensure, u):
     found = is_kp.sum(1)
     cnt = torch.clamp(found + live.sum(1), max=num) if ensure else \
         torch.where(found == 0, torch.ones_like(found), torch.clamp(found, max=num))
-    if order.shape[1] < num:
-        order = torch.cat((order, order[:, :1].expand(-1, num - order.shape[1])), 1)
-    slot = torch.arange(num, device=pc.device).unsqueeze(0)
-    order = torch.where(slot < cnt.unsqueeze(1), order, order[:, :1])  # the slots beyond count hold the first pick
-    kp = torch.gather(torch.cat((cand, pc), 2), 2, order.unsqueeze(1).expand(-1, 3, -1)).contiguous()
-    return kp, cnt.to(torch.int32), order
+    return _take(torch.cat((cand, pc), 2), order, cnt, num)
 
 
 def select_candidates(pc, count, candidates, mask, num: int, ensure: bool = True, seed: int = 0, frame_ids=None,

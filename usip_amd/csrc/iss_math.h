@@ -26,6 +26,16 @@ using usip_prep::TILE;
 
 USIP_HD bool member(double d2, double r2) { return d2 < r2; }
 
+// What every entry point of the baseline detectors (ISS, Harris3D, SIFT3D; device and host twin) refuses, and the live points
+// of frame f: the first count[f] of N, clamped
+USIP_HD bool bad_frames(int B, int N) { return B < 1 || B > 65535 || N < 1 || N > NMAX; }
+USIP_HD bool bad_radius(double r) { return !(r > 0.0) || !(r < (double)INFINITY); }
+USIP_HD int live_points(const int32_t* count, int f, int N)
+{
+    const int c = count ? count[f] : N;
+    return c < 0 ? 0 : (c > N ? N : c);
+}
+
 // What one query gathers on its way through the frame at the salient radius: the members and the six sums, in the order
 // the points are offered.
 struct Scatter {

@@ -4,15 +4,8 @@
 // csrc/prepare_math.h has the semantics and the arithmetic, which the host twin (csrc/prepare_cpu.cpp) shares.
 // No launch synchronises.
 //
-//   scan_knn_kernel<K>         a workgroup owns TILE = 256 consecutive queries of the scan SORTED ALONG X (the caller's
-//                              permutation), one lane per query, its K-list (float64 d2, int32 index) in registers.  Database
-//                              tiles of 256 points are staged in LDS as 16-byte rows and walked by every lane at the same
-//                              address (broadcast reads).  The walk starts at the workgroup's own tile and goes outward in
-//                              both directions; a direction ends once the squared x-gap between its next tile and the
-//                              workgroup's query range exceeds the largest K-th distance any lane still holds (a
-//                              workgroup-wide max through LDS).  Every point of a skipped tile has d2 >= fl(gap * gap) > that
-//                              K-th distance for every lane (float64 rounding is monotone), so it could not have entered
-//                              any list: the result is the all-pairs answer, ties on ORIGINAL indices included.
+//   scan_knn_kernel<K>         csrc/knn_walk.h's outward walk over the scan's float4 rows: a point is not its own
+//                              neighbour, four rows in flight; idx i32 [n][K], tiles_visited i32 [tiles].
 //   scan_normals_kernel        one lane per point: gathers its K neighbours, covariance, 3x3 Jacobi, flip -- in registers.
 //   scan_voxel_keys_kernel     one lane per point: the int64 key of its cell.
 //   scan_voxel_average_kernel  one lane per occupied cell: its members in ascending original index, float64 sums in that
@@ -20,16 +13,22 @@
 #include "common.h"
 #include "bank.h"
 #include "prepare_math.h"
-#include "tile_walk.h"
+#include "knn_walk.h"
 
 using namespace usip_prep;
 using usip_bank::safe_index;
-using usip_walk::block_minmax;
-using usip_walk::Tiles;
-
-static_assert(usip_prep::TILE == usip_walk::WALK_TILE, "scan_knn_kernel walks tile_walk.h's tiles");
+using usip_walk::nearest_rows;
 
 namespace {
+
+// the scan as knn_walk.h reads it
+struct ScanRows {
+    const float4* pts;
+    const int32_t* perm;
+    int n;
+    __device__ __forceinline__ int at(int s) const { return safe_index(perm[s], n); }
+    __device__ __forceinline__ float4 row(int j) const { return pts[j]; }
+};
 
 template <int K>
 __global__ __launch_bounds__(TILE) void scan_knn_kernel(const float4* __restrict__ pts, const int32_t* __restrict__ perm,
@@ -38,87 +37,8 @@ __global__ __launch_bounds__(TILE) void scan_knn_kernel(const float4* __restrict
     __shared__ float4 tile[2][TILE];
     __shared__ int32_t orig[2][TILE];
     __shared__ double slots[4];
-    const int l = threadIdx.x, b = blockIdx.x;
-    const int q = b * TILE + l;                                        // position in the sorted order
-    const bool live = q < n;
-    const int me = safe_index(perm[live ? q : n - 1], n);
-    const float4 p = pts[me];
-    const double xi = (double)p.x, yi = (double)p.y, zi = (double)p.z;
-    const auto x_at = [&](int s) { return (double)pts[safe_index(perm[s], n)].x; };
-    const Tiles<decltype(x_at)> tiles(n, x_at);
-    const double xlo = tiles.near_x(1, b), xhi = tiles.near_x(0, b);   // the x range of this workgroup's queries
-
-    KList<K> list;
-    list.clear();
-
-    auto stage = [&](int slot, int t) {                                // tile t of the sorted order -> LDS
-        const int s = t * TILE + l;
-        const int j = safe_index(perm[s < n ? s : n - 1], n);
-        tile[slot][l] = pts[j];
-        orig[slot][l] = j;
-    };
-    auto offer = [&](double d, int slot, int c) {
-        if (d <= list.worst()) {                                       // rare after the first tiles
-            const int32_t j = orig[slot][c];
-            if (j != me && list.admits(d, j)) list.insert(d, j);
-        }
-    };
-    auto walk = [&](int slot, int t, int count) {
-        int c = 0;
-        for (; c + 4 <= count; c += 4) {                               // four rows in flight: the LDS latency overlaps
-            const float4 o0 = tile[slot][c], o1 = tile[slot][c + 1], o2 = tile[slot][c + 2], o3 = tile[slot][c + 3];
-            const double d0 = sqdist(xi, yi, zi, o0.x, o0.y, o0.z), d1 = sqdist(xi, yi, zi, o1.x, o1.y, o1.z);
-            const double d2 = sqdist(xi, yi, zi, o2.x, o2.y, o2.z), d3 = sqdist(xi, yi, zi, o3.x, o3.y, o3.z);
-            const double lo01 = d0 < d1 ? d0 : d1, lo23 = d2 < d3 ? d2 : d3;
-            if ((lo01 < lo23 ? lo01 : lo23) <= list.worst()) {
-                offer(d0, slot, c);
-                offer(d1, slot, c + 1);
-                offer(d2, slot, c + 2);
-                offer(d3, slot, c + 3);
-            }
-        }
-        for (; c < count; ++c) {
-            const float4 o = tile[slot][c];
-            offer(sqdist(xi, yi, zi, o.x, o.y, o.z), slot, c);
-        }
-    };
-
-    stage(0, b);
-    __syncthreads();
-    if (live) walk(0, b, tiles.rows(b));
-    int left = b - 1, right = b + 1, seen = 1;
-    while (true) {
-        double unused = 0.0, bound = live ? list.worst() : -1.0;
-        __syncthreads();                                               // the previous round's reads are done
-        block_minmax<false, true>(unused, bound, slots);               // (also: every lane is done with the tiles)
-        if (left >= 0) {
-            const double gap = xlo - tiles.near_x(0, left);
-            if (gap * gap > bound) left = -1;
-        }
-        if (right < tiles.tiles) {
-            const double gap = tiles.near_x(1, right) - xhi;
-            if (gap * gap > bound) right = tiles.tiles;
-        }
-        if (left < 0 && right >= tiles.tiles) break;                   // workgroup-uniform
-        if (left >= 0) stage(0, left);
-        if (right < tiles.tiles) stage(1, right);
-        __syncthreads();
-        if (left >= 0) {
-            if (live) walk(0, left, tiles.rows(left));
-            --left;
-            ++seen;
-        }
-        if (right < tiles.tiles) {
-            if (live) walk(1, right, tiles.rows(right));
-            ++right;
-            ++seen;
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) idx[(long long)me * K + k] = list.j[k];
-    }
-    if (visited && l == 0) visited[b] = seen;
+    const int seen = nearest_rows<K, false, true>(ScanRows{pts, perm, n}, blockIdx.x, tile, orig, slots, idx);
+    if (visited && threadIdx.x == 0) visited[blockIdx.x] = seen;
 }
 
 __global__ __launch_bounds__(256) void scan_normals_kernel(const float4* __restrict__ pts, const int32_t* __restrict__ idx,

@@ -13,30 +13,26 @@
 //                              the heads of its own tile get their rank by ballot; a head's lane sums its cell in order and
 //                              writes row (heads before it).  Position s >= heads of the frame zeroes row s.  count_out[f] =
 //                              heads of the frame.
-//   sift_dog_kernel<S>         iss_walk.h's ascending walk at a radius r with r * r >= 9 sigma_{S-1}^2, so a skipped tile
+//   sift_dog_kernel<S>         ascending_walk.h's kernel at a radius r with r * r >= 9 sigma_{S-1}^2, so a skipped tile
 //                              holds no member of any scale and the sums are the all-pairs sums in the all-pairs order; the
 //                              field rides in the float4 row's fourth component; 2 S sums in registers; dog f64 [B][S-1][N]
 //                              at the cloud's own rows.
-//   sift_nearest_kernel        scan_knn_kernel's outward walk (csrc/prepare.hip, the same exactness argument: a side ends
-//                              once the squared x-gap to its next tile exceeds the largest 25th distance a lane holds), per
-//                              frame, the point itself included; KList<25> in registers; idx i32 [B][N][25].
+//   sift_nearest_kernel        csrc/knn_walk.h's outward walk per frame, the point itself included, one row at a time (a
+//                              frame may hold non-finite rows); KList<25> in registers; idx i32 [B][N][25].
 //   sift_extrema_kernel<S>     one lane per point: gathers dog at its 25 rows, minima and maxima per scale in registers;
 //                              mask u8 [B][N], scale_index i32 [B][N].
 // A frame with fewer than 25 points is empty for the last three.  Slots beyond count[b] get zeros.  An entry of perm or idx
 // outside [0, count) reads row 0: a wrong permutation gives wrong values, never a wild read.
-#include "iss_walk.h"
+#include "ascending_walk.h"
 #include "sift_math.h"
-#include "tile_walk.h"
+#include "knn_walk.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_sift;
 using usip_bank::safe_index;
-using usip_iss::Frame;
-using usip_iss::walk_tiles;
-using usip_prep::KList;
-using usip_prep::sqdist;
-using usip_walk::block_minmax;
-using usip_walk::Tiles;
+using usip_ascend::ascend;
+using usip_ascend::Frame;
+using usip_walk::nearest_rows;
 
 namespace {
 
@@ -112,46 +108,36 @@ __global__ __launch_bounds__(TILE) void sift_voxel_average_kernel(const float* _
 }
 
 template <int S>
+struct DogPass : usip_ascend::Plain {
+    static constexpr int ROWS = 1;
+    const Scales& sc;
+    const float* fl;
+    double* out;
+    int N;
+    ScaleSums<S> g;
+    USIP_DEV float stage(int, int, int j) const { return fl[j]; }      // the field rides in the row's fourth component
+    USIP_DEV void offer(double xi, double yi, double zi, float4 o, Side) { g.offer(xi, yi, zi, o.x, o.y, o.z, o.w, sc); }
+    USIP_DEV void dead(int q) const
+    {
+#pragma unroll
+        for (int s = 0; s + 1 < S; ++s) out[(long long)s * N + q] = 0.0;
+    }
+    USIP_DEV void write(int me, double, double, double) const { g.dog(out + me, N); }
+};
+
+template <int S>
 __global__ __launch_bounds__(TILE) void sift_dog_kernel(const float* __restrict__ pc, const float* __restrict__ field,
                                                         const int32_t* __restrict__ count, const int32_t* __restrict__ perm,
                                                         int N, Scales sc, double r, double* __restrict__ dog,
                                                         int32_t* __restrict__ visited)
 {
     __shared__ float4 tile[2][TILE];
-    const int l = threadIdx.x, w = blockIdx.x, f = blockIdx.y;
+    const int f = blockIdx.y;
     Frame F(pc, count, perm, N, f);
     F.n = F.n < MIN_POINTS ? 0 : F.n;
-    const float* fl = field + (long long)f * N;
-    const int q = w * TILE + l;
-    double* out = dog + (long long)f * (S - 1) * N;
-    if (q >= F.n && q < N) {
-#pragma unroll
-        for (int s = 0; s + 1 < S; ++s) out[(long long)s * N + q] = 0.0;
-    }
-    if (w * TILE >= F.n) {
-        if (visited && l == 0) visited[(long long)f * gridDim.x + w] = 0;
-        return;
-    }
-    const bool live = q < F.n;
-    const int me = F.at(q);
-    const double xi = (double)F.x[me], yi = (double)F.y[me], zi = (double)F.z[me];
-    ScaleSums<S> g;
-    g.clear();
-    const int seen = walk_tiles(
-        F, w, r, live,
-        [&](int slot, int t) {
-            const int j = F.at(t * TILE + l);
-            tile[slot][l] = make_float4(F.x[j], F.y[j], F.z[j], fl[j]);
-        },
-        [&](int slot) { return (double)tile[slot][0].x; },
-        [&](int slot, int rows) {
-            for (int c = 0; c < rows; ++c) {
-                const float4 o = tile[slot][c];
-                g.offer(xi, yi, zi, o.x, o.y, o.z, o.w, sc);
-            }
-        });
-    if (live) g.dog(out + me, N);
-    if (visited && l == 0) visited[(long long)f * gridDim.x + w] = seen;
+    DogPass<S> pass{{}, sc, field + (long long)f * N, dog + (long long)f * (S - 1) * N, N};
+    pass.g.clear();
+    ascend(F, N, r, tile, visited, pass);
 }
 
 __global__ __launch_bounds__(TILE) void sift_nearest_kernel(const float* __restrict__ pc, const int32_t* __restrict__ count,
@@ -170,66 +156,7 @@ __global__ __launch_bounds__(TILE) void sift_nearest_kernel(const float* __restr
         for (int k = 0; k < NEAREST; ++k) out[(long long)q * NEAREST + k] = 0;
     }
     if (b * TILE >= F.n) return;                                       // workgroup-uniform: no query here
-    const int n = F.n;
-    const bool live = q < n;
-    const int me = F.at(q);
-    const double xi = (double)F.x[me], yi = (double)F.y[me], zi = (double)F.z[me];
-    const auto x_at = [&](int s) { return F.xs(s); };
-    const Tiles<decltype(x_at)> tiles(n, x_at);
-    const double xlo = tiles.near_x(1, b), xhi = tiles.near_x(0, b);   // the x range of this workgroup's queries
-
-    KList<NEAREST> list;
-    list.clear();
-
-    auto stage = [&](int slot, int t) {                                // tile t of the sorted order -> LDS
-        const int j = F.at(t * TILE + l);
-        tile[slot][l] = make_float4(F.x[j], F.y[j], F.z[j], 0.0f);
-        orig[slot][l] = j;
-    };
-    auto walk = [&](int slot, int rows) {
-        for (int c = 0; c < rows; ++c) {
-            const float4 o = tile[slot][c];
-            const double d = sqdist(xi, yi, zi, o.x, o.y, o.z);
-            if (d <= list.worst()) {                                   // rare after the first tiles
-                const int32_t j = orig[slot][c];
-                if (list.admits(d, j)) list.insert(d, j);
-            }
-        }
-    };
-
-    stage(0, b);
-    __syncthreads();
-    if (live) walk(0, tiles.rows(b));
-    int left = b - 1, right = b + 1;
-    while (true) {
-        double unused = 0.0, bound = live ? list.worst() : -1.0;
-        __syncthreads();                                               // the previous round's reads are done
-        block_minmax<false, true>(unused, bound, slots);
-        if (left >= 0) {
-            const double gap = xlo - tiles.near_x(0, left);
-            if (gap * gap > bound) left = -1;
-        }
-        if (right < tiles.tiles) {
-            const double gap = tiles.near_x(1, right) - xhi;
-            if (gap * gap > bound) right = tiles.tiles;
-        }
-        if (left < 0 && right >= tiles.tiles) break;                   // workgroup-uniform
-        if (left >= 0) stage(0, left);
-        if (right < tiles.tiles) stage(1, right);
-        __syncthreads();
-        if (left >= 0) {
-            if (live) walk(0, tiles.rows(left));
-            --left;
-        }
-        if (right < tiles.tiles) {
-            if (live) walk(1, tiles.rows(right));
-            ++right;
-        }
-    }
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < NEAREST; ++k) out[(long long)me * NEAREST + k] = list.j[k];
-    }
+    nearest_rows<NEAREST, true, false>(F, b, tile, orig, slots, out);
 }
 
 template <int S>

@@ -6,35 +6,28 @@
 #include <algorithm>
 #include <cmath>
 #include <vector>
-#include "host_split.h"
+#include "frames_host.h"
 #include "bank.h"
 #include "sift_math.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_sift;
+using usip_host::for_each_query;
 using usip_host::split;
 
 namespace {
 
-// order[0 .. n): the frame's live points ascending along x, ties towards the lower index
-void sort_along_x(const float* x, int n, std::vector<int32_t>& order)
-{
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.begin() + n, [&](int32_t a, int32_t b) { return x[a] < x[b]; });
-}
-
+// sf: the field in the frame's sorted order
 template <int S>
-void dog_frame(const float* x, const float* y, const float* z, const float* sx, const float* sy, const float* sz,
-               const float* sf, int n, int N, const Scales& sc, double* out, int num_threads)
+void dog_frame(const float* x, const float* y, const float* z, const usip_host::SortedFrame& F, const float* sf, int N,
+               const Scales& sc, double* out, int num_threads)
 {
-    split(n, num_threads, [=, &sc](long long lo, long long hi) {
-        for (long long i = lo; i < hi; ++i) {
-            const double xi = (double)x[i], yi = (double)y[i], zi = (double)z[i];
-            ScaleSums<S> g;
-            g.clear();
-            for (int s = 0; s < n; ++s) g.offer(xi, yi, zi, sx[s], sy[s], sz[s], sf[s], sc);
-            g.dog(out + i, N);
-        }
+    for_each_query(F.n, num_threads, [=, &F, &sc](int i) {
+        const double xi = (double)x[i], yi = (double)y[i], zi = (double)z[i];
+        ScaleSums<S> g;
+        g.clear();
+        for (int s = 0; s < F.n; ++s) g.offer(xi, yi, zi, F.x[s], F.y[s], F.z[s], sf[s], sc);
+        g.dog(out + i, N);
     });
 }
 
@@ -106,18 +99,17 @@ extern "C" int usip_sift_dog_f32_cpu(const float* pc, const float* field, const 
 {
     if (bad_frames(B, N) || !good_scales(sigma2, S) || !pc || !field || !dog) return USIP_EINVAL;
     const Scales sc = make_scales(sigma2, S);
-    std::vector<float> sorted(4 * (size_t)N);
-    std::vector<int32_t> order(N);
+    usip_host::SortedFrame F(N);
+    std::vector<float> sf(N);
     for (int f = 0; f < B; ++f) {
-        const float *x = pc + 3LL * f * N, *y = x + N, *z = y + N, *fl = field + (long long)f * N;
+        const float *x = pc + 3LL * f * N, *y = x + N, *z = y + N;
         double* out = dog + (long long)f * (S - 1) * N;
         const int n = octave_points(count, f, N);
         for (int s = 0; s + 1 < S; ++s)
             for (int i = n; i < N; ++i) out[(long long)s * N + i] = 0.0;
-        sort_along_x(x, n, order);
-        float *sx = sorted.data(), *sy = sx + N, *sz = sy + N, *sf = sz + N;
-        for (int s = 0; s < n; ++s) { const int j = order[s]; sx[s] = x[j]; sy[s] = y[j]; sz[s] = z[j]; sf[s] = fl[j]; }
-#define USIP_SIFT_DOG(s) dog_frame<s>(x, y, z, sx, sy, sz, sf, n, N, sc, out, num_threads)
+        F.sort(x, y, z, n);
+        F.gather(field + (long long)f * N, sf.data());
+#define USIP_SIFT_DOG(s) dog_frame<s>(x, y, z, F, sf.data(), N, sc, out, num_threads)
         USIP_SIFT_DISPATCH(S, USIP_SIFT_DOG)
 #undef USIP_SIFT_DOG
     }
@@ -134,28 +126,22 @@ extern "C" int usip_sift_exp_f64_cpu(const double* x, long long n, double* out)
 extern "C" int usip_sift_nearest_f32_cpu(const float* pc, const int32_t* count, int B, int N, int32_t* idx, int num_threads)
 {
     if (bad_frames(B, N) || !pc || !idx) return USIP_EINVAL;
-    std::vector<float> sorted(3 * (size_t)N);
-    std::vector<int32_t> order(N);
+    usip_host::SortedFrame F(N);
     for (int f = 0; f < B; ++f) {
         const float *x = pc + 3LL * f * N, *y = x + N, *z = y + N;
         int32_t* out = idx + (long long)f * N * NEAREST;
         const int n = octave_points(count, f, N);
         for (long long i = (long long)n * NEAREST; i < (long long)N * NEAREST; ++i) out[i] = 0;
-        sort_along_x(x, n, order);
-        float *sx = sorted.data(), *sy = sx + N, *sz = sy + N;
-        for (int s = 0; s < n; ++s) { const int j = order[s]; sx[s] = x[j]; sy[s] = y[j]; sz[s] = z[j]; }
-        const int32_t* ord = order.data();
-        split(n, num_threads, [=](long long lo, long long hi) {
-            for (long long i = lo; i < hi; ++i) {
-                const double xi = (double)x[i], yi = (double)y[i], zi = (double)z[i];
-                usip_prep::KList<NEAREST> list;
-                list.clear();
-                for (int s = 0; s < n; ++s) {
-                    const double d = usip_prep::sqdist(xi, yi, zi, sx[s], sy[s], sz[s]);
-                    if (list.admits(d, ord[s])) list.insert(d, ord[s]);
-                }
-                for (int k = 0; k < NEAREST; ++k) out[i * NEAREST + k] = list.j[k];
+        F.sort(x, y, z, n);
+        for_each_query(n, num_threads, [=, &F](int i) {
+            const double xi = (double)x[i], yi = (double)y[i], zi = (double)z[i];
+            usip_prep::KList<NEAREST> list;
+            list.clear();
+            for (int s = 0; s < n; ++s) {
+                const double d = usip_prep::sqdist(xi, yi, zi, F.x[s], F.y[s], F.z[s]);
+                if (list.admits(d, F.order[s])) list.insert(d, F.order[s]);
             }
+            for (int k = 0; k < NEAREST; ++k) out[(long long)i * NEAREST + k] = list.j[k];
         });
     }
     return USIP_OK;

@@ -1,6 +1,7 @@
 // usip_amd/csrc/sift_math.h -- the arithmetic of the SIFT3D baseline detector, shared by the kernels of
 // csrc/sift.hip and the host twin of csrc/sift_cpu.cpp: both sides run the same float64 operations in the same order on the
-// float32 points of a frame, so their results are equal bit for bit.  It sits over prepare_math.h (sqdist, KList).
+// float32 points of a frame, so their results are equal bit for bit.  It sits over prepare_math.h (sqdist, KList) and
+// iss_math.h (bad_frames, live_points).
 //
 // Reference semantics: evaluation/save_keypoints.py:57-61, 314-325 asks an external PCL binding (PCLKeypoint.keypointSift)
 // for SIFT keypoints of the xyz columns with min_scale 0.5, n_octaves 4, n_scales_per_octave 8, min_contrast 0.1.  Neither
@@ -24,10 +25,11 @@
 //                  DoG_s[i] is extremal iff |v| >= min_contrast and (v == min_s and v < min_{s-1} and v < min_{s+1}) or the
 //                  same with maxima and >.  A keypoint iff extremal at some s; scale_index = the lowest such s (0: none)
 #pragma once
-#include "prepare_math.h"
+#include "iss_math.h"
 
 namespace usip_sift {
 
+using usip_iss::bad_frames;
 using usip_prep::NMAX;
 using usip_prep::TILE;
 
@@ -203,12 +205,9 @@ struct Extrema {
 // the live points of frame f as the three stages behind the voxel average see them
 USIP_HD int octave_points(const int32_t* count, int f, int N)
 {
-    const int c = count ? count[f] : N;
-    const int n = c < 0 ? 0 : (c > N ? N : c);
+    const int n = usip_iss::live_points(count, f, N);
     return n < MIN_POINTS ? 0 : n;
 }
-
-USIP_HD bool bad_frames(int B, int N) { return B < 1 || B > 65535 || N < 1 || N > NMAX; }
 
 // S -> the instantiation for it
 #define USIP_SIFT_DISPATCH(S, CALL)                                                      \

@@ -1,14 +1,14 @@
 // usip_amd/csrc/tile_walk.h -- the outward tile walk of the x-sorted neighbour searches: overlap_kernel<XQ>
 // (csrc/fragments.hip, existence within a radius), icp_nearest_kernel (csrc/icp.hip, the exact nearest row) and
-// scan_knn_kernel<K> (csrc/prepare.hip, the K nearest within one cloud; csrc/sift.hip's sift_nearest_kernel is its batched
-// form over Tiles and block_minmax).  A workgroup of 256 lanes owns 256 queries; the database, sorted along x, is cut into
+// csrc/knn_walk.h's nearest_rows (the K nearest within one cloud: scan_knn_kernel<K> of csrc/prepare.hip and sift_nearest_kernel
+// of csrc/sift.hip, over Tiles and block_minmax).  A workgroup of 256 lanes owns 256 queries; the database, sorted along x, is cut into
 // tiles of 256 rows; two of them are staged in LDS per round, one to either side of the start tile, every lane walks both at
 // the same LDS address, and a side ends once the x-gap to its next tile alone rules that tile out.  What a tile holds in LDS,
 // the per-row test and the rule that ends a side are the kernel's own (its stage, visit and prune); the order of the rounds,
 // the start tile, the x at a tile's near edge with the partial last tile clamped, and the workgroup's smallest / largest x
 // are here.  Device only.
-// csrc/iss_walk.h's walk_tiles (csrc/iss.hip, csrc/harris.hip, csrc/sift.hip's scale space) is not one of these: it walks
-// ascending because the order of its sums is part of those kernels' contracts.
+// csrc/ascending_walk.h's walk_tiles (csrc/iss.hip, csrc/harris.hip, csrc/sift.hip's scale space) is not one of these: it
+// walks ascending because the order of its sums is part of those kernels' contracts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,9 +67,9 @@ struct Tiles {
 // Rounds until both sides have ended (left < 0, right >= tiles).  prune(left, right) -> END_LEFT | END_RIGHT, workgroup-
 // uniform, holds the kernel's barriers and may end either side or both; stage(side, t) writes tile t into LDS slot `side`; one
 // barrier; visit(side, t, rows of tile t) runs per lane; then both sides step outward.
-// scan_knn_kernel<K> writes these same rounds out in its own body, over Tiles and block_minmax: its K-list of 3 K registers
-// is live across the whole walk, and with the rounds behind this function's boundary hipcc (ROCm 7.2) allocates 144 VGPRs
-// at K = 16 where the loop in place takes 127 of the 128 that four waves per SIMD allow (tests/test_prepare_isa.py).
+// csrc/knn_walk.h's nearest_rows writes these same rounds out in its own body, over Tiles and block_minmax: its K-list of 3 K
+// registers is live across the whole walk, and with the rounds behind this function's boundary hipcc (ROCm 7.2) allocates 144
+// VGPRs at K = 16 where the loop in place takes 126 of the 128 that four waves per SIMD allow (tests/test_prepare_isa.py).
 constexpr int END_LEFT = 1, END_RIGHT = 2;
 
 template <class XAt, class Prune, class Stage, class Visit>

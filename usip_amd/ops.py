@@ -1883,18 +1883,23 @@ def overlap_ratio(rows, offsets, frag1, frag2, Rt, perm1, perm2, radius: float):
 
 
 # ------------------------------------------------------------------------------------------------ f-11 baseline keypoints
-def _need_frames(pc, count, perm):
+def _need_frames(pc, count, perm=None, tag="iss"):
+    """pc f32 [B,3,N] with count i32 [B] or None and, where the kernel walks a sorted frame, perm i32 [B,N] (a missing one is
+    the library's to refuse) -> (B, N)"""
     _need(pc, "pc", torch.float32)
     if pc.dim() != 3 or pc.shape[1] != 3:
-        raise RuntimeError("iss: expected pc f32 [B,3,N]")
+        raise RuntimeError("%s: expected pc f32 [B,3,N]" % tag)
     B, _, N = pc.shape
     if not (1 <= N <= 1 << 20 and 1 <= B <= 65535):
-        raise RuntimeError("iss: N must be in 1..2^20 and B in 1..65535 (got B = %d, N = %d)" % (B, N))
+        raise RuntimeError("%s: N must be in 1..2^20 and B in 1..65535 (got B = %d, N = %d)" % (tag, B, N))
     _need_on(count, "count", torch.int32, (B,), pc.device)
     _need_on(perm, "perm", torch.int32, (B, N), pc.device)
-    if perm is None:
-        raise RuntimeError("iss: perm is required")
     return B, N
+
+
+def _visits(B, N, device, want):
+    """tiles_visited i32 [B, ceil(N/256)] for a kernel to fill, or None"""
+    return torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=device) if want else None
 
 
 def iss_saliency(pc, count, perm, salient_radius: float, gamma_21: float, gamma_32: float, min_neighbors: int,
@@ -1907,9 +1912,9 @@ def iss_saliency(pc, count, perm, salient_radius: float, gamma_21: float, gamma_
         raise RuntimeError("iss: salient_radius must be positive and min_neighbors at least 1")
     sal = torch.empty((B, N), dtype=torch.float64, device=pc.device)
     nb = torch.empty((B, N), dtype=torch.int32, device=pc.device)
-    visits = torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=pc.device) if want_visits else None
+    visits = _visits(B, N, pc.device, want_visits)
     with torch.cuda.device(pc.device), prof.kernel("iss_saliency", 28.0 * B * N, keyed=True):
-        _lib.check(_lib.lib().usip_iss_saliency_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), B, N, float(salient_radius),
+        _lib.check(_lib.lib().usip_iss_saliency_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), B, N, float(salient_radius),
                                                     float(gamma_21), float(gamma_32), int(min_neighbors), _ptr(sal),
                                                     _ptr(nb), _opt_ptr(visits), _stream(pc)), "usip_iss_saliency_f32")
     return (sal, nb, visits) if want_visits else (sal, nb)
@@ -1923,7 +1928,7 @@ def iss_nms(pc, count, perm, saliency, non_max_radius: float, min_neighbors: int
         raise RuntimeError("iss: saliency is required, non_max_radius must be positive and min_neighbors at least 1")
     kp = torch.empty((B, N), dtype=torch.uint8, device=pc.device)
     with torch.cuda.device(pc.device), prof.kernel("iss_nms", 25.0 * B * N, keyed=True):
-        _lib.check(_lib.lib().usip_iss_nms_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), _ptr(saliency), B, N,
+        _lib.check(_lib.lib().usip_iss_nms_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(saliency), B, N,
                                                float(non_max_radius), int(min_neighbors), _ptr(kp), _stream(pc)),
                    "usip_iss_nms_f32")
     return kp
@@ -1937,13 +1942,13 @@ def harris_normals(pc, count, perm, radius: float, min_neighbors: int = 3):
     """f-16: pc f32 [B,3,N], count i32 [B] or None, perm i32 [B,N] (every frame's live points ascending along x, stable)
     -> (normals f64 [B,3,N], neighbours i32 [B,N]); a point with fewer than min_neighbors members within radius has no
     normal: zeros."""
-    B, N = _need_frames(pc, count, perm)
+    B, N = _need_frames(pc, count, perm, "harris")
     if not (float(radius) > 0.0 and int(min_neighbors) >= 1):
         raise RuntimeError("harris: radius must be positive and min_neighbors at least 1")
     normals = torch.empty((B, 3, N), dtype=torch.float64, device=pc.device)
     nb = torch.empty((B, N), dtype=torch.int32, device=pc.device)
     with torch.cuda.device(pc.device), prof.kernel("harris_normals", 40.0 * B * N, keyed=True):
-        _lib.check(_lib.lib().usip_harris_normals_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), B, N, float(radius),
+        _lib.check(_lib.lib().usip_harris_normals_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), B, N, float(radius),
                                                       int(min_neighbors), _ptr(normals), _ptr(nb), _stream(pc)),
                    "usip_harris_normals_f32")
     return normals, nb
@@ -1952,7 +1957,7 @@ def harris_normals(pc, count, perm, radius: float, min_neighbors: int = 3):
 def harris_response(pc, count, perm, normals, radius: float, response: str = "harris", want_visits: bool = False):
     """f-16: normals f64 [B,3,N] (a row that is not finite or all zero: no normal) -> (response f64 [B,N], members i32
     [B,N]); with want_visits also the 256-point tiles each workgroup walked, i32 [B, ceil(N/256)]."""
-    B, N = _need_frames(pc, count, perm)
+    B, N = _need_frames(pc, count, perm, "harris")
     _need_on(normals, "normals", torch.float64, (B, 3, N), pc.device)
     if normals is None or not float(radius) > 0.0:
         raise RuntimeError("harris: normals are required and radius must be positive")
@@ -1960,9 +1965,9 @@ def harris_response(pc, count, perm, normals, radius: float, response: str = "ha
         raise RuntimeError("harris: response must be one of %s, got %r" % (sorted(HARRIS_METHODS), response))
     res = torch.empty((B, N), dtype=torch.float64, device=pc.device)
     members = torch.empty((B, N), dtype=torch.int32, device=pc.device)
-    visits = torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=pc.device) if want_visits else None
+    visits = _visits(B, N, pc.device, want_visits)
     with torch.cuda.device(pc.device), prof.kernel("harris_response", 64.0 * B * N, keyed=True):
-        _lib.check(_lib.lib().usip_harris_response_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), _ptr(normals), B, N,
+        _lib.check(_lib.lib().usip_harris_response_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(normals), B, N,
                                                        float(radius), HARRIS_METHODS[response], _ptr(res), _ptr(members),
                                                        _opt_ptr(visits), _stream(pc)), "usip_harris_response_f32")
     return (res, members, visits) if want_visits else (res, members)
@@ -1972,21 +1977,10 @@ def harris_response(pc, count, perm, normals, radius: float, response: str = "ha
 SIFT_NEAREST = 25
 
 
-def _need_cloud(pc, count):
-    _need(pc, "pc", torch.float32)
-    if pc.dim() != 3 or pc.shape[1] != 3:
-        raise RuntimeError("sift: expected pc f32 [B,3,N]")
-    B, _, N = pc.shape
-    if not (1 <= N <= 1 << 20 and 1 <= B <= 65535):
-        raise RuntimeError("sift: N must be in 1..2^20 and B in 1..65535 (got B = %d, N = %d)" % (B, N))
-    _need_on(count, "count", torch.int32, (B,), pc.device)
-    return B, N
-
-
 def sift_voxel_keys(pc, count, leaf: float):
     """f-17: pc f32 [B,3,N], count i32 [B] or None -> keys i64 [B,N]: the cell of every live point at `leaf` (floor(v / leaf) per
     axis, the grid anchored at the origin), INT64_MAX for a dead slot or a dropped row."""
-    B, N = _need_cloud(pc, count)
+    B, N = _need_frames(pc, count, tag="sift")
     if not 0.0 < float(leaf) < float("inf"):
         raise RuntimeError("sift: the leaf must be positive and finite")
     keys = torch.empty((B, N), dtype=torch.int64, device=pc.device)
@@ -2000,7 +1994,7 @@ def sift_voxel_average(pc, field, axis: int, sorted_keys, order):
     """f-17: sorted_keys i64 [B,N] ascending per frame, order i32 [B,N] the input index of each (a stable sort), field f32 [B,N]
     or None (the centroid's coordinate `axis`) -> (cloud f32 [B,3,N], field f32 [B,N], count i32 [B]): one row per distinct
     key, in key order; zeros behind them."""
-    B, N = _need_cloud(pc, None)
+    B, N = _need_frames(pc, None, tag="sift")
     _need_on(field, "field", torch.float32, (B, N), pc.device)
     _need_on(sorted_keys, "sorted_keys", torch.int64, (B, N), pc.device)
     _need_on(order, "order", torch.int32, (B, N), pc.device)
@@ -2029,26 +2023,26 @@ def sift_dog(pc, field, count, perm, sigma2, want_visits: bool = False):
     """f-17: the octave cloud pc f32 [B,3,N] with field f32 [B,N], perm i32 [B,N] (its live rows ascending along x, stable),
     sigma2 the S host float64 values sigma_s^2 -> dog f64 [B,S-1,N]; with want_visits also the 256-point tiles each workgroup
     walked, i32 [B, ceil(N/256)]."""
-    B, N = _need_frames(pc, count, perm)
+    B, N = _need_frames(pc, count, perm, "sift")
     _need_on(field, "field", torch.float32, (B, N), pc.device)
     if field is None:
         raise RuntimeError("sift: field is required")
     a = _sigma2(sigma2)
     S = a.shape[0]
     dog = torch.empty((B, S - 1, N), dtype=torch.float64, device=pc.device)
-    visits = torch.empty((B, (N + 255) // 256), dtype=torch.int32, device=pc.device) if want_visits else None
+    visits = _visits(B, N, pc.device, want_visits)
     with torch.cuda.device(pc.device), prof.kernel("sift_dog", 16.0 * B * N + 8.0 * B * (S - 1) * N, keyed=True):
-        _lib.check(_lib.lib().usip_sift_dog_f32(_ptr(pc), _ptr(field), _opt_ptr(count), _ptr(perm), B, N, S, a.ctypes.data,
+        _lib.check(_lib.lib().usip_sift_dog_f32(_ptr(pc), _ptr(field), _opt_ptr(count), _opt_ptr(perm), B, N, S, a.ctypes.data,
                                                 _ptr(dog), _opt_ptr(visits), _stream(pc)), "usip_sift_dog_f32")
     return (dog, visits) if want_visits else dog
 
 
 def sift_nearest(pc, count, perm):
     """f-17: -> idx i32 [B,N,25]: every row's 25 nearest rows of its frame, itself included, ascending (d2, row)."""
-    B, N = _need_frames(pc, count, perm)
+    B, N = _need_frames(pc, count, perm, "sift")
     idx = torch.empty((B, N, SIFT_NEAREST), dtype=torch.int32, device=pc.device)
     with torch.cuda.device(pc.device), prof.kernel("sift_nearest", (16.0 + 4.0 * SIFT_NEAREST) * B * N, keyed=True):
-        _lib.check(_lib.lib().usip_sift_nearest_f32(_ptr(pc), _opt_ptr(count), _ptr(perm), B, N, _ptr(idx), _stream(pc)),
+        _lib.check(_lib.lib().usip_sift_nearest_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), B, N, _ptr(idx), _stream(pc)),
                    "usip_sift_nearest_f32")
     return idx
 
