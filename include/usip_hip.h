@@ -1295,6 +1295,64 @@ int usip_sift_nearest_f32_cpu(const float* pc, const int32_t* count, int B, int 
 int usip_sift_extrema_f32_cpu(const double* dog, const int32_t* idx, const int32_t* count, int B, int N, int S,
                               double min_contrast, uint8_t* mask, int32_t* scale_index, int num_threads);
 
+/* ------------------------------------------------------------------ f-18  a fragment scene's ground truth: gt.log and gt.info
+ * The files every indoor number is scored against come from evaluation/matlab/eval_indoor/3dmatch/getGtInfoLog.m: for every
+ * pair i < j of a scene's fragments, relExt = inv(T_i) T_j from the fragments' camera-to-world poses, fragment j moved by it,
+ * for every moved row the distance d to the nearest row of fragment i (both clouds grid-averaged at 0.01 m), alignedRatio =
+ * #{d < 0.03} / (rows of fragment i) (the count is over fragment j's rows, the denominator fragment i's length: the reference's
+ * rule), the pair kept at alignedRatio >= 0.3, covMat = the sum of G'G, G = [I3 | -[q]x], over the moved rows q with d <
+ * 0.006, thinned to 5000 rows when there are more.  f-9's conventions: float64 arithmetic on float32 rows, never contracted,
+ * the moved point by f-9's xform, the strict sqrt(d2) < radius of f-9's within, every sum in a stated order, no floating-point
+ * atomics, no launch synchronises the host, every index read from memory is clamped.  csrc/ground_truth_math.h is the
+ * arithmetic.  MATLAB's pcdownsample 'random' draws from a stream that cannot be reproduced; the thinning here is this
+ * project's own: a key per near row, the `cap` smallest (key, row) kept.
+ *
+ * The bank and the pairs are f-13's: rows, row_len, offsets, num_frags, total_rows, perm1 i32 [total_rows]; frag1, frag2 i32
+ * [P] (clamped into the bank), Rt f64 [P][3][4] moving fragment 2 (n2 rows) into fragment 1's frame (n1 rows), mask u8 [P]
+ * (NULL: all ones), Lmax at least the length of every fragment a pair names.
+ *
+ * usip_gt_reach_f32: perm2 i32 [P][Lmax]: fragment 2's local row indices ascending along the moved x (usip_overlap_keys_f32 and
+ * a stable sort); it decides which rows share a workgroup and, as long as its first n2 slots hold a permutation, never a
+ * result (values are clamped; a row no slot names keeps cls 0 and the key of a row that is not near).  With q = R b_i + t and
+ * d2_i the least sqdist3(q, a_j) over the rows of fragment 1:
+ *   cls u8 [P][Lmax], in fragment 2's LOCAL row order: 2 when sqrt(d2_i) < near_radius, else 1 when sqrt(d2_i) < far_radius,
+ *     else 0; zeros beyond n2.  The answer is the all-pairs one as long as perm1 sorts: a tile of fragment 1 is skipped only
+ *     when its x-gap alone reaches far_radius (f-9's beyond), a row is no longer tested only once its class is 2.
+ *   hits i32 [P][2] = #{cls >= 1}, #{cls == 2}; ratio f64 [P][2] = hits[p][0] / n1 (the reference's alignedRatio), hits[p][0] /
+ *     n2; 0 for an empty fragment.
+ *   key u64 [P][Lmax]: for a row with cls 2 the first word of the Philox4x64-10 block (csrc/pairs_rng.h) of counter (i, 0,
+ *     pair id, 0) under key (seed, 0x67745f6b6579), shifted right by one bit; all ones for every other row and beyond n2 --
+ *     sorted ascending (stable) the near rows come first, the lower row among equal keys, and no near row's key equals the
+ *     padding's.  pair_ids i64 [P] (NULL: p): a pair's keys depend on (seed, pair id, row) only, never on P or the batch.
+ * A pair with mask 0, n1 = 0 or n2 = 0 gets cls 0, key all ones, hits 0, ratio 0.
+ *
+ * usip_gt_information_f32: order i32 [P][cap]: local rows of fragment 2 (clamped into it), count i32 [P] (clamped into 0 ..
+ * cap) -> info f64 [P][6][6] = the sum over s < count of G'G at q = R b_order[s] + t: the count, the three sums of q and the
+ * six distinct entries of [q]x'[q]x (qz qz + qy qy, qz qz + qx qx, qy qy + qx qx, qx qy, qx qz, qy qz); lane l of 256 adds
+ * positions l, l + 256, ... in ascending s, the 256 partial sums go through f-6's binary tree, the matrix is assigned entry
+ * by entry and so exactly symmetric.  G has no factor 2: this is not usip_information_f32's A.  A pair with count 0 (what a
+ * masked, empty or hit-less pair has after usip_gt_reach_f32) or n2 = 0 gets zeros, never a NaN.
+ *
+ * USIP_EINVAL: the bank's and P's limits of f-13, radii that are not positive or far_radius <= near_radius, cap outside 1 ..
+ * 65536, a NULL among the required pointers. */
+int usip_gt_reach_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                      const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt, const int32_t* perm2,
+                      const uint8_t* mask, int P, int Lmax, double far_radius, double near_radius, uint64_t seed,
+                      const int64_t* pair_ids, uint8_t* cls, int32_t* hits, double* ratio, uint64_t* key, void* stream);
+int usip_gt_information_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                            const int32_t* frag2, const double* Rt, const int32_t* order, const int32_t* count, int P, int Lmax,
+                            int cap, double* info, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order.  The reach twin takes no perm2: it tests the
+ * rows of fragment 1 for every row of fragment 2 in ascending row order -- all of them with prune = 0, otherwise outward along
+ * x (perm1) until the gap alone reaches far_radius.  num_threads splits the pairs. */
+int usip_gt_reach_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                          const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt, const uint8_t* mask,
+                          int P, int Lmax, double far_radius, double near_radius, uint64_t seed, const int64_t* pair_ids,
+                          int prune, uint8_t* cls, int32_t* hits, double* ratio, uint64_t* key, int num_threads);
+int usip_gt_information_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                                const int32_t* frag2, const double* Rt, const int32_t* order, const int32_t* count, int P,
+                                int Lmax, int cap, double* info, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,17 @@ SIGNATURES = {
     "usip_sift_exp_f64_cpu": ([ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p], _int),
     "usip_sift_nearest_f32_cpu": ([_f32p, _i32p, _int, _int, _i32p, _int], _int),
     "usip_sift_extrema_f32_cpu": ([ctypes.c_void_p, _i32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p, _int], _int),
+    # f-18 a fragment scene's ground truth: reach at two radii with selection keys, the information sum (usip_amd/ground_truth.py)
+    "usip_gt_reach_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p, ctypes.c_void_p, _i32p,
+                           ctypes.c_void_p, _int, _int, _dbl, _dbl, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, _i32p,
+                           ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
+    "usip_gt_information_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _i32p, _i32p,
+                                 _int, _int, _int, ctypes.c_void_p, _stream], _int),
+    "usip_gt_reach_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p, ctypes.c_void_p,
+                               ctypes.c_void_p, _int, _int, _dbl, _dbl, ctypes.c_uint64, ctypes.c_void_p, _int,
+                               ctypes.c_void_p, _i32p, ctypes.c_void_p, ctypes.c_void_p, _int], _int),
+    "usip_gt_information_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _i32p,
+                                     _i32p, _int, _int, _int, ctypes.c_void_p, _int], _int),
 }
 
 

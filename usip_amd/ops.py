@@ -2329,3 +2329,57 @@ def posegraph_optimize(n, ecount, edge_i, edge_j, X, info, T0, tau2: float = 0.0
             _ptr(out["weight1"]), _ptr(out["weight2"]), _ptr(out["energy"]), _ptr(out["kept"]), _ptr(out["iterations_done"]),
             _ptr(out["last_step"]), _ptr(out["status"]), _stream(T0)), "usip_posegraph_optimize_f64")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ f-18 scene ground truth
+GT_CAP_MAX = 65536
+
+
+def gt_reach(rows, offsets, perm1, frag1, frag2, Rt, perm2, far: float = 0.03, near: float = 0.006, seed: int = 0,
+             pair_ids=None, mask=None):
+    """f-18: getGtInfoLog.m's nearest distances at two radii on the CSR bank of icp_nearest: for every row of fragment 2 moved
+    by Rt f64 [P,3,4], whether fragment 1 has a row within `far` (class 1) or `near` (class 2).  perm2 i32 [P,Lmax]: fragment
+    2's rows ascending along the moved x.  -> dict(cls u8 [P,Lmax] in fragment 2's local row order, hits i32 [P,2] = rows with
+    class >= 1 and with class 2, ratio f64 [P,2] = hits[:,0] over n1 and over n2, key i64 [P,Lmax]: the u64 bit patterns of the
+    selection keys (63 random bits of (seed, pair id, row) for a class-2 row, all ones = -1 elsewhere)).  Zeros (key -1)
+    where mask u8 [P] is 0 or a fragment is empty.  No host synchronisation."""
+    P = _need_icp(rows, offsets, perm1, frag1, frag2, Rt, mask, perm2)
+    if perm2 is None:
+        raise RuntimeError("gt_reach: perm2 is required")
+    Lmax, dev = perm2.shape[1], rows.device
+    _need_on(pair_ids, "pair_ids", torch.int64, (P,), dev)
+    if not (float(near) > 0.0 and float(far) > float(near)) or not 1 <= Lmax <= 1 << 24:
+        raise RuntimeError("gt_reach: far > near > 0 and Lmax in 1..2^24 (got %r, %r, %d)" % (far, near, Lmax))
+    out = {"cls": torch.empty((P, Lmax), dtype=torch.uint8, device=dev),
+           "hits": torch.empty((P, 2), dtype=torch.int32, device=dev),
+           "ratio": torch.empty((P, 2), dtype=torch.float64, device=dev),
+           "key": torch.empty((P, Lmax), dtype=torch.int64, device=dev)}
+    with torch.cuda.device(dev), prof.kernel("gt_reach", 33.0 * P * Lmax):
+        _lib.check(_lib.lib().usip_gt_reach_f32(
+            *_bank_args(rows, offsets), _ptr(perm1), _ptr(frag1), _ptr(frag2), _ptr(Rt), _ptr(perm2), _opt_ptr(mask), P, Lmax,
+            float(far), float(near), int(seed) & 0xFFFFFFFFFFFFFFFF, _opt_ptr(pair_ids), _ptr(out["cls"]), _ptr(out["hits"]),
+            _ptr(out["ratio"]), _ptr(out["key"]), _stream(rows)), "usip_gt_reach_f32")
+    return out
+
+
+def gt_information(rows, offsets, frag2, Rt, order, count, Lmax: int):
+    """f-18: getGtInfoLog.m's covMat: order i32 [P,cap] (local rows of fragment 2), count i32 [P] -> info f64 [P,6,6] = the sum
+    of G'G, G = [I3 | -[q]x], over the first min(count, cap) rows of `order` at q = R b + t; Lmax as gt_reach's (at least the
+    longest fragment).  No host synchronisation."""
+    P = _need_bank(rows, offsets, None, frag2, Rt)
+    if Rt is None or order is None or count is None:
+        raise RuntimeError("gt_information: Rt, order and count are required")
+    dev = rows.device
+    _need(order, "order", torch.int32)
+    if order.dim() != 2 or order.shape[0] != P or not 1 <= order.shape[1] <= GT_CAP_MAX or order.device != dev:
+        raise RuntimeError("gt_information: order must be i32 [P,cap] with cap in 1..%d on %s" % (GT_CAP_MAX, dev))
+    _need_on(count, "count", torch.int32, (P,), dev)
+    if P > 65535 or not 1 <= int(Lmax) <= 1 << 24:
+        raise RuntimeError("gt_information: at most 65535 pairs per call and Lmax in 1..2^24 (got %d, %d)" % (P, Lmax))
+    cap = order.shape[1]
+    info = torch.empty((P, 6, 6), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), prof.kernel("gt_information", 16.0 * P * cap):
+        _lib.check(_lib.lib().usip_gt_information_f32(
+            *_bank_args(rows, offsets), _ptr(frag2), _ptr(Rt), _ptr(order), _ptr(count), P, int(Lmax), cap, _ptr(info),
+            _stream(rows)), "usip_gt_information_f32")
+    return info
