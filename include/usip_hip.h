@@ -338,6 +338,17 @@ int usip_mlp_gemm_x2h_red_f32(const void* planes, const float* X, const float* X
                               const float* pool_dp, const int32_t* pool_arg, int pool_group, float* Y,
                               const float* red_y, const float* red_coef, float* red_out, float* red_gsum,
                               int red_group, int M, int K, int P, int nb, void* stream);
+/* The pro 2 data gradient of usip_mlp_gemm_x2h_f32 whose output is the gradient of a tensor that is ALSO max-pooled over
+ * runs of fork_group positions (a layer output that is pooled and passed on, models/networks.py:706-709,
+ * layers.py:433-436): the pooling gradient fork_dp [nb][M][P / fork_group] is added to the position fork_arg
+ * [nb][M][P / fork_group] names in each run (0 <= arg < fork_group) at the kernel's store -- Y is bit-equal to
+ * usip_mlp_gemm_x2h_f32 followed by usip_group_max_backward_add_f32, without that second pass over Y.  Taken only where
+ * usip_mlp_gemm_x2h_f32 launches its one-wave-per-SIMD kernel (M, P multiples of 256, K of 64) and fork_group is 16, 32 or
+ * 64: usip_mlp_gemm_x2h_fork_supported() = 1; all pointers 16-B aligned; USIP_EINVAL otherwise. */
+int usip_mlp_gemm_x2h_fork_supported(int M, int K, int P, int nb, int fork_group);
+int usip_mlp_gemm_x2h_fork_f32(const void* planes, const float* X, const float* X2, const float* coef, float* Y, int y_rows,
+                               const float* fork_dp, const int32_t* fork_arg, int fork_group, int M, int K, int P, int nb,
+                               void* stream);
 /* The same for the 128-wide layers (M <= 128, K <= 128; a row bias only with pro 1 and rb_group a multiple of 32) with
  * the weight fragments resident in registers and persistent workgroups over 64-position tiles: a CU moves the streamed
  * operand in and the output out, not the weight planes again for every tile.

@@ -242,6 +242,92 @@ __device__ __forceinline__ void epilogue_x2f_direct(const GemmArgs& a, f32x16 (&
     }
 }
 
+// FORK (the data gradient of a tensor that is also max-pooled over runs of fork_group positions): the pooling gradient goes
+// into the ONE position of each run that fork_arg names, here, at the store -- the same single fp32 add the stand-alone pass
+// (group.hip: dz[row][arg[row]] += dpooled[row]) made over the whole tensor a launch later.  A tile's (dp, arg) block -- 256
+// rows x 256 / fork_group runs, 16 KB each at fork_group 16 -- is in LDS as [run][row (+ 4 pad)], so that a lane reads the values
+// of its run for the four rows of a store group with ONE ds_read_b128 each, a group ahead of their use.  Thread -> row tid
+// fetched the block with 16-B loads (four runs of its row per piece) during the PREVIOUS tile's epilogue (the first tile's: in
+// the kernel's set-up) and every K-loop barrier lies between those writes and these reads; two buffers by tile parity, since a
+// wave may be an epilogue ahead of another.  The lane's two positions 2 c, 2 c + 1 lie in one run (fork_group even).
+constexpr int FFRS = FBM + 4;                                  // floats per run row: the four runs of a half-wave read different banks
+constexpr int FFARR = 16 * FFRS * 4;                           // bytes of one array (dp or arg) of a hand-over buffer
+constexpr int FFORK = 2 * FFARR;                               // ... of the buffer: dp | arg
+
+struct ForkFill { u32x4 d[4], g[4]; };
+
+__device__ __forceinline__ void fork_fetch(ForkFill& F, __amdgpu_buffer_rsrc_t rFd, __amdgpu_buffer_rsrc_t rFa, int voff, int npc)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < npc) {
+            F.d[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rFd, voff, 16 * j, 0));
+            F.g[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rFa, voff, 16 * j, 0));
+        }
+}
+
+__device__ __forceinline__ void fork_put(const ForkFill& F, unsigned char* fk, int npc)
+{
+    unsigned* dst = reinterpret_cast<unsigned*>(fk) + threadIdx.x;      // (consecutive lanes, consecutive rows: conflict-free)
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j < npc) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                dst[(4 * j + u) * FFRS] = F.d[j][u];
+                dst[FFARR / 4 + (4 * j + u) * FFRS] = F.g[j][u];
+            }
+        }
+}
+
+// fk: this tile's block; fkn / nvoff: where the next tile's goes and where it comes from (fill: there is a next tile)
+__device__ __forceinline__ void epilogue_x2f_direct_fork(const GemmArgs& a, f32x16 (&acc)[8][2], float out_scale, int b, int m0, int p0,
+                                                         const unsigned char* fk, unsigned char* fkn, bool fill, int nvoff,
+                                                         __amdgpu_buffer_rsrc_t rFd, __amdgpu_buffer_rsrc_t rFa, int npc)
+{
+    const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, half = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(a.Y + (long long)b * a.y_rows * a.P), 0, (unsigned)a.y_rows * (unsigned)a.P * 4u, 0x00020000);
+    const int voff = ((m0 + 4 * half) * a.P + p0 + wave * 64 + 2 * c) * 4;
+    const int rowb = a.P * 4;
+    const int pl = wave * 64 + 2 * c;                          // (256 % fork_group == 0: the tile starts a run)
+    const int gi = pl / a.fork_group, kin = pl - gi * a.fork_group;
+    const unsigned char* fl = fk + (gi * FFRS + 4 * half) * 4;  // row 4 half of the lane's run
+    // (dp, arg) of rows 32 i + 8 g + 4 half + 0..3 of the lane's run
+    auto fetch = [&](int ig, u32x4& d, u32x4& r) {
+        d = *reinterpret_cast<const u32x4*>(fl + ig * 32);
+        r = *reinterpret_cast<const u32x4*>(fl + FFARR + ig * 32);
+    };
+    ForkFill F;
+    u32x4 cd, ca, nd, na;
+    fetch(0, cd, ca);
+#pragma unroll
+    for (int ig = 0; ig < 32; ++ig) {
+        const int i = ig >> 2, g = ig & 3;
+        // the next tile's block: requested behind three quarters of the stores, written behind the last (32 registers for a while)
+        if (ig == 24 && fill) fork_fetch(F, rFd, rFa, nvoff, npc);
+        if (ig < 31) fetch(ig + 1, nd, na);                    // a group ahead: its LDS latency passes under this group's stores
+        u32x2 v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float dp = __uint_as_float(cd[e]);
+            const int ar = (int)ca[e];
+            float x = f_aread(acc[i][0], 4 * g + e) * out_scale, y = f_aread(acc[i][1], 4 * g + e) * out_scale;
+            x = (ar == kin) ? x + dp : x;
+            y = (ar == kin + 1) ? y + dp : y;
+            v[e] = u32x2{__float_as_uint(x), __float_as_uint(y)};
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            __builtin_amdgcn_raw_buffer_store_b64(v[e], rY, voff, (i * 32 + 8 * g + e) * rowb, st_aux<ST_X2F_DGRAD>());
+        asm volatile("s_nop 7" ::: "memory");                  // the stores read their data registers late (see above)
+        __builtin_amdgcn_sched_barrier(0);                     // one group of rows at a time (see epilogue_x2f_direct)
+        cd = nd; ca = na;
+    }
+    if (fill) fork_put(F, fkn, npc);
+}
+
 // slot sl of a stage -> index among the slots that carry no fragment read (sl % 6 >= 2), or -1
 __host__ __device__ constexpr int f_ns(int sl) { return (sl % 6) >= 2 ? (sl / 6) * 4 + (sl % 6) - 2 : -1; }
 
@@ -268,10 +354,10 @@ namespace {
 #define X2F_TP(REG_, IDX_)
 #endif
 
-template <int PRO, int EPI, bool DIRECT>
-__global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_x2f_kernel(
-    const GemmArgs a, const uint4* __restrict__ planes)
+template <int PRO, int EPI, bool DIRECT, bool FORK>
+__device__ __forceinline__ void gemm_x2f_body(const GemmArgs& a, const uint4* __restrict__ planes)
 {
+    static_assert(!FORK || (DIRECT && PRO == PRO_BN_BWD), "FORK: the plain data-gradient form");
     constexpr bool POOL = (PRO == PRO_BN_BWD_POOL);
     constexpr bool TWO = (PRO == PRO_BN_BWD) || POOL;
     constexpr int NC = TWO ? 4 : 2;                            // prologue coefficients per input channel
@@ -280,7 +366,9 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int RING = FSLOTS * FSTAGE;
     // ONE array (a second __shared__ object makes hipcc drain vmcnt before LDS reads): ring | epilogue scratch | coefficients
     constexpr int SCR = DIRECT ? 64 : FSCR_FLOATS * 4;         // (the data-gradient epilogue stores straight from the registers)
-    __shared__ __attribute__((aligned(16))) unsigned char smem[RING + SCR + NC * KPAD * 4];
+    constexpr int FOFF = RING + SCR + NC * KPAD * 4;            // FORK: the two hand-over buffers, outside the ring
+    static_assert(FOFF % 16 == 0, "16-B pieces");
+    __shared__ __attribute__((aligned(16))) unsigned char smem[FOFF + (FORK ? 2 * FFORK : 0)];
     float* scr = reinterpret_cast<float*>(smem + RING);
     float* cf = reinterpret_cast<float*>(smem + RING + SCR);   // [k][NC]
 
@@ -345,6 +433,14 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                                                                          POOL ? pool_bytes : 4u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rPa = __builtin_amdgcn_make_buffer_rsrc((void*)(POOL ? (const float*)a.pool_arg : a.X), 0,
                                                                          POOL ? pool_bytes : 4u, 0x00020000);
+    // FORK: thread -> row tid of a tile's (dp, arg) block, npc 16-B pieces of four runs each
+    const int fgrp = FORK ? a.P / a.fork_group : 0, npc = FORK ? FBN / (4 * a.fork_group) : 0;
+    const unsigned fork_bytes = (unsigned)a.nb * (unsigned)a.M * (unsigned)fgrp * 4u;
+    const __amdgpu_buffer_rsrc_t rFd = __builtin_amdgcn_make_buffer_rsrc((void*)(FORK ? a.fork_dp : a.X), 0,
+                                                                         FORK ? fork_bytes : 4u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rFa = __builtin_amdgcn_make_buffer_rsrc((void*)(FORK ? (const float*)a.fork_arg : a.X), 0,
+                                                                         FORK ? fork_bytes : 4u, 0x00020000);
+    auto fork_voff = [&](int b, int m0, int p0) { return (((b * a.M + m0 + tid) * fgrp) + p0 / (FORK ? a.fork_group : 1)) * 4; };
     // lane parts of the operand addresses: positions (2 c, 2 c + 1) of the wave's 64, k-half h
     // (one address register per row of a stage: the row's offset in the VECTOR address leaves one scalar offset per stage --
     // the lone wave's loop is bound by its own instruction issue, ~5 cycles per instruction, profiles/r06g_*)
@@ -554,6 +650,8 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     {
         // the workgroup's first tile: stages 0..2 of the weights, stages 0 and 1 of the operand, stage 0 converted, stage 2
         // requested -- the state every later tile finds when its predecessor's last stage ends
+        [[maybe_unused]] ForkFill F0;
+        if constexpr (FORK) fork_fetch(F0, rFd, rFa, fork_voff(T.b, T.m0, T.p0), npc);   // (older than everything below)
 #pragma unroll
         for (int st = 0; st < 3; ++st) { dma_pair(T.wo, st, 0); dma_pair(T.wo, st, 1); }
 #pragma unroll
@@ -563,12 +661,14 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         convert_all(0, xs0, ah, al);                           // (waits for the loads of stage 0)
 #pragma unroll
         for (int i = 0; i < 8; ++i) load_x1(T.xo + 2 * XBK * rs, T.go + 2 * XBK * rsg, xs0, i);   // stage s lives in set s & 1
+        if constexpr (FORK) fork_put(F0, smem + FOFF, npc);    // (read behind the K loop's barriers)
         // the 12 DMA pieces are older than every load still in flight (2 NX): stages 0..2 of the weights have landed
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NX) : "memory");
         __builtin_amdgcn_s_barrier();
         read_frag(0, 0, 0, FA); read_frag(0, 0, 1, FA);
     }
     int prev_m0 = 0, prev_tn128 = -1;                          // the tile whose BatchNorm partials are still in LDS
+    [[maybe_unused]] int fq = 0;                               // FORK: the buffer that holds this tile's block
     for (;;) {
         const int vn = v + (int)gridDim.x;
         const bool more = vn < total;
@@ -604,7 +704,11 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         X2F_TP(trp, tix * 8 + 5)                               // 5: accumulators readable
-        if constexpr (DIRECT) epilogue_x2f_direct(a, acc, out_scale, T.b, T.m0, T.p0);
+        if constexpr (FORK) {
+            epilogue_x2f_direct_fork(a, acc, out_scale, T.b, T.m0, T.p0, smem + FOFF + fq * FFORK, smem + FOFF + (fq ^ 1) * FFORK,
+                                     more, fork_voff(Tn.b, Tn.m0, Tn.p0), rFd, rFa, npc);
+            fq ^= 1;
+        } else if constexpr (DIRECT) epilogue_x2f_direct(a, acc, out_scale, T.b, T.m0, T.p0);
         else if (a.rowbias) epilogue_x2f<EPI, true>(a, acc, out_scale, scr, T.b, T.m0, T.p0, prev_m0, prev_tn128, tpc * 2);
         else epilogue_x2f<EPI, false>(a, acc, out_scale, scr, T.b, T.m0, T.p0, prev_m0, prev_tn128, tpc * 2);
         prev_m0 = T.m0;
@@ -633,6 +737,20 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #endif
 }
 
+template <int PRO, int EPI, bool DIRECT>
+__global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_x2f_kernel(
+    const GemmArgs a, const uint4* __restrict__ planes)
+{
+    gemm_x2f_body<PRO, EPI, DIRECT, false>(a, planes);
+}
+
+// ... and the plain data-gradient form that also adds a pooling fork's gradient at its store (GemmArgs::fork_dp)
+__global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_x2f_fork_kernel(
+    const GemmArgs a, const uint4* __restrict__ planes)
+{
+    gemm_x2f_body<PRO_BN_BWD, EPI_NONE, true, true>(a, planes);
+}
+
 }  // namespace
 
 namespace usip_mlp {
@@ -654,6 +772,12 @@ bool gemm_x2f_takes(const GemmArgs& a, int pro)
     if ((reinterpret_cast<uintptr_t>(a.X) & 7u) != 0 || (reinterpret_cast<uintptr_t>(a.X2) & 7u) != 0) return false;
     if (pro == PRO_BN_BWD_POOL && (a.pool_group % 2 != 0 || FBN % a.pool_group != 0)) return false;
     if (pro != PRO_AFFINE_RELU && (a.stats || a.bias || a.rowbias)) return false;   // data gradients: the direct epilogue only
+    if (a.fork_dp) {
+        // FORK: whole runs inside a tile, as 16-B pieces of four runs; 32-bit offsets into (dp, arg)
+        if (pro != PRO_BN_BWD || !a.fork_arg || (a.fork_group != 16 && a.fork_group != 32 && a.fork_group != 64)) return false;
+        if ((long long)a.nb * a.M * (a.P / a.fork_group) * 4 >= (1LL << 31)) return false;
+        if (((reinterpret_cast<uintptr_t>(a.fork_dp) | reinterpret_cast<uintptr_t>(a.fork_arg)) & 15u) != 0) return false;
+    }
     return true;
 }
 
@@ -669,6 +793,8 @@ int launch_gemm_x2f(const GemmArgs& a_in, const uint4* pl, int pro, hipStream_t 
     if (pro == PRO_AFFINE_RELU) {
         if (a.stats) USIP_LAUNCH((gemm_x2f_kernel<PRO_AFFINE_RELU, EPI_STATS, false>), grid, block, 0, st, a, pl);
         else USIP_LAUNCH((gemm_x2f_kernel<PRO_AFFINE_RELU, EPI_NONE, false>), grid, block, 0, st, a, pl);
+    } else if (pro == PRO_BN_BWD && a.fork_dp) {
+        USIP_LAUNCH(gemm_x2f_fork_kernel, grid, block, 0, st, a, pl);
     } else if (pro == PRO_BN_BWD) {
         USIP_LAUNCH((gemm_x2f_kernel<PRO_BN_BWD, EPI_NONE, true>), grid, block, 0, st, a, pl);
     } else {

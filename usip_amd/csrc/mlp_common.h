@@ -77,6 +77,10 @@ struct GemmArgs {
     // [2][tiles][M] (sum d, sum d xhat with d = dX where relu is on) + [tiles * row tiles] maxima of |d|, tiles = nb *
     // ceil(P / 128); red_gsum (optional) [2][nb * M][P / red_group]: per-neighbourhood sums of d and of y
     const float* red_y; const float* red_coef; float* red_out; float* red_gsum; int red_group;
+    // gemm_x2f.hip, the FORK data-gradient launch only (null / 0 elsewhere): Y is the gradient of a tensor that is ALSO
+    // max-pooled over runs of fork_group positions; the pooling gradient fork_dp [nb][M][P / fork_group] is added to the one
+    // position fork_arg [nb][M][P / fork_group] names in each run, at the store
+    const float* fork_dp; const int* fork_arg; int fork_group;
 };
 
 // prologue on one element of the streamed operand, channel coefficients c0..c3

@@ -1366,6 +1366,46 @@ extern "C" int usip_mlp_gemm_x2h_f32(const void* planes, const float* X, const f
     return launch_x3p<4, 2, 2>(a, pl, pro, st);
 }
 
+// The pro 2 data gradient of usip_mlp_gemm_x2h_f32 for an output that is the gradient of a tensor which is ALSO max-pooled
+// over runs of fork_group positions (the layer output that is pooled and passed on: models/networks.py:706-709,
+// layers.py:433-436): Y[b][m][g * fork_group + fork_arg[b][m][g]] += fork_dp[b][m][g] happens at the kernel's store instead
+// of in a pass of its own over Y (usip_group_max_backward_add_f32) -- the same fp32 add on the same value, so Y is bit-equal
+// to that pair of launches.  Only where usip_mlp_gemm_x2h_f32 would launch gemm_x2f_kernel (whole 256 x 256 tiles) and
+// fork_group is 16, 32 or 64; usip_mlp_gemm_x2h_fork_supported says so for the shapes (pointers: 16-B aligned), and the
+// launch returns USIP_EINVAL where it does not hold.
+static bool x2h_fork_args(GemmArgs& a, const float* X, const float* X2, const float* coef, float* Y, int y_rows,
+                          const float* fork_dp, const int32_t* fork_arg, int fork_group, int M, int K, int P, int nb)
+{
+    if (M < 1 || K < 1 || K > 512 || P < 1 || nb < 1 || fork_group < 1 || P % fork_group != 0) return false;
+    if (y_rows == 0) y_rows = M;
+    if (y_rows < M) return false;
+    a = GemmArgs{nullptr, 0, X, X2, coef, nullptr, Y, nullptr, M, K, P, nb, nullptr, 1, nullptr, nullptr, 0,
+                 0, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    a.fork_dp = fork_dp; a.fork_arg = fork_arg; a.fork_group = fork_group;
+    // the route usip_mlp_gemm_x2h_f32 takes to launch_gemm_x2d, then gemm_x2f.hip's own conditions
+    if (usip_mlp_x3p_tile_rows(M, P, nb) == 128 || usip_mlp_x3p_tile_cols(M, P, nb, PRO_BN_BWD, 0) == 256) return false;
+    if ((usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) == 1 || (long long)K * P * 4 >= (1LL << 31)) return false;
+    return gemm_x2f_takes(a, PRO_BN_BWD);
+}
+
+extern "C" int usip_mlp_gemm_x2h_fork_supported(int M, int K, int P, int nb, int fork_group)
+{
+    GemmArgs a;
+    float* const al = reinterpret_cast<float*>(uintptr_t(16));           // (stands for any 16-B aligned pointer: never read)
+    return x2h_fork_args(a, al, al, al, al, 0, al, reinterpret_cast<const int32_t*>(al), fork_group, M, K, P, nb) ? 1 : 0;
+}
+
+extern "C" int usip_mlp_gemm_x2h_fork_f32(const void* planes, const float* X, const float* X2, const float* coef, float* Y,
+                                          int y_rows, const float* fork_dp, const int32_t* fork_arg, int fork_group,
+                                          int M, int K, int P, int nb, void* stream)
+{
+    if (!planes || !X || !X2 || !coef || !Y || !fork_dp || !fork_arg || (reinterpret_cast<uintptr_t>(planes) & 15u))
+        return USIP_EINVAL;
+    GemmArgs a;
+    if (!x2h_fork_args(a, X, X2, coef, Y, y_rows, fork_dp, fork_arg, fork_group, M, K, P, nb)) return USIP_EINVAL;
+    return launch_gemm_x2f(a, reinterpret_cast<const uint4*>(planes), PRO_BN_BWD, (hipStream_t)stream);
+}
+
 // Data-gradient launches of the direct kernel (gemm_x2d.hip) that also leave the BatchNorm-backward partial sums of the
 // layer that PRODUCED the activation dX is the gradient of (pre-BN output red_y [nb][M][P], coefficients red_coef [4][M]:
 // scale, shift, mean, invstd).  usip_mlp_gemm_x2d_red_tiles: the number of position tiles (= rows of the partial sums) of

@@ -382,8 +382,11 @@ class LazyAct:
     to or read back from HBM.  `y` is the autograd-tracked tensor and STANDS FOR the activated output:
     gradients flowing into it are gradients w.r.t. the activated output."""
 
-    def __init__(self, y: torch.Tensor, coef: torch.Tensor, relu: bool, shape, wsrc=None):
+    def __init__(self, y: torch.Tensor, coef: torch.Tensor, relu: bool, shape, wsrc=None, fork=None):
         self.y, self.coef, self.relu, self.shape = y, coef, relu, tuple(shape)
+        # (pooled, arg) of group_max_fork when y is the passed-on alias of a max-pooled tensor: a consumer that takes BOTH
+        # (conv1x1_bn_act_pooled) may add the pooling gradient where it produces the gradient of y (_GroupMaxActFork)
+        self.fork = fork
         # the gradient-free INPUT [nb, <= 8, P] of the layer that produced y (the detector's first layer), when the
         # consumer's fused backward may take that layer's weight-gradient sums on its way (ops.wsum_supported)
         self.wsrc = wsrc
@@ -728,8 +731,11 @@ class _SharedMLPLayerPooled(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, hcoef, dims, pooled, w2, bias, gamma, beta, running_mean, running_var, training, momentum,
-                eps, relu, pooled_first, defer, sink):
+                eps, relu, pooled_first, defer, sink, fork_arg=None):
         ctx.sink = sink
+        # i32 [B,Ch,M]: pooled = max over K of (the activation of) h, taken at these k (group_max_fork); no gradient
+        ctx.fork_arg = fork_arg if (fork_arg is not None and tuple(fork_arg.shape) == (dims[0], dims[1], dims[2])
+                                    and pooled.shape[1] == dims[1]) else None
         B, Ch, M, K = dims
         Cp = pooled.shape[1]
         Cout = w2.shape[0]
@@ -757,7 +763,7 @@ class _SharedMLPLayerPooled(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dz, _dcoef):
         if dz is None:
-            return (None,) * 17
+            return (None,) * 18
         h3, hcoef, pooled, w2, y, coef, mean, invstd, gamma = ctx.saved_tensors
         B, Ch, Cp, Cout, M, K, poff, hoff = ctx.dims
         dz = dz.contiguous().view(B, Cout, M * K)
@@ -770,6 +776,14 @@ class _SharedMLPLayerPooled(torch.autograd.Function):
         dpooled = dh = dw = None
         if ctx.needs_input_grad[3]:
             dpooled = ops.mlp_gemm(w2c, sdy, tag="dgrad_pooled", M=Cp, a_offset=poff)[0]
+        # FORK: h is also what `pooled` was taken from, so d(pooled) belongs to one element per neighbourhood of dh: the GEMM
+        # that produces dh adds it at its store where it can, and _GroupMaxActFork then has nothing left to do.  (Not the
+        # fused <= 128-wide layer backward: its BatchNorm sums would then run over dense + sparse in one chain, which moves
+        # conv1-conv3's gradients at rounding level -- and, through Adam, a training run)
+        fork = None
+        if (ops.POOL_GRAD_FOLD and ctx.fork_arg is not None and dpooled is not None and ctx.needs_input_grad[0]
+                and bool(GRAD_SINK)):
+            fork = (dpooled.contiguous(), ctx.fork_arg, K)
         want = FUSED_NARROW_BWD and ctx.needs_input_grad[0] and ctx.needs_input_grad[4] and ctx.relu
         x2 = want and ops.layer_backward_x2_supported(Ch, Cout, M * K, (dz, y, h3), coef4, hcoef)
         fused = x2 or (want and ops.narrow_backward_supported(Ch, Cout, M * K, (dz, y, h3)))
@@ -785,7 +799,13 @@ class _SharedMLPLayerPooled(torch.autograd.Function):
                 _register_pre_bn_sums(res[0], [res[2]])
             dh = res[0].view(ctx.h_shape)
         if ctx.needs_input_grad[0] and not fused:
-            dh = _dgrad(h3, w2c, dz, pro=2, X2=y, coef=coef4, M=Ch, a_offset=hoff, xcoef=hcoef).view(ctx.h_shape)
+            if fork is not None and not GEMM_RED:
+                dh, _, took = ops.mlp_gemm(w2c, dz, pro=2, X2=y, coef=coef4, tag="dgrad", M=Ch, a_offset=hoff, fork=fork)
+                dh = dh.view(ctx.h_shape)
+                if took:
+                    dpooled = None
+            else:
+                dh = _dgrad(h3, w2c, dz, pro=2, X2=y, coef=coef4, M=Ch, a_offset=hoff, xcoef=hcoef).view(ctx.h_shape)
         if ctx.needs_input_grad[4] and not fused:
             dw = sink[0].view(w2c.shape) if sink else torch.empty_like(w2c)
             with ops.reduce_now(not sink):
@@ -794,7 +814,7 @@ class _SharedMLPLayerPooled(torch.autograd.Function):
         db = torch.zeros_like(gamma) if (ctx.needs_input_grad[5] and not sink) else None
         if sink:
             dw = db = dgamma = dbeta = None
-        return (dh, None, None, dpooled, dw, db, dgamma, dbeta) + (None,) * 9
+        return (dh, None, None, dpooled, dw, db, dgamma, dbeta) + (None,) * 10
 
 
 def conv1x1_bn_act_pooled(h, pooled: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], bn,
@@ -810,11 +830,14 @@ def conv1x1_bn_act_pooled(h, pooled: torch.Tensor, weight: torch.Tensor, bias: O
         e = pooled.unsqueeze(3).expand(-1, -1, -1, K)
         return conv1x1_bn_act(torch.cat((e, ht) if pooled_first else (ht, e), dim=1), weight, bias, bn, relu,
                               defer=defer)
-    hcoef = None
+    hcoef = fork_arg = None
     if isinstance(h, LazyAct):
         if not h.relu:
             h = h.materialize()
         else:
+            # pooled IS the max over K of this very h (group_max_fork): the backward may fold the two gradients
+            if h.fork is not None and h.fork[0] is pooled:
+                fork_arg = h.fork[1]
             h, hcoef = h.y, h.coef
     require_device(h, "the shared MLP")
     w2 = weight.reshape(weight.shape[0], weight.shape[1])
@@ -822,7 +845,7 @@ def conv1x1_bn_act_pooled(h, pooled: torch.Tensor, weight: torch.Tensor, bias: O
         bn.num_batches_tracked.add_(1)
     out, coef = _SharedMLPLayerPooled.apply(h, hcoef, tuple(hshape), pooled, w2, bias, bn.weight, bn.bias,
                                             bn.running_mean, bn.running_var, True, bn.momentum, bn.eps, relu,
-                                            pooled_first, defer, _sink(weight, bias, bn.weight, bn.bias))
+                                            pooled_first, defer, _sink(weight, bias, bn.weight, bn.bias), fork_arg)
     oshape = (hshape[0], w2.shape[0], hshape[2], K)
     return LazyAct(out, coef, relu, oshape) if defer else out.view(oshape)
 
@@ -912,12 +935,15 @@ class _GroupMaxActFork(torch.autograd.Function):
         ctx.K = y4.shape[3]
         ctx.relu = bool(relu)
         ctx.set_materialize_grads(False)
-        return pooled, y4.view_as(y4)
+        ctx.mark_non_differentiable(arg)
+        return pooled, y4.view_as(y4), arg
 
     @staticmethod
-    def backward(ctx, dpooled, dy):
+    def backward(ctx, dpooled, dy, _darg=None):
         arg, y4, coef, yarg = ctx.saved_tensors
         if dpooled is None:
+            # nothing pooled downstream -- or the consumer of both outputs already added the pooling gradient into dy where
+            # it produced it (FORK: _SharedMLPLayerPooled.backward)
             return dy, None, None
         if dy is None:
             return ops.group_max_backward(dpooled.contiguous(), arg, ctx.K), None, None
@@ -941,8 +967,8 @@ def group_max_fork(z):
     """(max over K, z) for a tensor that is pooled AND passed on: for a LazyAct the returned z is an alias whose
     gradient is combined with the pooling gradient in one sparse update (see _GroupMaxActFork)."""
     if isinstance(z, LazyAct) and _group_sums_supported(z.shape[3]):
-        pooled, y = _GroupMaxActFork.apply(z.y.view(z.shape), z.coef, z.relu)
-        return pooled, LazyAct(y.view(z.y.shape), z.coef, z.relu, z.shape)
+        pooled, y, arg = _GroupMaxActFork.apply(z.y.view(z.shape), z.coef, z.relu)
+        return pooled, LazyAct(y.view(z.y.shape), z.coef, z.relu, z.shape, fork=(pooled, arg))
     return group_max(z), z
 
 

@@ -450,19 +450,27 @@ NARROW_FWD = _os.environ.get("USIP_NARROW_FWD", "1") not in ("0", "off")
 # f32x2 mode: the 128-wide layers on the register-resident-weights kernel; USIP_X2R=0 for A/B runs
 X2R = _os.environ.get("USIP_X2R", "1") not in ("0", "off")
 X2R_NARROW = _os.environ.get("USIP_X2R_NARROW", "1") not in ("0", "off")
+# The gradient of a layer output that is max-pooled AND passed on (functional.group_max_fork): the pooling part is added by
+# the kernel that produces the dense part, at its store (csrc/gemm_x2f.hip: FORK), where that launch can;
+# USIP_POOL_GRAD_FOLD=0 keeps the stand-alone pass (group_max_backward_add_) everywhere, for A/B runs.
+POOL_GRAD_FOLD = _os.environ.get("USIP_POOL_GRAD_FOLD", "1") not in ("0", "off")
 
 
 def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = False, pro: int = 0,
              X2=None, coef=None, tag: str = "fwd", rowbias=None, rb_group: int = 1,
              M: Optional[int] = None, a_offset: int = 0, pool=None, a_trans: bool = False, out=None,
-             out_row_offset: int = 0, red=None, red_group: int = 0):
+             out_row_offset: int = 0, red=None, red_group: int = 0, fork=None):
     """Y[b] = At^T . pro(X[b]) + bias (+ rowbias[b][:, p // rb_group]).
     At: K-major matrix operand, [K, lda] storage; the GEMM uses columns [a_offset, a_offset + M)
     (default: all of them).  X [nb,K,P] -> Y [nb,M,P] (+ stats [2,M,tiles] when want_stats).
     red = (y_prev [nb,M,P], coef_prev [>=4,M]) (data-gradient launches, pro 2 / 3): Y is the gradient of the lazily
     activated output of the layer with that pre-BN tensor and those coefficients; when the launch takes the direct f32x2
     kernel the call returns a THIRD value, the RedSums its epilogue left for that layer's BatchNorm backward (with .gsum
-    [2,nb,M,P/red_group] when red_group is 16 or 32), else None as the third value."""
+    [2,nb,M,P/red_group] when red_group is 16 or 32), else None as the third value.
+    fork = (dpooled [nb,M,P/group], arg i32 [nb,M,P/group], group) (data-gradient launches, pro 2, without red): Y is the
+    gradient of a tensor that is also max-pooled over runs of `group` positions; when the launch can
+    (usip_mlp_gemm_x2h_fork_f32) the pooling gradient is added at its store -- Y then equals this launch followed by
+    group_max_backward_add_ -- and the call returns True as a THIRD value, else it does nothing about it and returns False."""
     _need(At, "At", torch.float32)
     if a_trans:                               # At is [M_total, lda]: the operand is rows [m0, m0+M) x cols [a_offset, a_offset+K)
         M_rows, lda = At.shape
@@ -515,7 +523,7 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
                                                               _opt(rowbias), int(rb_group), y_ptr, int(y_rows),
                                                               _opt(stats), M, K, P, nb, _stream(X)),
                        "usip_mlp_narrow_forward_f32")
-        return (Y, stats, None) if red is not None else (Y, stats)
+        return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
     fn_name = {"bf16": "usip_mlp_gemm_bf16", "f32x3": "usip_mlp_gemm_f32x3",
                "f32x2": "usip_mlp_gemm_f32x3"}.get(_matmul_mode, "usip_mlp_gemm_f32")
     x3 = _x3_family() and (x2r_direct or bool(_lib.lib().usip_mlp_gemm_f32x3_used(M, K, P, nb)))
@@ -550,7 +558,7 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
                                                         _opt(pool_dp), _opt(pool_arg), int(pool_group), y_ptr,
                                                         int(y_rows), _opt(stats), M, K, P, nb, _stream(X)),
                        "usip_mlp_gemm_x2r_f32")
-            return (Y, stats, None) if red is not None else (Y, stats)
+            return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
         red_tiles = 0
         if (red is not None and x2h and not x2r and pro >= 2 and out is None and bias is None and rowbias is None
                 and red[1] is not None and red[1].shape[0] >= 4 and tuple(red[0].shape) == (nb, M, P)
@@ -567,19 +575,32 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
             r = RedSums(flat, M, blocks=red_tiles)
             r.gsum = gsum
             return Y, stats, r
+        if (fork is not None and x2h and pro == 2 and red is None and bias is None and rowbias is None and not want_stats
+                and POOL_GRAD_FOLD):
+            f_dp, f_arg, f_group = fork
+            _need(f_dp, "fork dpooled", torch.float32)
+            _need(f_arg, "fork arg", torch.int32)
+            if (f_group > 0 and P % f_group == 0 and tuple(f_dp.shape) == (nb, M, P // f_group) and f_arg.shape == f_dp.shape
+                    and f_dp.data_ptr() % 16 == 0 and f_arg.data_ptr() % 16 == 0 and X.data_ptr() % 16 == 0
+                    and X2.data_ptr() % 16 == 0 and y_ptr.value % 16 == 0
+                    and _lib.lib().usip_mlp_gemm_x2h_fork_supported(M, K, P, nb, int(f_group))):
+                _lib.check(_lib.lib().usip_mlp_gemm_x2h_fork_f32(_ptr(planes), _ptr(X), _ptr(X2), _ptr(coef), y_ptr,
+                                                                 int(y_rows), _ptr(f_dp), _ptr(f_arg), int(f_group), M, K, P,
+                                                                 nb, _stream(X)), "usip_mlp_gemm_x2h_fork_f32")
+                return Y, stats, True
         if x3p:
             fn = "usip_mlp_gemm_x2h_f32" if x2h else "usip_mlp_gemm_x3p_f32"
             _lib.check(getattr(_lib.lib(), fn)(_ptr(planes), None if pool is not None else _ptr(X), _opt(X2),
                                                _opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group),
                                                _opt(pool_dp), _opt(pool_arg), int(pool_group), y_ptr,
                                                int(y_rows), _opt(stats), M, K, P, nb, _stream(X)), fn)
-            return (Y, stats, None) if red is not None else (Y, stats)
+            return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
         _lib.check(getattr(_lib.lib(), fn_name)(a_ptr, -lda if a_trans else lda,
                                                 None if pool is not None else _ptr(X), _opt(X2),
                                                 _opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group),
                                                 _opt(pool_dp), _opt(pool_arg), int(pool_group),
                                                 y_ptr, int(y_rows), _opt(stats), M, K, P, nb, _stream(X)), fn_name)
-    return (Y, stats, None) if red is not None else (Y, stats)
+    return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
 
 
 def bn_finalize(stats, count, gamma, beta, eps, momentum, running_mean, running_var):
