@@ -27,6 +27,15 @@ lacks, default gt; --optimize-transform edge|graph: what the refined log holds, 
 carries loop_recall, loop_precision, loops_in and loops_kept, and <scene>_odom.log/.info, <scene>_loop.log/.info and
 <scene>_reg_refine_all.log are written beside <scene>.log.
 
+--descriptor-method fpfh (default learned: the descriptors of the results files) describes the keypoints by Fast Point Feature
+Histograms over the fragment clouds instead (usip_amd.baselines.FpfhDescriptor, 33 columns; --fpfh-radius, default 0.25 m,
+--fpfh-normal-radius, default 0.125 m, --fpfh-normals estimated|supplied: supplied reads columns 4 .. 6 of the fragment
+files).  The keypoints are the results files' (--method results) or, with --method iss | harris | sift | random, --top of them
+from usip_amd.baselines with the outdoor defaults times --scale (default 0.05): then no results file, no network and no
+checkpoint is read.  --write-descriptors DIR writes DIR/<scene>/<i>.bin rows [x y z d0 .. d32].  (On the synthetic room the
+results files' keypoints are shared landmarks and FPFH registers most pairs; a baseline detector's keypoints there are mostly
+the random points that pad the count, which no two fragments share, so that run only shows that the path works.)
+
 Prints ONE JSON line (what evaluate.m prints, per scene and as means, and the registrator) and writes <results>/<scene>.log as writeLog.m does;
 with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
 import argparse
@@ -59,12 +68,43 @@ def make_synthetic(root, fragments, points, dim, seed):
     return os.path.join(root, "scenes"), os.path.join(root, "results"), os.path.join(root, "gt")
 
 
+def add_fpfh_fragment(ev, i, xyz, cloud, args):
+    """--descriptor-method fpfh: fragment i's keypoints -- the results file's (xyz [M,3]) or, with --method iss | harris | sift |
+    random, --top of them from usip_amd.baselines at the outdoor defaults times --scale -- described by Fast Point Feature
+    Histograms over the fragment's cloud.  No network, no checkpoint."""
+    import torch
+    from usip_amd import baselines as bl
+    t = torch.from_numpy(np.ascontiguousarray(np.asarray(cloud).T, dtype=np.float32)).to(args.device)
+    pc = t[:3].unsqueeze(0).contiguous()
+    s = args.scale
+    if args.method == "results":
+        kp = torch.from_numpy(np.ascontiguousarray(np.asarray(xyz, np.float32).T)).to(args.device).unsqueeze(0)
+    else:
+        if args.method == "random":
+            kp, count = bl.random_keypoints(pc, None, args.top, args.seed, [i])
+        else:
+            detect = {"iss": lambda: bl.IssDetector(num=args.top, seed=args.seed, salient_radius=2.0 * s, non_max_radius=2.0 * s),
+                      "harris": lambda: bl.HarrisDetector(num=args.top, seed=args.seed, radius=1.0 * s),
+                      "sift": lambda: bl.SiftDetector(num=args.top, seed=args.seed, min_scale=0.5 * s)}[args.method]()
+            kp, count = detect(pc, None, [i])
+        kp = kp[:, :, :int(count[0])]
+    normals = None
+    if args.fpfh_normals == "supplied":
+        if t.shape[0] < 6:
+            raise SystemExit("--fpfh-normals supplied: fragment %d has no normal columns (expected rows [x y z nx ny nz ..])" % i)
+        normals = t[3:6].unsqueeze(0).contiguous()
+    desc = bl.FpfhDescriptor(args.fpfh_radius, args.fpfh_normal_radius)(pc, kp.contiguous(), None, None, normals)
+    return ev.add_fragment_result(i, kp[0].t(), desc[0].t(), cloud)
+
+
 def evaluate_scene(name, scenes, results, gt_root, args):
     clouds = sorted(glob.glob(os.path.join(scenes, name, "*.npy")), key=lambda p: int(os.path.basename(p)[:-4]))
     if not clouds:
         raise SystemExit("no fragments under %s" % os.path.join(scenes, name))
-    rows = [fr.read_descriptors_bin(os.path.join(results, name, "%d.bin" % i), args.dim) for i in range(len(clouds))]
-    top = max(len(x) for x, _ in rows)
+    rows = None
+    if args.method == "results":
+        rows = [fr.read_descriptors_bin(os.path.join(results, name, "%d.bin" % i), args.dim) for i in range(len(clouds))]
+    top = max(len(x) for x, _ in rows) if rows is not None else args.top
     ev = fr.FragmentEvaluator(None, None, None, args.device, top=top, k=args.k, max_trials=args.trials, seed=args.seed,
                               batch_pairs=args.batch_pairs, registrator=args.registration, refine=args.refine == "icp",
                               refine_args=dict(max_iterations=args.refine_iterations, tolerance=tuple(args.refine_tolerance)),
@@ -72,7 +112,14 @@ def evaluate_scene(name, scenes, results, gt_root, args):
                               optimize_args=dict(tau2=args.optimize_tau2, fill=args.optimize_fill,
                                                  transform=args.optimize_transform) if args.optimize else None)
     for i, path in enumerate(clouds):
-        ev.add_fragment_result(i, rows[i][0], rows[i][1], np.load(path))
+        if args.descriptor_method == "fpfh":
+            add_fpfh_fragment(ev, i, rows[i][0] if rows is not None else None, np.load(path), args)
+        else:
+            ev.add_fragment_result(i, rows[i][0], rows[i][1], np.load(path))
+    if args.write_descriptors:
+        os.makedirs(os.path.join(args.write_descriptors, name), exist_ok=True)
+        for i in ev.ids():
+            fr.write_descriptors_bin(os.path.join(args.write_descriptors, name, "%d.bin" % i), *ev.fragment_arrays(i))
     gt = fr.read_log(os.path.join(gt_root, "%s-evaluation" % name, "gt.log"))
     gt_info = fr.read_info(os.path.join(gt_root, "%s-evaluation" % name, "gt.info"))
     out = ev.evaluate(None, gt, gt_info)
@@ -117,7 +164,17 @@ def main():
     ap.add_argument("--batch-pairs", type=int, default=32)
     ap.add_argument("--pair-files", action="store_true")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--descriptor-method", choices=("learned", "fpfh"), default="learned")
+    ap.add_argument("--method", choices=("results", "iss", "harris", "sift", "random"), default="results")
+    ap.add_argument("--top", type=int, default=512)
+    ap.add_argument("--scale", type=float, default=0.05)
+    ap.add_argument("--fpfh-radius", type=float, default=0.25)
+    ap.add_argument("--fpfh-normal-radius", type=float, default=0.125)
+    ap.add_argument("--fpfh-normals", choices=("estimated", "supplied"), default="estimated")
+    ap.add_argument("--write-descriptors", metavar="DIR")
     args = ap.parse_args()
+    if args.method != "results" and args.descriptor_method != "fpfh":
+        ap.error("--method %s needs --descriptor-method fpfh (the results files hold the learned descriptors)" % args.method)
     if args.log_transform == "refined" and args.refine != "icp":
         ap.error("--log-transform refined needs --refine icp")
     if args.optimize and args.refine != "icp":
@@ -131,6 +188,8 @@ def main():
         ap.error("give --make-synthetic DIR, or --scenes, --results and --gt")
     per_scene = {n: evaluate_scene(n, scenes, results, gt, args) for n in names}
     out = {"scenes": per_scene, "registration": args.registration}
+    if args.descriptor_method != "learned":
+        out.update(descriptor_method=args.descriptor_method, method=args.method)
     if args.refine != "none":
         out.update(refine=args.refine, log_transform=args.log_transform)
     for k in ("recall", "precision", "inlier_num_mean", "inlier_ratio_mean"):          # evaluate.m's last line: means

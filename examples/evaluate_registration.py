@@ -7,12 +7,16 @@ as ONE JSON line.
     python examples/evaluate_registration.py --data /tmp/eval_data --detector det.pth --descriptor desc.pth \\
         --write-descriptors /tmp/descriptors
     python examples/evaluate_registration.py --data /tmp/eval_data --method iss      # or harris, sift, random: the baselines' numbers
+    python examples/evaluate_registration.py --data /tmp/eval_data --method iss --descriptor-method fpfh   # no network at all
 
 Data layout: <dir>/<id>.bin float32 rows [x y z nx ny nz curvature] and <dir>/pairs.txt with one pair per line,
 `anc_id pos_id tx ty tz qw qx qy qz`: the pose that moves the positive scan into the anchor's frame.  Without checkpoints
 the weights are the repository's seeded ones (usip_amd.synth.fill_parameters): the numbers then say nothing about USIP,
 only that the pipeline runs.  --method iss | harris | sift | random scores the reference's baseline detectors (evaluation/save_keypoints.py)
-instead of the learned one: --top keypoints per frame from usip_amd.baselines, described by the same descriptor."""
+instead of the learned one: --top keypoints per frame from usip_amd.baselines, described by the same descriptor.
+--descriptor-method fpfh describes the keypoints by Fast Point Feature Histograms (usip_amd.baselines.FpfhDescriptor, 33 columns)
+instead of the learned descriptor: with a baseline --method no network is constructed and no checkpoint is read.  --fpfh-normals
+supplied takes the scans' own normals (columns 4 .. 6) instead of estimating them over --fpfh-normal-radius."""
 import argparse
 import json
 import os
@@ -97,18 +101,20 @@ def seeded(module):
 
 
 def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, descriptor_ckpt=None, device="cuda:0",
-                    method="tsf"):
+                    method="tsf", descriptor_method="learned"):
     dev = torch.device(device)
     opt = DetectorOptions(surface_normal_len=CS, node_knn_k_1=16)
     detector = build_detector(model, opt).to(dev) if method == "tsf" else None     # the baselines need none
-    descriptor = DescriptorLiteOld(opt).to(dev)
+    descriptor = DescriptorLiteOld(opt).to(dev) if descriptor_method == "learned" else None       # FPFH needs none
     if detector is None:
         pass
     elif detector_ckpt:
         inference.load_detector_state(detector, torch.load(detector_ckpt, map_location=dev))
     else:
         seeded(detector)
-    if descriptor_ckpt:
+    if descriptor is None:
+        pass
+    elif descriptor_ckpt:
         inference.load_detector_state(descriptor, torch.load(descriptor_ckpt, map_location=dev))
     else:
         seeded(descriptor)
@@ -116,11 +122,22 @@ def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, des
                                             max_trials=max_trials, seed=seed)
 
 
-def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None, sift=None):
+def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None, sift=None, fpfh=None):
     """method 'iss' / 'harris' / 'sift' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss, harris,
     sift: IssDetector's / HarrisDetector's / SiftDetector's parameters; sift's field may be "x" | "y" | "z" or "curvature",
-    the scans' seventh column)."""
+    the scans' seventh column).  fpfh: dict(radius, normal_radius, normals "estimated" | "supplied") -- the keypoints are
+    described by baselines.FpfhDescriptor instead of the evaluator's descriptor."""
     dev = evaluator.device
+    fpfh = dict(fpfh) if fpfh is not None else None
+    supplied = fpfh is not None and fpfh.pop("normals", "estimated") == "supplied"
+    describe = baselines.FpfhDescriptor(**fpfh) if fpfh is not None else None
+
+    def add(fid, pc, sn, kp, count):
+        if describe is None:
+            return evaluator.add_frame_keypoints(fid, pc, sn, kp, count)
+        desc = describe(pc, kp, None, count, sn[:, :3].contiguous() if supplied else None)
+        return evaluator.add_frame_descriptors(fid, kp, desc, count)
+
     detect = baselines.IssDetector(num=evaluator.top, seed=seed, **(iss or {})) if method == "iss" else \
         baselines.HarrisDetector(num=evaluator.top, seed=seed, **(harris or {})) if method == "harris" else None
     sift = dict(sift or {})
@@ -132,14 +149,19 @@ def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None
         pc, sn = t[:3].unsqueeze(0).contiguous(), t[3:].unsqueeze(0).contiguous()
         if method == "tsf":
             first = torch.tensor([(seed + 7919 * int(fid)) % pc.shape[2]], dtype=torch.int32, device=dev)
-            evaluator.add_frame(fid, pc, sn, inference.sample_nodes(pc, nodes, first))
+            node = inference.sample_nodes(pc, nodes, first)
+            if describe is None:
+                evaluator.add_frame(fid, pc, sn, node)
+            else:
+                keypoints, sigmas = inference.run_model(evaluator.detector, pc, sn, node)
+                add(fid, pc, sn, *evaluation.select_keypoints_device(keypoints, sigmas, evaluator.nms_radius, evaluator.top))
         else:
             if method == "sift" and curvature:
                 kp, count = detect(pc, None, [int(fid)], field=t[6].unsqueeze(0).contiguous())
             else:
                 kp, count = detect(pc, None, [int(fid)]) if detect is not None else \
                     baselines.random_keypoints(pc, None, evaluator.top, seed, [int(fid)])
-            evaluator.add_frame_keypoints(fid, pc, sn, kp, count)
+            add(fid, pc, sn, kp, count)
 
 
 def main():
@@ -156,7 +178,7 @@ def main():
     ap.add_argument("--nms-radius", type=float, default=1.0)
     ap.add_argument("--max-trials", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there")
+    ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there (fpfh: d0 .. d32)")
     ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "sift", "random"],
                     help="tsf: the learned detector; iss, harris, sift, random: the baselines, --top keypoints per frame")
     ap.add_argument("--salient-radius", type=float, default=2.0)
@@ -171,6 +193,12 @@ def main():
     ap.add_argument("--sift-scales", type=int, default=8)
     ap.add_argument("--sift-contrast", type=float, default=0.1)
     ap.add_argument("--sift-field", default="z", choices=["x", "y", "z", "curvature"])
+    ap.add_argument("--descriptor-method", default="learned", choices=["learned", "fpfh"],
+                    help="learned: the descriptor network (--descriptor is its checkpoint); fpfh: Fast Point Feature Histograms")
+    ap.add_argument("--fpfh-radius", type=float, default=2.0)
+    ap.add_argument("--fpfh-normal-radius", type=float, default=1.0)
+    ap.add_argument("--fpfh-normals", default="estimated", choices=["estimated", "supplied"],
+                    help="supplied: the scans' own normals (columns 4 .. 6) instead of estimated ones")
     args = ap.parse_args()
     if args.make_synthetic:
         scans, pairs = make_synthetic(np.random.default_rng(args.seed), args.frames, args.points)
@@ -180,17 +208,22 @@ def main():
         ap.error("give --data DIR or --make-synthetic DIR")
     scans, pairs = read_dataset(args.data)
     evaluator = build_evaluator(args.model, args.detector, args.top, args.nms_radius, args.max_trials,
-                                args.seed, args.descriptor, method=args.method)
+                                args.seed, args.descriptor, method=args.method, descriptor_method=args.descriptor_method)
     add_scans(evaluator, scans, args.nodes, args.seed, args.method,
               dict(salient_radius=args.salient_radius, non_max_radius=args.non_max_radius, gamma_21=args.gamma_21,
                    gamma_32=args.gamma_32, min_neighbors=args.min_neighbors),
               dict(radius=args.harris_radius, threshold=args.harris_threshold),
               dict(min_scale=args.sift_min_scale, n_octaves=args.sift_octaves, n_scales_per_octave=args.sift_scales,
-                   min_contrast=args.sift_contrast, field=args.sift_field))
+                   min_contrast=args.sift_contrast, field=args.sift_field),
+              dict(radius=args.fpfh_radius, normal_radius=args.fpfh_normal_radius, normals=args.fpfh_normals)
+              if args.descriptor_method == "fpfh" else None)
     summary = evaluator.evaluate(pairs)
     summary.pop("per_pair")
-    summary["seeded_weights"] = not ((args.detector or args.method != "tsf") and args.descriptor)
+    fpfh = args.descriptor_method == "fpfh"
+    summary["seeded_weights"] = not ((args.detector or args.method != "tsf") and (args.descriptor or fpfh))
     summary["method"] = args.method
+    if fpfh:                                                      # (the default's line is what it was)
+        summary["descriptor_method"] = args.descriptor_method
     if args.write_descriptors:
         os.makedirs(args.write_descriptors, exist_ok=True)
         for fid, _ in scans:

@@ -1247,6 +1247,49 @@ int usip_harris_normals_f32_cpu(const float* pc, const int32_t* count, int B, in
 int usip_harris_response_f32_cpu(const float* pc, const int32_t* count, const double* normals, int B, int N, double radius,
                                  int method, double* response, int32_t* members, int num_threads);
 
+/* ------------------------------------------------------------------ f-19  baseline descriptor: FPFH
+ * The hand-crafted descriptor the reference's scoring scripts name beside the learned one (eval_indoor/3dmatch/evaluate.m,
+ * evaluate_optimization.m, eval_loop.m: descriptorName = 'my'; % 3dmatch, spin, fpfh) and do not contain: Fast Point Feature
+ * Histograms (Rusu, Blodow, Beetz 2009).  PCL is not part of the reference; the definition below is this project's own, written
+ * after PCL's FPFHEstimation / computePairFeatures (DESIGN 8o lists the deviations).  Float64 arithmetic on float32 inputs,
+ * never contracted; sqrt and division are the only operations beyond + - * and comparisons (no libm call feeds a decision or a
+ * result); csrc/fpfh_math.h is the arithmetic.  Frames, count, perm, membership (strict d2 < r * r) and the limits are f-11's.
+ *
+ * Normals f64 [B][3][N] are f-16's (usip_harris_normals_f32, or float32 normals cast to float64 and used as given).  A row HAS A
+ * NORMAL iff its components are finite and not all zero; a point without one is a member of nobody, its SPFH row is zero and
+ * its member count 0.
+ *
+ * usip_fpfh_spfh_f32: members i32 [B][N] = the points j != i with a normal and d2(i, j) < r2 (a query counts every such row and
+ * takes one off for itself); spfh i32 [B][N][33] = the INTEGER COUNTS of three 11-bin histograms over those members, bins h1 |
+ * 11 + h2 | 22 + h3 of the pair (i, j).  With d = p_j - p_i, f4 = sqrt(d2): f4 == 0 adds to no bin.  a1 = (n_i . d) / f4, a2 =
+ * (n_j . d) / f4 (dots as (a0 b0 + a1 b1) + a2 b2); |a1| < |a2|: n1 = n_j, n2 = n_i, d = -d, f3 = -a2; otherwise n1 = n_i, n2 =
+ * n_j, f3 = a1.  v = d x n1; |v| == 0 adds to no bin; else v /= |v|, w = n1 x v, f2 = v . n2, y = w . n2, x = n1 . n2.  h2, h3 =
+ * (11 (f + 1)) / 2 truncated and clamped to 0 .. 10.  h1 = the sector of width 2 pi / 11, counted from -pi, that holds the
+ * direction (x, y), decided by the signs of cross products against ten boundary directions kept as float64 literals (no
+ * inverse tangent); (0, 0) is bin 5, (x < 0, y == 0) is bin 10.  Integer counts do not depend on the order of the walk.
+ * tiles_visited as f-11's.
+ *
+ * usip_fpfh_gather_f32: keypoints f32 [B][3][M] (any positions), kp_count i32 [B] or NULL.  Over the cloud points j with
+ * members_j > 0 and 0 < d2(q, j) < r2 (kp_members i32 [B][M] counts them): sum[bin] += ((double)spfh_j[bin] * (100.0 /
+ * members_j)) * (1.0 / d2).  THE ORDER OF THE SUMS: 64 partial sums; partial sum l takes the positions lo + l + 64 k of the
+ * frame's stable order along x, ascending, lo = the first position with q_x - x < r; the 64 are folded by l += l ^ 32, 16, 8,
+ * 4, 2, 1.  Each block of eleven is then multiplied by 100 / (its sum, bins ascending) when that sum is positive and zero
+ * otherwise.  fpfh f64 [B][M][33].
+ * Slots beyond count[b] / kp_count[b] get zeros.  USIP_EINVAL: a shape outside the limits (M in 1 .. 65535), a radius that is
+ * not positive and finite, a NULL among the required pointers (count, kp_count and tiles_visited may be NULL). */
+int usip_fpfh_spfh_f32(const float* pc, const int32_t* count, const int32_t* perm, const double* normals, int B, int N,
+                       double radius, int32_t* spfh, int32_t* members, int32_t* tiles_visited, void* stream);
+int usip_fpfh_gather_f32(const float* pc, const int32_t* count, const int32_t* perm, const int32_t* spfh,
+                         const int32_t* members, const float* keypoints, const int32_t* kp_count, int B, int N, int M,
+                         double radius, double* fpfh, int32_t* kp_members, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; every query and keypoint tests all live
+ * points of its frame, in the frame's own stable order along x (no perm); num_threads splits the queries / keypoints. */
+int usip_fpfh_spfh_f32_cpu(const float* pc, const int32_t* count, const double* normals, int B, int N, double radius,
+                           int32_t* spfh, int32_t* members, int num_threads);
+int usip_fpfh_gather_f32_cpu(const float* pc, const int32_t* count, const int32_t* spfh, const int32_t* members,
+                             const float* keypoints, const int32_t* kp_count, int B, int N, int M, double radius, double* fpfh,
+                             int32_t* kp_members, int num_threads);
+
 /* ------------------------------------------------------------------ f-17  baseline keypoints: SIFT3D
  * The third hand-crafted detector the reference compares its learned one with (evaluation/save_keypoints.py:57-61, 314-325,
  * method = 'sift': PCLKeypoint.keypointSift(xyz, min_scale 0.5, n_octaves 4, n_scales_per_octave 8, min_contrast 0.1)).  The

@@ -291,6 +291,13 @@ SIGNATURES = {
                                ctypes.c_void_p, _i32p, ctypes.c_void_p, ctypes.c_void_p, _int], _int),
     "usip_gt_information_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _i32p,
                                      _i32p, _int, _int, _int, ctypes.c_void_p, _int], _int),
+    # f-19 baseline descriptor: FPFH's integer SPFH and the weighted gather at keypoints (usip_amd/baselines.py)
+    "usip_fpfh_spfh_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _i32p, _i32p, _i32p, _stream], _int),
+    "usip_fpfh_gather_f32": ([_f32p, _i32p, _i32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p,
+                              _stream], _int),
+    "usip_fpfh_spfh_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _i32p, _i32p, _int], _int),
+    "usip_fpfh_gather_f32_cpu": ([_f32p, _i32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p,
+                                  _int], _int),
 }
 
 

@@ -26,8 +26,18 @@ tensor of the caller's (curvature, reflectance); its keypoints are voxel-cell ce
   select_candidates  SIFT's candidates (and, with ensure, the cloud's points behind them) -> `num` keypoints per frame
   select_keypoints   mask -> exactly `num` keypoints per frame (or at most, with ensure=False)
   random_keypoints   `num` distinct points per frame
+  fpfh_spfh          (spfh i32 [B,N,33], members i32 [B,N], normals f64 [B,3,N]): every point's integer pair-feature histograms
+  fpfh_descriptors   (desc f32 [B,33,M], kp_members i32 [B,M]) at keypoints f32 [B,3,M] of any detector: FPFH
   *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp, csrc/harris_cpu.cpp,
-                     csrc/sift_cpu.cpp)
+                     csrc/sift_cpu.cpp, csrc/fpfh_cpu.cpp)
+
+The scoring scripts of the reference also name hand-crafted DESCRIPTORS (eval_indoor/3dmatch/evaluate.m: 'my'; % 3dmatch, spin,
+fpfh) that it does not contain.  FPFH (csrc/fpfh.hip, csrc/fpfh_math.h) describes the keypoints of any detector above without a
+network or a checkpoint:
+
+    fpfh = FpfhDescriptor(radius=2.0, normal_radius=1.0)     # this project's radii: the reference gives none
+    desc = fpfh(pc, kp, count, kp_count)                     # f32 [B,33,M]
+    evaluator.add_frame_descriptors(fid, kp, desc, kp_count) # evaluation.RegistrationEvaluator: score them
 
 The selection is reproducible and free of host synchronisation: one CPU generator per frame, seeded from (seed, frame_id) the
 way prepare._keep_rows seeds its own, draws u in [0, 1) for every point; a live point's key is u when it is a keypoint and
@@ -49,6 +59,7 @@ from . import _lib, ops
 ISS_DEFAULTS = dict(salient_radius=2.0, non_max_radius=2.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5)
 HARRIS_DEFAULTS = dict(radius=1.0, threshold=0.001, response="harris", min_neighbors=3)
 SIFT_DEFAULTS = dict(min_scale=0.5, n_octaves=4, n_scales_per_octave=8, min_contrast=0.1, field="z")
+FPFH_DEFAULTS = dict(radius=2.0, normal_radius=1.0, min_neighbors=3)   # this project's choice: the reference gives none
 
 
 def _check(salient_radius, non_max_radius, min_neighbors):
@@ -100,11 +111,11 @@ def _check_harris(radius, threshold, response, min_neighbors):
         raise ValueError("harris: response must be one of %s, got %r" % (sorted(ops.HARRIS_METHODS), response))
 
 
-def _supplied(normals, pc):
+def _supplied(normals, pc, tag="harris"):
     """PCL's setNormals: f32 [B,3,N], used as given -- cast to float64, not renormalised"""
     if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.shape != pc.shape \
             or normals.device != pc.device:
-        raise ValueError("harris: supplied normals must be f32 %s on %s" % (tuple(pc.shape), pc.device))
+        raise ValueError("%s: supplied normals must be f32 %s on %s" % (tag, tuple(pc.shape), pc.device))
     return normals.to(torch.float64).contiguous()
 
 
@@ -137,6 +148,52 @@ def harris_keypoints(pc, count=None, radius: float = 1.0, threshold: float = 0.0
     res, members, nrm = harris_response(pc, count, radius, normals, response, min_neighbors, perm)
     kept = torch.where(res >= float(threshold), res, torch.zeros_like(res))
     return ops.iss_nms(pc, count, perm, kept, radius, 1), res, members, nrm
+
+
+# ------------------------------------------------------------------------------------------------ FPFH
+def _check_fpfh(radius, normal_radius, min_neighbors):
+    if not (0.0 < float(radius) < float("inf") and 0.0 < float(normal_radius) < float("inf") and int(min_neighbors) >= 1):
+        raise ValueError("fpfh: the radii must be positive and finite and min_neighbors at least 1")
+
+
+def _keypoints(keypoints, kp_count, pc):
+    if not isinstance(keypoints, torch.Tensor) or keypoints.dim() != 3 or keypoints.shape[:2] != pc.shape[:2] \
+            or keypoints.dtype != torch.float32 or keypoints.device != pc.device:
+        raise ValueError("fpfh: expected keypoints f32 [B,3,M] beside the cloud")
+    if not 1 <= keypoints.shape[2] <= ops.FPFH_MMAX:
+        raise ValueError("fpfh: M must be in 1..%d, got %d" % (ops.FPFH_MMAX, keypoints.shape[2]))
+    return keypoints.contiguous(), None if kp_count is None else kp_count.to(torch.int32).contiguous()
+
+
+def fpfh_spfh(pc, count=None, radius: float = 2.0, normals=None, normal_radius: float = 1.0, min_neighbors: int = 3,
+              perm=None, want_visits: bool = False):
+    """pc f32 [B,3,N], count i32 [B], normals f32 [B,3,N] or None (harris_normals over normal_radius with min_neighbors) ->
+    (spfh i32 [B,N,33], members i32 [B,N], normals f64 [B,3,N][, tiles_visited i32 [B,ceil(N/256)]]): the integer counts of
+    the three 11-bin pair-feature histograms of every point over its members within `radius`.  radius 2 and normal_radius 1
+    (outdoor metres) are this project's choice: the reference gives none; indoor callers pass their own."""
+    _check_fpfh(radius, normal_radius, min_neighbors)
+    pc, count = _frames(pc, count)
+    perm = sort_along_x(pc, count) if perm is None else perm
+    nrm = ops.harris_normals(pc, count, perm, normal_radius, min_neighbors)[0] if normals is None else \
+        _supplied(normals, pc, "fpfh")
+    out = ops.fpfh_spfh(pc, count, perm, nrm, radius, want_visits)
+    return out[:2] + (nrm,) + out[2:]
+
+
+def fpfh_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, normals=None, normal_radius: float = 1.0,
+                     want_f64: bool = False, min_neighbors: int = 3):
+    """pc f32 [B,3,N], keypoints f32 [B,3,M] (any positions: cloud points or not), count, kp_count i32 [B] or None -> (desc f32
+    [B,33,M], kp_members i32 [B,M][, fpfh f64 [B,M,33]]): Fast Point Feature Histograms at the keypoints, the layout the learned
+    descriptor has (channels first).  The f32 descriptor is the cast of the f64 result.  One sort, no host synchronisation.
+    radius 2 and normal_radius 1 are this project's choice (fpfh_spfh)."""
+    _check_fpfh(radius, normal_radius, min_neighbors)
+    pc, count = _frames(pc, count)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    perm = sort_along_x(pc, count)
+    spfh, members, _ = fpfh_spfh(pc, count, radius, normals, normal_radius, min_neighbors, perm)
+    fpfh, kp_members = ops.fpfh_gather(pc, count, perm, spfh, members, keypoints, kp_count, radius)
+    desc = fpfh.to(torch.float32).transpose(1, 2).contiguous()
+    return (desc, kp_members, fpfh) if want_f64 else (desc, kp_members)
 
 
 # ------------------------------------------------------------------------------------------------ SIFT3D (DESIGN 8l)
@@ -390,6 +447,23 @@ class SiftDetector:
         return select_candidates(pc, count, self.last[0], self.last[1], self.num, self.ensure, self.seed, frame_ids)
 
 
+class FpfhDescriptor:
+    """FPFH with its parameters bundled, called where the learned descriptor is: __call__(pc, keypoints, count, kp_count,
+    normals) -> desc f32 [B,33,M]; .last holds (desc, kp_members) of the latest call.  normals f32 [B,3,N]: supplied ones (the
+    cloud's sn[:, :3]) instead of estimated ones."""
+
+    dim = 33
+
+    def __init__(self, radius: float = 2.0, normal_radius: float = 1.0, min_neighbors: int = 3):
+        _check_fpfh(radius, normal_radius, min_neighbors)
+        self.params = dict(radius=float(radius), normal_radius=float(normal_radius), min_neighbors=int(min_neighbors))
+        self.last = None
+
+    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
+        self.last = fpfh_descriptors(pc, keypoints, count, kp_count, normals=normals, **self.params)
+        return self.last[0]
+
+
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
 def _p(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
@@ -470,6 +544,52 @@ def harris_keypoints_cpu(pc, count=None, radius: float = 1.0, threshold: float =
     _lib.check(_lib.lib().usip_iss_nms_f32_cpu(_p(a), _p(c), _p(kept), B, N, float(radius), 1, _p(mask), int(num_threads)),
                "usip_iss_nms_f32_cpu")
     return mask, res, members, nrm
+
+
+def fpfh_spfh_cpu(pc, count=None, radius: float = 2.0, normals=None, normal_radius: float = 1.0, min_neighbors: int = 3,
+                  num_threads: int = 1):
+    """-> (spfh i32 [B,N,33], members i32 [B,N], normals f64 [B,3,N])"""
+    _check_fpfh(radius, normal_radius, min_neighbors)
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    if normals is None:
+        nrm = harris_normals_cpu(a, c, normal_radius, min_neighbors, num_threads)[0]
+    else:
+        nrm = np.asarray(normals)
+        if nrm.dtype != np.float32 or nrm.shape != a.shape:
+            raise ValueError("fpfh: supplied normals must be f32 %s" % (a.shape,))
+        nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    spfh, members = np.zeros((B, N, ops.FPFH_WIDTH), np.int32), np.zeros((B, N), np.int32)
+    _lib.check(_lib.lib().usip_fpfh_spfh_f32_cpu(_p(a), _p(c), _p(nrm), B, N, float(radius), _p(spfh), _p(members),
+                                                 int(num_threads)), "usip_fpfh_spfh_f32_cpu")
+    return spfh, members, nrm
+
+
+def fpfh_gather_cpu(pc, count, spfh, members, keypoints, kp_count, radius: float, num_threads: int = 1):
+    """-> (fpfh f64 [B,M,33], kp_members i32 [B,M])"""
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    kp = np.ascontiguousarray(keypoints, dtype=np.float32)
+    if kp.ndim != 3 or kp.shape[:2] != (B, 3):
+        raise ValueError("fpfh: expected keypoints f32 [B,3,M], got %s" % (kp.shape,))
+    M = kp.shape[2]
+    kc = None if kp_count is None else np.ascontiguousarray(kp_count, dtype=np.int32)
+    s, m = np.ascontiguousarray(spfh, dtype=np.int32), np.ascontiguousarray(members, dtype=np.int32)
+    if s.shape != (B, N, ops.FPFH_WIDTH) or m.shape != (B, N) or (kc is not None and kc.shape != (B,)):
+        raise ValueError("fpfh: expected spfh i32 [B,N,33], members i32 [B,N] and kp_count i32 [B]")
+    fpfh, kp_members = np.zeros((B, max(M, 1), ops.FPFH_WIDTH), np.float64), np.zeros((B, max(M, 1)), np.int32)
+    _lib.check(_lib.lib().usip_fpfh_gather_f32_cpu(_p(a), _p(c), _p(s), _p(m), _p(kp), _p(kc), B, N, M, float(radius),
+                                                   _p(fpfh), _p(kp_members), int(num_threads)), "usip_fpfh_gather_f32_cpu")
+    return fpfh, kp_members
+
+
+def fpfh_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, normals=None,
+                         normal_radius: float = 1.0, want_f64: bool = False, min_neighbors: int = 3, num_threads: int = 1):
+    """-> (desc f32 [B,33,M], kp_members i32 [B,M][, fpfh f64 [B,M,33]])"""
+    spfh, members, _ = fpfh_spfh_cpu(pc, count, radius, normals, normal_radius, min_neighbors, num_threads)
+    fpfh, kp_members = fpfh_gather_cpu(pc, count, spfh, members, keypoints, kp_count, radius, num_threads)
+    desc = np.ascontiguousarray(fpfh.astype(np.float32).transpose(0, 2, 1))
+    return (desc, kp_members, fpfh) if want_f64 else (desc, kp_members)
 
 
 def sift_exp_cpu(x):

@@ -182,7 +182,8 @@ class RegistrationEvaluator:
 
     add_frame(id, pc, sn, node) runs detector -> NMS / top-k -> descriptor on one frame ([1,3,N], [1,Cs,N], [1,3,M]
     device tensors) and caches its keypoints f32 [3,top], descriptors f32 [D,top] and count; add_frame_keypoints(id, pc,
-    sn, kp, count) takes a baseline detector's keypoints instead (the detector may then be None).  evaluate(pairs) with
+    sn, kp, count) takes a baseline detector's keypoints instead (the detector may then be None); add_frame_descriptors(id,
+    kp, desc, count) takes descriptors computed elsewhere too (baselines.FpfhDescriptor: both may be None).  evaluate(pairs) with
     pairs = [(anc_id, pos_id, T_gt 3x4 mapping the positive frame into the anchor's)] matches descriptors, runs RANSAC
     and repeatability in batches and returns evaluate_kitti.m's and eval_rep.m's printed quantities; the poses are in
     the frame the keypoints are in.  One host read at the end."""
@@ -201,6 +202,10 @@ class RegistrationEvaluator:
         keypoints, sigmas = inference.run_model(self.detector, pc, sn, node)
         kp, count = select_keypoints_device(keypoints, sigmas, self.nms_radius, self.top)
         desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
+        return self._cache(frame_id, kp, desc, count)
+
+    def _cache(self, frame_id, kp, desc, count):
+        """kp [1,3,M'], desc [1,D,M'], count [1] with M' <= top -> the cached (kp [3,top], desc [D,top], count)"""
         width = self.top
         if kp.shape[2] < width:                                   # fewer nodes than top: pad to one width for batching
             kp = torch.cat((kp, kp[:, :, :1].expand(-1, -1, width - kp.shape[2])), 2)
@@ -217,12 +222,21 @@ class RegistrationEvaluator:
         kp = kp.to(self.device, torch.float32).contiguous()
         count = torch.clamp(count.to(self.device, torch.int32).reshape(1), max=kp.shape[2])
         desc = inference.describe_keypoints(self.descriptor, pc, sn, kp)
-        width = self.top
-        if kp.shape[2] < width:
-            kp = torch.cat((kp, kp[:, :, :1].expand(-1, -1, width - kp.shape[2])), 2)
-            desc = torch.cat((desc, desc[:, :, :1].expand(-1, -1, width - desc.shape[2])), 2)
-        self.frames[frame_id] = (kp[0].contiguous(), desc[0].contiguous(), count[0])
-        return self.frames[frame_id]
+        return self._cache(frame_id, kp, desc, count)
+
+    def add_frame_descriptors(self, frame_id, kp, desc, count):
+        """Keypoints AND descriptors from elsewhere (usip_amd.baselines.FpfhDescriptor on a baseline detector's keypoints): kp
+        f32 [1,3,M'], desc f32 [1,D,M'] with M' <= top, count i32 [1] on the device.  Padded and cached exactly as
+        add_frame_keypoints does; the evaluator's detector and descriptor may both be None."""
+        if kp.dim() != 3 or kp.shape[0] != 1 or kp.shape[1] != 3 or not 1 <= kp.shape[2] <= self.top:
+            raise ValueError("add_frame_descriptors: expected kp [1,3,M'] with 1 <= M' <= top = %d, got %s"
+                             % (self.top, tuple(kp.shape)))
+        if desc.dim() != 3 or desc.shape[0] != 1 or desc.shape[1] < 1 or desc.shape[2] != kp.shape[2]:
+            raise ValueError("add_frame_descriptors: expected desc [1,D,%d], got %s" % (kp.shape[2], tuple(desc.shape)))
+        kp = kp.to(self.device, torch.float32).contiguous()
+        desc = desc.to(self.device, torch.float32).contiguous()
+        count = torch.clamp(count.to(self.device, torch.int32).reshape(1), max=kp.shape[2])
+        return self._cache(frame_id, kp, desc, count)
 
     def frame_arrays(self, frame_id) -> Tuple[np.ndarray, np.ndarray]:
         """(xyz [M',3], desc [M',D]) of a cached frame on the host: what write_descriptors_bin takes."""

@@ -1994,6 +1994,52 @@ def harris_response(pc, count, perm, normals, radius: float, response: str = "ha
     return (res, members, visits) if want_visits else (res, members)
 
 
+# ------------------------------------------------------------------------------------------------ f-19 baseline descriptor: FPFH
+FPFH_WIDTH, FPFH_MMAX = 33, 65535
+
+
+def fpfh_spfh(pc, count, perm, normals, radius: float, want_visits: bool = False):
+    """f-19: normals f64 [B,3,N] (a row that is not finite or all zero: no normal) -> (spfh i32 [B,N,33], the integer counts of
+    the three 11-bin pair-feature histograms over every point's members, members i32 [B,N]); with want_visits also the
+    256-point tiles each workgroup walked, i32 [B, ceil(N/256)]."""
+    B, N = _need_frames(pc, count, perm, "fpfh")
+    _need_on(normals, "normals", torch.float64, (B, 3, N), pc.device)
+    if normals is None or not float(radius) > 0.0:
+        raise RuntimeError("fpfh: normals are required and radius must be positive")
+    spfh = torch.empty((B, N, FPFH_WIDTH), dtype=torch.int32, device=pc.device)
+    members = torch.empty((B, N), dtype=torch.int32, device=pc.device)
+    visits = _visits(B, N, pc.device, want_visits)
+    with torch.cuda.device(pc.device), prof.kernel("fpfh_spfh", (40.0 + 4.0 * FPFH_WIDTH) * B * N, keyed=True):
+        _lib.check(_lib.lib().usip_fpfh_spfh_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(normals), B, N, float(radius),
+                                                 _ptr(spfh), _ptr(members), _opt_ptr(visits), _stream(pc)),
+                   "usip_fpfh_spfh_f32")
+    return (spfh, members, visits) if want_visits else (spfh, members)
+
+
+def fpfh_gather(pc, count, perm, spfh, members, keypoints, kp_count, radius: float):
+    """f-19: keypoints f32 [B,3,M] (any positions), kp_count i32 [B] or None -> (fpfh f64 [B,M,33], kp_members i32 [B,M]): the
+    SPFH rows of the cloud points within the radius of each keypoint, weighted by 1 / squared distance, each block of eleven
+    scaled to the sum 100."""
+    B, N = _need_frames(pc, count, perm, "fpfh")
+    _need(keypoints, "keypoints", torch.float32)
+    if keypoints.dim() != 3 or keypoints.shape[0] != B or keypoints.shape[1] != 3 or keypoints.device != pc.device \
+            or not 1 <= keypoints.shape[2] <= FPFH_MMAX:
+        raise RuntimeError("fpfh: expected keypoints f32 [B,3,M] on %s with M in 1..%d" % (pc.device, FPFH_MMAX))
+    M = keypoints.shape[2]
+    _need_on(spfh, "spfh", torch.int32, (B, N, FPFH_WIDTH), pc.device)
+    _need_on(members, "members", torch.int32, (B, N), pc.device)
+    _need_on(kp_count, "kp_count", torch.int32, (B,), pc.device)
+    if spfh is None or members is None or not float(radius) > 0.0:
+        raise RuntimeError("fpfh: spfh and members are required and radius must be positive")
+    fpfh = torch.empty((B, M, FPFH_WIDTH), dtype=torch.float64, device=pc.device)
+    kp_members = torch.empty((B, M), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("fpfh_gather", 16.0 * B * N + (8.0 * FPFH_WIDTH + 16.0) * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_fpfh_gather_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(spfh), _ptr(members),
+                                                   _ptr(keypoints), _opt_ptr(kp_count), B, N, M, float(radius), _ptr(fpfh),
+                                                   _ptr(kp_members), _stream(pc)), "usip_fpfh_gather_f32")
+    return fpfh, kp_members
+
+
 # ------------------------------------------------------------------------------------------------ f-17 baseline keypoints: SIFT3D
 SIFT_NEAREST = 25
 
