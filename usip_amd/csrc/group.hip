@@ -10,7 +10,12 @@
 //                     written straight into a channel slice of the (pre-concatenated) output.
 //   group_gather_bwd  dx[b,c,n] += sum_{(m,k): idx = n} dout[b, coff+c, m, k]   (float atomics, as
 //                     ATen's scatter_add; the only non-deterministic summation order on the path)
-//   group_max         pooled[b,c,m] = max_k z[b,c,m,k], arg = first k attaining it
+//   group_max         pooled[b,c,m] = max_k z[b,c,m,k], arg = first k attaining it.  A NaN counts as the largest value,
+//                     as in torch.max: a row that holds one pools to NaN and arg is the FIRST NaN's k; -0.0 and +0.0
+//                     tie (the first of them wins) and pooled carries the bits of z at arg.  With the activation on the
+//                     fly (group_max_act) the rule holds for the ACTIVATED values: without ReLU a NaN of
+//                     fma(y, scale, shift) wins, with ReLU fmaxf(NaN, 0) = 0 has already replaced it, exactly as in
+//                     bn_apply and in the GEMM prologues that read the same y.
 //   group_max_bwd     dz[b,c,m,k] = (k == arg[b,c,m]) ? dpooled[b,c,m] : 0
 #include "common.h"
 
@@ -48,6 +53,23 @@ __global__ __launch_bounds__(256) void group_gather_bwd_kernel(
     for (int c = 0; c < C; ++c) atomicAdd(&xb[(long long)c * N + n], gb[(long long)c * P + p]);
 }
 
+// The pooling order: NaN above everything, then the value; at equal values (two NaNs are equal here) the lower k.
+// Inside a lane, where k only grows, pool_gt<true> says whether a later element replaces the best so far.  A lane whose
+// best is a NaN then enters the cross-lane steps as (+inf, k - POOL_NAN): the steps' plain rule, ov > best ||
+// (ov == best && ok < bk), lets it beat a real +inf, lets the lowest NaN k win, and is the rule rows without NaN always
+// had; whoever stores finds bk < 0 and puts k and the NaN back.  NANS = false (values that passed through fmaxf(., 0)
+// cannot be NaN) is v > best and nothing else.
+constexpr int POOL_NAN = 0x40000000;
+template <bool NANS>
+__device__ __forceinline__ bool pool_gt(float v, float best)
+{
+    return NANS ? (!(v <= best) && best == best) : v > best;
+}
+__device__ __forceinline__ void pool_hide_nan(float& best, int& bk)
+{
+    if (best != best) { best = __builtin_inff(); bk -= POOL_NAN; }
+}
+
 // L lanes (a power of two, <= 64) cooperate on one row of K values; rows = B*C*M.
 template <int L>
 __global__ __launch_bounds__(256) void group_max_kernel(
@@ -62,16 +84,21 @@ __global__ __launch_bounds__(256) void group_max_kernel(
         const float* zr = z + row * K;
         for (int k = sub; k < K; k += L) {
             const float v = zr[k];
-            if (bk == 0x7fffffff || v > best) { best = v; bk = k; }   // first k wins this lane's ties
+            if (bk == 0x7fffffff || pool_gt<true>(v, best)) { best = v; bk = k; }   // first k wins this lane's ties
         }
     }
+    pool_hide_nan(best, bk);
 #pragma unroll
     for (int off = L / 2; off > 0; off >>= 1) {
         const float ov = __shfl_xor(best, off);
         const int ok = __shfl_xor(bk, off);
         if (ov > best || (ov == best && ok < bk)) { best = ov; bk = ok; }
     }
-    if (sub == 0 && row < rows) { pooled[row] = best; arg[row] = bk; }
+    if (sub == 0 && row < rows) {
+        if (bk < 0) { bk += POOL_NAN; best = z[row * K + bk]; }
+        pooled[row] = best;
+        arg[row] = bk;
+    }
 }
 
 // K % 4 == 0 and L = K/4 a power of two <= 64: every lane owns 4 consecutive neighbours (one 16-B load).
@@ -83,7 +110,8 @@ __global__ __launch_bounds__(256) void group_max_kernel(
 // the L lanes of a row through DPP lane permutations (quad_perm / row_half_mirror / row_mirror: pure VALU) instead of
 // three ds_bpermute per step.  Neither changed the time (70 us for 268 MB at K = 64, tools/group_max_bench.py): the pass
 // is bound by its read rate, not by instructions; eight rows per thread group instead of four halved the workgroups
-// and made the smaller pools slower (36 -> 50 us), so four it stays.)
+// and made the smaller pools slower (36 -> 50 us), so four it stays.  Instructions are not free either: three more compares in
+// every cross-lane step cost 16 % at K = 64 (33 -> 38.5 us, profiles/r08a_group_max_nan_ab.txt), hence NANS below.)
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v)
 {
@@ -108,7 +136,7 @@ __device__ __forceinline__ void argmax_step(float& best, int& bk, float& braw)
 // 46.8-47.8 (profiles/r05b_forms_ab.txt) -- many short workgroups spread this pass's reads over the chip better than
 // fewer long ones.  Kept behind knob r5_forms bit 3 as the measured form of that idea.  Same comparisons in the same
 // order: same results either way.
-template <int L>
+template <int L, bool NANS>
 __global__ __launch_bounds__(256) void group_max4_kernel(
     const float* __restrict__ z, float* __restrict__ pooled, int32_t* __restrict__ arg, long long rows,
     const float* __restrict__ coef, int relu, int C, int M, float* __restrict__ zarg, int nbatch)
@@ -141,9 +169,10 @@ __global__ __launch_bounds__(256) void group_max4_kernel(
             }
             float best = w.x, braw = v[j].x;              // braw: the INPUT value at the arg-max (the pre-BN output when
             int bk = sub * 4;                             // coef is given): the pooled layer's backward needs exactly it
-            if (w.y > best) { best = w.y; bk = sub * 4 + 1; braw = v[j].y; }
-            if (w.z > best) { best = w.z; bk = sub * 4 + 2; braw = v[j].z; }
-            if (w.w > best) { best = w.w; bk = sub * 4 + 3; braw = v[j].w; }
+            if (pool_gt<NANS>(w.y, best)) { best = w.y; bk = sub * 4 + 1; braw = v[j].y; }
+            if (pool_gt<NANS>(w.z, best)) { best = w.z; bk = sub * 4 + 2; braw = v[j].z; }
+            if (pool_gt<NANS>(w.w, best)) { best = w.w; bk = sub * 4 + 3; braw = v[j].w; }
+            if constexpr (NANS) pool_hide_nan(best, bk);
             if constexpr (L == 4 || L == 16) {
                 // every lane of the row ends up with the row's (max, first arg-max): the comparison is symmetric, so any
                 // pairing of lanes that covers the row works -- xor 1, xor 2 inside a quad, then the two mirror steps
@@ -163,6 +192,9 @@ __global__ __launch_bounds__(256) void group_max4_kernel(
                 }
             }
             if (sub == 0 && row < rows) {
+                if constexpr (NANS) {                       // without coef braw IS the NaN; with it, fma(braw, s0, s1) was
+                    if (bk < 0) { bk += POOL_NAN; best = coef ? __builtin_nanf("") : braw; }
+                }
                 pooled[row] = best;
                 arg[row] = bk;
                 if (zarg) zarg[row] = braw;
@@ -346,8 +378,12 @@ extern "C" int usip_group_max_act_f32(const float* y, const float* coef, int rel
         const int nbatch = group_max4_batches(batches);                                          \
         const long long blocks = (batches + nbatch - 1) / nbatch;                                \
         if (blocks > 0x7fffffffLL) return USIP_EINVAL;                                           \
-        USIP_LAUNCH((group_max4_kernel<L_>), dim3((unsigned)blocks), dim3(256), 0, st, y, pooled, arg, rows, \
-                    coef, relu, C, M, yarg, nbatch);                                             \
+        if (relu)                                                                                \
+            USIP_LAUNCH((group_max4_kernel<L_, false>), dim3((unsigned)blocks), dim3(256), 0, st, y, pooled, arg, rows, \
+                        coef, relu, C, M, yarg, nbatch);                                        \
+        else                                                                                     \
+            USIP_LAUNCH((group_max4_kernel<L_, true>), dim3((unsigned)blocks), dim3(256), 0, st, y, pooled, arg, rows, \
+                        coef, relu, C, M, yarg, nbatch);                                        \
     }
     USIP_GM4(1) USIP_GM4(2) USIP_GM4(4) USIP_GM4(8) USIP_GM4(16) USIP_GM4(32) USIP_GM4(64)
 #undef USIP_GM4
@@ -370,7 +406,7 @@ extern "C" int usip_group_max_f32(const float* z, float* pooled, int32_t* arg, l
             const int nbatch = group_max4_batches(batches);                                      \
             const long long blocks = (batches + nbatch - 1) / nbatch;                            \
             if (blocks > 0x7fffffffLL) return USIP_EINVAL;                                       \
-            USIP_LAUNCH((group_max4_kernel<L_>), dim3((unsigned)blocks), dim3(256), 0, st, z, pooled, arg, rows, \
+            USIP_LAUNCH((group_max4_kernel<L_, true>), dim3((unsigned)blocks), dim3(256), 0, st, z, pooled, arg, rows, \
                         (const float*)nullptr, 0, 1, 1, (float*)nullptr, nbatch);                \
         }
         USIP_GM4(1) USIP_GM4(2) USIP_GM4(4) USIP_GM4(8) USIP_GM4(16) USIP_GM4(32) USIP_GM4(64)
