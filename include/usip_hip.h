@@ -27,8 +27,11 @@ extern "C" {
 
 #define USIP_OK      0
 #define USIP_EINVAL (-1)
+/* Counts incompatible changes of this file; usip_version() reports it as "abi=<n>" and usip_amd/_lib.py, which reads the
+ * signatures, the structs and this number from this file, refuses a library that reports another (a bare decimal literal). */
+#define USIP_ABI 6
 
-/* Library identification: "usip_hip <version> gfx950". */
+/* Library identification: "usip_hip <version> gfx950 abi=<USIP_ABI> flags=<...>". */
 const char* usip_version(void);
 
 /* Launch-geometry knobs for measurement sweeps (tools/): they change HOW a result is computed (rows per

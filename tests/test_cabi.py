@@ -1,8 +1,10 @@
 """CPU tests of the drop-in boundary: the C-ABI library loads, exports every symbol that
 include/usip_hip.h declares, and the host-side mirror of the reference interface behaves like
 the reference's (names, argument meaning, error behaviour).  No device compute here."""
+import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -26,6 +28,88 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), "libusip_hip.so does not export %s" % name
         assert name in _lib.SIGNATURES, "no ctypes signature for %s" % name
     assert b"gfx950" in lib.usip_version()
+    # the signatures are read from the header (usip_amd/_lib.py): the reader neither misses nor invents a declaration
+    assert set(_lib.SIGNATURES) == set(declared)
+
+
+_V, _I, _D, _LL, _U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_longlong, ctypes.c_uint64
+# written by hand from include/usip_hip.h, one row for each kind of type the reader maps
+_PINNED_SIGNATURES = {
+    "usip_version": ([], ctypes.c_char_p),                                                          # const char* returned
+    "usip_launch_log_entry": ([_I, ctypes.POINTER(ctypes.c_uint)], ctypes.c_char_p),                # unsigned*
+    "usip_index_max_geometry": ([_I] * 4 + [ctypes.POINTER(ctypes.c_int)] * 3, _I),                 # int*
+    "usip_ball_query_f32": ([_V, _V, ctypes.c_float, _I, _I, _I, _I, _V], _I),                      # float
+    "usip_iss_saliency_f32": ([_V, _V, _V, _I, _I, _D, _D, _D, _I, _V, _V, _V, _V], _I),            # double
+    "usip_nearest_workspace": ([_I, _I, _I], _LL),                                                  # long long returned
+    "usip_pairs_build_f32": ([_V, _V, _V, _I, _V, _I, _LL, _U64, _U64, _LL, _V, _V, _V], _I),       # uint64_t, struct*
+    "usip_mlp_split3_multi_f32": ([_V, _I, _I, _V], _I),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_PINNED_SIGNATURES))
+def test_signatures_read_from_the_header_match_pinned_rows(name):
+    from usip_amd import _lib
+    assert _lib.SIGNATURES[name] == _PINNED_SIGNATURES[name]
+
+
+def test_struct_layouts_read_from_the_header_are_the_compilers(tmp_path):
+    """sizeof and every field's offset and size of every struct in _lib.STRUCTS, against a C program that includes the header
+    (the host C compiler oracle/Makefile uses; a missing compiler fails)."""
+    from usip_amd import _lib
+    assert len(_lib.STRUCTS) == 8
+    lines, expected = [], []
+    for name, cls in _lib.STRUCTS.items():
+        lines.append('printf("%s %%zu\\n", sizeof(%s));' % (name, name))
+        expected.append("%s %d" % (name, ctypes.sizeof(cls)))
+        for field, _ in cls._fields_:
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));'
+                         % (name, field, name, field, name, field))
+            expected.append("%s.%s %d %d" % (name, field, getattr(cls, field).offset, getattr(cls, field).size))
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "usip_hip.h"\nint main(void) {\n%s\nreturn 0;\n}\n'
+                   % "\n".join(lines))
+    subprocess.check_call([os.environ.get("CC", "gcc"), "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)])
+    assert subprocess.check_output([str(exe)]).decode().split("\n")[:-1] == expected
+    # a nested struct is the class already built, so ops.PairsRecipeC() can be assigned to recipe.cloud
+    assert dict(_lib.STRUCTS["usip_desc_pairs_recipe"]._fields_)["cloud"] is _lib.STRUCTS["usip_pairs_recipe"]
+
+
+_SYNTHETIC_HEADER = """
+/* no declaration: int usip_x(int a); */
+#define USIP_SOMETHING 3
+typedef struct usip_inner { int a, b; const float* p; double* q[2]; } usip_inner;
+typedef struct usip_outer {
+    usip_inner in;      // nested: int usip_y(void);
+    long long n; unsigned u;
+} usip_outer;
+const char* usip_name(void);
+int usip_three(const float* x,
+               int32_t* idx[2],
+               const usip_outer* o, uint64_t seed);
+"""
+
+
+def test_header_reader_on_synthetic_text():
+    from usip_amd import _lib
+    structs, signatures = _lib.read_header(_SYNTHETIC_HEADER)
+    assert list(structs) == ["usip_inner", "usip_outer"]
+    assert structs["usip_inner"]._fields_ == [("a", _I), ("b", _I), ("p", _V), ("q", _V * 2)]
+    assert structs["usip_outer"]._fields_ == [("in", structs["usip_inner"]), ("n", _LL), ("u", ctypes.c_uint)]
+    assert signatures == {"usip_name": ([], ctypes.c_char_p), "usip_three": ([_V, _V * 2, _V, _U64], _I)}
+    # what the reader does not know raises and quotes the declaration: it never falls back to int
+    for bad, quoted in (("int usip_bad(size_t n);", "size_t n"), ("size_t usip_bad(int n);", "size_t usip_bad"),
+                        ("typedef struct s { short a; } s;", "short a"), ("typedef int usip_t;", "typedef int usip_t"),
+                        ("int usip_bad(float** x);", "float** x"), ("int usip_bad(int);", "int")):
+        with pytest.raises(ValueError, match=re.escape(quoted)):
+            _lib.read_header(_SYNTHETIC_HEADER + bad)
+
+
+def test_abi_number_is_the_headers():
+    from usip_amd import _lib
+    text = open(os.path.join(ROOT, "include", "usip_hip.h")).read()
+    abi = int(re.search(r"^#define\s+USIP_ABI\s+(\d+)", text, re.M).group(1))
+    assert _lib.ABI == abi
+    assert _lib.lib().usip_version() == b"usip_hip 0.5 gfx950 abi=%d flags=no-contract,no-fast-math,no-slp" % abi
 
 
 # (channel rows, prefetch depth, threads) for the knob triples (ch, u, th) in (1, 2, 4, 8) x (1, 2, 4) x (256, 512, 1024), in

@@ -1,304 +1,92 @@
 """ctypes loader of libusip_hip.so -- the only way the product reaches its kernels.
 
 There is no fallback: if the library is missing or fails to load, every operator raises.
+
+The interface is declared once, in include/usip_hip.h.  This module reads that file when it is imported (read_header):
+SIGNATURES (the argument and result types lib() installs on every entry point), STRUCTS (the ctypes classes of the
+header's structs) and ABI all come from it, so a new entry point or struct field needs its declaration and nothing here.
+A declaration the reader cannot map is an error at import, never a guess.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # USIP_LIB=<path>: load another BUILD of the same library (same-box A/B of two builds, tools/ab_build.sh); never a fallback
 LIB_PATH = os.environ.get("USIP_LIB") or os.path.join(_HERE, "libusip_hip.so")
-ABI = 6                      # = "abi=<n>" of usip_version(): bumped with every incompatible change of include/usip_hip.h
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "usip_hip.h")      # where usip_amd/build.py takes it from
 _lib = None
 
-_f32p = ctypes.c_void_p
-_i32p = ctypes.c_void_p
-_int = ctypes.c_int
-_flt = ctypes.c_float
-_dbl = ctypes.c_double
-_stream = ctypes.c_void_p
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong,
+            "unsigned": ctypes.c_uint, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64}
+_POINTEES = ("void", "char", "uint8_t", "unsigned long long")               # types the header only ever points to
+_TYPED_POINTERS = {"char": ctypes.c_char_p, "int": ctypes.POINTER(ctypes.c_int), "unsigned": ctypes.POINTER(ctypes.c_uint)}
+_DECL = re.compile(r"\s*(?:typedef\s+struct\s+\w*\s*\{(?P<body>[^{}]*)\}\s*(?P<struct>\w+)\s*;"
+                   r"|(?P<res>[\w\s*]+?)\b(?P<fn>\w+)\s*\((?P<args>[^()]*)\)\s*;"
+                   r'|enum\s*\{[^{}]*\}\s*;|extern\s+"C"\s*\{|\})')
 
-# name -> argtypes; must list every symbol include/usip_hip.h declares (tests check this).
-SIGNATURES = {
-    "usip_version": ([], ctypes.c_char_p),
-    "usip_set_tuning": ([ctypes.c_char_p, _int], _int),
-    "usip_tuning_value": ([_int], _int),
-    "usip_launch_log": ([_int], _int),
-    "usip_launch_log_entry": ([_int, ctypes.POINTER(ctypes.c_uint)], ctypes.c_char_p),
-    "usip_wgrad_defer": ([_int], _int),
-    "usip_wgrad_defer_on": ([_stream], _int),
-    "usip_wgrad_defer_hold": ([_int], _int),
-    "usip_wgrad_flush": ([_stream], _int),
-    "usip_index_max_f32": ([_f32p, _i32p, _i32p, _int, _int, _int, _int, _stream], _int),
-    "usip_index_max_geometry": ([_int, _int, _int, _int] + [ctypes.POINTER(_int)] * 3, _int),
-    "usip_index_max_f32_cpu": ([_f32p, _i32p, _i32p, _int, _int, _int, _int, _int], _int),
-    "usip_ball_query_f32": ([_f32p, _i32p, _flt, _int, _int, _int, _int, _stream], _int),
-    "usip_ball_query_f32_cpu": ([_f32p, _i32p, _flt, _int, _int, _int, _int], _int),
-    "usip_pairwise_dist_f32_cpu": ([_f32p, _f32p, _f32p, _int, _int, _int], _int),
-    "usip_pairwise_dist_f32": ([_f32p, _f32p, _f32p, _int, _int, _int, _stream], _int),
-    "usip_som_assign_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _stream], _int),
-    "usip_som_cluster_f32": ([_f32p, _i32p, _f32p, _i32p, _f32p, _int, _int, _int, _stream], _int),
-    "usip_som_cluster_csr_f32": ([_f32p, _i32p, _i32p, _i32p, _f32p, _i32p, _f32p, _int, _int, _int, _stream], _int),
-    "usip_index_max_values_f32": ([_f32p, _i32p, _i32p, _i32p, _f32p, _int, _int, _int, _int, _int, _stream], _int),
-    "usip_index_max_values_backward_add_f32": ([_f32p, _i32p, _i32p, _f32p, _int, _int, _int, _int, _int, _int,
-                                                _stream], _int),
-    "usip_index_max_values_backward_f32": ([_f32p, _i32p, _i32p, _i32p, _f32p, _int, _int, _f32p, _int, _int, _int, _int,
-                                            _stream], _int),
-    "usip_mlp_narrow_forward_blocks": ([_int, _int, _int, _int], _int),
-    "usip_mlp_narrow_forward_f32": ([_f32p, _int, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _int, _f32p, _int, _int,
-                                     _int, _int, _stream], _int),
-    "usip_detector_head_f32": ([_f32p, _f32p, _flt, _f32p, _f32p, _int, _int, _stream], _int),
-    "usip_detector_head_backward_f32": ([_f32p, _f32p, _f32p, _f32p, _int, _int, _stream], _int),
-    "usip_rigid_transform_f32": ([_f32p, _f32p, _f32p, _f32p, _f32p, _int, _int, _int, _stream], _int),
-    "usip_detector_loss_combine_f32": ([_f32p, _f32p, _flt, _f32p, ctypes.c_longlong, _stream], _int),
-    "usip_fill_scaled_f32": ([_f32p, _flt, _f32p, ctypes.c_longlong, _stream], _int),
-    "usip_mlp_split3_blocks": ([_int, _int, _int], _int),
-    "usip_mlp_split3_multi_f32": ([ctypes.c_void_p, _int, _int, _stream], _int),
-    "usip_bn_group_dy_sum_f32": ([_f32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_csr_by_index_i32": ([_i32p, _i32p, _i32p, _int, _int, _int, _stream], _int),
-    "usip_segment_sum_supported": ([_int, _int], _int),
-    "usip_segment_sum_f32": ([_f32p, _i32p, _i32p, _f32p, _int, _int, _int, _int, _int, _int, _stream], _int),
-    "usip_nearest_backward_f32": ([_f32p, _f32p, _f32p, _i32p, _f32p, _f32p, _f32p, _int, _int, _int, _int, _stream],
-                                  _int),
-    "usip_nearest_nd_f32": ([_f32p, _f32p, _f32p, _i32p, _int, _int, _int, _int, _stream], _int),
-    "usip_chamfer_prob_f32": ([_f32p, _i32p, _f32p, _i32p, _f32p, _f32p, _f32p, _int, _int, _int, _stream], _int),
-    "usip_chamfer_prob_backward_f32": ([_f32p, _f32p, _i32p, _f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
-                                        _int, _int, _int, _stream], _int),
-    "usip_nearest_workspace": ([_int, _int, _int], ctypes.c_longlong),
-    "usip_nearest_f32": ([_f32p, _f32p, _f32p, _i32p, _f32p, _i32p, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_tiles": ([_int, _int, _int], _int),
-    "usip_mlp_gemm_f32": ([_f32p, _int, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int,
-                           _f32p, _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_bf16": ([_f32p, _int, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int,
-                            _f32p, _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_f32x3": ([_f32p, _int, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int,
-                             _f32p, _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_f32x3_used": ([_int, _int, _int, _int], _int),
-    "usip_mlp_x3p_tile_rows": ([_int, _int, _int], _int),
-    "usip_mlp_x3p_tile_cols": ([_int, _int, _int, _int, _int], _int),
-    "usip_mlp_split3_bytes": ([_int, _int], ctypes.c_longlong),
-    "usip_mlp_split3_f32": ([_f32p, _int, _int, _int, _int, ctypes.c_void_p, _stream], _int),
-    "usip_mlp_gemm_x3p_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int,
-                               _f32p, _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_x2r_tiles": ([_int, _int], _int),
-    "usip_mlp_gemm_x2r_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int, _f32p,
-                               _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_split2h_f32": ([_f32p, _int, _int, _int, _int, ctypes.c_void_p, _stream], _int),
-    "usip_mlp_gemm_x2h_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _i32p, _int,
-                               _f32p, _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_x2d_red_tiles": ([_int, _int, _int, _int, _int], _int),
-    "usip_mlp_gemm_x2h_red_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _int, _f32p, _i32p, _int, _f32p, _f32p, _f32p, _f32p,
-                                   _f32p, _int, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_gemm_x2h_fork_supported": ([_int, _int, _int, _int, _int], _int),
-    "usip_mlp_gemm_x2h_fork_f32": ([ctypes.c_void_p, _f32p, _f32p, _f32p, _f32p, _int, _f32p, _i32p, _int, _int, _int, _int,
-                                    _int, _stream], _int),
-    "usip_mlp_wgrad_f32x3_used": ([_int, _int, _int, _int], _int),
-    "usip_bn_pool_backward_reduce_f32": ([_f32p, _i32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _f32p, _f32p,
-                                          _f32p, _f32p, _int, _int, _int, _int, _int, _stream], _int),
-    "usip_bn_finalize_f32": ([_f32p, _int, _int, ctypes.c_longlong, _f32p, _f32p, _flt, _flt, _f32p, _f32p, _f32p,
-                              _f32p, _f32p, _stream], _int),
-    "usip_bn_apply_f32": ([_f32p, _f32p, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_bn_backward_reduce_f32": ([_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _f32p,
-                                     _f32p, _int, _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_wgrad_workspace": ([_int, _int, _int, _int], ctypes.c_longlong),
-    "usip_mlp_wgrad_f32": ([_f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _f32p, _int, _int,
-                            _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_wgrad_bf16": ([_f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _f32p, _int, _int,
-                             _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_wgrad_f32x3": ([_f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _f32p, _int, _int,
-                              _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_wgrad_x2h_f32": ([_f32p, _f32p, _f32p, _int, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _f32p, _int, _int,
-                                _int, _int, _int, _int, _stream], _int),
-    "usip_mlp_narrow_backward_supported": ([_int, _int, _int], _int),
-    "usip_mlp_narrow_backward_workspace": ([_int, _int, _int], ctypes.c_longlong),
-    "usip_mlp_narrow_backward_blocks": ([_int, _int, _int], _int),
-    "usip_mlp_layer_backward_x2h_supported": ([_int, _int, _int, _int], _int),
-    "usip_mlp_layer_backward_x2h_workspace": ([_int, _int, _int, _int], ctypes.c_longlong),
-    "usip_mlp_layer_backward_x2h_blocks": ([_int, _int, _int, _int], _int),
-    "usip_mlp_layer_backward_x2h_f32": ([_f32p, _f32p, _f32p, _f32p, _i32p, _int, _f32p, _int, _f32p, ctypes.c_void_p,
-                                         _f32p, _int, _f32p, _f32p, _int, _f32p, _f32p, _int, _int, _int, _int, _stream],
-                                        _int),
-    "usip_mlp_layer_backward_x2h_ws_f32": ([_f32p, _f32p, _f32p, _f32p, _int, _f32p, ctypes.c_void_p, _f32p, _int, _f32p,
-                                            _f32p, _int, _f32p, _f32p, _int, _f32p, _f32p, _int, _int, _int, _int, _stream],
-                                           _int),
-    "usip_mlp_wsum_finalize_f32": ([_f32p, _f32p, _int, _int, _f32p, _f32p, _int, _f32p, _int, _stream], _int),
-    "usip_mlp_narrow_backward_f32": ([_f32p, _f32p, _f32p, _f32p, _int, _f32p, _f32p, _int, _f32p, _int, _f32p, _f32p,
-                                      _int, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_bn_backward_finalize_f32": ([_f32p, _int, _int, ctypes.c_longlong, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
-                                       _stream], _int),
-    "usip_bn_backward_finalize_max_f32": ([_f32p, _int, _int, ctypes.c_longlong, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,
-                                           _f32p, _int, _f32p, _int, _stream], _int),
-    "usip_group_max_act_f32": ([_f32p, _f32p, _int, _f32p, _i32p, _f32p, _int, _int, _int, _int, _stream], _int),
-    "usip_group_gather_f32": ([_f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _int, _int, _int, _int,
-                               _stream], _int),
-    "usip_group_gather_backward_f32": ([_f32p, _i32p, _f32p, _int, _int, _int, _int, _int, _int, _int, _stream], _int),
-    "usip_group_max_f32": ([_f32p, _f32p, _i32p, ctypes.c_longlong, _int, _stream], _int),
-    "usip_group_max_backward_f32": ([_f32p, _i32p, _f32p, ctypes.c_longlong, _int, _stream], _int),
-    "usip_group_max_backward_add_f32": ([_f32p, _i32p, _f32p, ctypes.c_longlong, _int, _stream], _int),
-    "usip_multi_transpose_f32": ([_f32p, _f32p, _i32p, _int, _int, _stream], _int),
-    "usip_adam_step_f32": ([_f32p, _f32p, _f32p, _f32p, _f32p, _flt, _flt, _flt, _flt, ctypes.c_longlong, _stream], _int),
-    "usip_adam_step_hyper_f32": ([_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, ctypes.c_longlong, _stream], _int),
-    "usip_knn_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _stream], _int),
-    "usip_knn_points_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _stream], _int),
-    "usip_knn_layer_supported": ([_int, _int, _int], _int),
-    "usip_knn_layer_forward_f32": ([_f32p, _f32p, _int, _f32p, _f32p, _i32p, _f32p, _f32p, _int, _int, _int, _int, _int,
-                                    _stream], _int),
-    "usip_knn_layer_backward_f32": ([_f32p, _f32p, _f32p, _int, _f32p, _i32p, _i32p, _f32p, _f32p, _int, _int, _int, _int,
-                                     _int, _stream], _int),
-    "usip_fps_f32": ([_f32p, _i32p, _i32p, _int, _int, _int, _stream], _int),
-    "usip_nms_f32": ([_f32p, _f32p, _flt, _i32p, _i32p, _int, _int, _stream], _int),
-    "usip_ball_query_coords_f32": ([_f32p, _f32p, _i32p, _flt, _int, _int, _int, _int, _stream], _int),
-    # f-5 training pairs: the structs go by address (usip_amd/pairs.py builds them)
-    "usip_pairs_workspace_bytes": ([ctypes.c_void_p, _int], ctypes.c_longlong),
-    "usip_pairs_workspace_offset": ([ctypes.c_void_p, _int, _int], ctypes.c_longlong),
-    "usip_pairs_build_f32": ([ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int, ctypes.c_longlong,
-                              ctypes.c_uint64, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                              _stream], _int),
-    "usip_pairs_apply_f32": ([ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int,
-                              ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
-    "usip_pairs_build_f32_cpu": ([ctypes.c_void_p, ctypes.c_void_p, _f32p, ctypes.c_void_p, _int, _i32p, _int,
-                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p], _int),
-    # f-6 evaluation: RANSAC registration, repeatability, counted matching (usip_amd/evaluation.py)
-    "usip_ransac_trials_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p, _i32p,
-                                ctypes.c_void_p, _i32p, _stream], _int),
-    "usip_ransac_trials_explicit_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, _i32p, _i32p, ctypes.c_void_p,
-                                         _stream], _int),
-    "usip_ransac_select_f32": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p,
-                                _i32p, _i32p] + [ctypes.c_void_p] * 9 + [_stream], _int),
-    "usip_compare_transform_f64": ([ctypes.c_void_p] * 2 + [_int] + [ctypes.c_void_p] * 2 + [_stream], _int),
-    "usip_repeatability_f32": ([_f32p, _i32p, _f32p, _i32p, ctypes.c_void_p, _dbl, _int, _int, _int, ctypes.c_void_p,
-                                _i32p, ctypes.c_void_p, _stream], _int),
-    "usip_nearest_nd_counted_f32": ([_f32p, _f32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _int, _stream], _int),
-    "usip_ransac_trials_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p, _i32p,
-                                    _i32p, ctypes.c_void_p, _i32p, _int], _int),
-    "usip_ransac_select_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, _int, _dbl, ctypes.c_uint64, ctypes.c_void_p,
-                                    _i32p, _i32p] + [ctypes.c_void_p] * 9, _int),
-    "usip_compare_transform_f64_cpu": ([ctypes.c_void_p] * 2 + [_int] + [ctypes.c_void_p] * 2, _int),
-    "usip_repeatability_f32_cpu": ([_f32p, _i32p, _f32p, _i32p, ctypes.c_void_p, _dbl, _int, _int, _int, ctypes.c_void_p,
-                                    _i32p, ctypes.c_void_p], _int),
-    "usip_nearest_nd_counted_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _int], _int),
-    # f-7 raw scans prepared: neighbours, normals + curvature, voxel grid average (usip_amd/prepare.py)
-    "usip_scan_knn_f32": ([_f32p, _i32p, _int, _int, _i32p, _i32p, _stream], _int),
-    "usip_scan_normals_f32": ([_f32p, _i32p, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _f32p, _stream], _int),
-    "usip_scan_voxel_keys_f32": ([_f32p, _int, _f32p, _dbl, ctypes.c_void_p, _stream], _int),
-    "usip_scan_voxel_average_f32": ([_f32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _f32p, _stream], _int),
-    "usip_scan_knn_f32_cpu": ([_f32p, _int, _int, _i32p, _int], _int),
-    "usip_scan_normals_f32_cpu": ([_f32p, _i32p, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _f32p], _int),
-    "usip_scan_voxel_keys_f32_cpu": ([_f32p, _int, _f32p, _dbl, ctypes.c_void_p], _int),
-    "usip_scan_voxel_average_f32_cpu": ([_f32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _f32p], _int),
-    # f-8 descriptor training batches from posed scans: the structs go by address (usip_amd/desc_pairs.py builds them)
-    "usip_desc_pairs_workspace_bytes": ([ctypes.c_void_p, _int], ctypes.c_longlong),
-    "usip_desc_pairs_workspace_offset": ([ctypes.c_void_p, _int, _int], ctypes.c_longlong),
-    "usip_desc_pairs_build_f32": ([ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_uint64, ctypes.c_uint64,
-                                   ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
-    "usip_desc_pairs_apply_f32": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_void_p,
-                                   ctypes.c_void_p, _stream], _int),
-    "usip_desc_pairs_build_f32_cpu": ([ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _i32p, _int, ctypes.c_uint64,
-                                       ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p], _int),
-    # f-9 indoor fragment registration: top-k matching, union, information, overlap (usip_amd/fragments.py); RANSAC is f-6's
-    "usip_knn_nd_counted_f32": ([_f32p, _f32p, _i32p, _i32p, _int, _f32p, _i32p, _i32p, _int, _int, _int, _int, _stream],
-                                _int),
-    "usip_match_union_i32": ([_i32p] * 4 + [_int] * 4 + [_i32p, _i32p, _stream], _int),
-    "usip_information_f32": ([_f32p, ctypes.c_void_p, _int, _int, ctypes.c_void_p, _stream], _int),
-    "usip_overlap_keys_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _int, _int,
-                               ctypes.c_void_p, _stream], _int),
-    "usip_overlap_ratio_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, ctypes.c_void_p, _i32p,
-                                _i32p, _int, _int, _dbl, _i32p, ctypes.c_void_p, _stream], _int),
-    "usip_knn_nd_counted_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, _int, _f32p, _i32p, _i32p, _int, _int, _int, _int, _int],
-                                    _int),
-    "usip_match_union_i32_cpu": ([_i32p] * 4 + [_int] * 4 + [_i32p, _i32p], _int),
-    "usip_information_f32_cpu": ([_f32p, ctypes.c_void_p, _int, _int, ctypes.c_void_p], _int),
-    "usip_overlap_keys_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _int, _int,
-                                   ctypes.c_void_p], _int),
-    "usip_overlap_ratio_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, ctypes.c_void_p,
-                                    _i32p, _i32p, _int, _int, _dbl, _int, _i32p, ctypes.c_void_p, _int], _int),
-    # f-11 baseline keypoints: ISS saliency and non-maximum suppression (usip_amd/baselines.py)
-    "usip_iss_saliency_f32": ([_f32p, _i32p, _i32p, _int, _int, _dbl, _dbl, _dbl, _int, ctypes.c_void_p, _i32p, _i32p,
-                               _stream], _int),
-    "usip_iss_nms_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _stream], _int),
-    "usip_iss_saliency_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, _dbl, _dbl, _int, ctypes.c_void_p, _i32p, _int], _int),
-    "usip_iss_nms_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _int], _int),
-    # f-12 Fast Global Registration: mutual rows, normalisation, tuple test; the optimisation (usip_amd/fragments.py)
-    "usip_fgr_tuples_f32": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, ctypes.c_uint64, ctypes.c_void_p, _i32p, _i32p,
-                            ctypes.c_void_p, _i32p, _i32p, _i32p, _i32p, _int, _stream], _int),
-    "usip_fgr_tuples_explicit_f32": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, _i32p, _int, _i32p, _i32p, ctypes.c_void_p,
-                                     _i32p, _i32p, _i32p, _stream], _int),
-    "usip_fgr_optimize_f32": ([_f32p, _f32p, _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _dbl]
-                              + [ctypes.c_void_p] * 3 + [_i32p, _stream], _int),
-    "usip_fgr_tuples_f32_cpu": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, ctypes.c_uint64, ctypes.c_void_p, _i32p, _int,
-                                _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _i32p, _i32p, _int, _int], _int),
-    "usip_fgr_tuples_explicit_f32_cpu": ([_f32p, _f32p] + [_i32p] * 4 + [_int, _int, _i32p, _int, _i32p, _i32p,
-                                         ctypes.c_void_p, _i32p, _i32p, _i32p, _int], _int),
-    "usip_fgr_optimize_f32_cpu": ([_f32p, _f32p, _i32p, _i32p, ctypes.c_void_p, _i32p, _i32p, _int, _int, _dbl]
-                                  + [ctypes.c_void_p] * 3 + [_i32p, _int], _int),
-    "usip_fgr_sincos_f64_cpu": ([ctypes.c_void_p, _int, ctypes.c_void_p, ctypes.c_void_p], _int),
-    # f-13 trimmed ICP between downsampled fragments: the nearest pass, the whole loop (usip_amd/fragments.py)
-    "usip_icp_workspace_bytes": ([_int, _int], ctypes.c_longlong),
-    "usip_icp_nearest_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
-                             + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _i32p, ctypes.c_void_p, ctypes.c_void_p, _stream],
-                             _int),
-    "usip_icp_refine_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
-                            + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _dbl, _int, _dbl, _dbl, _dbl, ctypes.c_void_p,
-                                                       ctypes.c_longlong, ctypes.c_void_p, _i32p, ctypes.c_void_p,
-                                                       ctypes.c_void_p, _i32p, ctypes.c_void_p, ctypes.c_void_p, _i32p,
-                                                       ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
-    "usip_icp_nearest_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
-                                 + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _i32p, ctypes.c_void_p, _int], _int),
-    "usip_icp_refine_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
-                                + [ctypes.c_void_p] * 2 + [_i32p, _int, _int, _dbl, _int, _dbl, _dbl, _dbl, ctypes.c_void_p,
-                                                           _i32p, ctypes.c_void_p, ctypes.c_void_p, _i32p, ctypes.c_void_p,
-                                                           ctypes.c_void_p, _i32p, _i32p, ctypes.c_void_p, _int], _int),
-    # f-14 loop closures pruned by pose-graph optimisation: dense information, the optimiser (usip_amd/posegraph.py)
-    "usip_icp_information_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
-                                 + [ctypes.c_void_p] * 2 + [_int, _int, _dbl, ctypes.c_void_p, _i32p, _stream], _int),
-    "usip_posegraph_workspace_bytes": ([_int, _int, _int], ctypes.c_longlong),
-    "usip_posegraph_optimize_f64": ([_i32p] * 4 + [ctypes.c_void_p] * 3 + [_int, _int, _int, _dbl, _dbl, _int, _int,
-                                                                           ctypes.c_void_p, ctypes.c_longlong]
-                                    + [ctypes.c_void_p] * 5 + [_i32p, ctypes.c_void_p, _i32p, _stream], _int),
-    "usip_icp_information_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p]
-                                     + [ctypes.c_void_p] * 2 + [_int, _int, _dbl, ctypes.c_void_p, _i32p, _int], _int),
-    "usip_posegraph_optimize_f64_cpu": ([_i32p] * 4 + [ctypes.c_void_p] * 3 + [_int, _int, _int, _dbl, _dbl, _int, _int]
-                                        + [ctypes.c_void_p] * 5 + [_i32p, ctypes.c_void_p, _i32p, _int], _int),
-    # f-16 baseline keypoints: Harris3D normals and response (usip_amd/baselines.py); the suppression is f-11's
-    "usip_harris_normals_f32": ([_f32p, _i32p, _i32p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _stream], _int),
-    "usip_harris_response_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _i32p,
-                                  _stream], _int),
-    "usip_harris_normals_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _int], _int),
-    "usip_harris_response_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _int, ctypes.c_void_p, _i32p, _int],
-                                     _int),
-    # f-17 baseline keypoints: SIFT3D voxel average, scale space, 25 nearest and extrema (usip_amd/baselines.py)
-    "usip_sift_voxel_keys_f32": ([_f32p, _i32p, _int, _int, _dbl, ctypes.c_void_p, _stream], _int),
-    "usip_sift_voxel_average_f32": ([_f32p, _f32p, _int, ctypes.c_void_p, _i32p, _int, _int, _f32p, _f32p, _i32p, _stream],
-                                    _int),
-    "usip_sift_dog_f32": ([_f32p, _f32p, _i32p, _i32p, _int, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _i32p, _stream],
-                          _int),
-    "usip_sift_nearest_f32": ([_f32p, _i32p, _i32p, _int, _int, _i32p, _stream], _int),
-    "usip_sift_extrema_f32": ([ctypes.c_void_p, _i32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p, _stream], _int),
-    "usip_sift_voxel_keys_f32_cpu": ([_f32p, _i32p, _int, _int, _dbl, ctypes.c_void_p], _int),
-    "usip_sift_voxel_average_f32_cpu": ([_f32p, _f32p, _int, ctypes.c_void_p, _int, _int, _f32p, _f32p, _i32p, _int], _int),
-    "usip_sift_dog_f32_cpu": ([_f32p, _f32p, _i32p, _int, _int, _int, ctypes.c_void_p, ctypes.c_void_p, _int], _int),
-    "usip_sift_exp_f64_cpu": ([ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p], _int),
-    "usip_sift_nearest_f32_cpu": ([_f32p, _i32p, _int, _int, _i32p, _int], _int),
-    "usip_sift_extrema_f32_cpu": ([ctypes.c_void_p, _i32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p, _int], _int),
-    # f-18 a fragment scene's ground truth: reach at two radii with selection keys, the information sum (usip_amd/ground_truth.py)
-    "usip_gt_reach_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p, ctypes.c_void_p, _i32p,
-                           ctypes.c_void_p, _int, _int, _dbl, _dbl, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, _i32p,
-                           ctypes.c_void_p, ctypes.c_void_p, _stream], _int),
-    "usip_gt_information_f32": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _i32p, _i32p,
-                                 _int, _int, _int, ctypes.c_void_p, _stream], _int),
-    "usip_gt_reach_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, _i32p, _i32p, ctypes.c_void_p,
-                               ctypes.c_void_p, _int, _int, _dbl, _dbl, ctypes.c_uint64, ctypes.c_void_p, _int,
-                               ctypes.c_void_p, _i32p, ctypes.c_void_p, ctypes.c_void_p, _int], _int),
-    "usip_gt_information_f32_cpu": ([_f32p, _int, ctypes.c_void_p, _int, ctypes.c_longlong, _i32p, ctypes.c_void_p, _i32p,
-                                     _i32p, _int, _int, _int, ctypes.c_void_p, _int], _int),
-    # f-19 baseline descriptor: FPFH's integer SPFH and the weighted gather at keypoints (usip_amd/baselines.py)
-    "usip_fpfh_spfh_f32": ([_f32p, _i32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _i32p, _i32p, _i32p, _stream], _int),
-    "usip_fpfh_gather_f32": ([_f32p, _i32p, _i32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p,
-                              _stream], _int),
-    "usip_fpfh_spfh_f32_cpu": ([_f32p, _i32p, ctypes.c_void_p, _int, _int, _dbl, _i32p, _i32p, _int], _int),
-    "usip_fpfh_gather_f32_cpu": ([_f32p, _i32p, _i32p, _i32p, _f32p, _i32p, _int, _int, _int, _dbl, ctypes.c_void_p, _i32p,
-                                  _int], _int),
-}
+
+def _ctype(text, structs):
+    """C type text ("long long", "const float*", "usip_pairs_recipe") -> its ctypes type; every pointer that is not
+    const char*, int* or unsigned* goes as an address."""
+    base, stars = " ".join(re.sub(r"\bconst\b|\*", " ", text).split()), text.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base in structs:
+        return structs[base]
+    if stars == 1 and (base in _SCALARS or base in structs or base in _POINTEES):
+        return _TYPED_POINTERS.get(base, ctypes.c_void_p)
+    raise ValueError("usip_amd: include/usip_hip.h: unknown type %r" % text.strip())
+
+
+def _declaration(text, structs):
+    """`const float* At`, `double a, b`, `float* pc[2]` -> [(name, ctypes type)]."""
+    out, base = [], None
+    for part in text.split(","):
+        m = re.fullmatch(r"\s*(.*?)(\w+)\s*(?:\[(\d+)\])?\s*", part, re.S)
+        if m is None or (base is None and not m.group(1).strip()):
+            raise ValueError("usip_amd: include/usip_hip.h: cannot read the declaration %r" % " ".join(text.split()))
+        kind = m.group(1) if base is None else base + m.group(1)        # `double a, b`: b takes a's type without its stars
+        base = m.group(1).replace("*", " ") if base is None else base
+        try:
+            t = _ctype(kind, structs)
+        except ValueError as e:
+            raise ValueError("%s in %r" % (e, " ".join(text.split()))) from None
+        out.append((m.group(2), t * int(m.group(3)) if m.group(3) else t))
+    return out
+
+
+def read_header(text):
+    """C header text -> (STRUCTS: name -> ctypes.Structure class, SIGNATURES: name -> (argtypes, restype)), from every
+    `typedef struct ... { ... } name;` and every function declaration, in order.  Anything else but an enum and the
+    extern "C" braces raises, and so does a type that is not in the tables above: nothing is guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M).rstrip()
+    structs, signatures, pos = {}, {}, 0
+    while pos < len(text):
+        m = _DECL.match(text, pos)
+        if m is None:
+            raise ValueError("usip_amd: include/usip_hip.h: cannot read the declaration %r"
+                             % " ".join(text[pos:].split(";")[0].split()))
+        pos = m.end()
+        if m.group("struct"):
+            fields = [f for stmt in m.group("body").split(";") if stmt.strip() for f in _declaration(stmt, structs)]
+            structs[m.group("struct")] = type(m.group("struct"), (ctypes.Structure,), {"_fields_": fields})
+        elif m.group("fn"):
+            args = m.group("args").strip()
+            params = [] if args == "void" else [d for p in args.split(",") for d in _declaration(p, structs)]
+            try:
+                signatures[m.group("fn")] = ([t for _, t in params], _ctype(m.group("res"), structs))
+            except ValueError as e:
+                raise ValueError("%s in %r" % (e, " ".join(m.group(0).split()))) from None
+    return structs, signatures
+
+
+# once per process; ABI = "abi=<n>" of usip_version(), bumped in the header with every incompatible change of it
+with open(HEADER) as _f:
+    _text = _f.read()
+ABI = int(re.search(r"^#define USIP_ABI (\d+)$", _text, re.M).group(1))
+STRUCTS, SIGNATURES = read_header(_text)
 
 
 def lib():
@@ -328,7 +116,7 @@ def lib():
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res
-        # ctypes cannot see a changed signature, and results depend on three compile flags (an SLP-vectorised build gave
+        # ctypes cannot see that a library was built from another header, and results depend on three compile flags (an SLP-vectorised build gave
         # rare wrong values on gfx950): the library says what it is, anything else is refused
         ver = l.usip_version().decode()
         if ("abi=%d" % ABI) not in ver.split() or "flags=no-contract,no-fast-math,no-slp" not in ver.split():

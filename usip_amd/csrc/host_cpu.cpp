@@ -95,13 +95,16 @@ extern "C" int usip_pairwise_dist_f32_cpu(const float* a, const float* x, float*
     return USIP_OK;
 }
 
-// "usip_hip <version> gfx950 abi=<n> flags=<...>": abi counts incompatible changes of include/usip_hip.h (a signature that
-// gained an argument is not detectable through ctypes); flags names what the build MUST have been compiled with --
-// USIP_BUILD_FLAGS comes from usip_amd/build.py; a foreign build without it reports "unknown" and is refused.
+// "usip_hip <version> gfx950 abi=<n> flags=<...>": abi is the header's USIP_ABI, which counts incompatible changes of
+// include/usip_hip.h (a library built from another header is not detectable through ctypes); flags names what the build
+// MUST have been compiled with -- USIP_BUILD_FLAGS comes from usip_amd/build.py; a foreign build without it reports
+// "unknown" and is refused.
 #ifndef USIP_BUILD_FLAGS
 #define USIP_BUILD_FLAGS "unknown"
 #endif
-extern "C" const char* usip_version(void) { return "usip_hip 0.5 gfx950 abi=6 flags=" USIP_BUILD_FLAGS; }
+#define USIP_STR_(x) #x
+#define USIP_STR(x) USIP_STR_(x)
+extern "C" const char* usip_version(void) { return "usip_hip 0.5 gfx950 abi=" USIP_STR(USIP_ABI) " flags=" USIP_BUILD_FLAGS; }
 
 // Launch-geometry knobs (speed only, never results): 0 = the library's own heuristic.  tools/ sweeps set them to
 // measure alternatives on the GPU; the product never does.

@@ -429,8 +429,7 @@ class PlanesPlan:
             rows.append((ptr + 4 * off, planes.data_ptr(), lda, M, K, blocks, trows, 2 if npl == 2 else 0))
             blocks += int(_lib.lib().usip_mlp_split3_blocks(M, K, trows))
         self.blocks = blocks
-        dt = np.dtype([("At", "<u8"), ("planes", "<u8"), ("lda", "<i4"), ("M", "<i4"), ("K", "<i4"), ("first", "<i4"),
-                       ("tile_rows", "<i4"), ("reserved", "<i4")])
+        dt = np.dtype(_lib.STRUCTS["usip_split3_desc"])      # the rows above are in the header's field order
         table = np.array(rows, dtype=dt) if rows else np.zeros(0, dtype=dt)
         dev = next(iter(self.entries.values()))[1].device if rows else None
         self.table = torch.from_numpy(table.view(np.uint8).copy()).to(dev) if rows else None
@@ -1295,26 +1294,10 @@ def index_max_cpu(data: torch.Tensor, index: torch.Tensor, K: int, num_threads: 
 
 
 # ------------------------------------------------------------------------------------------------ f-5 training pairs
-class PairsRecipeC(ctypes.Structure):
-    """usip_pairs_recipe (include/usip_hip.h), field for field."""
-    _fields_ = [(n, ctypes.c_double) for n in (
-        "aug_scale_lo", "aug_scale_hi", "shift_range", "height_lo", "height_hi", "pc_sigma", "pc_clip", "sn_sigma",
-        "sn_clip", "node_sigma", "node_clip", "pert_sigma", "pert_clip", "dst_scale_thre", "dst_shift_thre")] + \
-        [(n, ctypes.c_int) for n in (
-            "N", "M", "Cs", "n_sub", "row_len", "sn_last", "train", "rot_horizontal", "rot_3d", "rot_perturbation",
-            "translation_perturbation", "height_scaling", "enu_to_cam", "require_full", "dst_rot_type",
-            "dst_rot_perturbation")]
-
-
-class PairsDrawsC(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("rows", "cand", "first", "jit_pc", "jit_sn", "jit_node", "params")]
-
-
-class PairsOutC(ctypes.Structure):
-    _fields_ = [("pc", ctypes.c_void_p * 2), ("sn", ctypes.c_void_p * 2), ("node", ctypes.c_void_p * 2),
-                ("R", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
-                ("rows", ctypes.c_void_p), ("node_slots", ctypes.c_void_p)]
-
+# The structs that go by address are the header's own (include/usip_hip.h), read by _lib: their fields are documented there.
+PairsRecipeC = _lib.STRUCTS["usip_pairs_recipe"]
+PairsDrawsC = _lib.STRUCTS["usip_pairs_draws"]
+PairsOutC = _lib.STRUCTS["usip_pairs_out"]
 
 PAIRS_KEYS = ("src_pc", "src_sn", "src_node", "dst_pc", "dst_sn", "dst_node", "R", "scale", "shift")
 
@@ -1426,27 +1409,11 @@ def pairs_workspace_bytes(recipe: PairsRecipeC, P: int) -> int:
 
 
 # ------------------------------------------------------------------------------- f-8 descriptor batches from posed scans
-class DescPairsRecipeC(ctypes.Structure):
-    """usip_desc_pairs_recipe (include/usip_hip.h), field for field."""
-    _fields_ = [("cloud", PairsRecipeC), ("positive_radius", ctypes.c_double), ("negative_radius", ctypes.c_double),
-                ("mine", ctypes.c_int)]
-
-
-class DescPairsBankC(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ("rows", "offsets", "poses", "seq_of", "seq_start", "seq_start_host")] + \
-        [("num_scans", ctypes.c_int), ("num_seq", ctypes.c_int), ("min_rows", ctypes.c_longlong)]
-
-
-class DescPairsDrawsC(ctypes.Structure):
-    _fields_ = [("cloud", PairsDrawsC), ("params", ctypes.c_void_p), ("tries", ctypes.c_void_p),
-                ("neg_pick", ctypes.c_void_p), ("T", ctypes.c_int)]
-
-
-class DescPairsOutC(ctypes.Structure):
-    _fields_ = [("pc", ctypes.c_void_p * 2), ("sn", ctypes.c_void_p * 2), ("node", ctypes.c_void_p * 2)] + \
-        [(n, ctypes.c_void_p) for n in ("anc_pose", "pos_pose", "anc_seq", "pos_id", "neg_idx", "neg_fail", "rows",
-                                        "node_slots")]
-
+# the header's structs again (recipe.cloud is a PairsRecipeC, draws.cloud a PairsDrawsC: the reader nests the classes)
+DescPairsRecipeC = _lib.STRUCTS["usip_desc_pairs_recipe"]
+DescPairsBankC = _lib.STRUCTS["usip_desc_pairs_bank"]
+DescPairsDrawsC = _lib.STRUCTS["usip_desc_pairs_draws"]
+DescPairsOutC = _lib.STRUCTS["usip_desc_pairs_out"]
 
 DESC_PAIRS_KEYS = ("anc_pc", "anc_sn", "anc_node", "pos_pc", "pos_sn", "pos_node", "anc_pose", "pos_pose", "anc_seq",
                    "pos_id", "neg_idx", "neg_fail")
