@@ -37,11 +37,20 @@ const char* usip_version(void);
 /* Launch-geometry knobs for measurement sweeps (tools/): they change HOW a result is computed (rows per
  * workgroup, prefetch depth, tile order), never the result.  0 restores the library's heuristic.  No reference
  * counterpart.  Returns USIP_EINVAL for an unknown name. */
-/* "x2_direct" (USIP_TUNE_X2_DIRECT), low four bits: 1 = the LDS-staged f32x2 GEMM of round 3 instead of csrc/gemm_x2d.hip,
- * 2 = one stage of operand loads in flight, 4 = one tile per workgroup, 8 = the LDS-transposing epilogue for data gradients
- * too, 10 = csrc/gemm_x2e.hip (both operands by LDS-DMA, 8-wave workgroups) for the forward launches that fit it, 12 = never
- * csrc/gemm_x2f.hip (round 6: one wave per SIMD, 256 x 256 tiles -- the default wherever it fits); bits 4-5
- * skip the main loop / the epilogue (time splits: wrong results, tools/x2_knob_bench.py only).
+/* "x2_direct" (USIP_TUNE_X2_DIRECT) chooses among the f32x2 GEMMs of the 256..640-wide layers.  Its whole value set is 0, 1, 8
+ * and 12; each value other than 0 is kept because tests take their reference from it (every other value acts as 12):
+ *    0 = the product: csrc/gemm_x2f.hip (one wave per SIMD, 256 x 256 tiles) wherever a launch fits it, csrc/gemm_x2d.hip for
+ *        what it refuses -- K tails, partial tiles, stage counts that are no multiple of 4: a selection by the input;
+ *    1 = the LDS-staged gemm_x3p_kernel<.., 4, 2, 2> of round 3 instead of either: also the only kernel for clouds of
+ *        K * P * 4 >= 2^31 bytes, and the reference of test_direct_gemm_forward_is_fp32_accurate;
+ *    8 = csrc/gemm_x2d.hip with the LDS-transposing epilogue for data gradients too: the reference of
+ *        test_data_gradient_stores_straight_from_the_registers_at_chip_filling_size;
+ *   12 = csrc/gemm_x2d.hip only, never csrc/gemm_x2f.hip: the reference of the gemm_x2f bit-identity test and of the
+ *        profiling-key test.
+ * The forms that lost their measurement are gone together with the values that selected them (one stage of loads in flight, one
+ * tile per workgroup, the all-DMA forward kernel, the prologue subsets of gemm_x2f, the time-split aid: profiles/HISTORY.md).
+ * The REDK form of gemm_x2d.hip (usip_mlp_gemm_x2h_red_f32, off by default, measured slower) stays as the only working form
+ * of an idea the project still wants, with the only test of its arithmetic; it is chosen by its own entry point, not by a knob.
  * "r5_forms" (USIP_TUNE_R5_FORMS), bit flags that bring back round 4's form of a kernel for same-box A/B runs: 1 = the f32x2
  * weight gradient with half-line loads (wgrad_x3_kernel<.., 2> instead of wgrad_x2l_kernel); and that switch ON forms round 5
  * measured and did not keep: 2 / 4 = two / four loop iterations' loads in flight in the BatchNorm-backward reduction (default

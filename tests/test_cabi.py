@@ -247,3 +247,118 @@ def test_bn_momentum_decay_rule_matches_reference():
         bn = cls(4, momentum=0.1, momentum_decay_step=None, momentum_decay=0.6)
         bn.decay_momentum(40)
         assert bn.momentum == 0.1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The shared-MLP GEMM entries refuse what they refused.  Every row below is a call that returns before any launch: a
+# well-formed call (the base calls of `_gemm_table`, never issued) with ONE argument broken, or with no positions at all -- the pointers are
+# small fake integers, so nothing here may reach a kernel (checked per call through the launch log).
+_GEMM_KINDS = {
+    "tile": "At lda X X2 coef pro bias rowbias rb_group pool_dp pool_arg pool_group Y y_rows stats M K P nb stream",
+    "planes": "planes X X2 coef pro bias rowbias rb_group pool_dp pool_arg pool_group Y y_rows stats M K P nb stream",
+    "fork": "planes X X2 coef Y y_rows fork_dp fork_arg fork_group M K P nb stream",
+    "red": "planes X X2 coef pro pool_dp pool_arg pool_group Y red_y red_coef red_out red_gsum red_group M K P nb stream",
+    "narrow": "At lda X coef pro bias rowbias rb_group Y y_rows stats M K P nb stream",
+}
+_PTRS = ("At planes X X2 coef bias rowbias pool_dp pool_arg Y stats fork_dp fork_arg red_y red_coef red_out red_gsum").split()
+_SET = {p: 0x1000 * (i + 1) for i, p in enumerate(_PTRS)}           # what a present pointer is: 4096-B aligned
+_PRO2 = dict(pro=2, X2=_SET["X2"])
+_PRO3 = dict(pro=3, X=None, X2=_SET["X2"], pool_dp=_SET["pool_dp"], pool_arg=_SET["pool_arg"], pool_group=4)
+_RB = dict(rowbias=_SET["rowbias"])
+
+
+def _base(kind, **over):
+    call = {a: None if a in _PTRS or a == "stream" else 0 for a in _GEMM_KINDS[kind].split()}
+    call.update({a: _SET[a] for a in ("At", "planes", "X", "coef", "Y") if a in call})
+    call.update(over)
+    return call
+
+
+# entry -> (kind, the well-formed call, what the EMPTY call (P = 0) returns, the broken arguments).  A dict is merged into
+# the base; several keys = the prologue that the broken argument belongs to, then the break.
+def _gemm_table():
+    shared = [dict(pro=0, X=None), dict(X=None), dict(coef=None), dict(_PRO2, X=None), dict(_PRO2, X2=None),
+              dict(_PRO2, coef=None), dict(_PRO2, stats=_SET["stats"]), dict(_PRO3, X2=None), dict(_PRO3, coef=None),
+              dict(_PRO3, stats=_SET["stats"]), dict(_PRO3, pool_dp=None), dict(_PRO3, pool_arg=None),
+              dict(_PRO3, pool_group=0), dict(_PRO3, pool_group=3), dict(_PRO3, pool_group=48),
+              dict(_RB, rb_group=0), dict(_RB, rb_group=48), dict(y_rows=63), dict(Y=None), dict(pro=4), dict(pro=-1),
+              dict(M=0), dict(K=0), dict(P=-1), dict(nb=-1)]
+    tile = _base("tile", lda=64, pro=1, rb_group=1, M=64, K=32, P=64, nb=2)
+    tile_own = [dict(At=None), dict(lda=63), dict(lda=-31), dict(_PRO3, pool_group=2)]     # (fp32 entries: pool_group % 4)
+    pl = _base("planes", pro=1, rb_group=1, M=64, K=32, P=64, nb=2)
+    pl_own = [dict(planes=None), dict(planes=_SET["planes"] + 8), dict(K=641), dict(_PRO2, K=513), dict(_PRO3, K=513)]
+    x2r_own = [dict(pro=0), dict(M=129, y_rows=0), dict(K=129), dict(_RB, rb_group=16), dict(_PRO2, **_RB, rb_group=32),
+               dict(K=128, P=1 << 23)]
+    big = dict(M=256, K=128, P=32768, nb=1)                          # the smallest launch of whole 256 x 256 tiles
+    fork = _base("fork", X2=_SET["X2"], fork_dp=_SET["fork_dp"], fork_arg=_SET["fork_arg"], fork_group=16, **big)
+    fork_bad = [{p: None} for p in "planes X X2 coef Y fork_dp fork_arg".split()] + [
+        dict(planes=_SET["planes"] + 8), dict(M=0), dict(K=0), dict(K=576), dict(nb=0), dict(fork_group=0), dict(fork_group=48),
+        dict(fork_group=8), dict(fork_group=128), dict(y_rows=255), dict(M=128), dict(M=300), dict(P=32768 - 256), dict(P=32768 + 128),
+        dict(K=160), dict(Y=_SET["Y"] + 4), dict(X=_SET["X"] + 4), dict(X2=_SET["X2"] + 4), dict(fork_dp=_SET["fork_dp"] + 8),
+        dict(fork_arg=_SET["fork_arg"] + 8)]
+    red = _base("red", pro=2, X2=_SET["X2"], red_y=_SET["red_y"], red_coef=_SET["red_coef"], red_out=_SET["red_out"], **big)
+    red3 = dict(pro=3, X=None, pool_dp=_SET["pool_dp"], pool_arg=_SET["pool_arg"], pool_group=16)
+    red_bad = [{p: None} for p in "planes X X2 coef Y red_y red_coef red_out".split()] + [
+        dict(planes=_SET["planes"] + 8), dict(pro=0), dict(pro=1), dict(pro=4), dict(M=128), dict(M=300), dict(K=0), dict(K=513),
+        dict(P=32768 - 128), dict(P=32768 + 64), dict(nb=0), dict(red_gsum=_SET["red_gsum"], red_group=8),
+        dict(Y=_SET["Y"] + 4), dict(red_y=_SET["red_y"] + 4), dict(red3, pool_dp=None), dict(red3, pool_arg=None),
+        dict(red3, pool_group=0), dict(red3, pool_group=3)]
+    nf = _base("narrow", lda=64, pro=1, rb_group=1, M=64, K=64, P=196608, nb=1)
+    nf_bad = [dict(At=None), dict(X=None), dict(Y=None), dict(coef=None), dict(lda=63), dict(pro=2), dict(pro=-1), dict(K=32),
+              dict(M=32), dict(P=196610), dict(P=196608 - 64), dict(nb=0), dict(X=_SET["X"] + 8), dict(_RB, rb_group=0),
+              dict(_RB, rb_group=16), dict(_RB, rb_group=48), dict(_RB, rb_group=160), dict(y_rows=63), dict(y_rows=21846)]
+    no_x2h = [dict(pro=0)]                                           # x2h and x2r take prologues 1, 2, 3 only
+    table = {"usip_mlp_gemm_%s" % m: ("tile", tile, 0, shared + tile_own) for m in ("f32", "bf16", "f32x3")}
+    table["usip_mlp_gemm_x3p_f32"] = ("planes", pl, 0, shared + pl_own)
+    table["usip_mlp_gemm_x2h_f32"] = ("planes", pl, 0, shared[1:] + pl_own + no_x2h)
+    table["usip_mlp_gemm_x2r_f32"] = ("planes", pl, 0, shared[1:] + pl_own[:2] + x2r_own)
+    table["usip_mlp_gemm_x2h_fork_f32"] = ("fork", fork, -1, fork_bad)   # (no empty launch: P, nb >= 1)
+    table["usip_mlp_gemm_x2h_red_f32"] = ("red", red, -1, red_bad)       # (the same)
+    table["usip_mlp_narrow_forward_f32"] = ("narrow", nf, -1, nf_bad)    # (the same: the shape is not its own)
+    return table
+
+
+def _gemm_rows():
+    rows = []
+    for entry, (kind, base, empty, bad) in _gemm_table().items():
+        assert 16 <= len(bad), entry
+        for change in bad:
+            call = dict(base, **change)
+            assert call != base and (call["P"] != 0), (entry, change)         # never the well-formed call itself
+            rows.append((entry, kind, call, -1))
+        rows.append((entry, kind, dict(base, P=0), empty))
+    return rows
+
+
+def test_gemm_entries_refuse_what_they_refused():
+    from usip_amd import _lib
+    lib = _lib.lib()
+    assert all(lib.usip_tuning_value(knob) == 0 for knob in range(8))     # the fork and `red` routes read the knobs
+    wrong = []
+    for entry, kind, call, want in _gemm_rows():
+        lib.usip_launch_log(1)
+        got = getattr(lib, entry)(*[call[a] for a in _GEMM_KINDS[kind].split()])
+        launched = lib.usip_launch_log(0)
+        assert launched == 0, (entry, call)
+        if got != want:
+            wrong.append((entry, {k: v for k, v in call.items() if v}, got, want))
+    assert not wrong, wrong
+
+
+def test_fork_and_red_queries_answer_as_before():
+    """usip_mlp_gemm_x2h_fork_supported(M, K, P, nb, fork_group) and usip_mlp_gemm_x2d_red_tiles(M, K, P, nb, red_group) on
+    both sides of their thresholds (host arithmetic only); the values are the library's before the GEMM entries shared
+    their checks."""
+    from usip_amd import _lib
+    lib = _lib.lib()
+    fork = {(256, 128, 32768, 1, 16): 1, (256, 128, 32512, 1, 16): 0, (512, 128, 16384, 1, 16): 1, (512, 128, 16128, 1, 16): 0,
+            (256, 128, 8192, 4, 16): 1, (256, 128, 32768, 1, 8): 0, (256, 128, 32768, 1, 32): 1, (256, 128, 32768, 1, 64): 1,
+            (256, 128, 32768, 1, 128): 0, (256, 192, 32768, 1, 16): 1, (256, 160, 32768, 1, 16): 0, (256, 512, 32768, 1, 16): 1,
+            (256, 576, 32768, 1, 16): 0, (256, 128, 32896, 1, 16): 0, (300, 128, 32768, 1, 16): 0, (128, 128, 32768, 1, 16): 0,
+            (256, 128, 32768, 1, 0): 0, (256, 128, 0, 1, 16): 0}
+    red = {(256, 128, 32768, 1, 0): 256, (256, 128, 32768, 1, 16): 256, (256, 128, 32768, 1, 32): 256, (256, 128, 32768, 1, 8): 0,
+           (256, 128, 32640, 1, 0): 0, (512, 128, 16384, 1, 0): 128, (512, 128, 16256, 1, 0): 0, (256, 128, 8192, 4, 16): 256,
+           (256, 512, 32768, 1, 0): 256, (256, 513, 32768, 1, 0): 0, (256, 16, 32768, 1, 0): 256, (300, 128, 32768, 1, 0): 0,
+           (128, 128, 32768, 1, 0): 0, (256, 128, 32832, 1, 0): 0, (256, 128, 32768, 0, 0): 0}
+    assert {k: lib.usip_mlp_gemm_x2h_fork_supported(*k) for k in fork} == fork
+    assert {k: lib.usip_mlp_gemm_x2d_red_tiles(*k) for k in red} == red

@@ -681,40 +681,6 @@ def test_data_gradient_stores_straight_from_the_registers_at_chip_filling_size(p
         ops.PLANES_CACHE = None
 
 
-@pytest.mark.parametrize("shape", [(4, 256, 256, 8192), (2, 512, 512, 8192), (8, 256, 512, 4096), (4, 64, 256, 8192)])
-@pytest.mark.parametrize("stats", [False, True])
-def test_all_dma_forward_gemm_equals_the_direct_one_bit_for_bit(shape, stats, x2_forced):
-    """csrc/gemm_x2e.hip (both operands by LDS-DMA, one 8-wave workgroup per CU; opt-in, knob x2_direct = 10) computes
-    what csrc/gemm_x2d.hip computes, in the same order: outputs bit-identical, statistics equal after the sum over the
-    tiles (its 256-position tile fills the first of two 128-position slots), with and without a row bias."""
-    from usip_amd import _lib, ops
-    nb, K, M, P = shape
-    g = torch.Generator().manual_seed(11)
-    At = (torch.randn(K, M, generator=g) * (2.0 / K) ** 0.5).to(DEV)
-    X = (torch.randn(nb, K, P, generator=g) * 1.7 + 0.2).to(DEV)
-    bias = torch.randn(M, generator=g).to(DEV)
-    mu, var = X.mean(dim=(0, 2)), X.var(dim=(0, 2), unbiased=False)
-    istd = torch.rsqrt(var + 1e-5)
-    coef = torch.stack([istd, -mu * istd, mu, istd]).contiguous()
-    rowbias = torch.randn(nb, M, P // 64, generator=g).to(DEV)
-    ops.PLANES_CACHE = {}
-    try:
-        for rb in (None, rowbias):
-            kw = dict(want_stats=stats, pro=1, coef=coef, rowbias=rb, rb_group=64 if rb is not None else 1)
-            y0, s0 = ops.mlp_gemm(At, X, bias, **kw)
-            _lib.lib().usip_set_tuning(b"x2_direct", 10)
-            y1, s1 = ops.mlp_gemm(At, X, bias, **kw)
-            _lib.lib().usip_set_tuning(b"x2_direct", 0)
-            assert torch.equal(y0, y1)
-            if stats:
-                assert not torch.equal(s0, s1)                  # (it did run: its second slots are zero)
-                t0, t1 = s0.double().sum(dim=2), s1.double().sum(dim=2)
-                assert float((t0 - t1).abs().max() / t0.abs().max()) < 1e-6
-    finally:
-        _lib.lib().usip_set_tuning(b"x2_direct", 0)
-        ops.PLANES_CACHE = None
-
-
 def _launched(lib, call):
     """-> (call(), the demangled names of the kernels the library launched for it on this thread, in order)"""
     lib.usip_launch_log(1)
@@ -922,3 +888,29 @@ def test_direct_gemm_backward_leaves_the_producing_layers_bn_sums(shape, group, 
         again = ops.mlp_gemm(W, None if pooled else dZ, pro=3 if pooled else 2, X2=Yp, coef=coef4, tag="dgrad",
                              pool=(dp, arg, G) if pooled else None, red=(Yprev, cprev), red_group=group)[2]
         assert torch.equal(again.flat, red.flat)
+
+
+def test_every_gemm_route_launches_the_kernels_it_launched_before_the_rejected_forms_were_retired():
+    """tests/golden/make_gemm_routes_golden.py: one ops.mlp_gemm call per route of the family (matmul mode, shape, prologue,
+    epilogue, the three values of knob x2_direct the tests use for their references), each at the smallest shape that takes
+    it; the fixture holds the launch log of every call -- kernel names and workgroup counts, in order -- from the commit before
+    the all-DMA forward kernel, the measurement aid of gemm_x2d_kernel and the other values of x2_direct went."""
+    import json
+    import sys
+    from conftest import GOLDEN
+    sys.path.insert(0, GOLDEN)
+    import make_gemm_routes_golden as routes
+    with open(routes.PATH) as f:
+        pinned = json.load(f)
+    table = routes.rows()
+    assert routes.digest(table) == pinned["inputs_sha256"], "the generators no longer give the fixture's inputs"
+    assert [r["name"] for r in table] == sorted(pinned["rows"], key=[r["name"] for r in table].index)
+    differ = {}
+    for r in table:
+        want = pinned["rows"][r["name"]]
+        assert want["call"] == r, (r, want["call"])             # a threshold that moved changes the smallest shape
+        got = routes.launches(r)
+        print(r["name"], got)
+        if got != want["launches"]:
+            differ[r["name"]] = (got, want["launches"])
+    assert not differ, differ

@@ -114,7 +114,7 @@ def test_split_gemm_main_loop_order_and_counts(tmp_path):
     assert seen >= 20 and deep >= 10                           # every 128-row-tile instantiation also exists with the deep ring
 
 
-@pytest.mark.parametrize("src", ["gemm_x2d.hip", "gemm_x2e.hip", "gemm_x2f.hip"])
+@pytest.mark.parametrize("src", ["gemm_x2d.hip", "gemm_x2f.hip"])
 def test_lds_dma_statements_save_and_restore_m0(src, tmp_path):
     """The weight / operand DMA of the direct GEMMs is inline asm (`buffer_load_dwordx4 ... offen lds`; a builtin would make
     hipcc drain vmcnt in front of every LDS read).  Its LDS base travels in m0.  Round 5 listed "m0" as a clobber

@@ -35,19 +35,6 @@ constexpr int DBM = 256, DBN = 128, DNT = 256, DSLOTS = 4;
 constexpr int DPL = DBM * 32;                                  // bytes of one plane of one 16-k stage of the weights
 constexpr int DSTAGE = 2 * DPL;                                // hi + lo
 
-// byte offset of (row, 16-B half) inside a [rows][16 fp16] plane (the image usip_mlp_split2h_f32 writes)
-__device__ __forceinline__ int d_lds_off(int row, int half) { return row * 32 + ((half ^ (row >> 3)) & 1) * 16; }
-
-// two fp32 -> packed fp16 high parts and packed fp16 low parts (x = hi + lo up to 2^-22 |x|), 3 VALU instructions
-__device__ __forceinline__ void split_pair_mix(float x, float y, unsigned& hi, unsigned& lo)
-{
-    const f32x2 v = {x, y};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));          // v_cvt_pk_f16_f32, RNE
-    // lo.lo16 = f16(x - f32(hi.lo16)), lo.hi16 = f16(y - f32(hi.hi16)): the differences are exact in fp32
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(y), "v"(hi));
-}
-
 // Output epilogue of the direct kernel.  A wave holds 32 positions x 256 channels: lane = channel (l & 31) of each of the
 // eight 32-channel tiles, positions 8g + 4 (l >> 5) + e.  Stored straight from that layout (mlp_common.h's epilogue) a
 // store instruction writes 32 rows x 32 B -- measured: the epilogue of the 512 x 512 layer cost 70 of the launch's 240
@@ -377,10 +364,6 @@ __global__ __launch_bounds__(DNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tpc = (a.P + DBN - 1) / DBN, nmt = (a.M + DBM - 1) / DBM;
     const int total = a.nb * tpc * nmt;
     const int nk = (a.K + XBK - 1) / XBK;
-    // measurement aid (tools/x2_knob_bench.py, knob x2_direct = 16 / 32 / 48): bit 0 = run only two stages of the main
-    // loop, bit 1 = no epilogue -- wrong results, used to split a launch's time into prologue / loop / epilogue
-    const int dbg = a.a_trans;
-    const int nk_run = (dbg & 1) ? min(nk, 2) : nk;
 
     // operand scales (see gemm_x3p_kernel): weights carry theirs behind the image, the streamed operand's comes from a
     // rigorous bound of what the prologue can produce
@@ -517,7 +500,7 @@ __global__ __launch_bounds__(DNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         for (int r = 0; r < 16; ++r) acc[t][0][r] = 0.0f;
 
     // weight fragment of channel tile t: row t*32 + c, half h; (row >> 3) & 1 does not depend on t
-    const int fa0 = d_lds_off(c, h);
+    const int fa0 = lds_off(c, h);
     // fragments of one PAIR of channel tiles (2u, 2u+1): 16 registers; two sets, used alternately
     struct Frag { f16x8 lo[2], hi[2]; };
     Frag FA, FB;
@@ -638,12 +621,12 @@ __global__ __launch_bounds__(DNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     read_pair(0, 0, 0, FA); read_pair(0, 0, 1, FA);
     if constexpr (DEPTH == 2) {
         // two stages per trip (nk is even: the launcher sends odd nk to DEPTH 1): register sets and plane sets swap roles
-        for (int kt = 0; kt < nk_run; kt += 2) {
+        for (int kt = 0; kt < nk; kt += 2) {
             stage(kt, xs1, ah, al, bh, bl);
             stage(kt + 1, xs0, bh, bl, ah, al);
         }
     } else {
-        for (int kt = 0; kt < nk_run; ++kt) {
+        for (int kt = 0; kt < nk; ++kt) {
             stage(kt, xs1, ah, al, bh, bl);
 #pragma unroll
             for (int j = 0; j < 4; ++j) { ah[j] = bh[j]; al[j] = bl[j]; }
@@ -657,19 +640,14 @@ __global__ __launch_bounds__(DNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
     for (int t = 0; t < 8; ++t) asm volatile("s_nop 7\n\ts_nop 7" : "+a"(acc[t][0]));
     // epilogue scratch: ring slots 2 and 3 (every DMA has landed and every fragment read is done: drains + barrier above)
-    if (dbg & 2) {
-        if (a.P == -12345) a.Y[tid] = acc[0][0][0] + acc[1][0][1] + acc[2][0][2] + acc[3][0][3] + acc[4][0][4] + acc[5][0][5] +
-                                      acc[6][0][6] + acc[7][0][7];
-    } else {
-        float* scr = reinterpret_cast<float*>(smem + 2 * DSTAGE);
-        // GEN (chosen by the launcher when not every tile lies inside the tensor, or the stores cannot be 16-B vectors):
-        // the general epilogue; otherwise only the lean one is compiled in (both in one kernel cost registers)
-        if constexpr (DIRECT) epilogue_x2d_direct(a, acc, out_scale, b, m0, p0);
-        else if constexpr (GEN) epilogue_x2d<EPI>(a, acc, out_scale, scr, 2 * DSTAGE / 4, b, m0, p0, tn, tpc);
-        else if constexpr (REDK) epilogue_x2d_fast<EPI_NONE, false, true>(a, acc, out_scale, scr, b, m0, p0, tn, tpc);
-        else if (a.rowbias) epilogue_x2d_fast<EPI, true>(a, acc, out_scale, scr, b, m0, p0, tn, tpc);
-        else epilogue_x2d_fast<EPI, false>(a, acc, out_scale, scr, b, m0, p0, tn, tpc);
-    }
+    float* scr = reinterpret_cast<float*>(smem + 2 * DSTAGE);
+    // GEN (chosen by the launcher when not every tile lies inside the tensor, or the stores cannot be 16-B vectors):
+    // the general epilogue; otherwise only the lean one is compiled in (both in one kernel cost registers)
+    if constexpr (DIRECT) epilogue_x2d_direct(a, acc, out_scale, b, m0, p0);
+    else if constexpr (GEN) epilogue_x2d<EPI>(a, acc, out_scale, scr, 2 * DSTAGE / 4, b, m0, p0, tn, tpc);
+    else if constexpr (REDK) epilogue_x2d_fast<EPI_NONE, false, true>(a, acc, out_scale, scr, b, m0, p0, tn, tpc);
+    else if (a.rowbias) epilogue_x2d_fast<EPI, true>(a, acc, out_scale, scr, b, m0, p0, tn, tpc);
+    else epilogue_x2d_fast<EPI, false>(a, acc, out_scale, scr, b, m0, p0, tn, tpc);
     if constexpr (!DIRECT) __syncthreads();                    // the scratch becomes ring again (DIRECT never used it)
     }                                                          // tiles
 }
@@ -678,30 +656,26 @@ __global__ __launch_bounds__(DNT) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 namespace usip_mlp {
 
-int launch_gemm_x2d(const GemmArgs& a_in, const uint4* pl, int pro, hipStream_t st)
+int launch_gemm_x2d(const GemmArgs& a, const uint4* pl, int pro, hipStream_t st)
 {
-    if (!a_in.red_out && gemm_x2e_takes(a_in, pro)) return launch_gemm_x2e(a_in, pl, st);
-    if (gemm_x2f_takes(a_in, pro)) return launch_gemm_x2f(a_in, pl, pro, st);   // round 6: one wave per SIMD, 64-position wave tiles
-    GemmArgs a = a_in;
-    a.a_trans = usip_tuning_value(USIP_TUNE_X2_DIRECT) >> 4;   // measurement aid, see the kernel (0 in the product)
+    if (gemm_x2f_takes(a, pro)) return launch_gemm_x2f(a, pl, pro, st);   // round 6: one wave per SIMD, 64-position wave tiles
     const int tpc = (a.P + DBN - 1) / DBN, nmt = (a.M + DBM - 1) / DBM;
     const long long total = (long long)a.nb * tpc * nmt;
     if (total > 0x7fffffffLL || (long long)a.K * a.P * 4 >= (1LL << 31)) return USIP_EINVAL;
     const int epi = a.stats ? EPI_STATS : EPI_NONE;
     const bool tail = (a.K % XBK) != 0;
-    // two stages of operand loads in flight (DEPTH 2) needs an even number of stages; knob x2_direct = 2: DEPTH 1
-    const bool deep = !tail && ((a.K / XBK) % 2 == 0) && (usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) != 2;
+    // two stages of operand loads in flight (DEPTH 2) needs an even number of stages
+    const bool deep = !tail && ((a.K / XBK) % 2 == 0);
     // persistent: two workgroups per CU (LDS: 70 KiB each); 8-aligned so that v & 7 is the same XCD for every tile of a block
     const int cus = usip_cu_count();
     const long long slots = (long long)(2 * cus) / 8 * 8;
     // the lean epilogue needs every tile inside the tensor, 16-B vector stores, 32-bit offsets, a row bias per run of 4
     const bool gen = !(a.y_vec && a.M % DBM == 0 && a.P % DBN == 0 && (!a.rowbias || a.rb_group % 4 == 0) &&
                        (long long)a.y_rows * a.P * 4 < (1LL << 31));
-    const bool one_tile_each = (usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) == 4;     // measurement: knob x2_direct = 4
-    dim3 grid((unsigned)((total <= slots || (total & 7) || one_tile_each) ? total : slots)), block(DNT);
+    dim3 grid((unsigned)((total <= slots || (total & 7)) ? total : slots)), block(DNT);
     // data gradients whose output needs nothing but the scale: unswapped MFMA operands, stores straight from the registers
     const bool direct = !gen && !tail && deep && epi == EPI_NONE && !a.red_out && !a.bias && !a.rowbias &&
-                        (usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) != 8;              // measurement: knob x2_direct = 8
+                        usip_tuning_value(USIP_TUNE_X2_DIRECT) != 8;   // knob x2_direct = 8: the LDS-transposing epilogue (a test's reference)
     if (direct && pro == PRO_BN_BWD) {
         USIP_LAUNCH((gemm_x2d_kernel<PRO_BN_BWD, EPI_NONE, false, 2, false, false, true>), grid, block, 0, st, a, pl);
         USIP_LAUNCH_CHECK();

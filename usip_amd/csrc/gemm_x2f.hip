@@ -30,8 +30,8 @@
 //     workgroup per CU has 160 KB), so the next tile's first weight stages and operand loads are requested BEFORE the epilogue
 //     and have landed when it ends (gemm_x2d.hip: 5-8 k cycles of set-up per tile exposed).
 // Launch conditions (gemm_x2f_takes): M % 256 == 0, P % 256 == 0, K % 64 == 0, 16-B aligned whole-tile output, row bias per run of
-// >= 8 positions, no REDK form; everything else stays with gemm_x2d.hip.  Knob x2_direct = 12 switches this kernel off (A/B);
-// the product runs every launch that fits on it.
+// >= 8 positions, no REDK form; everything else stays with gemm_x2d.hip.  Knob x2_direct = 12 switches this kernel off (the
+// tests' reference); the product runs every launch that fits on it.
 #include "mlp_common.h"
 #include "split_common.h"
 #include <type_traits>
@@ -45,18 +45,6 @@ constexpr int FPL = FBM * 32;                                  // bytes of one p
 constexpr int FSTAGE = 2 * FPL;                                // hi + lo: 16 KB
 constexpr int FTRS = 68;                                       // floats per transposition row (64 + 4: conflict-free b128 writes)
 constexpr int FSCR_FLOATS = 4 * 2 * 32 * FTRS + 2 * 4 * FBM;   // transposition areas (two per wave) + statistics exchange
-
-// byte offset of (row, 16-B half) inside a [rows][16 fp16] plane (the image usip_mlp_split2h_f32 writes)
-__device__ __forceinline__ int f_lds_off(int row, int half) { return row * 32 + ((half ^ (row >> 3)) & 1) * 16; }
-
-// two fp32 -> packed fp16 high parts and packed fp16 low parts (x = hi + lo up to 2^-22 |x|), 3 VALU instructions
-__device__ __forceinline__ void f_split_pair(float x, float y, unsigned& hi, unsigned& lo)
-{
-    const f32x2 v = {x, y};
-    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));          // v_cvt_pk_f16_f32, RNE
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x), "v"(hi));
-    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(y), "v"(hi));
-}
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
@@ -463,7 +451,7 @@ __device__ __forceinline__ void gemm_x2f_body(const GemmArgs& a, const uint4* __
     constexpr int BARRIER_VMCNT = 2 * NX + 4;
     static_assert(BARRIER_VMCNT <= 63, "vmcnt is six bits");
 
-    const int fa0 = f_lds_off(c, h);                           // weight fragment of channel tile t: row t*32 + c, half h
+    const int fa0 = lds_off(c, h);                           // weight fragment of channel tile t: row t*32 + c, half h
     const float4* cfl = reinterpret_cast<const float4*>(cf) + h * (8 * NC / 4);
 
     struct Tile { int b, m0, p0, tn128; int xo, go, wo; };    // xo / go / wo: scalar byte offsets of the tile's operand / pool / planes
@@ -526,7 +514,7 @@ __device__ __forceinline__ void gemm_x2f_body(const GemmArgs& a, const uint4* __
 #pragma unroll
         for (int bk = 0; bk < 2; ++bk)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) f_split_pair(cv[bk][2 * j], cv[bk][2 * j + 1], ph[bk][j], pl_[bk][j]);
+            for (int j = 0; j < 4; ++j) split_pair_mix(cv[bk][2 * j], cv[bk][2 * j + 1], ph[bk][j], pl_[bk][j]);
     };
 
     f32x16 acc[8][2];
@@ -592,11 +580,11 @@ __device__ __forceinline__ void gemm_x2f_body(const GemmArgs& a, const uint4* __
                     if (ns == base) { conv_blk(S, 2 * j, 0); conv_blk(S, 2 * j, 1); }
                     if (ns == base + 1) { conv_blk(S, 2 * j + 1, 0); conv_blk(S, 2 * j + 1, 1); }
                     if (ns == base + 2) {
-                        f_split_pair(cv[0][2 * j], cv[0][2 * j + 1], nh[0][j], nl[0][j]);
+                        split_pair_mix(cv[0][2 * j], cv[0][2 * j + 1], nh[0][j], nl[0][j]);
                         load_x1(so3, sg3, S, 2 * j);
                     }
                     if (ns == base + 3) {
-                        f_split_pair(cv[1][2 * j], cv[1][2 * j + 1], nh[1][j], nl[1][j]);
+                        split_pair_mix(cv[1][2 * j], cv[1][2 * j + 1], nh[1][j], nl[1][j]);
                         load_x1(so3, sg3, S, 2 * j + 1);
                     }
                 }
@@ -618,11 +606,11 @@ __device__ __forceinline__ void gemm_x2f_body(const GemmArgs& a, const uint4* __
                     if (ns == base + 2) conv_blk(S, 2 * j + 1, 0);
                     if (ns == base + 3) conv_blk(S, 2 * j + 1, 1);
                     if (ns == base + 4) {
-                        f_split_pair(cv[0][2 * j], cv[0][2 * j + 1], nh[0][j], nl[0][j]);
+                        split_pair_mix(cv[0][2 * j], cv[0][2 * j + 1], nh[0][j], nl[0][j]);
                         load_x1(so3, sg3, S, 2 * j);
                     }
                     if (ns == base + 5) {
-                        f_split_pair(cv[1][2 * j], cv[1][2 * j + 1], nh[1][j], nl[1][j]);
+                        split_pair_mix(cv[1][2 * j], cv[1][2 * j + 1], nh[1][j], nl[1][j]);
                         load_x1(so3, sg3, S, 2 * j + 1);
                     }
                 }
@@ -755,14 +743,12 @@ __global__ __launch_bounds__(FNT) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 namespace usip_mlp {
 
-// Does gemm_x2f_kernel take this launch?  (The default for every shape it fits; knob x2_direct = 12: never.)
+// Does gemm_x2f_kernel take this launch?  (The default for every shape it fits.)
 bool gemm_x2f_takes(const GemmArgs& a, int pro)
 {
-    // Knob x2_direct: 0 (the product) = every launch that fits; 12 and every measurement knob of the family: gemm_x2d.hip only;
-    // 13 = the forward launches only, 14 = all but pro 2, 15 = all but pro 3 (same-box A/B of the data-gradient forms).
-    const int knob = usip_tuning_value(USIP_TUNE_X2_DIRECT);
-    if (knob != 0 && (knob < 13 || knob > 15)) return false;
-    if ((knob == 13 && pro != PRO_AFFINE_RELU) || (knob == 14 && pro == PRO_BN_BWD) || (knob == 15 && pro == PRO_BN_BWD_POOL)) return false;
+    // knob x2_direct (include/usip_hip.h): 12 = never; 8 = gemm_x2d.hip's LDS-transposing epilogue, which is not this kernel's
+    // either (1 never gets here)
+    if (usip_tuning_value(USIP_TUNE_X2_DIRECT) != 0) return false;
     if (pro != PRO_AFFINE_RELU && pro != PRO_BN_BWD && pro != PRO_BN_BWD_POOL) return false;
     if (a.red_out) return false;
     if (a.M % FBM != 0 || a.P % FBN != 0 || a.K % (4 * XBK) != 0) return false;   // (four ring slots: stages continue across tiles)

@@ -83,6 +83,27 @@ struct GemmArgs {
     const float* fork_dp; const int* fork_arg; int fork_group;
 };
 
+// What every GEMM entry of the C ABI checks of a call that has positions (P * nb > 0), and the argument block of its launch
+// (host).  With the entry stay the checks that are its own: the matrix operand (At / lda, or the planes and their
+// alignment), its K limits, the prologues it takes and what else its kernel asks for.
+inline bool gemm_entry_args(GemmArgs& a, const float* X, const float* X2, const float* coef, int pro, const float* bias,
+                            const float* rowbias, int rb_group, const float* pool_dp, const int32_t* pool_arg,
+                            int pool_group, float* Y, int y_rows, float* stats, int M, int K, int P, int nb)
+{
+    const bool bwd = pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL;
+    if (!Y || pro < 0 || pro > 3) return false;
+    if (pro != PRO_BN_BWD_POOL && !X) return false;
+    if (pro != PRO_NONE && !coef) return false;
+    if (bwd && (!X2 || stats)) return false;
+    if (pro == PRO_BN_BWD_POOL && (!pool_dp || !pool_arg || pool_group < 1 || P % pool_group != 0)) return false;
+    if (rowbias && (rb_group < 1 || P % rb_group != 0)) return false;
+    if (y_rows == 0) y_rows = M;                               // Y is a dense [nb][M][P] tensor
+    if (y_rows < M) return false;
+    a = GemmArgs{nullptr, 0, X, X2, coef, bias, Y, stats, M, K, P, nb, rowbias, rb_group, pool_dp, pool_arg, pool_group,
+                 0, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    return true;
+}
+
 // prologue on one element of the streamed operand, channel coefficients c0..c3
 template <int PRO>
 __device__ __forceinline__ float pro_apply(float x, float x2, float c0, float c1, float c2, float c3)
@@ -288,9 +309,6 @@ int launch_wgrad_x3_256(const WgradArgs& a, int pro, bool xpro, unsigned blocks,
 // f32x2 forward / data gradient with the streamed operand global -> registers -> MFMA (gemm_x2d.hip); `pl` = the
 // usip_mlp_split2h_f32 image with 256-row tiles; tiles of 256 channels x 128 positions
 int launch_gemm_x2d(const GemmArgs& a, const uint4* pl, int pro, hipStream_t st);
-// gemm_x2e.hip: the forward launches of that family with both operands by LDS-DMA (one 8-wave workgroup per CU)
-bool gemm_x2e_takes(const GemmArgs& a, int pro);
-int launch_gemm_x2e(const GemmArgs& a, const uint4* pl, hipStream_t st);
 // gemm_x2f.hip (round 6): the launches of that family with whole 256 x 256 tiles as ONE wave per SIMD, 64 positions per wave
 bool gemm_x2f_takes(const GemmArgs& a, int pro);
 int launch_gemm_x2f(const GemmArgs& a, const uint4* pl, int pro, hipStream_t st);

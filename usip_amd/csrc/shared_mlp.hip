@@ -1017,17 +1017,13 @@ static int mlp_gemm_impl(int mode, const float* At, int lda, const float* X, con
     if (a_trans) lda = -lda;
     if (M < 1 || K < 1 || P < 0 || nb < 0 || lda < (a_trans ? K : M)) return USIP_EINVAL;
     if ((long long)P * nb == 0) return USIP_OK;
-    if (!At || !Y || pro < 0 || pro > 3) return USIP_EINVAL;
-    if (pro != PRO_BN_BWD_POOL && !X) return USIP_EINVAL;
-    if (pro != PRO_NONE && !coef) return USIP_EINVAL;
-    if ((pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL) && (!X2 || stats)) return USIP_EINVAL;
-    if (pro == PRO_BN_BWD_POOL && (!pool_dp || !pool_arg || pool_group < 4 || pool_group % 4 != 0 ||
-                                   P % pool_group != 0 || P % 4 != 0)) return USIP_EINVAL;
-    if (rowbias && (rb_group < 1 || P % rb_group != 0)) return USIP_EINVAL;
-    if (y_rows == 0) y_rows = M;                           // Y is a dense [nb][M][P] tensor
-    if (y_rows < M) return USIP_EINVAL;
-    GemmArgs a{At, lda, X, X2, coef, bias, Y, stats, M, K, P, nb, rowbias, rb_group, pool_dp, pool_arg, pool_group,
-               a_trans, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    if (!At) return USIP_EINVAL;
+    // these kernels alone read the pooled prologue's (dpooled, arg) as float4 runs inside one neighbourhood
+    if (pro == PRO_BN_BWD_POOL && (pool_group % 4 != 0 || P % 4 != 0)) return USIP_EINVAL;
+    GemmArgs a;
+    if (!gemm_entry_args(a, X, X2, coef, pro, bias, rowbias, rb_group, pool_dp, pool_arg, pool_group, Y, y_rows, stats,
+                         M, K, P, nb)) return USIP_EINVAL;
+    a.At = At; a.lda = lda; a.a_trans = a_trans;
     hipStream_t st = (hipStream_t)stream;
     if (mode == 1) return launch_gemm_bf16(a, pro, st);
     if (mode == 2 && x3_gemm_pays(M, K, P, nb)) return launch_gemm_x3(a, pro, st);

@@ -25,9 +25,6 @@ using namespace usip_mlp;
 
 namespace {
 
-// byte offset of (row, 16-B half) inside a [rows][16 bf16] plane: halves swapped in every other block of 8 rows
-__device__ __forceinline__ int lds_off(int row, int half) { return row * 32 + ((half ^ (row >> 3)) & 1) * 16; }
-
 // Scale of a weight operand for the two-plane fp16 image: 2^e with max|A| 2^e in [2^13, 2^14).  Two levels without
 // atomics: X2H_PARTS workgroups per operand each leave the maximum of their share behind the image (floats
 // [4, 4 + X2H_PARTS) of the trailer); the split kernel combines them (every workgroup the same way) and the operand's
@@ -1308,17 +1305,11 @@ extern "C" int usip_mlp_gemm_x3p_f32(const void* planes, const float* X, const f
 {
     if (M < 1 || K < 1 || K > 640 || P < 0 || nb < 0) return USIP_EINVAL;
     if ((pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL) && K > 512) return USIP_EINVAL;
-    if ((long long)P * nb == 0) return USIP_OK;
-    if (!planes || !Y || pro < 0 || pro > 3 || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
-    if (pro != PRO_BN_BWD_POOL && !X) return USIP_EINVAL;
-    if (pro != PRO_NONE && !coef) return USIP_EINVAL;
-    if ((pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL) && (!X2 || stats)) return USIP_EINVAL;
-    if (pro == PRO_BN_BWD_POOL && (!pool_dp || !pool_arg || pool_group < 1 || P % pool_group != 0)) return USIP_EINVAL;
-    if (rowbias && (rb_group < 1 || P % rb_group != 0)) return USIP_EINVAL;
-    if (y_rows == 0) y_rows = M;
-    if (y_rows < M) return USIP_EINVAL;
-    GemmArgs a{nullptr, 0, X, X2, coef, bias, Y, stats, M, K, P, nb, rowbias, rb_group, pool_dp, pool_arg, pool_group,
-               0, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    if ((long long)P * nb == 0) return USIP_OK;              // (whatever pro is: the prologue set is checked of a launch only)
+    if (!planes || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
+    GemmArgs a;
+    if (!gemm_entry_args(a, X, X2, coef, pro, bias, rowbias, rb_group, pool_dp, pool_arg, pool_group, Y, y_rows, stats,
+                         M, K, P, nb)) return USIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const uint4* pl = reinterpret_cast<const uint4*>(planes);
     if (usip_mlp_x3p_tile_rows(M, P, nb) == 128) return launch_x3p<2, 2>(a, pl, pro, st);
@@ -1343,25 +1334,21 @@ extern "C" int usip_mlp_gemm_x2h_f32(const void* planes, const float* X, const f
                                      int M, int K, int P, int nb, void* stream)
 {
     if (M < 1 || K < 1 || K > 640 || P < 0 || nb < 0) return USIP_EINVAL;
+    // (an unbounded operand has no scale: no pro 0; unlike usip_mlp_gemm_x3p_f32 an empty call is refused for it too)
     if (pro != PRO_AFFINE_RELU && pro != PRO_BN_BWD && pro != PRO_BN_BWD_POOL) return USIP_EINVAL;
     if ((pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL) && K > 512) return USIP_EINVAL;
     if ((long long)P * nb == 0) return USIP_OK;
-    if (!planes || !Y || !coef || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
-    if (pro != PRO_BN_BWD_POOL && !X) return USIP_EINVAL;
-    if ((pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL) && (!X2 || stats)) return USIP_EINVAL;
-    if (pro == PRO_BN_BWD_POOL && (!pool_dp || !pool_arg || pool_group < 1 || P % pool_group != 0)) return USIP_EINVAL;
-    if (rowbias && (rb_group < 1 || P % rb_group != 0)) return USIP_EINVAL;
-    if (y_rows == 0) y_rows = M;
-    if (y_rows < M) return USIP_EINVAL;
-    GemmArgs a{nullptr, 0, X, X2, coef, bias, Y, stats, M, K, P, nb, rowbias, rb_group, pool_dp, pool_arg, pool_group,
-               0, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    if (!planes || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
+    GemmArgs a;
+    if (!gemm_entry_args(a, X, X2, coef, pro, bias, rowbias, rb_group, pool_dp, pool_arg, pool_group, Y, y_rows, stats,
+                         M, K, P, nb)) return USIP_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const uint4* pl = reinterpret_cast<const uint4*>(planes);
     if (usip_mlp_x3p_tile_rows(M, P, nb) == 128) return launch_x3p<2, 2, 2>(a, pl, pro, st);
     if (usip_mlp_x3p_tile_cols(M, P, nb, pro, stats != nullptr) == 256) return launch_x3p<4, 4, 2>(a, pl, pro, st);
-    // round 4: the streamed operand goes global -> registers -> MFMA (gemm_x2d.hip); knob x2_direct = 1 restores the
-    // LDS-staged kernel for A/B runs
-    if ((usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) != 1 && (long long)K * P * 4 < (1LL << 31))
+    // round 4: the streamed operand goes global -> registers -> MFMA (gemm_x2d.hip); the LDS-staged kernel stays for clouds
+    // beyond that family's 32-bit byte offsets, and under knob x2_direct = 1 as the tests' reference
+    if (usip_tuning_value(USIP_TUNE_X2_DIRECT) != 1 && (long long)K * P * 4 < (1LL << 31))
         return launch_gemm_x2d(a, pl, pro, st);
     return launch_x3p<4, 2, 2>(a, pl, pro, st);
 }
@@ -1376,15 +1363,14 @@ extern "C" int usip_mlp_gemm_x2h_f32(const void* planes, const float* X, const f
 static bool x2h_fork_args(GemmArgs& a, const float* X, const float* X2, const float* coef, float* Y, int y_rows,
                           const float* fork_dp, const int32_t* fork_arg, int fork_group, int M, int K, int P, int nb)
 {
+    // (no empty launch here, unlike usip_mlp_gemm_x2h_f32: P, nb >= 1)
     if (M < 1 || K < 1 || K > 512 || P < 1 || nb < 1 || fork_group < 1 || P % fork_group != 0) return false;
-    if (y_rows == 0) y_rows = M;
-    if (y_rows < M) return false;
-    a = GemmArgs{nullptr, 0, X, X2, coef, nullptr, Y, nullptr, M, K, P, nb, nullptr, 1, nullptr, nullptr, 0,
-                 0, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    if (!gemm_entry_args(a, X, X2, coef, PRO_BN_BWD, nullptr, nullptr, 1, nullptr, nullptr, 0, Y, y_rows, nullptr, M, K, P, nb))
+        return false;
     a.fork_dp = fork_dp; a.fork_arg = fork_arg; a.fork_group = fork_group;
     // the route usip_mlp_gemm_x2h_f32 takes to launch_gemm_x2d, then gemm_x2f.hip's own conditions
     if (usip_mlp_x3p_tile_rows(M, P, nb) == 128 || usip_mlp_x3p_tile_cols(M, P, nb, PRO_BN_BWD, 0) == 256) return false;
-    if ((usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) == 1 || (long long)K * P * 4 >= (1LL << 31)) return false;
+    if (usip_tuning_value(USIP_TUNE_X2_DIRECT) == 1 || (long long)K * P * 4 >= (1LL << 31)) return false;
     return gemm_x2f_takes(a, PRO_BN_BWD);
 }
 
@@ -1399,8 +1385,7 @@ extern "C" int usip_mlp_gemm_x2h_fork_f32(const void* planes, const float* X, co
                                           int y_rows, const float* fork_dp, const int32_t* fork_arg, int fork_group,
                                           int M, int K, int P, int nb, void* stream)
 {
-    if (!planes || !X || !X2 || !coef || !Y || !fork_dp || !fork_arg || (reinterpret_cast<uintptr_t>(planes) & 15u))
-        return USIP_EINVAL;
+    if (!planes || !fork_dp || !fork_arg || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
     GemmArgs a;
     if (!x2h_fork_args(a, X, X2, coef, Y, y_rows, fork_dp, fork_arg, fork_group, M, K, P, nb)) return USIP_EINVAL;
     return launch_gemm_x2f(a, reinterpret_cast<const uint4*>(planes), PRO_BN_BWD, (hipStream_t)stream);
@@ -1417,7 +1402,7 @@ extern "C" int usip_mlp_gemm_x2d_red_tiles(int M, int K, int P, int nb, int red_
     if (M < 256 || M % 256 || P < 128 || P % 128 || nb < 1 || K < 1 || K > 512) return 0;
     if (red_group != 0 && red_group != 16 && red_group != 32) return 0;
     if (usip_mlp_x3p_tile_rows(M, P, nb) != 256 || usip_mlp_x3p_tile_cols(M, P, nb, 2, 0) != 128) return 0;
-    if ((usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) == 1 || (usip_tuning_value(USIP_TUNE_X2_DIRECT) & 15) == 8) return 0;
+    if (usip_tuning_value(USIP_TUNE_X2_DIRECT) == 1 || usip_tuning_value(USIP_TUNE_X2_DIRECT) == 8) return 0;
     if ((long long)K * P * 4 >= (1LL << 31) || (long long)M * P * 4 >= (1LL << 31)) return 0;
     return nb * (P / 128);
 }
@@ -1429,13 +1414,12 @@ extern "C" int usip_mlp_gemm_x2h_red_f32(const void* planes, const float* X, con
 {
     if (pro != PRO_BN_BWD && pro != PRO_BN_BWD_POOL) return USIP_EINVAL;
     if (!usip_mlp_gemm_x2d_red_tiles(M, K, P, nb, red_gsum ? red_group : 0)) return USIP_EINVAL;
-    if (!planes || !Y || !coef || !X2 || !red_y || !red_coef || !red_out || (reinterpret_cast<uintptr_t>(planes) & 15u))
-        return USIP_EINVAL;
+    if (!planes || !red_y || !red_coef || !red_out || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
     if ((reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(red_y)) & 15u) return USIP_EINVAL;
-    if (pro == PRO_BN_BWD && !X) return USIP_EINVAL;
-    if (pro == PRO_BN_BWD_POOL && (!pool_dp || !pool_arg || pool_group < 1 || P % pool_group != 0)) return USIP_EINVAL;
-    GemmArgs a{nullptr, 0, X, X2, coef, nullptr, Y, nullptr, M, K, P, nb, nullptr, 1, pool_dp, pool_arg, pool_group,
-               0, M, 1, red_y, red_coef, red_out, red_gsum, red_gsum ? red_group : 0};
+    GemmArgs a;                                                // (Y is dense and, with P % 128 == 0, stored as float4: y_vec = 1)
+    if (!gemm_entry_args(a, X, X2, coef, pro, nullptr, nullptr, 1, pool_dp, pool_arg, pool_group, Y, M, nullptr, M, K, P, nb))
+        return USIP_EINVAL;
+    a.red_y = red_y; a.red_coef = red_coef; a.red_out = red_out; a.red_gsum = red_gsum; a.red_group = red_gsum ? red_group : 0;
     return launch_gemm_x2d(a, reinterpret_cast<const uint4*>(planes), pro, (hipStream_t)stream);
 }
 
@@ -1453,19 +1437,17 @@ extern "C" int usip_mlp_gemm_x2r_f32(const void* planes, const float* X, const f
                                      const int32_t* pool_arg, int pool_group, float* Y, int y_rows, float* stats, int M,
                                      int K, int P, int nb, void* stream)
 {
+    // (the row-bias rule is checked of an empty call too, unlike the other entries' rowbias checks)
     if (rowbias && (pro != PRO_AFFINE_RELU || rb_group < 32 || rb_group % 32 != 0 || P % rb_group != 0)) return USIP_EINVAL;
     if (M < 1 || M > 128 || K < 1 || K > 128 || P < 0 || nb < 0) return USIP_EINVAL;
     if (pro != PRO_AFFINE_RELU && pro != PRO_BN_BWD && pro != PRO_BN_BWD_POOL) return USIP_EINVAL;
     if ((long long)P * nb == 0) return USIP_OK;
-    if (!planes || !Y || !coef || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
-    if (pro != PRO_BN_BWD_POOL && !X) return USIP_EINVAL;
-    if ((pro == PRO_BN_BWD || pro == PRO_BN_BWD_POOL) && (!X2 || stats)) return USIP_EINVAL;
-    if (pro == PRO_BN_BWD_POOL && (!pool_dp || !pool_arg || pool_group < 1 || P % pool_group != 0)) return USIP_EINVAL;
-    if ((long long)K * P >= (1LL << 30)) return USIP_EINVAL;
-    if (y_rows == 0) y_rows = M;
-    if (y_rows < M) return USIP_EINVAL;
-    GemmArgs a{nullptr, 0, X, X2, coef, bias, Y, stats, M, K, P, nb, rowbias, rowbias ? rb_group : 1, pool_dp, pool_arg,
-               pool_group, 0, y_rows, (P % 4 == 0 && (reinterpret_cast<uintptr_t>(Y) & 15u) == 0) ? 1 : 0};
+    if ((long long)K * P >= (1LL << 30)) return USIP_EINVAL;   // 32-bit byte offsets inside a cloud
+    if (!planes || (reinterpret_cast<uintptr_t>(planes) & 15u)) return USIP_EINVAL;
+    GemmArgs a;
+    if (!gemm_entry_args(a, X, X2, coef, pro, bias, rowbias, rb_group, pool_dp, pool_arg, pool_group, Y, y_rows, stats,
+                         M, K, P, nb)) return USIP_EINVAL;
+    if (!rowbias) a.rb_group = 1;                              // (the other entries pass an unused rb_group through)
     const long long total = (long long)nb * ((P + 63) / 64);
     const unsigned grid = (unsigned)(total < 512 ? total : 512);             // two workgroups per CU, persistent
     hipStream_t st = (hipStream_t)stream;

@@ -1,5 +1,6 @@
 // usip_amd/csrc/split_common.h -- exact splits of fp32 operands into 16-bit planes for the matrix cores, shared by the
-// split-product kernels (shared_mlp_x3.hip, layer_bwd_x2.hip).  See shared_mlp_x3.hip for the arithmetic.
+// split-product kernels (shared_mlp_x3.hip, gemm_x2d.hip, gemm_x2f.hip, layer_bwd_x2.hip).  See shared_mlp_x3.hip for the
+// arithmetic.
 #pragma once
 #include "mlp_common.h"
 
@@ -10,6 +11,10 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int XBK = 16;                                        // k per stage: one MFMA step
+
+// byte offset of (row, 16-B half) inside a [rows][16 x 16-bit] plane (the image usip_mlp_split3_f32 / usip_mlp_split2h_f32
+// write): halves swapped in every other block of 8 rows
+__device__ __forceinline__ int lds_off(int row, int half) { return row * 32 + ((half ^ (row >> 3)) & 1) * 16; }
 
 // 2^e with bound * 2^e in [2^(top-1), 2^top) for a positive normal bound; e clamped to [-60, 60] (an all-zero operand
 // gets 2^60, which still maps it to zero); inf / NaN bounds leave the operand unscaled (the result is inf / NaN then,
@@ -55,4 +60,14 @@ __device__ __forceinline__ void split_pair_h(float x, float y, unsigned& p0, uns
     v = v - hf;                                                // exact
     f16x2 l = __builtin_convertvector(v, f16x2);
     p1 = __builtin_bit_cast(unsigned, l);
+}
+
+// The same split in 3 VALU instructions: two fp32 -> packed fp16 high parts and packed fp16 low parts
+__device__ __forceinline__ void split_pair_mix(float x, float y, unsigned& hi, unsigned& lo)
+{
+    const f32x2 v = {x, y};
+    hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));          // v_cvt_pk_f16_f32, RNE
+    // lo.lo16 = f16(x - f32(hi.lo16)), lo.hi16 = f16(y - f32(hi.hi16)): the differences are exact in fp32
+    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%2 op_sel_hi:[0,0,1]" : "=v"(lo) : "v"(x), "v"(hi));
+    asm("v_fma_mixhi_f16 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(lo) : "v"(y), "v"(hi));
 }

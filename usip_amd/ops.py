@@ -446,9 +446,6 @@ class PlanesPlan:
 # The narrow forward layers run the streaming kernel; USIP_NARROW_FWD=0 sends them through the generic tile kernel
 # again (A/B measurement, tools/ab_env.sh).
 NARROW_FWD = _os.environ.get("USIP_NARROW_FWD", "1") not in ("0", "off")
-# f32x2 mode: the 128-wide layers on the register-resident-weights kernel; USIP_X2R=0 for A/B runs
-X2R = _os.environ.get("USIP_X2R", "1") not in ("0", "off")
-X2R_NARROW = _os.environ.get("USIP_X2R_NARROW", "1") not in ("0", "off")
 # The gradient of a layer output that is max-pooled AND passed on (functional.group_max_fork): the pooling part is added by
 # the kernel that produces the dense part, at its store (csrc/gemm_x2f.hip: FORK), where that launch can;
 # USIP_POOL_GRAD_FOLD=0 keeps the stand-alone pass (group_max_backward_add_) everywhere, for A/B runs.
@@ -504,102 +501,82 @@ def mlp_gemm(At: torch.Tensor, X: torch.Tensor, bias=None, want_stats: bool = Fa
     # narrow layers (64 inputs, 64 / 128 outputs) at many positions: the streaming kernel (csrc/narrow_fwd.hip)
     # f32x2 mode: the 64 -> 128 layer (the feature half of conv4, with its row bias) goes to the register-resident f32x2
     # kernel -- the streaming kernel's fp32 MFMAs make it matrix-bound there (stand-alone 79-146 us depending on the box
-    # against 82-109; in the step the same or better).  USIP_X2R_NARROW=0 for A/B runs.
-    rb_ok = rowbias is None or (rb_group % 32 == 0 and P % rb_group == 0)
-    x2r_direct = (X2R and X2R_NARROW and _matmul_mode == "f32x2" and pro == 1 and coef is not None and coef.shape[0] >= 4
+    # against 82-109; in the step the same or better).
+    lib = _lib.lib()
+    rb_ok = rowbias is None or (rb_group % 32 == 0 and P % rb_group == 0)       # a row bias those two kernels can take
+    x2r_direct = (_matmul_mode == "f32x2" and pro == 1 and coef is not None and coef.shape[0] >= 4
                   and M == 128 and K == 64 and not a_trans and pool is None and X2 is None and rb_ok
                   and nb * P >= 65536 and K * P < 2 ** 30)
     nf_blocks = 0
     if (NARROW_FWD and not x2r_direct and _matmul_mode != "bf16" and not a_trans and pool is None and X2 is None and pro in (0, 1)
-            and K == 64 and M in (64, 128) and X.data_ptr() % 16 == 0
-            and (rowbias is None or (rb_group % 32 == 0 and P % rb_group == 0))):
-        nf_blocks = int(_lib.lib().usip_mlp_narrow_forward_blocks(M, K, P, nb))
-    if nf_blocks:
-        stats = torch.empty((2, M, nf_blocks), dtype=torch.float32, device=X.device) if want_stats else None
-        with torch.cuda.device(X.device), prof.kernel(
-                "shared_mlp_gemm_%s %dx%d" % (tag, M, K), 4.0 * nb * P * (K + M), 2.0 * M * K * nb * P, keyed=True):
-            _lib.check(_lib.lib().usip_mlp_narrow_forward_f32(a_ptr, lda, _ptr(X), _opt(coef), int(pro), _opt(bias),
-                                                              _opt(rowbias), int(rb_group), y_ptr, int(y_rows),
-                                                              _opt(stats), M, K, P, nb, _stream(X)),
-                       "usip_mlp_narrow_forward_f32")
-        return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
-    fn_name = {"bf16": "usip_mlp_gemm_bf16", "f32x3": "usip_mlp_gemm_f32x3",
-               "f32x2": "usip_mlp_gemm_f32x3"}.get(_matmul_mode, "usip_mlp_gemm_f32")
-    x3 = _x3_family() and (x2r_direct or bool(_lib.lib().usip_mlp_gemm_f32x3_used(M, K, P, nb)))
+            and K == 64 and M in (64, 128) and X.data_ptr() % 16 == 0 and rb_ok):
+        nf_blocks = int(lib.usip_mlp_narrow_forward_blocks(M, K, P, nb))
+    x3 = not nf_blocks and _x3_family() and (x2r_direct or bool(lib.usip_mlp_gemm_f32x3_used(M, K, P, nb)))
     x3p = x3 and not a_trans and K <= (512 if pro >= 2 else 640)       # weight operand split ahead of time
     # two fp16 planes: only where the streamed operand's bound is known (see usip_mlp_gemm_x2h_f32)
     x2h = (x3p and _matmul_mode == "f32x2" and coef is not None and
            ((pro == 1 and coef.shape[0] >= 4 and bound_covers(coef, nb * P)) or (pro >= 2 and coef.shape[0] >= 5)))
     # 128-wide layers: weight fragments resident in registers, persistent workgroups (usip_mlp_gemm_x2r_f32)
-    x2r = (x2h and M <= 128 and K <= 128 and X2R and K * P < 2 ** 30          # (usip_mlp_gemm_x2r_f32's own limits)
+    x2r = (x2h and M <= 128 and K <= 128 and K * P < 2 ** 30                  # (usip_mlp_gemm_x2r_f32's own limits)
            and (rowbias is None or (pro == 1 and rb_ok and rb_group >= 32)))
     stats = None
     if want_stats:
-        tiles = _lib.lib().usip_mlp_gemm_x2r_tiles(P, nb) if x2r else _lib.lib().usip_mlp_gemm_tiles(M, P, nb)
+        tiles = nf_blocks or (lib.usip_mlp_gemm_x2r_tiles(P, nb) if x2r else lib.usip_mlp_gemm_tiles(M, P, nb))
         stats = torch.empty((2, M, tiles), dtype=torch.float32, device=X.device)
 
     planes = weight_planes(At, a_offset, M, K, 2 if x2h else 3, P, nb) if x3p else None
     moved = 0.0
     if x3p:      # bytes into the CUs: per (tile, 16-k stage) the weight planes (L2) + the streamed operand, + the output
-        bm_ = int(_lib.lib().usip_mlp_x3p_tile_rows(M, P, nb))
-        bn_ = 128 if x2h else int(_lib.lib().usip_mlp_x3p_tile_cols(M, P, nb, int(pro), 1 if want_stats else 0))
+        bm_ = int(lib.usip_mlp_x3p_tile_rows(M, P, nb))
+        bn_ = 128 if x2h else int(lib.usip_mlp_x3p_tile_cols(M, P, nb, int(pro), 1 if want_stats else 0))
         ntiles = nb * ((P + bn_ - 1) // bn_) * ((M + bm_ - 1) // bm_)
         moved = ntiles * ((K + 15) // 16) * ((2 if x2h else 3) * bm_ * 32 + 16 * bn_ * 4 * (2 if pro == 2 else 1)) \
             + 4.0 * nb * M * P
         if x2r:                                               # the weight fragments stay in registers
             moved = 4.0 * nb * P * (K * (2 if pro == 2 else 1) + M)
+    plain_dgrad = x2h and not x2r and pro >= 2 and bias is None and rowbias is None     # what the red and fork launches take
+    red_tiles = 0
+    if (red is not None and plain_dgrad and out is None
+            and red[1] is not None and red[1].shape[0] >= 4 and tuple(red[0].shape) == (nb, M, P)
+            and red[0].is_contiguous() and red[0].data_ptr() % 16 == 0):
+        red_tiles = int(lib.usip_mlp_gemm_x2d_red_tiles(M, K, P, nb, int(red_group)))
+    fork_fold = False
+    if fork is not None and plain_dgrad and pro == 2 and red is None and not want_stats and POOL_GRAD_FOLD:
+        f_dp, f_arg, f_group = fork
+        _need(f_dp, "fork dpooled", torch.float32)
+        _need(f_arg, "fork arg", torch.int32)
+        fork_fold = bool(f_group > 0 and P % f_group == 0 and tuple(f_dp.shape) == (nb, M, P // f_group)
+                         and f_arg.shape == f_dp.shape and f_dp.data_ptr() % 16 == 0 and f_arg.data_ptr() % 16 == 0
+                         and X.data_ptr() % 16 == 0 and X2.data_ptr() % 16 == 0 and y_ptr.value % 16 == 0
+                         and lib.usip_mlp_gemm_x2h_fork_supported(M, K, P, nb, int(f_group)))
+    third = None                                              # red: the RedSums or None; fork: folded or not
+    x_ptr = None if pool is not None else _ptr(X)
+    epi = (_opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group))
+    pooled = (_opt(pool_dp), _opt(pool_arg), int(pool_group))
+    shape = (M, K, P, nb, _stream(X))
+    if nf_blocks:
+        fn, args = "usip_mlp_narrow_forward_f32", (a_ptr, lda, x_ptr) + epi + (y_ptr, int(y_rows), _opt(stats))
+    elif red_tiles:
+        flat = torch.empty(2 * red_tiles * M + red_tiles * (M // 256), dtype=torch.float32, device=X.device)
+        third = RedSums(flat, M, blocks=red_tiles)
+        third.gsum = torch.empty((2, nb, M, P // red_group), dtype=torch.float32, device=X.device) if red_group else None
+        fn, args = "usip_mlp_gemm_x2h_red_f32", (_ptr(planes), x_ptr, _opt(X2), _opt(coef), int(pro)) + pooled + (
+            y_ptr, _ptr(red[0]), _ptr(red[1]), _ptr(flat), _opt(third.gsum), int(red_group))
+    elif fork_fold:
+        third = True
+        fn, args = "usip_mlp_gemm_x2h_fork_f32", (_ptr(planes), _ptr(X), _ptr(X2), _ptr(coef), y_ptr, int(y_rows),
+                                                  _ptr(f_dp), _ptr(f_arg), int(f_group))
+    else:       # the entries that share usip_mlp_gemm_f32's signature, with the split image in place of (At, lda) for three
+        fn = (("usip_mlp_gemm_x2r_f32" if x2r else "usip_mlp_gemm_x2h_f32" if x2h else "usip_mlp_gemm_x3p_f32") if x3p else
+              {"bf16": "usip_mlp_gemm_bf16", "f32x3": "usip_mlp_gemm_f32x3", "f32x2": "usip_mlp_gemm_f32x3"}.get(
+                  _matmul_mode, "usip_mlp_gemm_f32"))
+        args = ((_ptr(planes),) if x3p else (a_ptr, -lda if a_trans else lda)) + (x_ptr, _opt(X2)) + epi + pooled + (
+            y_ptr, int(y_rows), _opt(stats))
     with torch.cuda.device(X.device), prof.kernel("shared_mlp_gemm_%s %dx%d" % (tag, M, K),
                                                   4.0 * nb * P * (K * (2 if pro == 2 else 1) + M),
                                                   2.0 * M * K * nb * P, keyed=True, moved=moved):
-        if x2r:
-            _lib.check(_lib.lib().usip_mlp_gemm_x2r_f32(_ptr(planes), None if pool is not None else _ptr(X), _opt(X2),
-                                                        _opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group),
-                                                        _opt(pool_dp), _opt(pool_arg), int(pool_group), y_ptr,
-                                                        int(y_rows), _opt(stats), M, K, P, nb, _stream(X)),
-                       "usip_mlp_gemm_x2r_f32")
-            return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
-        red_tiles = 0
-        if (red is not None and x2h and not x2r and pro >= 2 and out is None and bias is None and rowbias is None
-                and red[1] is not None and red[1].shape[0] >= 4 and tuple(red[0].shape) == (nb, M, P)
-                and red[0].is_contiguous() and red[0].data_ptr() % 16 == 0):
-            red_tiles = int(_lib.lib().usip_mlp_gemm_x2d_red_tiles(M, K, P, nb, int(red_group)))
-        if red_tiles:
-            flat = torch.empty(2 * red_tiles * M + red_tiles * (M // 256), dtype=torch.float32, device=X.device)
-            gsum = torch.empty((2, nb, M, P // red_group), dtype=torch.float32, device=X.device) if red_group else None
-            _lib.check(_lib.lib().usip_mlp_gemm_x2h_red_f32(_ptr(planes), None if pool is not None else _ptr(X), _opt(X2),
-                                                            _opt(coef), int(pro), _opt(pool_dp), _opt(pool_arg),
-                                                            int(pool_group), y_ptr, _ptr(red[0]), _ptr(red[1]), _ptr(flat),
-                                                            _opt(gsum), int(red_group), M, K, P, nb, _stream(X)),
-                       "usip_mlp_gemm_x2h_red_f32")
-            r = RedSums(flat, M, blocks=red_tiles)
-            r.gsum = gsum
-            return Y, stats, r
-        if (fork is not None and x2h and pro == 2 and red is None and bias is None and rowbias is None and not want_stats
-                and POOL_GRAD_FOLD):
-            f_dp, f_arg, f_group = fork
-            _need(f_dp, "fork dpooled", torch.float32)
-            _need(f_arg, "fork arg", torch.int32)
-            if (f_group > 0 and P % f_group == 0 and tuple(f_dp.shape) == (nb, M, P // f_group) and f_arg.shape == f_dp.shape
-                    and f_dp.data_ptr() % 16 == 0 and f_arg.data_ptr() % 16 == 0 and X.data_ptr() % 16 == 0
-                    and X2.data_ptr() % 16 == 0 and y_ptr.value % 16 == 0
-                    and _lib.lib().usip_mlp_gemm_x2h_fork_supported(M, K, P, nb, int(f_group))):
-                _lib.check(_lib.lib().usip_mlp_gemm_x2h_fork_f32(_ptr(planes), _ptr(X), _ptr(X2), _ptr(coef), y_ptr,
-                                                                 int(y_rows), _ptr(f_dp), _ptr(f_arg), int(f_group), M, K, P,
-                                                                 nb, _stream(X)), "usip_mlp_gemm_x2h_fork_f32")
-                return Y, stats, True
-        if x3p:
-            fn = "usip_mlp_gemm_x2h_f32" if x2h else "usip_mlp_gemm_x3p_f32"
-            _lib.check(getattr(_lib.lib(), fn)(_ptr(planes), None if pool is not None else _ptr(X), _opt(X2),
-                                               _opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group),
-                                               _opt(pool_dp), _opt(pool_arg), int(pool_group), y_ptr,
-                                               int(y_rows), _opt(stats), M, K, P, nb, _stream(X)), fn)
-            return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
-        _lib.check(getattr(_lib.lib(), fn_name)(a_ptr, -lda if a_trans else lda,
-                                                None if pool is not None else _ptr(X), _opt(X2),
-                                                _opt(coef), int(pro), _opt(bias), _opt(rowbias), int(rb_group),
-                                                _opt(pool_dp), _opt(pool_arg), int(pool_group),
-                                                y_ptr, int(y_rows), _opt(stats), M, K, P, nb, _stream(X)), fn_name)
-    return (Y, stats, None) if red is not None else ((Y, stats, False) if fork is not None else (Y, stats))
+        _lib.check(getattr(lib, fn)(*args, *shape), fn)
+    return (Y, stats, third) if red is not None else ((Y, stats, bool(third)) if fork is not None else (Y, stats))
 
 
 def bn_finalize(stats, count, gamma, beta, eps, momentum, running_mean, running_var):
