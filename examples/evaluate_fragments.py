@@ -35,6 +35,8 @@ from usip_amd.baselines with the outdoor defaults times --scale (default 0.05): 
 checkpoint is read.  --write-descriptors DIR writes DIR/<scene>/<i>.bin rows [x y z d0 .. d32].  (On the synthetic room the
 results files' keypoints are shared landmarks and FPFH registers most pairs; a baseline detector's keypoints there are mostly
 the random points that pad the count, which no two fragments share, so that run only shows that the path works.)
+--descriptor-method shot does the same with SHOT-352 (usip_amd.baselines.ShotDescriptor, 352 columns; --shot-radius, default
+0.25 m, --shot-normal-radius, default 0.125 m; --fpfh-normals chooses its normals too).
 
 Prints ONE JSON line (what evaluate.m prints, per scene and as means, and the registrator) and writes <results>/<scene>.log as writeLog.m does;
 with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
@@ -69,9 +71,9 @@ def make_synthetic(root, fragments, points, dim, seed):
 
 
 def add_fpfh_fragment(ev, i, xyz, cloud, args):
-    """--descriptor-method fpfh: fragment i's keypoints -- the results file's (xyz [M,3]) or, with --method iss | harris | sift |
+    """--descriptor-method fpfh | shot: fragment i's keypoints -- the results file's (xyz [M,3]) or, with --method iss | harris | sift |
     random, --top of them from usip_amd.baselines at the outdoor defaults times --scale -- described by Fast Point Feature
-    Histograms over the fragment's cloud.  No network, no checkpoint."""
+    Histograms, or by SHOT-352, over the fragment's cloud.  No network, no checkpoint."""
     import torch
     from usip_amd import baselines as bl
     t = torch.from_numpy(np.ascontiguousarray(np.asarray(cloud).T, dtype=np.float32)).to(args.device)
@@ -93,7 +95,9 @@ def add_fpfh_fragment(ev, i, xyz, cloud, args):
         if t.shape[0] < 6:
             raise SystemExit("--fpfh-normals supplied: fragment %d has no normal columns (expected rows [x y z nx ny nz ..])" % i)
         normals = t[3:6].unsqueeze(0).contiguous()
-    desc = bl.FpfhDescriptor(args.fpfh_radius, args.fpfh_normal_radius)(pc, kp.contiguous(), None, None, normals)
+    describe = bl.ShotDescriptor(args.shot_radius, args.shot_normal_radius) if args.descriptor_method == "shot" else \
+        bl.FpfhDescriptor(args.fpfh_radius, args.fpfh_normal_radius)
+    desc = describe(pc, kp.contiguous(), None, None, normals)
     return ev.add_fragment_result(i, kp[0].t(), desc[0].t(), cloud)
 
 
@@ -112,7 +116,7 @@ def evaluate_scene(name, scenes, results, gt_root, args):
                               optimize_args=dict(tau2=args.optimize_tau2, fill=args.optimize_fill,
                                                  transform=args.optimize_transform) if args.optimize else None)
     for i, path in enumerate(clouds):
-        if args.descriptor_method == "fpfh":
+        if args.descriptor_method != "learned":
             add_fpfh_fragment(ev, i, rows[i][0] if rows is not None else None, np.load(path), args)
         else:
             ev.add_fragment_result(i, rows[i][0], rows[i][1], np.load(path))
@@ -164,17 +168,20 @@ def main():
     ap.add_argument("--batch-pairs", type=int, default=32)
     ap.add_argument("--pair-files", action="store_true")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--descriptor-method", choices=("learned", "fpfh"), default="learned")
+    ap.add_argument("--descriptor-method", choices=("learned", "fpfh", "shot"), default="learned")
     ap.add_argument("--method", choices=("results", "iss", "harris", "sift", "random"), default="results")
     ap.add_argument("--top", type=int, default=512)
     ap.add_argument("--scale", type=float, default=0.05)
     ap.add_argument("--fpfh-radius", type=float, default=0.25)
     ap.add_argument("--fpfh-normal-radius", type=float, default=0.125)
     ap.add_argument("--fpfh-normals", choices=("estimated", "supplied"), default="estimated")
+    ap.add_argument("--shot-radius", type=float, default=0.25)
+    ap.add_argument("--shot-normal-radius", type=float, default=0.125)
     ap.add_argument("--write-descriptors", metavar="DIR")
     args = ap.parse_args()
-    if args.method != "results" and args.descriptor_method != "fpfh":
-        ap.error("--method %s needs --descriptor-method fpfh (the results files hold the learned descriptors)" % args.method)
+    if args.method != "results" and args.descriptor_method == "learned":
+        ap.error("--method %s needs --descriptor-method fpfh or shot (the results files hold the learned descriptors)"
+                 % args.method)
     if args.log_transform == "refined" and args.refine != "icp":
         ap.error("--log-transform refined needs --refine icp")
     if args.optimize and args.refine != "icp":

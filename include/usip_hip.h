@@ -1302,6 +1302,69 @@ int usip_fpfh_gather_f32_cpu(const float* pc, const int32_t* count, const int32_
                              const float* keypoints, const int32_t* kp_count, int B, int N, int M, double radius, double* fpfh,
                              int32_t* kp_members, int num_threads);
 
+/* ------------------------------------------------------------------ f-20  baseline descriptor: SHOT
+ * The hand-crafted descriptor the reference's outdoor scoring script is set to (eval_outdoor/kitti/evaluate_kitti.m reads
+ * .../kitti/shot/iss_256 with FEATURE_DIM = 352) and the reference does not contain: SHOT-352 (Tombari, Salti, Di Stefano 2010)
+ * at keypoints of any detector.  PCL is not part of the reference; the definition below is this project's own, written after
+ * PCL's SHOTEstimation / SHOTLocalReferenceFrameEstimation (DESIGN 8p lists the deviations).  Float64 arithmetic on float32
+ * inputs, never contracted; only + - * / sqrt fabs and comparisons feed a result; csrc/shot_math.h is the arithmetic.  Frames,
+ * count, perm, membership (strict d2 < r * r over f-7's sqdist(q, p_j)), the limits and the normals f64 [B][3][N] (a row HAS A
+ * NORMAL iff its components are finite and not all zero) are f-19's; keypoints f32 [B][3][M] (any positions), kp_count i32 [B]
+ * or NULL.  Every dot product is (a0 b0 + a1 b1) + a2 b2.
+ *
+ * usip_shot_lrf_f32: the local reference frame of keypoint q over ALL live rows within r (lrf_members i32 [B][M] counts them; no
+ * normal is needed, a row at d2 == 0 counts).  d = p_j - q, w = r - sqrt(d2); seven sums: w, and with wda = w * da: wd0 d0,
+ * wd0 d1, wd0 d2, wd1 d1, wd1 d2, wd2 d2.  THE ORDER OF THE SUMS is f-19's: 64 partial sums, partial sum l over the positions
+ * lo + l + 64 k of the frame's stable order along x, ascending, lo = the first position with q_x - x < r; the 64 are folded by
+ * l += l ^ 32, 16, 8, 4, 2, 1.  C = the six sums / sum w; f-7's 8 cyclic Jacobi sweeps in f-7's order; x = the eigenvector
+ * column of the largest diagonal entry, z = of the smallest (the first of equal entries either way).  Sign of x: the members
+ * with d . x >= 0 are counted against those with d . x < 0; x is negated iff the first count is the smaller (a tie keeps x); z
+ * likewise; y = z cross x.  lrf f64 [B][M][9] = the rows x, y, z.  Fewer than 5 members, a sum w that is not positive or a
+ * component that is not finite: NO FRAME, nine zeros.
+ *
+ * usip_shot_hist_f32: lrf f64 [B][M][9] as above or supplied; a row of it IS A FRAME iff its nine numbers are finite and x is
+ * not all zero.  The members of q: rows with a normal, d2 < r2 and d2 > 0 (kp_members i32 [B][M] counts them, with or without
+ * a frame).  x' = d . x, y' = d . y, z' = d . z, dist = sqrt(d2), c = n_j . z clamped to [-1, 1].
+ *   hard bins   t = (1 + c) * 5, cb = (int)(t + 0.5) in 0 .. 10; sh = dist > r / 2; el = z' > 0; az = the sector of width pi / 4,
+ *               counted from -pi, that holds the direction (x', y'), decided by signs and |x'| against |y'| alone.  THE TIE RULE:
+ *               a boundary direction belongs to the sector that begins there, the direction pi (y' == 0 of either sign, x' < 0)
+ *               to sector 7, (0, 0) is the direction 0 (sector 4): with y' >= 0, x' > 0 gives 4 when |y'| < |x'| and 5
+ *               otherwise, x' <= 0 gives 6 when |y'| > |x'| and 7 otherwise; with y' < 0, x' < 0 gives 0 when |y'| < |x'| and 1
+ *               otherwise, x' >= 0 gives 2 when |y'| > |x'| and 3 otherwise.  column = ((az * 2 + el) * 2 + sh) * 11 + cb.
+ *   offsets     from the centre of the member's own bin, each clamped to [-1/2, 1/2].  cosine: t - cb, neighbour cb + 1 or cb -
+ *               1 by its sign where that lies in 0 .. 10.  radial: dist / (r / 2) - 1/2 (inner shell; neighbour the outer shell
+ *               for an offset > 0) or (dist - r / 2) / (r / 2) - 1/2 (outer shell; neighbour the inner shell for an offset < 0);
+ *               no neighbour towards the centre or beyond r.  elevation: u = z' / dist clamped to [-1, 1], theta =
+ *               angle(sqrt((1 - u) * (1 + u)), u), offset (theta - centre) / (pi / 2) with centre pi / 4 (el = 1) or 3 pi / 4
+ *               (el = 0); the neighbour is the other half on the equator side only (el = 1: offset > 0; el = 0: offset < 0).
+ *               azimuth: phi = angle(y', x'), offset (phi - (az - 3.5) * (pi / 4)) / (pi / 4), neighbour az + 1 or az - 1 modulo 8
+ *               by its sign.  angle(y, x) is csrc/shot_math.h's own inverse tangent of two arguments (an octant reduction by
+ *               comparisons, one division, a float64 polynomial in Horner's order), the same operations on either side; a zero
+ *               of either sign counts as +0.
+ *   weights     INTEGERS, quantum 2^-32: q_k = (int64)(|offset_k| * 4294967296.0); the member's own column gets the sum over
+ *               the four k of 2^32 - q_k, each existing neighbour column its q_k; a q_k towards a missing neighbour is dropped.
+ *               hist i64 [B][M][352].  Integer sums do not depend on the order of the walk.
+ *   descriptor  h_b = (double)hist_b; s = sum h_b * h_b: 64 partial sums, partial l over the columns l + 64 k ascending,
+ *               folded as above; shot f64 [B][M][352] = h / sqrt(s), zeros when s == 0 or there is no frame.
+ * Slots beyond kp_count[b] get zeros.  A wrong perm gives wrong values, never a wild read.  USIP_EINVAL: a shape outside the
+ * limits (M in 1 .. 65535), a radius that is not positive and finite, a NULL among the required pointers (count and kp_count
+ * may be NULL). */
+int usip_shot_lrf_f32(const float* pc, const int32_t* count, const int32_t* perm, const float* keypoints,
+                      const int32_t* kp_count, int B, int N, int M, double radius, double* lrf, int32_t* lrf_members,
+                      void* stream);
+int usip_shot_hist_f32(const float* pc, const int32_t* count, const int32_t* perm, const double* normals,
+                       const float* keypoints, const int32_t* kp_count, const double* lrf, int B, int N, int M, double radius,
+                       int64_t* hist, double* shot, int32_t* kp_members, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; every keypoint tests all live points of its
+ * frame, in the frame's own stable order along x (no perm); num_threads splits the keypoints. */
+int usip_shot_lrf_f32_cpu(const float* pc, const int32_t* count, const float* keypoints, const int32_t* kp_count, int B, int N,
+                          int M, double radius, double* lrf, int32_t* lrf_members, int num_threads);
+int usip_shot_hist_f32_cpu(const float* pc, const int32_t* count, const double* normals, const float* keypoints,
+                           const int32_t* kp_count, const double* lrf, int B, int N, int M, double radius, int64_t* hist,
+                           double* shot, int32_t* kp_members, int num_threads);
+/* out[i] = angle(y[i], x[i]), i < n: the inverse tangent as either side evaluates it, for measuring it against a libm */
+int usip_shot_angle_f64_cpu(const double* y, const double* x, long long n, double* out);
+
 /* ------------------------------------------------------------------ f-17  baseline keypoints: SIFT3D
  * The third hand-crafted detector the reference compares its learned one with (evaluation/save_keypoints.py:57-61, 314-325,
  * method = 'sift': PCLKeypoint.keypointSift(xyz, min_scale 0.5, n_octaves 4, n_scales_per_octave 8, min_contrast 0.1)).  The

@@ -11,7 +11,8 @@ the reference's own Python surface:
   usip_amd.evaluation                      keypoint repeatability and RANSAC registration (the reference's MATLAB
                                            evaluation) on the device: `from usip_amd import evaluation`
   usip_amd.baselines                       the baseline detectors it is compared with: ISS, Harris3D, SIFT3D and random keypoints,
-                                           and a hand-crafted descriptor for any keypoints: FPFH
+                                           and two hand-crafted descriptors for any keypoints: FPFH
+                                           (FpfhDescriptor) and SHOT-352 (ShotDescriptor)
 
 `usip_amd.install()` registers the drop-in extension modules under their reference names
 (`import index_max`, `import ball_query`) so that the reference's models/networks.py runs

@@ -28,8 +28,10 @@ tensor of the caller's (curvature, reflectance); its keypoints are voxel-cell ce
   random_keypoints   `num` distinct points per frame
   fpfh_spfh          (spfh i32 [B,N,33], members i32 [B,N], normals f64 [B,3,N]): every point's integer pair-feature histograms
   fpfh_descriptors   (desc f32 [B,33,M], kp_members i32 [B,M]) at keypoints f32 [B,3,M] of any detector: FPFH
+  shot_frames        (lrf f64 [B,M,9], lrf_members i32 [B,M]): every keypoint's local reference frame, zeros without one
+  shot_descriptors   (desc f32 [B,352,M], kp_members i32 [B,M]) at keypoints f32 [B,3,M] of any detector: SHOT
   *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp, csrc/harris_cpu.cpp,
-                     csrc/sift_cpu.cpp, csrc/fpfh_cpu.cpp)
+                     csrc/sift_cpu.cpp, csrc/fpfh_cpu.cpp, csrc/shot_cpu.cpp)
 
 The scoring scripts of the reference also name hand-crafted DESCRIPTORS (eval_indoor/3dmatch/evaluate.m: 'my'; % 3dmatch, spin,
 fpfh) that it does not contain.  FPFH (csrc/fpfh.hip, csrc/fpfh_math.h) describes the keypoints of any detector above without a
@@ -38,6 +40,9 @@ network or a checkpoint:
     fpfh = FpfhDescriptor(radius=2.0, normal_radius=1.0)     # this project's radii: the reference gives none
     desc = fpfh(pc, kp, count, kp_count)                     # f32 [B,33,M]
     evaluator.add_frame_descriptors(fid, kp, desc, kp_count) # evaluation.RegistrationEvaluator: score them
+
+The outdoor scoring script is set to SHOT (eval_outdoor/kitti/evaluate_kitti.m: .../kitti/shot/iss_256, FEATURE_DIM = 352);
+ShotDescriptor (csrc/shot.hip, csrc/shot_math.h) is called the same way and gives f32 [B,352,M].
 
 The selection is reproducible and free of host synchronisation: one CPU generator per frame, seeded from (seed, frame_id) the
 way prepare._keep_rows seeds its own, draws u in [0, 1) for every point; a live point's key is u when it is a keypoint and
@@ -60,6 +65,7 @@ ISS_DEFAULTS = dict(salient_radius=2.0, non_max_radius=2.0, gamma_21=0.975, gamm
 HARRIS_DEFAULTS = dict(radius=1.0, threshold=0.001, response="harris", min_neighbors=3)
 SIFT_DEFAULTS = dict(min_scale=0.5, n_octaves=4, n_scales_per_octave=8, min_contrast=0.1, field="z")
 FPFH_DEFAULTS = dict(radius=2.0, normal_radius=1.0, min_neighbors=3)   # this project's choice: the reference gives none
+SHOT_DEFAULTS = dict(radius=2.0, normal_radius=1.0, min_neighbors=3)   # this project's choice too
 
 
 def _check(salient_radius, non_max_radius, min_neighbors):
@@ -194,6 +200,37 @@ def fpfh_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2
     fpfh, kp_members = ops.fpfh_gather(pc, count, perm, spfh, members, keypoints, kp_count, radius)
     desc = fpfh.to(torch.float32).transpose(1, 2).contiguous()
     return (desc, kp_members, fpfh) if want_f64 else (desc, kp_members)
+
+
+# ------------------------------------------------------------------------------------------------ SHOT
+def shot_frames(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, perm=None):
+    """pc f32 [B,3,N], keypoints f32 [B,3,M] (any positions), count, kp_count i32 [B] or None -> (lrf f64 [B,M,9], lrf_members
+    i32 [B,M]): the rows x, y, z of every keypoint's local reference frame over the live points within `radius`; zeros where
+    there is none (fewer than 5 members)."""
+    _check_fpfh(radius, 1.0, 1)
+    pc, count = _frames(pc, count)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    perm = sort_along_x(pc, count) if perm is None else perm
+    return ops.shot_lrf(pc, count, perm, keypoints, kp_count, radius)
+
+
+def shot_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, normals=None, normal_radius: float = 1.0,
+                     want_f64: bool = False, min_neighbors: int = 3):
+    """pc f32 [B,3,N], keypoints f32 [B,3,M] (any positions: cloud points or not), count, kp_count i32 [B] or None, normals f32
+    [B,3,N] or None (harris_normals over normal_radius with min_neighbors) -> (desc f32 [B,352,M], kp_members i32 [B,M][, shot
+    f64 [B,M,352], hist i64 [B,M,352], lrf f64 [B,M,9], lrf_members i32 [B,M]]): SHOT-352 at the keypoints, the layout the
+    learned descriptor has (channels first).  The f32 descriptor is the cast of the f64 result.  One sort, no host
+    synchronisation.  radius 2 and normal_radius 1 (outdoor metres) are this project's choice: the reference gives none."""
+    _check_fpfh(radius, normal_radius, min_neighbors)
+    pc, count = _frames(pc, count)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    perm = sort_along_x(pc, count)
+    nrm = ops.harris_normals(pc, count, perm, normal_radius, min_neighbors)[0] if normals is None else \
+        _supplied(normals, pc, "shot")
+    lrf, lrf_members = ops.shot_lrf(pc, count, perm, keypoints, kp_count, radius)
+    hist, shot, kp_members = ops.shot_hist(pc, count, perm, nrm, keypoints, kp_count, lrf, radius)
+    desc = shot.to(torch.float32).transpose(1, 2).contiguous()
+    return (desc, kp_members, shot, hist, lrf, lrf_members) if want_f64 else (desc, kp_members)
 
 
 # ------------------------------------------------------------------------------------------------ SIFT3D (DESIGN 8l)
@@ -464,6 +501,23 @@ class FpfhDescriptor:
         return self.last[0]
 
 
+class ShotDescriptor:
+    """SHOT-352 with its parameters bundled, called where the learned descriptor is: __call__(pc, keypoints, count, kp_count,
+    normals) -> desc f32 [B,352,M]; .last holds (desc, kp_members) of the latest call.  normals f32 [B,3,N]: supplied ones (the
+    cloud's sn[:, :3]) instead of estimated ones."""
+
+    dim = 352
+
+    def __init__(self, radius: float = 2.0, normal_radius: float = 1.0, min_neighbors: int = 3):
+        _check_fpfh(radius, normal_radius, min_neighbors)
+        self.params = dict(radius=float(radius), normal_radius=float(normal_radius), min_neighbors=int(min_neighbors))
+        self.last = None
+
+    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
+        self.last = shot_descriptors(pc, keypoints, count, kp_count, normals=normals, **self.params)
+        return self.last[0]
+
+
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
 def _p(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
@@ -590,6 +644,73 @@ def fpfh_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float
     fpfh, kp_members = fpfh_gather_cpu(pc, count, spfh, members, keypoints, kp_count, radius, num_threads)
     desc = np.ascontiguousarray(fpfh.astype(np.float32).transpose(0, 2, 1))
     return (desc, kp_members, fpfh) if want_f64 else (desc, kp_members)
+
+
+def _keypoints_np(keypoints, kp_count, B):
+    kp = np.ascontiguousarray(keypoints, dtype=np.float32)
+    if kp.ndim != 3 or kp.shape[:2] != (B, 3):
+        raise ValueError("shot: expected keypoints f32 [B,3,M], got %s" % (kp.shape,))
+    kc = None if kp_count is None else np.ascontiguousarray(kp_count, dtype=np.int32)
+    if kc is not None and kc.shape != (B,):
+        raise ValueError("shot: kp_count must be i32 [B]")
+    return kp, kc
+
+
+def shot_frames_cpu(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, num_threads: int = 1):
+    """-> (lrf f64 [B,M,9], lrf_members i32 [B,M])"""
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    kp, kc = _keypoints_np(keypoints, kp_count, B)
+    M = kp.shape[2]
+    lrf, members = np.zeros((B, max(M, 1), 9), np.float64), np.zeros((B, max(M, 1)), np.int32)
+    _lib.check(_lib.lib().usip_shot_lrf_f32_cpu(_p(a), _p(c), _p(kp), _p(kc), B, N, M, float(radius), _p(lrf), _p(members),
+                                                int(num_threads)), "usip_shot_lrf_f32_cpu")
+    return lrf, members
+
+
+def shot_hist_cpu(pc, count, normals, keypoints, kp_count, lrf, radius: float, num_threads: int = 1):
+    """normals f64 [B,3,N], lrf f64 [B,M,9] -> (hist i64 [B,M,352], shot f64 [B,M,352], kp_members i32 [B,M])"""
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    kp, kc = _keypoints_np(keypoints, kp_count, B)
+    M = kp.shape[2]
+    nrm, frames = np.ascontiguousarray(normals, dtype=np.float64), np.ascontiguousarray(lrf, dtype=np.float64)
+    if nrm.shape != a.shape or frames.shape != (B, M, 9):
+        raise ValueError("shot: expected normals f64 [B,3,N] and lrf f64 [B,M,9]")
+    hist, shot = np.zeros((B, max(M, 1), ops.SHOT_WIDTH), np.int64), np.zeros((B, max(M, 1), ops.SHOT_WIDTH), np.float64)
+    kp_members = np.zeros((B, max(M, 1)), np.int32)
+    _lib.check(_lib.lib().usip_shot_hist_f32_cpu(_p(a), _p(c), _p(nrm), _p(kp), _p(kc), _p(frames), B, N, M, float(radius),
+                                                 _p(hist), _p(shot), _p(kp_members), int(num_threads)), "usip_shot_hist_f32_cpu")
+    return hist, shot, kp_members
+
+
+def shot_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, normals=None,
+                         normal_radius: float = 1.0, want_f64: bool = False, min_neighbors: int = 3, num_threads: int = 1):
+    """-> (desc f32 [B,352,M], kp_members i32 [B,M][, shot f64 [B,M,352], hist i64 [B,M,352], lrf f64 [B,M,9], lrf_members i32
+    [B,M]])"""
+    _check_fpfh(radius, normal_radius, min_neighbors)
+    a, c = _frames_np(pc, count)
+    if normals is None:
+        nrm = harris_normals_cpu(a, c, normal_radius, min_neighbors, num_threads)[0]
+    else:
+        nrm = np.asarray(normals)
+        if nrm.dtype != np.float32 or nrm.shape != a.shape:
+            raise ValueError("shot: supplied normals must be f32 %s" % (a.shape,))
+        nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    lrf, lrf_members = shot_frames_cpu(a, keypoints, c, kp_count, radius, num_threads)
+    hist, shot, kp_members = shot_hist_cpu(a, c, nrm, keypoints, kp_count, lrf, radius, num_threads)
+    desc = np.ascontiguousarray(shot.astype(np.float32).transpose(0, 2, 1))
+    return (desc, kp_members, shot, hist, lrf, lrf_members) if want_f64 else (desc, kp_members)
+
+
+def shot_angle_cpu(y, x):
+    """csrc/shot_math.h's inverse tangent of two arguments, as the kernels and the twin evaluate it"""
+    a, b = np.ascontiguousarray(y, dtype=np.float64), np.ascontiguousarray(x, dtype=np.float64)
+    if a.shape != b.shape:
+        raise ValueError("shot: y and x must have one shape")
+    out = np.zeros_like(a)
+    _lib.check(_lib.lib().usip_shot_angle_f64_cpu(_p(a), _p(b), a.size, _p(out)), "usip_shot_angle_f64_cpu")
+    return out
 
 
 def sift_exp_cpu(x):

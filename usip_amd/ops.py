@@ -1984,6 +1984,57 @@ def fpfh_gather(pc, count, perm, spfh, members, keypoints, kp_count, radius: flo
     return fpfh, kp_members
 
 
+# ------------------------------------------------------------------------------------------------ f-20 baseline descriptor: SHOT
+SHOT_WIDTH = 352
+
+
+def _need_keypoints(pc, keypoints, kp_count, tag):
+    """keypoints f32 [B,3,M] beside pc f32 [B,3,N], kp_count i32 [B] or None -> M"""
+    _need(keypoints, "keypoints", torch.float32)
+    if keypoints.dim() != 3 or keypoints.shape[0] != pc.shape[0] or keypoints.shape[1] != 3 or keypoints.device != pc.device \
+            or not 1 <= keypoints.shape[2] <= FPFH_MMAX:
+        raise RuntimeError("%s: expected keypoints f32 [B,3,M] on %s with M in 1..%d" % (tag, pc.device, FPFH_MMAX))
+    _need_on(kp_count, "kp_count", torch.int32, (pc.shape[0],), pc.device)
+    return keypoints.shape[2]
+
+
+def shot_lrf(pc, count, perm, keypoints, kp_count, radius: float):
+    """f-20: keypoints f32 [B,3,M] (any positions), kp_count i32 [B] or None -> (lrf f64 [B,M,9], the rows x, y, z of every
+    keypoint's local reference frame over the live points within the radius, zeros where there is none; lrf_members i32
+    [B,M])."""
+    B, N = _need_frames(pc, count, perm, "shot")
+    M = _need_keypoints(pc, keypoints, kp_count, "shot")
+    if not float(radius) > 0.0:
+        raise RuntimeError("shot: radius must be positive")
+    lrf = torch.empty((B, M, 9), dtype=torch.float64, device=pc.device)
+    members = torch.empty((B, M), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("shot_lrf", 16.0 * B * N + 88.0 * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_shot_lrf_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(keypoints), _opt_ptr(kp_count),
+                                                B, N, M, float(radius), _ptr(lrf), _ptr(members), _stream(pc)),
+                   "usip_shot_lrf_f32")
+    return lrf, members
+
+
+def shot_hist(pc, count, perm, normals, keypoints, kp_count, lrf, radius: float):
+    """f-20: normals f64 [B,3,N] (a row that is not finite or all zero: no normal), lrf f64 [B,M,9] (shot_lrf's, or supplied) ->
+    (hist i64 [B,M,352], the integer weights in quanta of 2^-32; shot f64 [B,M,352] = hist over its Euclidean norm, zeros
+    without a frame or a member; kp_members i32 [B,M])."""
+    B, N = _need_frames(pc, count, perm, "shot")
+    M = _need_keypoints(pc, keypoints, kp_count, "shot")
+    _need_on(normals, "normals", torch.float64, (B, 3, N), pc.device)
+    _need_on(lrf, "lrf", torch.float64, (B, M, 9), pc.device)
+    if normals is None or lrf is None or not float(radius) > 0.0:
+        raise RuntimeError("shot: normals and lrf are required and radius must be positive")
+    hist = torch.empty((B, M, SHOT_WIDTH), dtype=torch.int64, device=pc.device)
+    shot = torch.empty((B, M, SHOT_WIDTH), dtype=torch.float64, device=pc.device)
+    kp_members = torch.empty((B, M), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("shot_hist", 40.0 * B * N + (16.0 * SHOT_WIDTH + 88.0) * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_shot_hist_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(normals), _ptr(keypoints),
+                                                 _opt_ptr(kp_count), _ptr(lrf), B, N, M, float(radius), _ptr(hist), _ptr(shot),
+                                                 _ptr(kp_members), _stream(pc)), "usip_shot_hist_f32")
+    return hist, shot, kp_members
+
+
 # ------------------------------------------------------------------------------------------------ f-17 baseline keypoints: SIFT3D
 SIFT_NEAREST = 25
 
