@@ -37,6 +37,10 @@ results files' keypoints are shared landmarks and FPFH registers most pairs; a b
 the random points that pad the count, which no two fragments share, so that run only shows that the path works.)
 --descriptor-method shot does the same with SHOT-352 (usip_amd.baselines.ShotDescriptor, 352 columns; --shot-radius, default
 0.25 m, --shot-normal-radius, default 0.125 m; --fpfh-normals chooses its normals too).
+--descriptor-method spin does the same with spin images (usip_amd.baselines.SpinDescriptor, 153 columns; --spin-radius, default
+0.25 m, --spin-axis-radius, default 0.25 m: the SHOT frame whose z is the axis, --spin-support-angle-cos, default 0: no support
+angle and no normals, otherwise normals over 0.125 m or, with --fpfh-normals supplied, the files'; --spin-structure rectangular |
+radial): the `spin` of evaluate.m's descriptorName comment.
 
 Prints ONE JSON line (what evaluate.m prints, per scene and as means, and the registrator) and writes <results>/<scene>.log as writeLog.m does;
 with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
@@ -54,6 +58,7 @@ from usip_amd import fragments as fr            # noqa: E402
 from usip_amd import posegraph as pg            # noqa: E402
 
 LOOP_KEYS = ("loop_recall", "loop_precision", "loops_in", "loops_kept")
+SPIN_NORMAL_RADIUS = 0.125                      # metres: the normals a spin image's support angle reads, when one is set
 
 
 def make_synthetic(root, fragments, points, dim, seed):
@@ -71,9 +76,9 @@ def make_synthetic(root, fragments, points, dim, seed):
 
 
 def add_fpfh_fragment(ev, i, xyz, cloud, args):
-    """--descriptor-method fpfh | shot: fragment i's keypoints -- the results file's (xyz [M,3]) or, with --method iss | harris | sift |
-    random, --top of them from usip_amd.baselines at the outdoor defaults times --scale -- described by Fast Point Feature
-    Histograms, or by SHOT-352, over the fragment's cloud.  No network, no checkpoint."""
+    """--descriptor-method fpfh | shot | spin: fragment i's keypoints -- the results file's (xyz [M,3]) or, with --method iss | harris |
+    sift | random, --top of them from usip_amd.baselines at the outdoor defaults times --scale -- described by Fast Point Feature
+    Histograms, by SHOT-352 or by spin images, over the fragment's cloud.  No network, no checkpoint."""
     import torch
     from usip_amd import baselines as bl
     t = torch.from_numpy(np.ascontiguousarray(np.asarray(cloud).T, dtype=np.float32)).to(args.device)
@@ -96,6 +101,8 @@ def add_fpfh_fragment(ev, i, xyz, cloud, args):
             raise SystemExit("--fpfh-normals supplied: fragment %d has no normal columns (expected rows [x y z nx ny nz ..])" % i)
         normals = t[3:6].unsqueeze(0).contiguous()
     describe = bl.ShotDescriptor(args.shot_radius, args.shot_normal_radius) if args.descriptor_method == "shot" else \
+        bl.SpinDescriptor(args.spin_radius, args.spin_axis_radius, args.spin_support_angle_cos, SPIN_NORMAL_RADIUS,
+                          structure=args.spin_structure) if args.descriptor_method == "spin" else \
         bl.FpfhDescriptor(args.fpfh_radius, args.fpfh_normal_radius)
     desc = describe(pc, kp.contiguous(), None, None, normals)
     return ev.add_fragment_result(i, kp[0].t(), desc[0].t(), cloud)
@@ -168,7 +175,7 @@ def main():
     ap.add_argument("--batch-pairs", type=int, default=32)
     ap.add_argument("--pair-files", action="store_true")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--descriptor-method", choices=("learned", "fpfh", "shot"), default="learned")
+    ap.add_argument("--descriptor-method", choices=("learned", "fpfh", "shot", "spin"), default="learned")
     ap.add_argument("--method", choices=("results", "iss", "harris", "sift", "random"), default="results")
     ap.add_argument("--top", type=int, default=512)
     ap.add_argument("--scale", type=float, default=0.05)
@@ -177,10 +184,14 @@ def main():
     ap.add_argument("--fpfh-normals", choices=("estimated", "supplied"), default="estimated")
     ap.add_argument("--shot-radius", type=float, default=0.25)
     ap.add_argument("--shot-normal-radius", type=float, default=0.125)
+    ap.add_argument("--spin-radius", type=float, default=0.25)
+    ap.add_argument("--spin-axis-radius", type=float, default=0.25)
+    ap.add_argument("--spin-support-angle-cos", type=float, default=0.0)
+    ap.add_argument("--spin-structure", choices=("rectangular", "radial"), default="rectangular")
     ap.add_argument("--write-descriptors", metavar="DIR")
     args = ap.parse_args()
     if args.method != "results" and args.descriptor_method == "learned":
-        ap.error("--method %s needs --descriptor-method fpfh or shot (the results files hold the learned descriptors)"
+        ap.error("--method %s needs --descriptor-method fpfh, shot or spin (the results files hold the learned descriptors)"
                  % args.method)
     if args.log_transform == "refined" and args.refine != "icp":
         ap.error("--log-transform refined needs --refine icp")

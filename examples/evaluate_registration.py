@@ -19,7 +19,10 @@ instead of the learned descriptor: with a baseline --method no network is constr
 supplied takes the scans' own normals (columns 4 .. 6) instead of estimating them over --fpfh-normal-radius.
 --descriptor-method shot does the same with SHOT-352 (usip_amd.baselines.ShotDescriptor, 352 columns; --shot-radius, default 2,
 --shot-normal-radius, default 1): --method iss --top 256 --descriptor-method shot is the iss_256 + SHOT configuration the
-reference's evaluate_kitti.m is set to."""
+reference's evaluate_kitti.m is set to.
+--descriptor-method spin does the same with spin images (usip_amd.baselines.SpinDescriptor, 153 columns; --spin-radius, default
+2, --spin-axis-radius, default the radius, --spin-support-angle-cos, default 0: no support angle, --spin-structure rectangular |
+radial): the `spin` of eval_indoor/3dmatch/evaluate.m's descriptorName comment."""
 import argparse
 import json
 import os
@@ -108,7 +111,7 @@ def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, des
     dev = torch.device(device)
     opt = DetectorOptions(surface_normal_len=CS, node_knn_k_1=16)
     detector = build_detector(model, opt).to(dev) if method == "tsf" else None     # the baselines need none
-    descriptor = DescriptorLiteOld(opt).to(dev) if descriptor_method == "learned" else None       # FPFH and SHOT need none
+    descriptor = DescriptorLiteOld(opt).to(dev) if descriptor_method == "learned" else None       # the hand-crafted ones need none
     if detector is None:
         pass
     elif detector_ckpt:
@@ -125,18 +128,20 @@ def build_evaluator(model, detector_ckpt, top, nms_radius, max_trials, seed, des
                                             max_trials=max_trials, seed=seed)
 
 
-def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None, sift=None, fpfh=None, shot=None):
+def add_scans(evaluator, scans, nodes, seed, method="tsf", iss=None, harris=None, sift=None, fpfh=None, shot=None, spin=None):
     """method 'iss' / 'harris' / 'sift' / 'random': evaluator.top keypoints per frame from usip_amd.baselines (iss, harris,
     sift: IssDetector's / HarrisDetector's / SiftDetector's parameters; sift's field may be "x" | "y" | "z" or "curvature",
     the scans' seventh column).  fpfh: dict(radius, normal_radius, normals "estimated" | "supplied") -- the keypoints are
     described by baselines.FpfhDescriptor instead of the evaluator's descriptor.  shot: dict(radius, normal_radius) -- by
-    baselines.ShotDescriptor."""
+    baselines.ShotDescriptor.  spin: dict(radius, axis_radius, support_angle_cos, structure) -- by baselines.SpinDescriptor."""
     dev = evaluator.device
     fpfh = dict(fpfh) if fpfh is not None else None
     supplied = fpfh is not None and fpfh.pop("normals", "estimated") == "supplied"
     describe = baselines.FpfhDescriptor(**fpfh) if fpfh is not None else None
     if shot is not None:
         describe = baselines.ShotDescriptor(**shot)
+    if spin is not None:
+        describe = baselines.SpinDescriptor(**spin)
 
     def add(fid, pc, sn, kp, count):
         if describe is None:
@@ -184,7 +189,7 @@ def main():
     ap.add_argument("--nms-radius", type=float, default=1.0)
     ap.add_argument("--max-trials", type=int, default=10000)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there (fpfh: d0 .. d32, shot: d0 .. d351)")
+    ap.add_argument("--write-descriptors", metavar="DIR", help="write <id>.bin rows [x y z d0 .. d127] there (fpfh: d0 .. d32, shot: d0 .. d351, spin: d0 .. d152)")
     ap.add_argument("--method", default="tsf", choices=["tsf", "iss", "harris", "sift", "random"],
                     help="tsf: the learned detector; iss, harris, sift, random: the baselines, --top keypoints per frame")
     ap.add_argument("--salient-radius", type=float, default=2.0)
@@ -199,15 +204,21 @@ def main():
     ap.add_argument("--sift-scales", type=int, default=8)
     ap.add_argument("--sift-contrast", type=float, default=0.1)
     ap.add_argument("--sift-field", default="z", choices=["x", "y", "z", "curvature"])
-    ap.add_argument("--descriptor-method", default="learned", choices=["learned", "fpfh", "shot"],
+    ap.add_argument("--descriptor-method", default="learned", choices=["learned", "fpfh", "shot", "spin"],
                     help="learned: the descriptor network (--descriptor is its checkpoint); fpfh: Fast Point Feature Histograms; "
-                         "shot: SHOT-352")
+                         "shot: SHOT-352; spin: spin images")
     ap.add_argument("--fpfh-radius", type=float, default=2.0)
     ap.add_argument("--fpfh-normal-radius", type=float, default=1.0)
     ap.add_argument("--fpfh-normals", default="estimated", choices=["estimated", "supplied"],
                     help="supplied: the scans' own normals (columns 4 .. 6) instead of estimated ones")
     ap.add_argument("--shot-radius", type=float, default=2.0)
     ap.add_argument("--shot-normal-radius", type=float, default=1.0)
+    ap.add_argument("--spin-radius", type=float, default=2.0)
+    ap.add_argument("--spin-axis-radius", type=float, default=None, help="the radius of the SHOT frame whose z is the axis "
+                                                                         "(default: --spin-radius)")
+    ap.add_argument("--spin-support-angle-cos", type=float, default=0.0,
+                    help="> 0: only members whose estimated normal has |n . axis| at or above it")
+    ap.add_argument("--spin-structure", default="rectangular", choices=["rectangular", "radial"])
     args = ap.parse_args()
     if args.make_synthetic:
         scans, pairs = make_synthetic(np.random.default_rng(args.seed), args.frames, args.points)
@@ -227,10 +238,13 @@ def main():
               dict(radius=args.fpfh_radius, normal_radius=args.fpfh_normal_radius, normals=args.fpfh_normals)
               if args.descriptor_method == "fpfh" else None,
               dict(radius=args.shot_radius, normal_radius=args.shot_normal_radius)
-              if args.descriptor_method == "shot" else None)
+              if args.descriptor_method == "shot" else None,
+              dict(radius=args.spin_radius, axis_radius=args.spin_axis_radius, support_angle_cos=args.spin_support_angle_cos,
+                   structure=args.spin_structure)
+              if args.descriptor_method == "spin" else None)
     summary = evaluator.evaluate(pairs)
     summary.pop("per_pair")
-    fpfh = args.descriptor_method in ("fpfh", "shot")             # hand-crafted: there are no descriptor weights
+    fpfh = args.descriptor_method in ("fpfh", "shot", "spin")             # hand-crafted: there are no descriptor weights
     summary["seeded_weights"] = not ((args.detector or args.method != "tsf") and (args.descriptor or fpfh))
     summary["method"] = args.method
     if fpfh:                                                      # (the default's line is what it was)

@@ -1365,6 +1365,48 @@ int usip_shot_hist_f32_cpu(const float* pc, const int32_t* count, const double* 
 /* out[i] = angle(y[i], x[i]), i < n: the inverse tangent as either side evaluates it, for measuring it against a libm */
 int usip_shot_angle_f64_cpu(const double* y, const double* x, long long n, double* out);
 
+/* ------------------------------------------------------------------ f-21  baseline descriptor: spin images
+ * The last hand-crafted descriptor the reference's indoor scoring scripts name (eval_indoor/3dmatch/evaluate.m,
+ * evaluate_optimization.m, loop_evaluation/eval_loop.m: descriptorName = 'my'; % 3dmatch, spin, fpfh) and the reference does not
+ * contain: spin images (Johnson, Hebert 1999) at keypoints of any detector.  PCL is not part of the reference; the definition
+ * below is this project's own, written after PCL's SpinImageEstimation (DESIGN 8q lists the deviations).  Float64 arithmetic on
+ * float32 inputs, never contracted; only + - * / sqrt fabs floor and comparisons feed a result; csrc/spin_math.h is the
+ * arithmetic.  Frames, count, perm, membership (strict d2 < r * r over f-7's sqdist(q, p_j)), the limits, keypoints f32
+ * [B][3][M] (any positions) and kp_count are f-20's.  Every dot product is (a0 b0 + a1 b1) + a2 b2.
+ *
+ * usip_spin_image_f32:
+ *   axis        a row v of axes f64 [B][M][3] (f-20's z row, lrf[..][6 .. 8], or the caller's) IS AN AXIS iff its three numbers
+ *               are finite and v . v is positive and finite; a = v / sqrt(v . v).  Without an axis: zeros, no member.
+ *   members     live rows with d2 > 0 and d2 < r * r.  d = p_j - q, beta = d . a.  With support_angle_cos = s > 0: normals f64
+ *               [B][3][N] as f-19's; a row without a normal is skipped and so is one with fabs(n_j . a) < s (a counter-directed
+ *               normal passes); normals are used as given.  With s == 0 no normal is read and normals may be NULL.
+ *   structure 0 (rectangular) W = 8, bin = (r * 0.70710678118654757) / W: the cylinder inscribed in the search sphere.  alpha =
+ *               sqrt(max(0, d2 - beta * beta)), u = alpha / bin, v = beta / bin; the row is a member iff u < W, v < W and v > -W.
+ *   structure 1 (radial) bin = r / W, u = sqrt(d2) / bin; c = beta / sqrt(d2) clamped to [-1, 1], theta = angle(c, sqrt((1 - c) *
+ *               (1 + c))), f-20's inverse tangent: the arc sine of c in [-pi / 2, pi / 2]; v = theta / ((pi / 2) / W).  Every row
+ *               of the sphere is a member; a u that reaches W after rounding goes to ab = W - 1 and a v that reaches W to bb =
+ *               2 W - 1, with the largest offset below 1 (2^20 - 1 quanta).
+ *   cells       ab = (int)floor(u), bb = (int)floor(v) + W, offsets u - floor(u) and v - floor(v).
+ *   weights     INTEGERS, quantum 2^-20 per axis: qa = (int64)(offset_a * 1048576.0) capped at 2^20 - 1, qb likewise; the cells
+ *               (ab, bb), (ab + 1, bb), (ab, bb + 1), (ab + 1, bb + 1) get (2^20 - qa)(2^20 - qb), qa (2^20 - qb), (2^20 - qa) qb,
+ *               qa qb: exactly 2^40 per member.  column = row * (2 W + 1) + col: hist i64 [B][M][153] (9 rows of alpha, 17
+ *               columns of beta).  N <= 2^20 keeps a row's total below 2^61.  Integer sums do not depend on the order of the walk.
+ *   descriptor  kp_members i32 [B][M] counts the rows that added; spin f64 [B][M][153] = (double)hist_b / ((double)kp_members *
+ *               2^40), zeros when kp_members == 0.
+ * Slots beyond kp_count[b] get zeros.  A wrong perm gives wrong values, never a wild read.  USIP_EINVAL: a shape outside the
+ * limits (M in 1 .. 65535), a radius that is not positive and finite, support_angle_cos outside [0, 1] or not finite,
+ * support_angle_cos > 0 with normals NULL, a structure other than 0 and 1, a NULL among the required pointers (count, kp_count
+ * and, without a support angle, normals may be NULL). */
+int usip_spin_image_f32(const float* pc, const int32_t* count, const int32_t* perm, const double* normals,
+                        const float* keypoints, const int32_t* kp_count, const double* axes, int B, int N, int M, double radius,
+                        double support_angle_cos, int structure, int64_t* hist, double* spin, int32_t* kp_members, void* stream);
+/* HOST twin (every pointer on the host): the same arithmetic; every keypoint tests all live points of its frame, in the
+ * frame's own stable order along x (no perm); num_threads splits the keypoints. */
+int usip_spin_image_f32_cpu(const float* pc, const int32_t* count, const double* normals, const float* keypoints,
+                            const int32_t* kp_count, const double* axes, int B, int N, int M, double radius,
+                            double support_angle_cos, int structure, int64_t* hist, double* spin, int32_t* kp_members,
+                            int num_threads);
+
 /* ------------------------------------------------------------------ f-17  baseline keypoints: SIFT3D
  * The third hand-crafted detector the reference compares its learned one with (evaluation/save_keypoints.py:57-61, 314-325,
  * method = 'sift': PCLKeypoint.keypointSift(xyz, min_scale 0.5, n_octaves 4, n_scales_per_octave 8, min_contrast 0.1)).  The

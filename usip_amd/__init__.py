@@ -11,8 +11,9 @@ the reference's own Python surface:
   usip_amd.evaluation                      keypoint repeatability and RANSAC registration (the reference's MATLAB
                                            evaluation) on the device: `from usip_amd import evaluation`
   usip_amd.baselines                       the baseline detectors it is compared with: ISS, Harris3D, SIFT3D and random keypoints,
-                                           and two hand-crafted descriptors for any keypoints: FPFH
-                                           (FpfhDescriptor) and SHOT-352 (ShotDescriptor)
+                                           and three hand-crafted descriptors for any keypoints: FPFH
+                                           (FpfhDescriptor), SHOT-352 (ShotDescriptor) and spin images
+                                           (SpinDescriptor, also `from usip_amd import SpinDescriptor`)
 
 `usip_amd.install()` registers the drop-in extension modules under their reference names
 (`import index_max`, `import ball_query`) so that the reference's models/networks.py runs
@@ -35,4 +36,7 @@ def __getattr__(name):
     if name == "evaluation":
         import importlib
         return importlib.import_module(".evaluation", __name__)
+    if name == "SpinDescriptor":                                       # likewise: `from usip_amd import SpinDescriptor`
+        import importlib
+        return importlib.import_module(".baselines", __name__).SpinDescriptor
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

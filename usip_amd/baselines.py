@@ -30,8 +30,9 @@ tensor of the caller's (curvature, reflectance); its keypoints are voxel-cell ce
   fpfh_descriptors   (desc f32 [B,33,M], kp_members i32 [B,M]) at keypoints f32 [B,3,M] of any detector: FPFH
   shot_frames        (lrf f64 [B,M,9], lrf_members i32 [B,M]): every keypoint's local reference frame, zeros without one
   shot_descriptors   (desc f32 [B,352,M], kp_members i32 [B,M]) at keypoints f32 [B,3,M] of any detector: SHOT
+  spin_descriptors   (desc f32 [B,153,M], kp_members i32 [B,M]) at keypoints f32 [B,3,M] of any detector: spin images
   *_cpu              the same on numpy arrays over the library's host twins (csrc/iss_cpu.cpp, csrc/harris_cpu.cpp,
-                     csrc/sift_cpu.cpp, csrc/fpfh_cpu.cpp, csrc/shot_cpu.cpp)
+                     csrc/sift_cpu.cpp, csrc/fpfh_cpu.cpp, csrc/shot_cpu.cpp, csrc/spin_cpu.cpp)
 
 The scoring scripts of the reference also name hand-crafted DESCRIPTORS (eval_indoor/3dmatch/evaluate.m: 'my'; % 3dmatch, spin,
 fpfh) that it does not contain.  FPFH (csrc/fpfh.hip, csrc/fpfh_math.h) describes the keypoints of any detector above without a
@@ -42,7 +43,8 @@ network or a checkpoint:
     evaluator.add_frame_descriptors(fid, kp, desc, kp_count) # evaluation.RegistrationEvaluator: score them
 
 The outdoor scoring script is set to SHOT (eval_outdoor/kitti/evaluate_kitti.m: .../kitti/shot/iss_256, FEATURE_DIM = 352);
-ShotDescriptor (csrc/shot.hip, csrc/shot_math.h) is called the same way and gives f32 [B,352,M].
+ShotDescriptor (csrc/shot.hip, csrc/shot_math.h) is called the same way and gives f32 [B,352,M].  SpinDescriptor (csrc/spin.hip,
+csrc/spin_math.h) is the `spin` of evaluate.m's comment: f32 [B,153,M], about the z axis of SHOT's local reference frame.
 
 The selection is reproducible and free of host synchronisation: one CPU generator per frame, seeded from (seed, frame_id) the
 way prepare._keep_rows seeds its own, draws u in [0, 1) for every point; a live point's key is u when it is a keypoint and
@@ -66,6 +68,8 @@ HARRIS_DEFAULTS = dict(radius=1.0, threshold=0.001, response="harris", min_neigh
 SIFT_DEFAULTS = dict(min_scale=0.5, n_octaves=4, n_scales_per_octave=8, min_contrast=0.1, field="z")
 FPFH_DEFAULTS = dict(radius=2.0, normal_radius=1.0, min_neighbors=3)   # this project's choice: the reference gives none
 SHOT_DEFAULTS = dict(radius=2.0, normal_radius=1.0, min_neighbors=3)   # this project's choice too
+SPIN_DEFAULTS = dict(radius=2.0, axis_radius=None, support_angle_cos=0.0, normal_radius=1.0, min_neighbors=3,
+                     structure="rectangular")                          # likewise; axis_radius None: the radius
 
 
 def _check(salient_radius, non_max_radius, min_neighbors):
@@ -231,6 +235,51 @@ def shot_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2
     hist, shot, kp_members = ops.shot_hist(pc, count, perm, nrm, keypoints, kp_count, lrf, radius)
     desc = shot.to(torch.float32).transpose(1, 2).contiguous()
     return (desc, kp_members, shot, hist, lrf, lrf_members) if want_f64 else (desc, kp_members)
+
+
+# ------------------------------------------------------------------------------------------------ spin images
+def _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure):
+    _check_fpfh(radius, normal_radius, min_neighbors)
+    if axis_radius is not None:
+        _check_fpfh(axis_radius, 1.0, 1)
+    if not 0.0 <= float(support_angle_cos) <= 1.0:
+        raise ValueError("spin: support_angle_cos must be in [0, 1], got %r" % (support_angle_cos,))
+    if structure not in ops.SPIN_STRUCTURES:
+        raise ValueError("spin: structure must be one of %s, got %r" % (sorted(ops.SPIN_STRUCTURES), structure))
+
+
+def spin_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, axes=None, axis_radius=None,
+                     support_angle_cos: float = 0.0, normals=None, normal_radius: float = 1.0, want_f64: bool = False,
+                     min_neighbors: int = 3, structure: str = "rectangular"):
+    """pc f32 [B,3,N], keypoints f32 [B,3,M] (any positions: cloud points or not), count, kp_count i32 [B] or None -> (desc f32
+    [B,153,M], kp_members i32 [B,M][, spin f64 [B,M,153], hist i64 [B,M,153], axes f64 [B,M,3], lrf_members i32 [B,M] or
+    None]): spin images at the keypoints, 9 rows of the distance from the axis by 17 columns of the height along it, the layout
+    the learned descriptor has (channels first).  axes f64 [B,M,3] or None: the z row of shot_frames over axis_radius (None:
+    radius), so a keypoint with fewer than 5 points there has no descriptor; supplied axes (normals oriented to the sensor,
+    say) need not be of unit length.  support_angle_cos s > 0 keeps the members whose normal has |n . axis| >= s: normals f32
+    [B,3,N] or None (harris_normals over normal_radius with min_neighbors); with s == 0 no normal is estimated or read.
+    structure "rectangular" (the cylinder inscribed in the sphere) or "radial" (distance by elevation).  The f32 descriptor is
+    the cast of the f64 result.  One sort, no host synchronisation.  The radii (outdoor metres) are this project's choice."""
+    _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure)
+    pc, count = _frames(pc, count)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    perm = sort_along_x(pc, count)
+    nrm = None
+    if float(support_angle_cos) > 0.0:
+        nrm = ops.harris_normals(pc, count, perm, normal_radius, min_neighbors)[0] if normals is None else \
+            _supplied(normals, pc, "spin")
+    lrf_members = None
+    if axes is None:
+        lrf, lrf_members = ops.shot_lrf(pc, count, perm, keypoints, kp_count, radius if axis_radius is None else axis_radius)
+        axes = lrf[:, :, 6:9].contiguous()
+    elif not isinstance(axes, torch.Tensor) or axes.dtype != torch.float64 or axes.device != pc.device \
+            or tuple(axes.shape) != (pc.shape[0], keypoints.shape[2], 3):
+        raise ValueError("spin: supplied axes must be f64 [B,M,3] on %s" % (pc.device,))
+    else:
+        axes = axes.contiguous()
+    hist, spin, kp_members = ops.spin_image(pc, count, perm, nrm, keypoints, kp_count, axes, radius, support_angle_cos, structure)
+    desc = spin.to(torch.float32).transpose(1, 2).contiguous()
+    return (desc, kp_members, spin, hist, axes, lrf_members) if want_f64 else (desc, kp_members)
 
 
 # ------------------------------------------------------------------------------------------------ SIFT3D (DESIGN 8l)
@@ -518,6 +567,26 @@ class ShotDescriptor:
         return self.last[0]
 
 
+class SpinDescriptor:
+    """Spin images with their parameters bundled, called where the learned descriptor is: __call__(pc, keypoints, count,
+    kp_count, normals) -> desc f32 [B,153,M]; .last holds (desc, kp_members) of the latest call.  normals f32 [B,3,N]: supplied
+    ones (the cloud's sn[:, :3]) instead of estimated ones, read only with a support angle."""
+
+    dim = 153
+
+    def __init__(self, radius: float = 2.0, axis_radius=None, support_angle_cos: float = 0.0, normal_radius: float = 1.0,
+                 min_neighbors: int = 3, structure: str = "rectangular"):
+        _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure)
+        self.params = dict(radius=float(radius), axis_radius=None if axis_radius is None else float(axis_radius),
+                           support_angle_cos=float(support_angle_cos), normal_radius=float(normal_radius),
+                           min_neighbors=int(min_neighbors), structure=structure)
+        self.last = None
+
+    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
+        self.last = spin_descriptors(pc, keypoints, count, kp_count, normals=normals, **self.params)
+        return self.last[0]
+
+
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
 def _p(a):
     return ctypes.c_void_p(a.ctypes.data) if a is not None else None
@@ -711,6 +780,55 @@ def shot_angle_cpu(y, x):
     out = np.zeros_like(a)
     _lib.check(_lib.lib().usip_shot_angle_f64_cpu(_p(a), _p(b), a.size, _p(out)), "usip_shot_angle_f64_cpu")
     return out
+
+
+def spin_image_cpu(pc, count, normals, keypoints, kp_count, axes, radius: float, support_angle_cos: float = 0.0,
+                   structure: str = "rectangular", num_threads: int = 1):
+    """normals f64 [B,3,N] or None, axes f64 [B,M,3] -> (hist i64 [B,M,153], spin f64 [B,M,153], kp_members i32 [B,M])"""
+    a, c = _frames_np(pc, count)
+    B, _, N = a.shape
+    kp, kc = _keypoints_np(keypoints, kp_count, B)
+    M = kp.shape[2]
+    nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
+    ax = np.ascontiguousarray(axes, dtype=np.float64)
+    if (nrm is not None and nrm.shape != a.shape) or ax.shape != (B, M, 3):
+        raise ValueError("spin: expected normals f64 [B,3,N] or None and axes f64 [B,M,3]")
+    if structure not in ops.SPIN_STRUCTURES:
+        raise ValueError("spin: structure must be one of %s, got %r" % (sorted(ops.SPIN_STRUCTURES), structure))
+    hist, spin = np.zeros((B, max(M, 1), ops.SPIN_WIDTH), np.int64), np.zeros((B, max(M, 1), ops.SPIN_WIDTH), np.float64)
+    kp_members = np.zeros((B, max(M, 1)), np.int32)
+    _lib.check(_lib.lib().usip_spin_image_f32_cpu(_p(a), _p(c), _p(nrm), _p(kp), _p(kc), _p(ax), B, N, M, float(radius),
+                                                  float(support_angle_cos), ops.SPIN_STRUCTURES[structure], _p(hist), _p(spin),
+                                                  _p(kp_members), int(num_threads)), "usip_spin_image_f32_cpu")
+    return hist, spin, kp_members
+
+
+def spin_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, axes=None, axis_radius=None,
+                         support_angle_cos: float = 0.0, normals=None, normal_radius: float = 1.0, want_f64: bool = False,
+                         min_neighbors: int = 3, structure: str = "rectangular", num_threads: int = 1):
+    """-> (desc f32 [B,153,M], kp_members i32 [B,M][, spin f64 [B,M,153], hist i64 [B,M,153], axes f64 [B,M,3], lrf_members i32
+    [B,M] or None])"""
+    _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure)
+    a, c = _frames_np(pc, count)
+    nrm = None
+    if float(support_angle_cos) > 0.0:
+        if normals is None:
+            nrm = harris_normals_cpu(a, c, normal_radius, min_neighbors, num_threads)[0]
+        else:
+            nrm = np.asarray(normals)
+            if nrm.dtype != np.float32 or nrm.shape != a.shape:
+                raise ValueError("spin: supplied normals must be f32 %s" % (a.shape,))
+            nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    lrf_members = None
+    if axes is None:
+        lrf, lrf_members = shot_frames_cpu(a, keypoints, c, kp_count, radius if axis_radius is None else axis_radius,
+                                           num_threads)
+        axes = np.ascontiguousarray(lrf[:, :, 6:9])
+    hist, spin, kp_members = spin_image_cpu(a, c, nrm, keypoints, kp_count, axes, radius, support_angle_cos, structure,
+                                            num_threads)
+    desc = np.ascontiguousarray(spin.astype(np.float32).transpose(0, 2, 1))
+    return (desc, kp_members, spin, hist, np.ascontiguousarray(axes, dtype=np.float64), lrf_members) if want_f64 else \
+        (desc, kp_members)
 
 
 def sift_exp_cpu(x):

@@ -2035,6 +2035,39 @@ def shot_hist(pc, count, perm, normals, keypoints, kp_count, lrf, radius: float)
     return hist, shot, kp_members
 
 
+# ------------------------------------------------------------------------------------------------ f-21 baseline descriptor: spin images
+SPIN_WIDTH = 153
+SPIN_STRUCTURES = {"rectangular": 0, "radial": 1}
+
+
+def spin_image(pc, count, perm, normals, keypoints, kp_count, axes, radius: float, support_angle_cos: float = 0.0,
+               structure: str = "rectangular"):
+    """f-21: axes f64 [B,M,3] (shot_lrf's z rows, or supplied; a row that is not finite or all zero: no axis), normals f64
+    [B,3,N] or None (required only with support_angle_cos > 0) -> (hist i64 [B,M,153], the integer bilinear weights in quanta
+    of 2^-40 per member; spin f64 [B,M,153] = hist / (kp_members * 2^40), zeros without an axis or a member; kp_members i32
+    [B,M])."""
+    B, N = _need_frames(pc, count, perm, "spin")
+    M = _need_keypoints(pc, keypoints, kp_count, "spin")
+    _need_on(normals, "normals", torch.float64, (B, 3, N), pc.device)
+    _need_on(axes, "axes", torch.float64, (B, M, 3), pc.device)
+    s = float(support_angle_cos)
+    if axes is None or not float(radius) > 0.0 or not 0.0 <= s <= 1.0 or (s > 0.0 and normals is None):
+        raise RuntimeError("spin: axes are required, radius must be positive, support_angle_cos in [0, 1], and normals are "
+                           "required with a support angle")
+    if structure not in SPIN_STRUCTURES:
+        raise RuntimeError("spin: structure must be one of %s, got %r" % (sorted(SPIN_STRUCTURES), structure))
+    hist = torch.empty((B, M, SPIN_WIDTH), dtype=torch.int64, device=pc.device)
+    spin = torch.empty((B, M, SPIN_WIDTH), dtype=torch.float64, device=pc.device)
+    kp_members = torch.empty((B, M), dtype=torch.int32, device=pc.device)
+    with torch.cuda.device(pc.device), prof.kernel("spin_image", (16.0 if s == 0.0 else 40.0) * B * N
+                                                   + (16.0 * SPIN_WIDTH + 40.0) * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_spin_image_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _opt_ptr(normals), _ptr(keypoints),
+                                                  _opt_ptr(kp_count), _ptr(axes), B, N, M, float(radius), s,
+                                                  SPIN_STRUCTURES[structure], _ptr(hist), _ptr(spin), _ptr(kp_members),
+                                                  _stream(pc)), "usip_spin_image_f32")
+    return hist, spin, kp_members
+
+
 # ------------------------------------------------------------------------------------------------ f-17 baseline keypoints: SIFT3D
 SIFT_NEAREST = 25
 
