@@ -13,6 +13,12 @@
 // ordering dependence between lanes -- bit-identical to the serial loop.  The table starts at
 // key(-1000, n = none); values <= -1000 and NaN are filtered before the atomic (strict >).
 // HBM-bound by design: data + index in, B*C*K ints out.
+//
+// The values (usip_index_max_values_f32) are decoded from the winning key, and fold() turns -0.0 into +0.0 before it
+// builds the key (so that the two zeros tie and the lower n wins).  The contract therefore: the values equal the
+// reference's gather(data, max_idx) * mask NUMERICALLY, and a winning -0.0 is returned as +0.0 where the gather carries
+// -0.0 (tests/test_segment_kernels_gpu.py pins exactly this).  A node without a maximum above -1000 reports index 0 and
+// the value data[b, c, 0] itself, whatever its bits; a node with count <= 0 reports +0.0.
 #include "common.h"
 
 namespace {

@@ -139,7 +139,7 @@ extern "C" int usip_csr_by_index_i32(const int32_t* idx, int32_t* start, int32_t
 {
     if (B < 0 || P < 0 || N < 1 || N > 4 * CSR_T) return USIP_EINVAL;
     if (B == 0) return USIP_OK;
-    if (!start || !perm || (P > 0 && !idx)) return USIP_EINVAL;
+    if (!start || (P > 0 && (!idx || !perm))) return USIP_EINVAL;   // P == 0: perm has no entries (an empty tensor's null)
     const size_t lds = (size_t)(CSR_W + 1) * N * sizeof(int);
     if (lds > 65536) return USIP_EINVAL;
     USIP_LAUNCH(csr_build_kernel, dim3(B), dim3(CSR_T), lds, (hipStream_t)stream, idx, start, perm, P, N);

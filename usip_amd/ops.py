@@ -54,7 +54,9 @@ def index_max(data: torch.Tensor, index: torch.Tensor, K: int) -> torch.Tensor:
 
 def index_max_values(data: torch.Tensor, index: torch.Tensor, count, K: int, C: Optional[int] = None):
     """index_max plus the gather + mask the reference applies to it (networks.py:117-118): -> (max_idx i32 [B,C,K],
-    data[b,c,max_idx] * (count > 0) f32 [B,C,K]).  data [B,Ctot,N]; C: use only the first C channels."""
+    data[b,c,max_idx] * (count > 0) f32 [B,C,K]).  data [B,Ctot,N]; C: use only the first C channels.
+    The values equal gather * mask numerically; a winning -0.0 is returned as +0.0 (csrc/index_max.hip: the two zeros tie
+    in the key).  count None: every node counts.  index must lie in [0, K): the kernel does not guard it."""
     K = int(K)
     _need(data, "data", torch.float32)
     _need(index, "index", torch.int32)
