@@ -182,6 +182,44 @@ int usip_nearest_f32(const float* a, const float* b, float* min_d, int32_t* arg,
 int usip_nearest_backward_f32(const float* a, const float* b, const float* d, const int32_t* arg,
                               const float* gd, float* ga, float* gb, int B, int C, int Ma, int Nb, void* stream);
 
+/* ------------------------------------------------------------------ cell grid: the same two searches without the pairs
+ * (csrc/cell_grid.hip).  usip_cell_grid_build_f32 sorts every cloud of x f32 [B,3,N] into a uniform 3-D grid over the
+ * bounding box of its points, cell edge >= `edge` (grown until the grid has at most usip_cell_grid_cap() cells):
+ *   hdr        i32 [B][USIP_CELL_HDR_WORDS]       the words below (floats as their bits)
+ *   cell_start i32 [B][usip_cell_grid_cap() + 1]  first sorted position of every cell, x fastest; [cells] = N
+ *   pts        f32 [B][N][4], 16-B aligned        the points in cell order: x, y, z, and the point's index as its bits
+ * USABLE is 0 -- and the rest of that cloud's grid unwritten -- for a cloud with a non-finite coordinate or an extent that
+ * is not finite, N = 0 or N > 2^20, an edge that is not finite or below 2^-50, or (max_block > 0) a dense cloud: one whose
+ * 27-cell blocks hold more than max_block points on average, N * 27 / cells; such a cloud is not sorted at all, its rows
+ * scan.  For a ball query with K samples max_block = sqrt(N * K) states the row rule below for the whole cloud.  The searches read the header on the
+ * device: nothing here allocates, synchronises or reads device data on the host. */
+#define USIP_CELL_HDR_WORDS 12
+enum { USIP_CELL_OX = 0, USIP_CELL_OY = 1, USIP_CELL_OZ = 2, USIP_CELL_EDGE = 3, USIP_CELL_INV = 4, USIP_CELL_NX = 5,
+       USIP_CELL_NY = 6, USIP_CELL_NZ = 7, USIP_CELL_USABLE = 8 };
+#define USIP_CELL_CAP 15360
+enum { USIP_ROUTE_SCAN = 0, USIP_ROUTE_GRID = 1 };
+int usip_cell_grid_cap(void);
+float usip_cell_grid_edge_factor(void);          /* 1.03125: ask for edge = radius * this for a ball query of that radius */
+int usip_cell_grid_hdr_word(const char* name);   /* "ox" "oy" "oz" "edge" "inv" "nx" "ny" "nz" "usable" -> word; "words" -> count */
+int usip_cell_grid_build_f32(const float* x, float edge, int max_block, int32_t* hdr, int32_t* cell_start, float* pts,
+                             int B, int N, void* stream);
+/* usip_ball_query_coords_f32's rows, bit for bit, from the points of the 27 cells around every node.  The grid must be the
+ * one built from this x with edge = radius * usip_cell_grid_edge_factor() or more (the kernel insists on radius * 1.015625;
+ * csrc/cell_grid.h says why); a row whose cloud is not
+ * USABLE or has a narrower edge, or whose 27 cells hold more than 512 points or more than sqrt(N * K) (the index-order
+ * scan with its exit after K hits is then the shorter one), is scanned in index order by the same launch.
+ * route (may be NULL): u8 [B,M], USIP_ROUTE_GRID or USIP_ROUTE_SCAN per row. */
+int usip_ball_query_grid_f32(const float* node, const float* x, const int32_t* hdr, const int32_t* cell_start,
+                             const float* pts, int32_t* out_idx, uint8_t* route, float radius, int K, int B, int M, int N,
+                             void* stream);
+/* usip_nearest_f32's (min_d, arg), bit for bit, for a f32 [B,3,Ma] against the gridded x f32 [B,3,N] (any edge): blocks of
+ * 3^3, 5^3, 7^3 cells around the query's cell until no point outside the block can be the answer; a query
+ * that is not settled by then or whose block holds more than 1024 points, and every query of a cloud that is not USABLE,
+ * is scanned in index order by the same launch.
+ * route (may be NULL): u8 [B,Ma]. */
+int usip_nearest_grid_f32(const float* a, const float* x, const int32_t* hdr, const int32_t* cell_start,
+                          const float* pts, float* min_d, int32_t* arg, uint8_t* route, int B, int Ma, int N, void* stream);
+
 /* a-8 / a-11: the element-wise tail of the step, one launch each way per line of the reference (csrc/head.hip).
  * keypoints[b][:][m] = ks[b][0:3][m] + centre[b][:][m];  sigmas[b][m] = softplus(ks[b][3][m]) + sigma_lower_bound
  * (models/networks.py:150-154; torch.nn.Softplus defaults).  ks [B][4][M], centre [B][3][M]. */

@@ -216,9 +216,12 @@ class _NearestDistance(torch.autograd.Function):
     to the selected partner for a, its negative scattered onto b, zero at zero distance."""
 
     @staticmethod
-    def forward(ctx, a, b):
+    def forward(ctx, a, b, grid=None):
         a, b = a.contiguous(), b.contiguous()
-        d, arg32 = ops.nearest(a, b) if a.shape[1] == 3 else ops.nearest_nd(a, b)
+        if grid is not None:                                  # b sorted into cells already: same (d, arg), bit for bit
+            d, arg32 = ops.nearest_grid(a, grid)
+        else:
+            d, arg32 = ops.nearest(a, b) if a.shape[1] == 3 else ops.nearest_nd(a, b)
         ctx.save_for_backward(a, b, d, arg32)
         ctx.mark_non_differentiable(arg32)
         ctx.set_materialize_grads(False)
@@ -227,16 +230,18 @@ class _NearestDistance(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gd, _garg):
         if gd is None:
-            return None, None
+            return None, None, None
         a, b, d, arg32 = ctx.saved_tensors
         ga, gb = ops.nearest_backward(a, b, d, arg32, gd.contiguous(), ctx.needs_input_grad[1])
-        return (ga if ctx.needs_input_grad[0] else None), gb
+        return (ga if ctx.needs_input_grad[0] else None), gb, None
 
 
-def nearest_distance_i32(a: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """As nearest_distance, arg-min as the kernels produce it (int32)."""
+def nearest_distance_i32(a: torch.Tensor, b: torch.Tensor, grid=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """As nearest_distance, arg-min as the kernels produce it (int32).  grid: an ops.CellGrid built from b (C == 3)."""
     require_device(a, "nearest_distance")
-    return _NearestDistance.apply(a, b)
+    if grid is not None and not (a.shape[1] == 3 and grid.built_from(b)):
+        raise RuntimeError("nearest_distance: the cell grid was not built from these candidates")
+    return _NearestDistance.apply(a, b, grid)
 
 
 class _ChamferProb(torch.autograd.Function):

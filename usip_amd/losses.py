@@ -33,8 +33,8 @@ class SingleSideChamferLoss_Brute(nn.Module):
         self.opt = opt
         self.dimension = 3
 
-    def forward(self, pc_src_input, pc_dst_input):
-        return Fh.nearest_distance_i32(pc_src_input, pc_dst_input)[0]
+    def forward(self, pc_src_input, pc_dst_input, grid=None):
+        return Fh.nearest_distance_i32(pc_src_input, pc_dst_input, grid)[0]
 
 
 class PointOnSurfaceLoss(nn.Module):
@@ -70,10 +70,11 @@ class KeypointOnPCLoss(nn.Module):
         self.single_side_chamfer = SingleSideChamferLoss_Brute(opt)
         self.keypoint_on_surface = PointOnSurfaceLoss(opt)
 
-    def forward(self, keypoint, pc, sn=None):
+    def forward(self, keypoint, pc, sn=None, grid=None):
+        """grid: an ops.CellGrid built from pc; the point-to-point distances then come through it (same values)."""
         if sn is not None:
             return self.keypoint_on_surface(keypoint, pc, sn)
-        return self.single_side_chamfer(keypoint, pc)
+        return self.single_side_chamfer(keypoint, pc, grid)
 
 
 class DescPairScanLoss(nn.Module):

@@ -141,9 +141,17 @@ class RPN_Detector_Ball(_DetectorTail):
         self._build_tail(opt)
         self.ball_radius = 2
         self.ball_k = 64
+        self.cell_grid = True               # False: this call scans (DetectorStep clears it for keep_idx dropout batches)
+        self.last_grid = None               # ops.CellGrid of the last forward's x, until whoever searches x next takes it
 
     def _neighbourhoods(self, node, x):
         """-> (int32 [B,M,K] point indices of every node's neighbourhood, name of the index tensor)."""
+        self.last_grid = None
+        if ops.CELL_GRID and self.cell_grid and x.shape[2] > 0:
+            # the same rows through a cell grid of x (csrc/cell_grid.hip), built once and kept for the step's losses
+            self.last_grid = ops.cell_grid_build(x, self.ball_radius * ops.cell_edge_factor(),
+                                                 ops.ball_block_limit(x.shape[2], self.ball_k))
+            return ops.ball_query_grid(node, self.last_grid, self.ball_radius, self.ball_k), "ball_idx"
         return ops.ball_query_coords(node, x, self.ball_radius, self.ball_k), "ball_idx"   # :694-698 fused
 
     def forward(self, x, sn, node, is_train=False, epoch=None):
@@ -175,6 +183,7 @@ class RPN_Detector_KNN(RPN_Detector_Ball):
     towards the lower index -- `last_indices["nn_idx"]`."""
 
     def _neighbourhoods(self, node, x):
+        self.last_grid = None
         return ops.knn_points(node, x, self.ball_k), "nn_idx"                              # :576-581 fused
 
 

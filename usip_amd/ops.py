@@ -249,6 +249,106 @@ def nearest(a: torch.Tensor, b: torch.Tensor):
     return d, arg
 
 
+# USIP_CELL_GRID=0: the Ball detector's ball query and the step's keypoint-on-cloud distances go back to the two
+# brute-force launches (ball_query_coords, nearest) -- the A/B switch of csrc/cell_grid.hip; results are the same bits.
+CELL_GRID = os.environ.get("USIP_CELL_GRID", "1") not in ("0", "off")
+
+
+def cell_edge_factor() -> float:
+    """Cell edge to ask cell_grid_build for = ball radius * this (usip_cell_grid_edge_factor, csrc/cell_grid.h)."""
+    return float(_lib.lib().usip_cell_grid_edge_factor())
+
+
+@functools.lru_cache(maxsize=None)
+def _cell_hdr_word(name: str) -> int:
+    w = int(_lib.lib().usip_cell_grid_hdr_word(name.encode()))
+    if w < 0:
+        raise RuntimeError("usip_amd: usip_cell_grid_hdr_word does not know %r" % name)
+    return w
+
+
+
+class CellGrid:
+    """A cloud batch sorted into cells by cell_grid_build: x f32 [B,3,N] itself (the searches fall back to scanning it)
+    and the three tensors of usip_cell_grid_build_f32.  header() reads the per-cloud header back (synchronises)."""
+
+    def __init__(self, x, edge, hdr, cell_start, pts):
+        self.x, self.edge, self.hdr, self.cell_start, self.pts = x, float(edge), hdr, cell_start, pts
+
+    def built_from(self, x: torch.Tensor) -> bool:
+        return x.data_ptr() == self.x.data_ptr() and x.shape == self.x.shape and x.is_contiguous()
+
+    def header(self):
+        h = self.hdr.cpu()
+        f = h.view(torch.float32)
+        w = _cell_hdr_word
+        return [dict(origin=[float(f[b, w(k)]) for k in ("ox", "oy", "oz")], edge=float(f[b, w("edge")]),
+                     inv=float(f[b, w("inv")]), dim=[int(h[b, w(k)]) for k in ("nx", "ny", "nz")],
+                     usable=bool(h[b, w("usable")])) for b in range(h.shape[0])]
+
+
+def cell_grid_build(x: torch.Tensor, edge: float, max_block: int = 0) -> CellGrid:
+    """x [B,3,N] -> its CellGrid with cells at least `edge` wide (wider when the cloud needs more cells than the
+    kernel counts).  max_block > 0: a cloud whose 27-cell blocks hold more points than that on average is dense, is
+    left unsorted and its rows scan; ball_block_limit(N, K) for a grid that serves a ball query."""
+    _need_pts(x, "x")
+    B, _, N = x.shape
+    cap = int(_lib.lib().usip_cell_grid_cap())
+    hdr = torch.empty((B, _cell_hdr_word("words")), dtype=torch.int32, device=x.device)
+    cell_start = torch.empty((B, cap + 1), dtype=torch.int32, device=x.device)
+    pts = torch.empty((B, N, 4), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), prof.kernel("cell_grid_build", 4.0 * (3 * 3 * B * N + 4 * B * N), 0.0):
+        _lib.check(_lib.lib().usip_cell_grid_build_f32(_ptr(x), float(edge), int(max_block), _ptr(hdr), _ptr(cell_start), _ptr(pts),
+                                                       B, N, _stream(x)), "usip_cell_grid_build_f32")
+    return CellGrid(x, edge, hdr, cell_start, pts)
+
+
+def ball_block_limit(N: int, K: int) -> int:
+    """cell_grid_build's max_block for a ball query with K samples: floor(sqrt(N * K)), the candidate count up to which a
+    row of ball_query_grid_kernel takes the grid (cand^2 <= N * K).  From shapes alone."""
+    return max(1, math.isqrt(int(N) * int(K)))
+
+
+def ball_query_grid(node: torch.Tensor, grid: CellGrid, radius: float, K: int, with_route: bool = False):
+    """ball_query_coords(node, grid.x, radius, K), bit for bit, through the grid; with_route: -> (idx, u8 [B,M] with 1
+    where the row came from the grid and 0 where the launch scanned it in index order)."""
+    K = int(K)
+    _need(node, "node", torch.float32)
+    x = grid.x
+    if node.dim() != 3 or node.shape[1] != 3 or node.shape[0] != x.shape[0]:
+        raise RuntimeError("ball_query_grid: expected node [B,3,M] for a grid of x [B,3,N]")
+    B, _, M = node.shape
+    N = x.shape[2]
+    out = torch.empty((B, M, K), dtype=torch.int32, device=node.device)
+    route = torch.empty((B, M), dtype=torch.uint8, device=node.device) if with_route else None
+    # flops: the pair count of the brute-force launch this replaces (8 per pair, as "ball_query_coords"), NOT executed
+    # work -- the grid tests a few dozen points per row; kept so that the two routes share a column in bench.py --full
+    with torch.cuda.device(node.device), prof.kernel("ball_query_grid", 4.0 * (3 * B * M + B * M * K), 8.0 * B * M * N):
+        _lib.check(_lib.lib().usip_ball_query_grid_f32(_ptr(node), _ptr(x), _ptr(grid.hdr), _ptr(grid.cell_start),
+                                                       _ptr(grid.pts), _ptr(out), _opt(route), float(radius), K,
+                                                       B, M, N, _stream(node)), "usip_ball_query_grid_f32")
+    return (out, route) if with_route else out
+
+
+def nearest_grid(a: torch.Tensor, grid: CellGrid, with_route: bool = False):
+    """nearest(a, grid.x), bit for bit, through the grid; with_route as ball_query_grid."""
+    _need_pts(a, "a")
+    x = grid.x
+    B, _, Ma = a.shape
+    N = x.shape[2]
+    if x.shape[0] != B or N < 1:
+        raise RuntimeError("nearest_grid: expected a [B,3,Ma] for a grid of x [B,3,N], N >= 1")
+    d = torch.empty((B, Ma), dtype=torch.float32, device=a.device)
+    arg = torch.empty((B, Ma), dtype=torch.int32, device=a.device)
+    route = torch.empty((B, Ma), dtype=torch.uint8, device=a.device) if with_route else None
+    # flops: the brute-force-equivalent pair count (8 per pair, as "nearest"), not executed work
+    with torch.cuda.device(a.device), prof.kernel("nearest_grid", 4.0 * (3 * B * Ma + 2 * B * Ma), 8.0 * B * Ma * N):
+        _lib.check(_lib.lib().usip_nearest_grid_f32(_ptr(a), _ptr(x), _ptr(grid.hdr), _ptr(grid.cell_start),
+                                                    _ptr(grid.pts), _ptr(d), _ptr(arg), _opt(route), B, Ma, N,
+                                                    _stream(a)), "usip_nearest_grid_f32")
+    return (d, arg, route) if with_route else (d, arg)
+
+
 def chamfer_prob(a, J, c, I, sigma_src, sigma_dst):
     """(loss, chamfer_pure, chamfer_weighted) as a 3-vector from the nearest-neighbour minima a [B,M] / J i32
     and c [B,N] / I i32 and the two sigma maps (models/losses.py:82-99)."""

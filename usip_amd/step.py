@@ -586,7 +586,14 @@ class DetectorStep(_GraphedStep):
         self.detector.train()                                 # keypoint_detector.py:171
         pc, sn, node = (batch[both] if both in batch else torch.cat((batch[a], batch[b]), 0)
                         for a, b, both in self._SIAMESE)
+        if hasattr(self.detector, "cell_grid"):               # Ball detector: dropout batches keep the index-order scans
+            self.detector.cell_grid = getattr(self, "_replay_this_call", True)
         nodes, kp, sg, _ = self.detector(pc, sn, node, True, epoch)   # forward_siamese :141-156
+        grid = getattr(self.detector, "last_grid", None)      # the cells the ball query sorted pc into, or None
+        if grid is not None:
+            self.detector.last_grid = None                    # taken: the step does not keep pc's sorted copy alive
+            if not grid.built_from(pc):
+                grid = None
         kp_src, kp_dst = torch.split(kp, B, dim=0)            # :147-149 (split: one backward node, no zero fills)
         sg_src, sg_dst = torch.split(sg, B, dim=0)
         # :182-184  R.kp*s + t  as one batched GEMM with the scale folded into R (inputs, no gradient)
@@ -600,7 +607,7 @@ class DetectorStep(_GraphedStep):
             on_src, on_dst = torch.mean(on[:B]) * alpha, torch.mean(on[B:]) * alpha
             loss = loss_chamfer + on_src + on_dst
         else:
-            loss, on_src, on_dst = Fh.detector_loss_combine(self.keypoint_on_pc_criteria(kp, pc, None), loss_chamfer,
+            loss, on_src, on_dst = Fh.detector_loss_combine(self.keypoint_on_pc_criteria(kp, pc, None, grid), loss_chamfer,
                                                             alpha)   # :204
         self.last = dict(node=nodes, keypoints=kp, sigmas=sg, loss=loss, loss_chamfer=loss_chamfer,
                          chamfer_pure=pure, chamfer_weighted=weighted, loss_on_pc_src=on_src,
