@@ -1562,6 +1562,64 @@ int usip_gt_information_f32_cpu(const float* rows, int row_len, const int64_t* o
                                 const int32_t* frag2, const double* Rt, const int32_t* order, const int32_t* count, int P,
                                 int Lmax, int cap, double* info, int num_threads);
 
+/* ------------------------------------------------------------------ f-22  the indoor descriptor's loss: CGF triplets
+ * losses.DescCGFLoss (models/losses.py:240-314) without its B x C x M x M difference tensor, its B x M x M norm and its three
+ * random B x M x M matrices: the three indices it reads per anchor depend on the keypoints and the random numbers only, the
+ * loss needs three C-long distances per anchor, and the backward pass scatters three unit vectors.  csrc/cgf_math.h is the
+ * arithmetic.  anc_kp, pos_kp f32 [B][3][M] (anc_kp already in the positive's frame), anc_desc, pos_desc f32 [B][C][M],
+ * anc_sigma f32 [B][M].  1 <= B, 1 <= M <= 65535, 1 <= C <= 4096, radius > 0 (also as a float32).
+ *
+ * usip_cgf_select_f32: float32 decisions, as the reference's.  For anchor i and candidate j: d_ij = sqrtf((dx dx + dy dy) + dz
+ * dz), never contracted; pos_ij = d_ij <= (float)radius; has_i = any_j pos_ij; j_pos = argmax_j (pos_ij ? u1_ij : 0); j_far =
+ * argmin_j of the float32 value d_ij + (pos_ij ? 1000.f : 0.f) -- the one float32 add, with its quantisation, is the
+ * reference's and decides the all-inside row as it does; j_out = argmax_j (d_ij > (float)radius ? u2_ij : 0); every tie goes
+ * to the LOWEST j, so an all-zero row gives 0; a NaN key is never chosen and a row of NaN keys gives 0.  take_far_i = u3_i <
+ * 0.5f; j_neg = take_far ? j_far : j_out.  sel i32 [B][M][3] = (j_pos, j_far, j_out); has, take_far u8 [B][M].
+ * Draws: u1, u2 f32 [B][M][M] and u3 f32 [B][M], all three or none (the recorded draws of the reference: tests only).  None:
+ * Philox4x64-10 (csrc/pairs_rng.h), key (seed, "cgf_loss"), counter (i << 16 | j, 27 << 8, elem_base + b, step) -> words 0, 1
+ * give u1_ij, u2_ij; counter (i, 27 << 8 | 1, elem_base + b, step) -> word 0 gives u3_i; a uniform is the word's top 24 bits
+ * times 2^-24 (exact in float32, in [0, 1)).  A draw depends on (seed, step, elem_base + b, i, j) only: never on B, the rank
+ * split or the launch.  step_dev, when not NULL, is a DEVICE word read by the kernel in place of `step`: a captured graph
+ * draws fresh numbers on every replay after the caller increments the word.
+ *
+ * usip_cgf_loss_f32: float64 arithmetic from the float32 inputs, never contracted, f-9's conventions; indices read from sel
+ * are clamped into 0 .. M-1.  D(i, j) = sqrt(sum_c (a_ci - p_cj)^2): lane l of 64 adds channels l, l + 64, ... ascending, the 64
+ * partial sums go through the binary tree part[l] += part[l + s], s = 32 .. 1.  dist f64 [B][M][2] = D(i, j_pos), D(i, j_neg),
+ * for every anchor.  n_b = sum_i has_i; before_i = has_i ? (D(i, j_pos) - D(i, j_neg)) + gamma : 0; active f32 [B] = #{before_i >
+ * 1e-5} / (n_b + 1); raw_i = max(sigma_max - sigma_i, 0); mean_b = (sum_i raw_i) / M, the sum as 256 strided partial sums in
+ * ascending i and the same kind of tree; w_i = raw_i / mean_b, and 0 when mean_b is 0 (every sigma at or above sigma_max: the
+ * reference divides 0 by 0 and returns NaN; here the row is 0); coef f64 [B][M] = (w_i * M) / (n_b + 1) where before_i > 0, else
+ * 0; loss f32 [B][M] = coef_i * before_i where before_i > 0, else 0; loss and active are rounded once.
+ *
+ * usip_cgf_loss_backward_f32: grad_loss f32 [B][M]; g_i = grad_loss_i * coef_i; unit(v) = v / |v| with the saved distance, ZERO
+ * at distance 0 (torch's norm backward).  d_anc[:, i] = g_i * (unit(a_i - p_jpos) - unit(a_i - p_jneg)).  d_pos[:, j] = the sum
+ * over the anchors i ascending of -(g_i * unit(a_i - p_j)) when j_pos(i) == j, followed by +(g_i * unit(a_i - p_j)) when j_neg(i)
+ * == j, from 0, rounded once; no floating-point atomics.  Keypoints and sigmas receive no gradient (the reference detaches
+ * the weights; masks and arg-mins carry none).
+ *
+ * No launch synchronises the host; no B x M x M or B x C x M x M array exists on the Philox path.  USIP_EINVAL: a shape outside
+ * the limits, a radius that is not positive, some but not all of u1, u2, u3, a NULL among the required pointers. */
+int usip_cgf_select_f32(const float* anc_kp, const float* pos_kp, int B, int M, double radius, const float* u1, const float* u2,
+                        const float* u3, uint64_t seed, uint64_t step, const uint64_t* step_dev, uint64_t elem_base, int32_t* sel,
+                        uint8_t* has, uint8_t* take_far, void* stream);
+int usip_cgf_loss_f32(const float* anc_desc, const float* pos_desc, const float* anc_sigma, const int32_t* sel, const uint8_t* has,
+                      const uint8_t* take_far, int B, int M, int C, double gamma, double sigma_max, float* loss, float* active,
+                      double* dist, double* coef, void* stream);
+int usip_cgf_loss_backward_f32(const float* anc_desc, const float* pos_desc, const int32_t* sel, const uint8_t* take_far,
+                               const double* dist, const double* coef, const float* grad_loss, int B, int M, int C, float* d_anc,
+                               float* d_pos, void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same orders; num_threads splits the anchors (the columns
+ * of d_pos).  The selection twin takes `step` by value only. */
+int usip_cgf_select_f32_cpu(const float* anc_kp, const float* pos_kp, int B, int M, double radius, const float* u1, const float* u2,
+                            const float* u3, uint64_t seed, uint64_t step, uint64_t elem_base, int32_t* sel, uint8_t* has,
+                            uint8_t* take_far, int num_threads);
+int usip_cgf_loss_f32_cpu(const float* anc_desc, const float* pos_desc, const float* anc_sigma, const int32_t* sel,
+                          const uint8_t* has, const uint8_t* take_far, int B, int M, int C, double gamma, double sigma_max,
+                          float* loss, float* active, double* dist, double* coef, int num_threads);
+int usip_cgf_loss_backward_f32_cpu(const float* anc_desc, const float* pos_desc, const int32_t* sel, const uint8_t* take_far,
+                                   const double* dist, const double* coef, const float* grad_loss, int B, int M, int C,
+                                   float* d_anc, float* d_pos, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1212,3 +1212,54 @@ def som_pool_layer(x, weight, bias, min_idx32, count, csr, M: int, concat: bool)
 def knn_group(feat, database, query, idx32):
     require_device(feat, "knn_group")
     return _KnnGroup.apply(feat, database, query, idx32)
+
+
+# --------------------------------------------------------------------------- the indoor descriptor's loss (f-22)
+class _CgfTriplet(torch.autograd.Function):
+    """losses.DescCGFLoss (models/losses.py:240-314) as a selection, a loss and a backward launch group: three indices and
+    two distances per anchor instead of the reference's B x C x M x M difference tensor.  Host tensors go to the host twins.
+    Gradients reach the two descriptor tensors only, as in the reference (detached weights, masks and arg-mins)."""
+
+    @staticmethod
+    def forward(ctx, anc_kp, anc_desc, pos_kp, pos_desc, anc_sigma, radius, gamma, sigma_max, draws, seed, step, elem_base,
+                num_threads):
+        anc_kp, pos_kp = anc_kp.detach().contiguous(), pos_kp.detach().contiguous()
+        anc_desc, pos_desc, anc_sigma = anc_desc.contiguous(), pos_desc.contiguous(), anc_sigma.detach().contiguous()
+        if anc_desc.is_cuda:
+            sel, has, take_far = ops.cgf_select(anc_kp, pos_kp, radius, draws, seed, step, elem_base)
+            loss, active, dist, coef = ops.cgf_loss(anc_desc, pos_desc, anc_sigma, sel, has, take_far, gamma, sigma_max)
+        else:
+            sel, has, take_far = ops.cgf_select_cpu(anc_kp, pos_kp, radius, draws, seed, int(step), elem_base, num_threads)
+            loss, active, dist, coef = ops.cgf_loss_cpu(anc_desc, pos_desc, anc_sigma, sel, has, take_far, gamma, sigma_max,
+                                                        num_threads)
+        ctx.save_for_backward(anc_desc, pos_desc, sel, take_far, dist, coef)
+        ctx.num_threads = num_threads
+        ctx.mark_non_differentiable(active, sel, has, take_far)
+        ctx.set_materialize_grads(False)
+        return loss, active, sel, has, take_far
+
+    @staticmethod
+    def backward(ctx, gloss, *_):
+        if gloss is None:
+            return (None,) * 13
+        anc_desc, pos_desc, sel, take_far, dist, coef = ctx.saved_tensors
+        if anc_desc.is_cuda:
+            d_anc, d_pos = ops.cgf_loss_backward(anc_desc, pos_desc, sel, take_far, dist, coef, gloss.contiguous())
+        else:
+            d_anc, d_pos = ops.cgf_loss_backward_cpu(anc_desc, pos_desc, sel, take_far, dist, coef, gloss.contiguous(),
+                                                     ctx.num_threads)
+        return (None, d_anc if ctx.needs_input_grad[1] else None, None, d_pos if ctx.needs_input_grad[3] else None) + (None,) * 9
+
+
+def cgf_triplet(anc_kp, anc_desc, pos_kp, pos_desc, anc_sigma, radius: float, gamma: float, sigma_max: float, draws=None,
+                seed: int = 0, step=0, elem_base: int = 0, num_threads: int = 1):
+    """-> (loss f32 [B,M], active f32 [B], sel i32 [B,M,3], has u8 [B,M], take_far u8 [B,M]).  All tensors on one device, or all
+    on the host (the host twin).  draws: None (Philox from (seed, step, elem_base + b)) or the dict u1, u2, u3 of explicit
+    uniforms; step: an int or, on the device, a one-element int64 tensor read when the kernel runs."""
+    tensors = [anc_kp, anc_desc, pos_kp, pos_desc, anc_sigma] + ([] if draws is None else [draws[k] for k in ("u1", "u2", "u3")])
+    if len({t.device for t in tensors}) != 1:
+        raise RuntimeError("usip_amd: cgf_triplet needs all its tensors on one device")
+    if not anc_desc.is_cuda and isinstance(step, torch.Tensor):
+        step = int(step.item())
+    return _CgfTriplet.apply(anc_kp, anc_desc, pos_kp, pos_desc, anc_sigma, float(radius), float(gamma), float(sigma_max), draws,
+                             int(seed), step, int(elem_base), int(num_threads))

@@ -97,3 +97,51 @@ class DescPairScanLoss(nn.Module):
         w = torch.clamp(self.opt.sigma_max - anc_sigmas, min=0)
         w = (w / torch.mean(w, dim=1, keepdim=True)).detach()
         return w * torch.clamp(before_clamp, min=0), active_percentage
+
+
+class DescCGFLoss(nn.Module):
+    """The indoor descriptor's CGF triplet loss (models/losses.py:240-314): for every anchor keypoint a random
+    positive keypoint within opt.CGF_radius and, with equal odds, the nearest keypoint beyond the radius or a random one
+    beyond it; clamp(d_pos - d_neg + opt.triple_loss_gamma, 0) over the matched anchors, rescaled by M / (matched + 1) and
+    weighted by clamp(opt.sigma_max - sigma, 0) normalised to mean 1.
+    forward(anc_keypoints Bx3xM (in the positive's frame), anc_descriptors BxCxM, pos_keypoints Bx3xM, pos_descriptors BxCxM,
+    anc_sigmas BxM, anc_pc=None, pos_pc=None) -> (loss BxM, active_percentage B).  anc_pc and pos_pc are accepted and ignored
+    (the reference reads them in commented-out code only).  The reference's B x C x M x M difference tensor and its three
+    random B x M x M matrices are replaced by the fused selection and distance kernels.  When every sigma of a batch element
+    is at or above sigma_max the reference returns NaN (0 / 0); here that row is 0.
+
+    Random numbers: counter-based (Philox) from (seed, step, batch element, i, j).  Keyword-only additions: seed at
+    construction; on the call draws = dict(u1, u2 f32 BxMxM, u3 f32 BxM) for recorded uniforms, and step = an int or a
+    one-element int64 device tensor.  By default an internal device word is the step and is incremented in-stream after each
+    call in training mode, so a captured graph draws fresh numbers on every replay.  last_indices = (sel i32 BxMx3 =
+    (j_pos, j_far, j_out), has u8 BxM, take_far u8 BxM).  Host tensors go to the host twin."""
+
+    def __init__(self, opt, *, seed: int = 0):
+        super().__init__()
+        self.opt = opt
+        self.seed = int(seed)
+        self._step_dev = None                                           # one int64 word per device, made on first use
+        self._step_host = 0
+
+    def _step(self, device):
+        if device.type != "cuda":
+            return self._step_host
+        if self._step_dev is None or self._step_dev.device != device:
+            self._step_dev = torch.full((1,), self._step_host, dtype=torch.int64, device=device)
+        return self._step_dev
+
+    def forward(self, anc_keypoints, anc_descriptors, pos_keypoints, pos_descriptors, anc_sigmas, anc_pc=None, pos_pc=None, *,
+                draws=None, step=None):
+        own = step is None and draws is None
+        if step is None:
+            step = self._step(anc_descriptors.device) if own else 0
+        loss, active, sel, has, take_far = Fh.cgf_triplet(
+            anc_keypoints, anc_descriptors, pos_keypoints, pos_descriptors, anc_sigmas, self.opt.CGF_radius,
+            self.opt.triple_loss_gamma, self.opt.sigma_max, draws, self.seed, step)
+        self.last_indices = (sel, has, take_far)
+        if own and self.training:
+            if isinstance(step, torch.Tensor):
+                step.add_(1)                                            # in-stream: behind the selection that read it
+            else:
+                self._step_host += 1
+        return loss, active

@@ -2580,3 +2580,175 @@ def gt_information(rows, offsets, frag2, Rt, order, count, Lmax: int):
             *_bank_args(rows, offsets), _ptr(frag2), _ptr(Rt), _ptr(order), _ptr(count), P, int(Lmax), cap, _ptr(info),
             _stream(rows)), "usip_gt_information_f32")
     return info
+
+
+# ------------------------------------------------------------------------------------------------ f-22 the indoor descriptor's CGF triplet loss
+CGF_MAX_M, CGF_MAX_C = 65535, 4096
+
+
+def _cgf_shapes(anc_kp, pos_kp, host: bool):
+    for t, name in ((anc_kp, "anc_keypoints"), (pos_kp, "pos_keypoints")):
+        _need_host(t, name, torch.float32) if host else _need(t, name, torch.float32)
+    if anc_kp.dim() != 3 or anc_kp.shape[1] != 3 or pos_kp.shape != anc_kp.shape or pos_kp.device != anc_kp.device:
+        raise RuntimeError("cgf: expected anc_keypoints and pos_keypoints f32 [B,3,M] on one device")
+    B, M = anc_kp.shape[0], anc_kp.shape[2]
+    if B < 1 or not 1 <= M <= CGF_MAX_M:
+        raise RuntimeError("cgf: B >= 1 and M in 1..%d (got %d, %d)" % (CGF_MAX_M, B, M))
+    return B, M
+
+
+def _need_host(t, name: str, dtype):
+    if not isinstance(t, torch.Tensor) or t.is_cuda or not t.is_contiguous() or t.dtype != dtype:
+        raise RuntimeError("%s must be a contiguous CPU %s tensor" % (name, dtype))
+
+
+def _cgf_draws(draws, B: int, M: int, device, host: bool):
+    """None (Philox) or the dict u1, u2 f32 [B,M,M], u3 f32 [B,M] -> the three tensors or three Nones"""
+    if draws is None:
+        return None, None, None
+    out = []
+    for k, shape in (("u1", (B, M, M)), ("u2", (B, M, M)), ("u3", (B, M))):
+        t = draws[k]
+        _need_host(t, k, torch.float32) if host else _need(t, k, torch.float32)
+        if tuple(t.shape) != shape or t.device != device:
+            raise RuntimeError("cgf: draws[%r] must be f32 %s on %s" % (k, shape, device))
+        out.append(t)
+    return tuple(out)
+
+
+def _cgf_desc(anc_desc, pos_desc, B: int, M: int, host: bool):
+    for t, name in ((anc_desc, "anc_descriptors"), (pos_desc, "pos_descriptors")):
+        _need_host(t, name, torch.float32) if host else _need(t, name, torch.float32)
+    if anc_desc.dim() != 3 or anc_desc.shape[0] != B or anc_desc.shape[2] != M or pos_desc.shape != anc_desc.shape \
+            or pos_desc.device != anc_desc.device or not 1 <= anc_desc.shape[1] <= CGF_MAX_C:
+        raise RuntimeError("cgf: expected anc_descriptors and pos_descriptors f32 [B,C,M] with C in 1..%d on one device" % CGF_MAX_C)
+    return anc_desc.shape[1]
+
+
+def _cgf_need(t, name: str, dtype, shape, device):
+    _need(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or t.device != device:
+        raise RuntimeError("cgf: %s must be %s %s on %s" % (name, dtype, tuple(shape), device))
+
+
+def _cgf_u64(v: int) -> int:
+    return int(v) & 0xFFFFFFFFFFFFFFFF
+
+
+def cgf_select(anc_kp, pos_kp, radius: float, draws=None, seed: int = 0, step=0, elem_base: int = 0):
+    """f-22: anc_kp, pos_kp f32 [B,3,M] -> (sel i32 [B,M,3] = (j_pos, j_far, j_out), has u8 [B,M], take_far u8 [B,M]).  draws:
+    None (Philox: (seed, step, elem_base + b, i, j)) or the dict u1, u2 f32 [B,M,M], u3 f32 [B,M].  step: an int, or a
+    one-element int64 DEVICE tensor the kernel reads when it runs (a captured graph draws anew after the word is incremented)."""
+    B, M = _cgf_shapes(anc_kp, pos_kp, False)
+    dev = anc_kp.device
+    u1, u2, u3 = _cgf_draws(draws, B, M, dev, False)
+    step_dev = None
+    if isinstance(step, torch.Tensor):
+        _need(step, "step", torch.int64)
+        if step.numel() != 1 or step.device != dev:
+            raise RuntimeError("cgf: a tensor step must hold one int64 on %s" % dev)
+        step_dev, step = step, 0
+    if not float(radius) > 0.0:
+        raise RuntimeError("cgf: the radius must be positive")
+    sel = torch.empty((B, M, 3), dtype=torch.int32, device=dev)
+    has = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    take_far = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev), prof.kernel("cgf_select", 24.0 * B * M + 14.0 * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_cgf_select_f32(_ptr(anc_kp), _ptr(pos_kp), B, M, float(radius), _opt_ptr(u1), _opt_ptr(u2),
+                                                  _opt_ptr(u3), _cgf_u64(seed), _cgf_u64(step), _opt_ptr(step_dev),
+                                                  _cgf_u64(elem_base), _ptr(sel), _ptr(has), _ptr(take_far), _stream(anc_kp)),
+                   "usip_cgf_select_f32")
+    return sel, has, take_far
+
+
+def _cgf_picks(sel, has, take_far, B: int, M: int, device, host: bool):
+    for t, name, dt, shape in ((sel, "sel", torch.int32, (B, M, 3)), (has, "has", torch.uint8, (B, M)),
+                               (take_far, "take_far", torch.uint8, (B, M))):
+        if t is None:
+            continue
+        _need_host(t, name, dt) if host else _need(t, name, dt)
+        if tuple(t.shape) != shape or t.device != device:
+            raise RuntimeError("cgf: %s must be %s %s on %s" % (name, dt, shape, device))
+
+
+def cgf_loss(anc_desc, pos_desc, anc_sigma, sel, has, take_far, gamma: float, sigma_max: float):
+    """f-22: -> (loss f32 [B,M], active f32 [B], dist f64 [B,M,2], coef f64 [B,M]); dist and coef are what the backward needs."""
+    B, M = anc_desc.shape[0], anc_desc.shape[2]
+    C = _cgf_desc(anc_desc, pos_desc, B, M, False)
+    dev = anc_desc.device
+    _cgf_need(anc_sigma, "anc_sigmas", torch.float32, (B, M), dev)
+    _cgf_picks(sel, has, take_far, B, M, dev, False)
+    loss = torch.empty((B, M), dtype=torch.float32, device=dev)
+    active = torch.empty((B,), dtype=torch.float32, device=dev)
+    dist = torch.empty((B, M, 2), dtype=torch.float64, device=dev)
+    coef = torch.empty((B, M), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev), prof.kernel("cgf_loss", 12.0 * B * C * M + 50.0 * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_cgf_loss_f32(_ptr(anc_desc), _ptr(pos_desc), _ptr(anc_sigma), _ptr(sel), _ptr(has),
+                                                _ptr(take_far), B, M, C, float(gamma), float(sigma_max), _ptr(loss), _ptr(active),
+                                                _ptr(dist), _ptr(coef), _stream(anc_desc)), "usip_cgf_loss_f32")
+    return loss, active, dist, coef
+
+
+def cgf_loss_backward(anc_desc, pos_desc, sel, take_far, dist, coef, grad_loss):
+    """f-22: grad_loss f32 [B,M] -> (d_anc, d_pos) f32 [B,C,M]"""
+    B, M = anc_desc.shape[0], anc_desc.shape[2]
+    C = _cgf_desc(anc_desc, pos_desc, B, M, False)
+    dev = anc_desc.device
+    _cgf_picks(sel, None, take_far, B, M, dev, False)
+    _cgf_need(dist, "dist", torch.float64, (B, M, 2), dev)
+    _cgf_need(coef, "coef", torch.float64, (B, M), dev)
+    _cgf_need(grad_loss, "grad_loss", torch.float32, (B, M), dev)
+    d_anc, d_pos = torch.empty_like(anc_desc), torch.empty_like(pos_desc)
+    with torch.cuda.device(dev), prof.kernel("cgf_loss_backward", 16.0 * B * C * M + 40.0 * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_cgf_loss_backward_f32(_ptr(anc_desc), _ptr(pos_desc), _ptr(sel), _ptr(take_far), _ptr(dist),
+                                                         _ptr(coef), _ptr(grad_loss), B, M, C, _ptr(d_anc), _ptr(d_pos),
+                                                         _stream(anc_desc)), "usip_cgf_loss_backward_f32")
+    return d_anc, d_pos
+
+
+def cgf_select_cpu(anc_kp, pos_kp, radius: float, draws=None, seed: int = 0, step: int = 0, elem_base: int = 0,
+                   num_threads: int = 1):
+    """Host twin of cgf_select: HOST tensors."""
+    B, M = _cgf_shapes(anc_kp, pos_kp, True)
+    u1, u2, u3 = _cgf_draws(draws, B, M, anc_kp.device, True)
+    if not float(radius) > 0.0:
+        raise RuntimeError("cgf: the radius must be positive")
+    sel = torch.zeros((B, M, 3), dtype=torch.int32)
+    has, take_far = torch.zeros((B, M), dtype=torch.uint8), torch.zeros((B, M), dtype=torch.uint8)
+    _lib.check(_lib.lib().usip_cgf_select_f32_cpu(_ptr(anc_kp), _ptr(pos_kp), B, M, float(radius), _opt_ptr(u1), _opt_ptr(u2),
+                                                  _opt_ptr(u3), _cgf_u64(seed), _cgf_u64(step), _cgf_u64(elem_base), _ptr(sel),
+                                                  _ptr(has), _ptr(take_far), int(num_threads)), "usip_cgf_select_f32_cpu")
+    return sel, has, take_far
+
+
+def cgf_loss_cpu(anc_desc, pos_desc, anc_sigma, sel, has, take_far, gamma: float, sigma_max: float, num_threads: int = 1):
+    """Host twin of cgf_loss: HOST tensors."""
+    B, M = anc_desc.shape[0], anc_desc.shape[2]
+    C = _cgf_desc(anc_desc, pos_desc, B, M, True)
+    _need_host(anc_sigma, "anc_sigmas", torch.float32)
+    if tuple(anc_sigma.shape) != (B, M):
+        raise RuntimeError("cgf: anc_sigmas must be f32 [B,M]")
+    _cgf_picks(sel, has, take_far, B, M, anc_desc.device, True)
+    loss, active = torch.zeros((B, M), dtype=torch.float32), torch.zeros((B,), dtype=torch.float32)
+    dist, coef = torch.zeros((B, M, 2), dtype=torch.float64), torch.zeros((B, M), dtype=torch.float64)
+    _lib.check(_lib.lib().usip_cgf_loss_f32_cpu(_ptr(anc_desc), _ptr(pos_desc), _ptr(anc_sigma), _ptr(sel), _ptr(has),
+                                                _ptr(take_far), B, M, C, float(gamma), float(sigma_max), _ptr(loss), _ptr(active),
+                                                _ptr(dist), _ptr(coef), int(num_threads)), "usip_cgf_loss_f32_cpu")
+    return loss, active, dist, coef
+
+
+def cgf_loss_backward_cpu(anc_desc, pos_desc, sel, take_far, dist, coef, grad_loss, num_threads: int = 1):
+    """Host twin of cgf_loss_backward: HOST tensors."""
+    B, M = anc_desc.shape[0], anc_desc.shape[2]
+    C = _cgf_desc(anc_desc, pos_desc, B, M, True)
+    _cgf_picks(sel, None, take_far, B, M, anc_desc.device, True)
+    for t, name, dt, shape in ((dist, "dist", torch.float64, (B, M, 2)), (coef, "coef", torch.float64, (B, M)),
+                               (grad_loss, "grad_loss", torch.float32, (B, M))):
+        _need_host(t, name, dt)
+        if tuple(t.shape) != shape:
+            raise RuntimeError("cgf: %s must be %s %s" % (name, dt, shape))
+    d_anc, d_pos = torch.zeros_like(anc_desc), torch.zeros_like(pos_desc)
+    _lib.check(_lib.lib().usip_cgf_loss_backward_f32_cpu(_ptr(anc_desc), _ptr(pos_desc), _ptr(sel), _ptr(take_far), _ptr(dist),
+                                                         _ptr(coef), _ptr(grad_loss), B, M, C, _ptr(d_anc), _ptr(d_pos),
+                                                         int(num_threads)), "usip_cgf_loss_backward_f32_cpu")
+    return d_anc, d_pos
