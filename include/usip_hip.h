@@ -239,6 +239,29 @@ int usip_detector_loss_combine_f32(const float* d, const float* chamfer, float a
 /* out[0:n] = g[0] * factor (the gradient of a mean). */
 int usip_fill_scaled_f32(const float* g, float factor, float* out, long long n, void* stream);
 
+/* The loss segment of the detector step, keypoints / sigmas to their gradients, in three launches (csrc/loss_tail.hip)
+ * instead of the chain rigid_transform, 2 x nearest, chamfer_prob, loss_combine and their backwards with what autograd
+ * launches around them.  Same arithmetic, operation for operation: every result equals the chain's bit for bit.
+ * keypoints f32 [2B][3][M] and sigmas f32 [2B][M] hold the src clouds in rows [0,B) and the dst clouds in [B,2B);
+ * R [B][3][3], scale [B], shift [B][3].  1 <= M <= 1024 (a pair is staged in LDS) and 1 <= B <= 65535; anything else,
+ * or a NULL pointer, is USIP_EINVAL with nothing launched (callers then run the chain).
+ * scan: kp_t [B][3][M] = (R scale) . keypoints_src + shift; (a, J) [B][M] = usip_nearest_f32(kp_t, keypoints_dst),
+ * (c, I) [B][M] = usip_nearest_f32(keypoints_dst, kp_t).  One launch. */
+int usip_loss_tail_scan_f32(const float* keypoints, const float* R, const float* scale, const float* shift, float* kp_t,
+                            float* a, int32_t* J, float* c, int32_t* I, int B, int M, void* stream);
+/* sums: out6 = (loss, loss_chamfer, chamfer_pure, chamfer_weighted, alpha * mean(d[0:B]), alpha * mean(d[B:2B])) with
+ * the middle three as usip_chamfer_prob_f32 and the others as usip_detector_loss_combine_f32; d f32 [2B][M] are the
+ * keypoint-to-cloud distances.  One launch of one workgroup. */
+int usip_loss_tail_sums_f32(const float* a, const int32_t* J, const float* c, const int32_t* I, const float* sigmas,
+                            const float* d, float alpha, float* out6, int B, int M, void* stream);
+/* backward: g_keypoints [2B][3][M] and g_sigmas [2B][M] (every element written) for the upstream gradient gloss[0] of
+ * the loss.  (d, arg) [2B][M] are the keypoint-to-cloud minima against pc f32 [2B][3][N]; factor = alpha / (B * M) as
+ * a float, the factor usip_fill_scaled_f32 is given for the same gradient.  One launch, no atomics. */
+int usip_loss_tail_backward_f32(const float* gloss, const float* keypoints, const float* sigmas, const float* kp_t,
+                                const float* a, const int32_t* J, const float* c, const int32_t* I, const float* d,
+                                const int32_t* arg, const float* pc, const float* R, const float* scale, float factor,
+                                float* g_keypoints, float* g_sigmas, int B, int M, int N, void* stream);
+
 /* ------------------------------------------------------------------ a-11  optimizer.step()
  * One Adam step (models/keypoint_detector.py:42-45, :207: torch.optim.Adam(lr, betas = (0.9, 0.999)), eps 1e-8, no
  * weight decay) on flat fp32 buffers of n elements, 16-B aligned: step_count[0] += 1 (device float, so the update can

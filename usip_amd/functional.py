@@ -350,6 +350,49 @@ def detector_loss_combine(d, chamfer, alpha: float):
     return _DetectorLossCombine.apply(d, chamfer, float(alpha))
 
 
+class _DetectorLossTail(torch.autograd.Function):
+    """The loss segment of the detector step (models/keypoint_detector.py:182-204) from keypoints / sigmas to the loss:
+    rigid_transform, the probabilistic chamfer loss between the two keypoint sets and the point-to-point keypoint-on-cloud
+    term, as csrc/loss_tail.hip runs them -- scan, the on-cloud search (its own launch, as in the chain), sums forward,
+    one launch backward -- with the chain's results bit for bit.  kp [2B,3,M], sg [2B,M]: src clouds first."""
+
+    @staticmethod
+    def forward(ctx, kp, sg, R, scale, shift, pc, grid, alpha):
+        kp, sg, pc = kp.contiguous(), sg.contiguous(), pc.contiguous()
+        R, scale = R.contiguous(), scale.contiguous()
+        kp_t, a, J, c, I = ops.loss_tail_scan(kp, R, scale, shift.contiguous())
+        d, arg = ops.nearest_grid(kp, grid) if grid is not None else ops.nearest(kp, pc)
+        out = ops.loss_tail_sums(a, J, c, I, sg, d, alpha)
+        ctx.save_for_backward(kp, sg, kp_t, a, J, c, I, d, arg, pc, R, scale)
+        ctx.factor = float(alpha) / (d.numel() // 2)           # as _DetectorLossCombine.backward hands it to fill_scaled
+        loss, rest = out[0], (out[1], out[2], out[3], out[4], out[5], J, I)
+        ctx.mark_non_differentiable(*rest)
+        ctx.set_materialize_grads(False)
+        return (loss,) + rest
+
+    @staticmethod
+    def backward(ctx, gloss, *_):
+        if gloss is None:
+            return (None,) * 8
+        g_kp, g_sg = ops.loss_tail_backward(gloss.contiguous().reshape(1), *ctx.saved_tensors, ctx.factor)
+        return g_kp, g_sg, None, None, None, None, None, None
+
+
+def detector_loss_tail_supported(kp, sg) -> bool:
+    return (ops.LOSS_TAIL and kp.is_cuda and sg is not None and kp.dim() == 3 and kp.shape[0] % 2 == 0
+            and kp.shape[0] >= 2 and 1 <= kp.shape[2] <= ops.LOSS_TAIL_MAX_M)
+
+
+def detector_loss_tail(kp, sg, R, scale, shift, pc, grid, alpha: float):
+    """-> (loss, loss_chamfer, chamfer_pure, chamfer_weighted, alpha*mean(d_src), alpha*mean(d_dst), J, I); only the
+    loss carries a gradient (to kp and sg).  grid: an ops.CellGrid built from pc, or None."""
+    require_device(kp, "detector_loss_tail")
+    if grid is not None and not grid.built_from(pc):
+        raise RuntimeError("detector_loss_tail: the cell grid was not built from these candidates")
+    B = kp.shape[0] // 2
+    return _DetectorLossTail.apply(kp, sg, R, scale.reshape(-1), shift.reshape(B, 3), pc, grid, float(alpha))
+
+
 def nearest_distance(a: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """a [B,C,Ma], b [B,C,Nb] -> (min distance [B,Ma], arg-min int64 [B,Ma] as torch.min returns it).  C == 3:
     coordinates (exact oracle arithmetic); any other C: descriptors (Nb <= 1024)."""

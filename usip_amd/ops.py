@@ -449,6 +449,66 @@ def fill_scaled(g, factor: float, shape):
     return out
 
 
+# USIP_LOSS_TAIL=0: the detector step's loss segment goes back to the chain of launches (rigid_transform, 2 x nearest,
+# chamfer_prob, loss_combine and their backwards) -- the A/B switch of csrc/loss_tail.hip; results are the same bits.
+LOSS_TAIL = os.environ.get("USIP_LOSS_TAIL", "1") not in ("0", "off")
+LOSS_TAIL_MAX_M = 1024                                        # a pair's keypoints are staged in LDS
+
+
+def loss_tail_scan(kp, R, scale, shift):
+    """kp [2B,3,M] (src clouds first) -> (kp_t [B,3,M], a, J, c, I [B,M]): rigid_transform of the src half and nearest
+    in both directions against the dst half, bit for bit, in one launch."""
+    _need_pts(kp, "keypoints")
+    for t, n in ((R, "R"), (scale, "scale"), (shift, "shift")):
+        _need(t, n, torch.float32)
+    B, M = kp.shape[0] // 2, kp.shape[2]
+    if kp.shape[0] != 2 * B or R.numel() != 9 * B or scale.numel() != B or shift.numel() != 3 * B:
+        raise RuntimeError("loss_tail_scan: expected keypoints [2B,3,M], R [B,3,3], scale [B], shift [B,3]")
+    kp_t = torch.empty((B, 3, M), dtype=torch.float32, device=kp.device)
+    a, c = (torch.empty((B, M), dtype=torch.float32, device=kp.device) for _ in range(2))
+    J, I = (torch.empty((B, M), dtype=torch.int32, device=kp.device) for _ in range(2))
+    with torch.cuda.device(kp.device), prof.kernel("loss_tail_scan", 4.0 * (9 * B * M + 4 * B * M), 2 * 8.0 * B * M * M):
+        _lib.check(_lib.lib().usip_loss_tail_scan_f32(_ptr(kp), _ptr(R), _ptr(scale), _ptr(shift), _ptr(kp_t), _ptr(a),
+                                                      _ptr(J), _ptr(c), _ptr(I), B, M, _stream(kp)),
+                   "usip_loss_tail_scan_f32")
+    return kp_t, a, J, c, I
+
+
+def loss_tail_sums(a, J, c, I, sg, d, alpha: float):
+    """-> 6-vector (loss, loss_chamfer, chamfer_pure, chamfer_weighted, alpha*mean(d_src), alpha*mean(d_dst)): chamfer_prob
+    on (a, J, c, I) and the two halves of sg [2B,M], then detector_loss_combine on d [2B,M], in one launch."""
+    for t, n in ((a, "a"), (c, "c"), (sg, "sigmas"), (d, "d")):
+        _need(t, n, torch.float32)
+    _need(J, "J", torch.int32)
+    _need(I, "I", torch.int32)
+    B, M = a.shape
+    if not (J.shape == I.shape == c.shape == a.shape) or tuple(sg.shape) != (2 * B, M) or tuple(d.shape) != (2 * B, M):
+        raise RuntimeError("loss_tail_sums: shapes do not match")
+    out = torch.empty(6, dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device), prof.kernel("loss_tail_sums", 4.0 * 8 * B * M, 0.0):
+        _lib.check(_lib.lib().usip_loss_tail_sums_f32(_ptr(a), _ptr(J), _ptr(c), _ptr(I), _ptr(sg), _ptr(d), float(alpha),
+                                                      _ptr(out), B, M, _stream(a)), "usip_loss_tail_sums_f32")
+    return out
+
+
+def loss_tail_backward(gloss, kp, sg, kp_t, a, J, c, I, d, arg, pc, R, scale, factor: float):
+    """-> (g_kp [2B,3,M], g_sg [2B,M]) for the upstream gradient `gloss` (device scalar) of the loss; (d, arg) are the
+    keypoint-to-cloud minima against pc [2B,3,N]; factor: what fill_scaled gets for d's gradient, alpha / (B * M)."""
+    _need(gloss, "gloss", torch.float32)
+    _need_pts(pc, "pc")
+    _need(arg, "arg", torch.int32)
+    B, M = a.shape
+    if pc.shape[0] != 2 * B or tuple(d.shape) != (2 * B, M) or tuple(arg.shape) != (2 * B, M):
+        raise RuntimeError("loss_tail_backward: shapes do not match")
+    g_kp, g_sg = torch.empty_like(kp), torch.empty_like(sg)
+    with torch.cuda.device(kp.device), prof.kernel("loss_tail_bwd", 4.0 * 30 * B * M, 0.0):
+        _lib.check(_lib.lib().usip_loss_tail_backward_f32(_ptr(gloss), _ptr(kp), _ptr(sg), _ptr(kp_t), _ptr(a), _ptr(J),
+                                                          _ptr(c), _ptr(I), _ptr(d), _ptr(arg), _ptr(pc), _ptr(R),
+                                                          _ptr(scale), float(factor), _ptr(g_kp), _ptr(g_sg), B, M,
+                                                          pc.shape[2], _stream(kp)), "usip_loss_tail_backward_f32")
+    return g_kp, g_sg
+
+
 # --------------------------------------------------------------------------- shared MLP
 def _opt(t):
     return _ptr(t) if t is not None else None

@@ -594,12 +594,22 @@ class DetectorStep(_GraphedStep):
             self.detector.last_grid = None                    # taken: the step does not keep pc's sorted copy alive
             if not grid.built_from(pc):
                 grid = None
+        alpha = self.opt.keypoint_on_pc_alpha
+        if (getattr(self.opt, "keypoint_on_pc_type", "point_to_point") != "point_to_plane" and kp.shape[0] == 2 * B
+                and getattr(self, "_replay_this_call", True) and Fh.detector_loss_tail_supported(kp, sg)):
+            # :182-204 in three launches and one backward launch (csrc/loss_tail.hip), the chain below bit for bit
+            loss, loss_chamfer, pure, weighted, on_src, on_dst, J, I = Fh.detector_loss_tail(
+                kp, sg, batch["R"], batch["scale"], batch["shift"], pc, grid, alpha)
+            self.chamfer_criteria.last_indices = (J, I)
+            self.last = dict(node=nodes, keypoints=kp, sigmas=sg, loss=loss, loss_chamfer=loss_chamfer,
+                             chamfer_pure=pure, chamfer_weighted=weighted, loss_on_pc_src=on_src,
+                             loss_on_pc_dst=on_dst)
+            return loss
         kp_src, kp_dst = torch.split(kp, B, dim=0)            # :147-149 (split: one backward node, no zero fills)
         sg_src, sg_dst = torch.split(sg, B, dim=0)
         # :182-184  R.kp*s + t  as one batched GEMM with the scale folded into R (inputs, no gradient)
         kp_t = Fh.rigid_transform(kp_src, batch["R"], batch["scale"], batch["shift"])
         loss_chamfer, pure, weighted = self.chamfer_criteria(kp_t, kp_dst, sg_src, sg_dst)
-        alpha = self.opt.keypoint_on_pc_alpha
         # :196-203  keypoint-on-pc for src and dst: both clouds of every pair in ONE nearest-neighbour launch
         # (rows [0,B) = src, [B,2B) = dst; every cloud is independent, so the values are the reference's)
         if getattr(self.opt, "keypoint_on_pc_type", "point_to_point") == "point_to_plane":     # :197-201
