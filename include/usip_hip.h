@@ -620,6 +620,24 @@ int usip_group_max_backward_f32(const float* dpooled, const int32_t* arg, float*
 int usip_group_max_backward_add_f32(const float* dpooled, const int32_t* arg, float* dz,
                                     long long rows, int K, void* stream);
 
+/* ------------------------------------------------------------------ neighbourhoods wider than 256 samples
+ * (csrc/group_wide.hip; the indoor descriptor groups 448 points per keypoint).  One wave per neighbourhood.
+ * usip_group_max_f32 / usip_group_max_act_f32 for K % 4 == 0, 256 < K <= 1024 and y 16-byte aligned; any other K or a
+ * misaligned y is USIP_EINVAL, zero rows is USIP_OK.  coef == NULL: y [B][C][M][K] is already activated (relu is
+ * ignored) and the NaN rule of usip_group_max_f32 applies; else the maximum is over relu?(fma(y, coef[0][c], coef[1][c])),
+ * c = (row / M) % C.  arg is the FIRST k attaining the maximum, pooled carries that element's bits, yarg (may be NULL) is
+ * y at arg.  A NaN ranks above everything; -0.0 and +0.0 tie. */
+int usip_group_max_wide_f32(const float* y, const float* coef, int relu, float* pooled, int32_t* arg, float* yarg,
+                            int B, int C, int M, int K, void* stream);
+/* usip_bn_backward_reduce_f32 with the per-neighbourhood sums for group % 4 == 0, 256 < group <= 1024: the same arguments
+ * and the same outputs (partial, dgamma, dbeta, coef4 with row 4 under want_bound, gsum [2][nb][C][P/group]).  gsum and Y
+ * are required (no plain mode), P % group == 0, dZ and Y 16-byte aligned; anything else is USIP_EINVAL.  The summation
+ * order is this entry's own and fixed: the same bits on every run, not those of usip_bn_backward_reduce_f32. */
+int usip_bn_backward_reduce_wide_f32(const float* dZ, const float* Y, const float* coef_fwd,
+                                     const float* mean, const float* invstd, const float* gamma, int relu,
+                                     float* partial, float* dgamma, float* dbeta, float* coef4,
+                                     float* gsum, int group, int nb, int C, int P, int want_bound, void* stream);
+
 /* ------------------------------------------------------------------ a-7  node KNN
  * idx[b][m][0..K) = the K database points nearest to query m, ascending distance (lower index first on
  * exact ties): torch.norm + torch.topk(K, largest=False, sorted=True) of models/layers.py:417-421 without

@@ -18,6 +18,7 @@
 //                     bn_apply and in the GEMM prologues that read the same y.
 //   group_max_bwd     dz[b,c,m,k] = (k == arg[b,c,m]) ? dpooled[b,c,m] : 0
 #include "common.h"
+#include "pool_order.h"
 
 namespace {
 
@@ -53,22 +54,7 @@ __global__ __launch_bounds__(256) void group_gather_bwd_kernel(
     for (int c = 0; c < C; ++c) atomicAdd(&xb[(long long)c * N + n], gb[(long long)c * P + p]);
 }
 
-// The pooling order: NaN above everything, then the value; at equal values (two NaNs are equal here) the lower k.
-// Inside a lane, where k only grows, pool_gt<true> says whether a later element replaces the best so far.  A lane whose
-// best is a NaN then enters the cross-lane steps as (+inf, k - POOL_NAN): the steps' plain rule, ov > best ||
-// (ov == best && ok < bk), lets it beat a real +inf, lets the lowest NaN k win, and is the rule rows without NaN always
-// had; whoever stores finds bk < 0 and puts k and the NaN back.  NANS = false (values that passed through fmaxf(., 0)
-// cannot be NaN) is v > best and nothing else.
-constexpr int POOL_NAN = 0x40000000;
-template <bool NANS>
-__device__ __forceinline__ bool pool_gt(float v, float best)
-{
-    return NANS ? (!(v <= best) && best == best) : v > best;
-}
-__device__ __forceinline__ void pool_hide_nan(float& best, int& bk)
-{
-    if (best != best) { best = __builtin_inff(); bk -= POOL_NAN; }
-}
+// (the pooling order -- pool_gt, pool_hide_nan, POOL_NAN -- is pool_order.h's, shared with group_wide.hip)
 
 // L lanes (a power of two, <= 64) cooperate on one row of K values; rows = B*C*M.
 template <int L>

@@ -106,7 +106,11 @@ def _pooled_act(y4, coef, relu, want_yarg=False):
     """(max over K of the lazily activated y4 [B,C,M,K], arg-max i32 [B,C,M][, y4 at the arg-max]); coef None: y4 is
     already activated."""
     yarg = None
-    if coef is not None and want_yarg:
+    if ops.wide_group_supported(y4.shape[3]):                # 256 < K <= 1024: one wave per neighbourhood (csrc/group_wide.hip)
+        res = ops.group_max_wide(y4, coef, relu, want_yarg=coef is not None and want_yarg)
+        pooled, arg = res[0], res[1]
+        yarg = res[2] if len(res) == 3 else None
+    elif coef is not None and want_yarg:
         pooled, arg, yarg = ops.group_max_act(y4, coef, relu, want_yarg=True)
     else:
         pooled, arg = ops.group_max_act(y4, coef, relu) if coef is not None else ops.group_max(y4)
@@ -501,8 +505,8 @@ def _own_bn_backward(dz, y, coef, mean, invstd, gamma, relu, sink, group=0, took
         gsum = getattr(pre[1][0], "gsum", None)
         if gsum is not None and gsum.shape[3] * group == dz.shape[2]:
             return ops.bn_backward_from_partials(pre[1], dz.shape[0] * dz.shape[2], coef, mean, invstd, go, bo) + (gsum,)
-    dgamma, dbeta, coef4, gsum = ops.bn_backward_reduce(dz, y, coef, mean, invstd, gamma, relu, group=group,
-                                                        dgamma_out=go, dbeta_out=bo)
+    reduce = ops.bn_backward_reduce_wide if (group and ops.wide_group_supported(group)) else ops.bn_backward_reduce
+    dgamma, dbeta, coef4, gsum = reduce(dz, y, coef, mean, invstd, gamma, relu, group=group, dgamma_out=go, dbeta_out=bo)
     return (dgamma, dbeta, coef4, gsum) if group else (dgamma, dbeta, coef4)
 
 
@@ -765,6 +769,15 @@ def _group_sums_supported(K: int) -> bool:
     return K >= 4 and K % 4 == 0 and (lpg & (lpg - 1)) == 0 and lpg <= 64
 
 
+def _group_path(K: int) -> str:
+    """Which kernels pool and reduce a neighbourhood of K samples: "fused" (K = 4 ... 256 with K/4 a power of two:
+    group_max4_kernel, bn_bwd_reduce_kernel<true, .>), "wide" (256 < K <= 1024 with K % 32 == 0, unless USIP_WIDE_GROUPS=0:
+    csrc/group_wide.hip) or "fallback" (the activated tensor materialised, the literal concat)."""
+    if _group_sums_supported(K):
+        return "fused"
+    return "wide" if ops.wide_group_supported(K) else "fallback"
+
+
 class _SharedMLPLayerPooled(torch.autograd.Function):
     """The shared-MLP layer whose input is cat(h, expand(pooled)) over channels -- the reference
     expands the max-pooled neighbourhood feature over K and concatenates it (networks.py:706-709,
@@ -871,7 +884,7 @@ def conv1x1_bn_act_pooled(h, pooled: torch.Tensor, weight: torch.Tensor, bias: O
     concatenated tensor.  h [B,Ch,M,K] (tensor or LazyAct), pooled [B,Cp,M].  defer=True returns a LazyAct."""
     hshape = h.shape
     K = hshape[3]
-    fused = (bn is not None and bn.training and bias is not None and _group_sums_supported(K)
+    fused = (bn is not None and bn.training and bias is not None and _group_path(K) != "fallback"
              and torch.is_grad_enabled())
     if not fused:
         ht = as_tensor(h)
@@ -1014,7 +1027,7 @@ class _GroupMaxActFork(torch.autograd.Function):
 def group_max_fork(z):
     """(max over K, z) for a tensor that is pooled AND passed on: for a LazyAct the returned z is an alias whose
     gradient is combined with the pooling gradient in one sparse update (see _GroupMaxActFork)."""
-    if isinstance(z, LazyAct) and _group_sums_supported(z.shape[3]):
+    if isinstance(z, LazyAct) and _group_path(z.shape[3]) != "fallback":
         pooled, y, arg = _GroupMaxActFork.apply(z.y.view(z.shape), z.coef, z.relu)
         return pooled, LazyAct(y.view(z.y.shape), z.coef, z.relu, z.shape, fork=(pooled, arg))
     return group_max(z), z
@@ -1024,7 +1037,7 @@ def group_max(z) -> torch.Tensor:
     """z [B,C,M,K] (tensor or LazyAct) -> [B,C,M]."""
     if isinstance(z, LazyAct):
         K = z.shape[3]
-        if _group_sums_supported(K):
+        if _group_path(K) != "fallback":
             return _GroupMaxAct.apply(z.y.view(z.shape), z.coef, z.relu)
         z = z.materialize()
     require_device(z, "group_max")

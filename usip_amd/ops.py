@@ -834,6 +834,31 @@ def bn_backward_reduce(dZ, Y, coef_fwd, mean, invstd, gamma, relu: bool, group: 
     return dgamma, dbeta, coef4, gsum
 
 
+def bn_backward_reduce_wide(dZ, Y, coef_fwd, mean, invstd, gamma, relu: bool, group: int,
+                            dgamma_out=None, dbeta_out=None, want_bound=None, want_partial: bool = False):
+    """bn_backward_reduce(group=...) for group % 4 == 0, 256 < group <= 1024 -> (dgamma [C], dbeta [C], coef4, gsum
+    [2,nb,C,P/group]); want_bound None: as the matmul mode asks.  want_partial: the per-row partial sums as a fifth value."""
+    nb, C, P = dZ.shape
+    dev = dZ.device
+    if want_bound is None:
+        want_bound = _matmul_mode == "f32x2"
+    want_bound = int(bool(want_bound))
+    if group <= 0 or P % group:
+        raise RuntimeError("bn_backward_reduce_wide: P = %d is no multiple of group = %d" % (P, group))
+    partial = torch.empty((3 if want_bound else 2) * nb * C, dtype=torch.float32, device=dev)
+    dbeta = dbeta_out if dbeta_out is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    dgamma = dgamma_out if dgamma_out is not None else torch.empty(C, dtype=torch.float32, device=dev)
+    coef4 = torch.empty((5 if want_bound else 4, C), dtype=torch.float32, device=dev)
+    gsum = torch.empty((2, nb, C, P // group), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), prof.kernel("bn_backward_reduce_wide", 8.0 * nb * C * P):
+        _lib.check(_lib.lib().usip_bn_backward_reduce_wide_f32(_opt(dZ), _opt(Y), _opt(coef_fwd), _opt(mean),
+                                                               _opt(invstd), _opt(gamma), int(bool(relu)), _ptr(partial),
+                                                               _ptr(dgamma), _ptr(dbeta), _ptr(coef4), _ptr(gsum),
+                                                               int(group), nb, C, P, want_bound, _stream(dZ)),
+                   "usip_bn_backward_reduce_wide_f32")
+    return (dgamma, dbeta, coef4, gsum, partial) if want_partial else (dgamma, dbeta, coef4, gsum)
+
+
 # Deferred weight-gradient reductions (include/usip_hip.h: usip_wgrad_defer / usip_wgrad_flush): inside a training step the
 # fixed-order sums of partial tiles are recorded by the library and issued together after backward.  The partial-tile
 # workspaces must outlive the flush, so while the mode is on every workspace allocated here is kept in _DEFER_KEEP.
@@ -1218,6 +1243,32 @@ def group_max_act(y4, coef, relu: bool, want_yarg: bool = False):
     with torch.cuda.device(y4.device), prof.kernel("group_max", 4.0 * B * C * M * (K + 2)):
         _lib.check(_lib.lib().usip_group_max_act_f32(_ptr(y4), _ptr(coef), int(bool(relu)), _ptr(pooled), _ptr(arg),
                                                      _opt(yarg), B, C, M, K, _stream(y4)), "usip_group_max_act_f32")
+    return (pooled, arg, yarg) if want_yarg else (pooled, arg)
+
+
+# USIP_WIDE_GROUPS=0: neighbourhoods wider than 256 samples go back to the forms they had before csrc/group_wide.hip (the
+# activated tensor materialised and pooled by group_max_kernel<64>, the literal cat(h, expand(pooled)) in front of the
+# pooled-concat layer), for A/B runs.  functional.py reads the attribute at every call, so one process can alternate.
+WIDE_GROUPS = os.environ.get("USIP_WIDE_GROUPS", "1") not in ("0", "off")
+
+
+def wide_group_supported(K: int) -> bool:
+    """K is a neighbourhood size csrc/group_wide.hip takes AND the GEMM / layer-backward forms with a row bias or a
+    pooled group take (K % 32)."""
+    return bool(WIDE_GROUPS) and 256 < K <= 1024 and K % 32 == 0
+
+
+def group_max_wide(y4, coef=None, relu: bool = False, want_yarg: bool = False):
+    """group_max (coef None: y4 is already activated) / group_max_act for K % 4 == 0, 256 < K <= 1024
+    -> (pooled, arg[, yarg])."""
+    _need(y4, "y", torch.float32)
+    B, C, M, K = y4.shape
+    pooled = torch.empty((B, C, M), dtype=torch.float32, device=y4.device)
+    arg = torch.empty((B, C, M), dtype=torch.int32, device=y4.device)
+    yarg = torch.empty((B, C, M), dtype=torch.float32, device=y4.device) if want_yarg else None
+    with torch.cuda.device(y4.device), prof.kernel("group_max_wide", 4.0 * B * C * M * (K + 2)):
+        _lib.check(_lib.lib().usip_group_max_wide_f32(_ptr(y4), _opt(coef), int(bool(relu)), _ptr(pooled), _ptr(arg),
+                                                      _opt(yarg), B, C, M, K, _stream(y4)), "usip_group_max_wide_f32")
     return (pooled, arg, yarg) if want_yarg else (pooled, arg)
 
 
