@@ -20,13 +20,17 @@ import functools
 import os
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
 import fpfh_oracle as fo
-from conftest import ROOT
+from conftest import GOLDEN, ROOT
 from usip_amd import baselines as bl
+
+sys.path.insert(0, GOLDEN)
+import make_descriptor_walk_golden as golden  # noqa: E402
 
 U = 2.0 ** -53
 MARGIN = 1e-9
@@ -361,3 +365,12 @@ def test_twin_runs_clean_under_address_and_undefined_behaviour_sanitizers(tmp_pa
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     print(r.stdout.decode()[-2000:])
     assert r.returncode == 0 and b"runtime error" not in r.stdout and b"AddressSanitizer" not in r.stdout
+
+
+# ---------------------------------------------------------------------------------------------------- the bits pinned at one commit
+@pytest.mark.parametrize("num_threads", [1, 3])
+@pytest.mark.parametrize("name", sorted(golden.CASES))
+def test_twin_equals_the_bits_pinned_before_the_shared_keypoint_loop(name, num_threads):
+    """tests/golden/make_descriptor_walk_golden.py: what this twin computed before csrc/keypoints_host.h and
+    csrc/keypoint_walk.h, every entry =="""
+    golden.check("fpfh", name, golden.host(name, "fpfh", num_threads), "host twin, %d threads" % num_threads)

@@ -305,3 +305,10 @@ def test_the_example_scores_iss_with_fpfh_without_a_network(tmp_path, monkeypatc
     assert s["seeded_weights"] is False                                 # nothing seeded, nothing loaded: there are no weights
     for fid in (0, 1):                                                  # rows [x y z d0 .. d32]
         assert os.path.getsize(os.path.join(out, "%06d.bin" % fid)) == 64 * 36 * 4
+
+
+@pytest.mark.parametrize("name", sorted(host.golden.CASES))
+def test_device_equals_the_bits_pinned_before_the_shared_keypoint_walk(name):
+    """tests/golden/make_descriptor_walk_golden.py: what the host twin computed before csrc/keypoint_walk.h held the kernels'
+    walk, every entry =="""
+    host.golden.check("fpfh", name, host.golden.device(name, "fpfh", DEV), "device")

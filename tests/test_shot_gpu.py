@@ -323,3 +323,10 @@ def test_the_fragments_example_scores_shot_without_a_network(tmp_path, monkeypat
     for i in range(3):
         size = os.path.getsize(os.path.join(out, "synthetic", "%d.bin" % i))
         assert size > 0 and size % (355 * 4) == 0
+
+
+@pytest.mark.parametrize("name", sorted(host.golden.CASES))
+def test_device_equals_the_bits_pinned_before_the_shared_keypoint_walk(name):
+    """tests/golden/make_descriptor_walk_golden.py: what the host twin computed before csrc/keypoint_walk.h held the kernels'
+    walk, every entry =="""
+    host.golden.check("shot", name, host.golden.device(name, "shot", DEV), "device")

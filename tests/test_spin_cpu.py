@@ -25,6 +25,8 @@ import test_fpfh_cpu as fp
 from conftest import ROOT
 from usip_amd import baselines as bl
 
+golden = fp.golden
+
 EPS_A = 4.4408920985006262e-16                                         # csrc/shot_math.h's inverse tangent against numpy's (8p)
 MARGIN = 1e-9
 Q, ONE = 1 << 20, 1 << 40
@@ -400,3 +402,12 @@ def test_twin_runs_clean_under_address_and_undefined_behaviour_sanitizers(tmp_pa
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     print(r.stdout.decode()[-2000:])
     assert r.returncode == 0 and b"runtime error" not in r.stdout and b"AddressSanitizer" not in r.stdout
+
+
+# ---------------------------------------------------------------------------------------------------- the bits pinned at one commit
+@pytest.mark.parametrize("num_threads", [1, 3])
+@pytest.mark.parametrize("name", sorted(golden.CASES))
+def test_twin_equals_the_bits_pinned_before_the_shared_keypoint_loop(name, num_threads):
+    """tests/golden/make_descriptor_walk_golden.py: what this twin computed before csrc/keypoints_host.h and
+    csrc/keypoint_walk.h, every entry =="""
+    golden.check("spin", name, golden.host(name, "spin", num_threads), "host twin, %d threads" % num_threads)

@@ -121,8 +121,11 @@ def _check_harris(radius, threshold, response, min_neighbors):
         raise ValueError("harris: response must be one of %s, got %r" % (sorted(ops.HARRIS_METHODS), response))
 
 
-def _supplied(normals, pc, tag="harris"):
-    """PCL's setNormals: f32 [B,3,N], used as given -- cast to float64, not renormalised"""
+def _normals_for(pc, count, perm, normals, radius, min_neighbors, tag):
+    """normals f64 [B,3,N]: estimated over `radius` (harris_normals), or the supplied f32 [B,3,N] used as given (PCL's
+    setNormals) -- cast to float64, not renormalised"""
+    if normals is None:
+        return ops.harris_normals(pc, count, perm, radius, min_neighbors)[0]
     if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.shape != pc.shape \
             or normals.device != pc.device:
         raise ValueError("%s: supplied normals must be f32 %s on %s" % (tag, tuple(pc.shape), pc.device))
@@ -144,7 +147,7 @@ def harris_response(pc, count=None, radius: float = 1.0, normals=None, response:
     _check_harris(radius, 0.0, response, min_neighbors)
     pc, count = _frames(pc, count)
     perm = sort_along_x(pc, count) if perm is None else perm
-    nrm = ops.harris_normals(pc, count, perm, radius, min_neighbors)[0] if normals is None else _supplied(normals, pc)
+    nrm = _normals_for(pc, count, perm, normals, radius, min_neighbors, "harris")
     out = ops.harris_response(pc, count, perm, nrm, radius, response, want_visits)
     return out[:2] + (nrm,) + out[2:]
 
@@ -161,18 +164,28 @@ def harris_keypoints(pc, count=None, radius: float = 1.0, threshold: float = 0.0
 
 
 # ------------------------------------------------------------------------------------------------ FPFH
-def _check_fpfh(radius, normal_radius, min_neighbors):
+def _check_radii(radius, normal_radius, min_neighbors, tag):
     if not (0.0 < float(radius) < float("inf") and 0.0 < float(normal_radius) < float("inf") and int(min_neighbors) >= 1):
-        raise ValueError("fpfh: the radii must be positive and finite and min_neighbors at least 1")
+        raise ValueError("%s: the radii must be positive and finite and min_neighbors at least 1" % tag)
 
 
-def _keypoints(keypoints, kp_count, pc):
+def _keypoints(keypoints, kp_count, pc, tag):
     if not isinstance(keypoints, torch.Tensor) or keypoints.dim() != 3 or keypoints.shape[:2] != pc.shape[:2] \
             or keypoints.dtype != torch.float32 or keypoints.device != pc.device:
-        raise ValueError("fpfh: expected keypoints f32 [B,3,M] beside the cloud")
+        raise ValueError("%s: expected keypoints f32 [B,3,M] beside the cloud" % tag)
     if not 1 <= keypoints.shape[2] <= ops.FPFH_MMAX:
-        raise ValueError("fpfh: M must be in 1..%d, got %d" % (ops.FPFH_MMAX, keypoints.shape[2]))
+        raise ValueError("%s: M must be in 1..%d, got %d" % (tag, ops.FPFH_MMAX, keypoints.shape[2]))
     return keypoints.contiguous(), None if kp_count is None else kp_count.to(torch.int32).contiguous()
+
+
+def _channels_first(rows, kp_members, want_f64, *more):
+    """a descriptor's f64 [B,M,W] rows -> (desc f32 [B,W,M], the layout the learned descriptor has, kp_members[, rows, *more]);
+    tensors or numpy arrays"""
+    if isinstance(rows, torch.Tensor):
+        desc = rows.to(torch.float32).transpose(1, 2).contiguous()
+    else:
+        desc = np.ascontiguousarray(rows.astype(np.float32).transpose(0, 2, 1))
+    return (desc, kp_members, rows) + more if want_f64 else (desc, kp_members)
 
 
 def fpfh_spfh(pc, count=None, radius: float = 2.0, normals=None, normal_radius: float = 1.0, min_neighbors: int = 3,
@@ -181,11 +194,10 @@ def fpfh_spfh(pc, count=None, radius: float = 2.0, normals=None, normal_radius: 
     (spfh i32 [B,N,33], members i32 [B,N], normals f64 [B,3,N][, tiles_visited i32 [B,ceil(N/256)]]): the integer counts of
     the three 11-bin pair-feature histograms of every point over its members within `radius`.  radius 2 and normal_radius 1
     (outdoor metres) are this project's choice: the reference gives none; indoor callers pass their own."""
-    _check_fpfh(radius, normal_radius, min_neighbors)
+    _check_radii(radius, normal_radius, min_neighbors, "fpfh")
     pc, count = _frames(pc, count)
     perm = sort_along_x(pc, count) if perm is None else perm
-    nrm = ops.harris_normals(pc, count, perm, normal_radius, min_neighbors)[0] if normals is None else \
-        _supplied(normals, pc, "fpfh")
+    nrm = _normals_for(pc, count, perm, normals, normal_radius, min_neighbors, "fpfh")
     out = ops.fpfh_spfh(pc, count, perm, nrm, radius, want_visits)
     return out[:2] + (nrm,) + out[2:]
 
@@ -196,14 +208,13 @@ def fpfh_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2
     [B,33,M], kp_members i32 [B,M][, fpfh f64 [B,M,33]]): Fast Point Feature Histograms at the keypoints, the layout the learned
     descriptor has (channels first).  The f32 descriptor is the cast of the f64 result.  One sort, no host synchronisation.
     radius 2 and normal_radius 1 are this project's choice (fpfh_spfh)."""
-    _check_fpfh(radius, normal_radius, min_neighbors)
+    _check_radii(radius, normal_radius, min_neighbors, "fpfh")
     pc, count = _frames(pc, count)
-    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc, "fpfh")
     perm = sort_along_x(pc, count)
     spfh, members, _ = fpfh_spfh(pc, count, radius, normals, normal_radius, min_neighbors, perm)
     fpfh, kp_members = ops.fpfh_gather(pc, count, perm, spfh, members, keypoints, kp_count, radius)
-    desc = fpfh.to(torch.float32).transpose(1, 2).contiguous()
-    return (desc, kp_members, fpfh) if want_f64 else (desc, kp_members)
+    return _channels_first(fpfh, kp_members, want_f64)
 
 
 # ------------------------------------------------------------------------------------------------ SHOT (DESIGN 8p)
@@ -211,9 +222,9 @@ def shot_frames(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, p
     """pc f32 [B,3,N], keypoints f32 [B,3,M] (any positions), count, kp_count i32 [B] or None -> (lrf f64 [B,M,9], lrf_members
     i32 [B,M]): the rows x, y, z of every keypoint's local reference frame over the live points within `radius`; zeros where
     there is none (fewer than 5 members)."""
-    _check_fpfh(radius, 1.0, 1)
+    _check_radii(radius, 1.0, 1, "shot")
     pc, count = _frames(pc, count)
-    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc, "shot")
     perm = sort_along_x(pc, count) if perm is None else perm
     return ops.shot_lrf(pc, count, perm, keypoints, kp_count, radius)
 
@@ -225,23 +236,21 @@ def shot_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2
     f64 [B,M,352], hist i64 [B,M,352], lrf f64 [B,M,9], lrf_members i32 [B,M]]): SHOT-352 at the keypoints, the layout the
     learned descriptor has (channels first).  The f32 descriptor is the cast of the f64 result.  One sort, no host
     synchronisation.  radius 2 and normal_radius 1 (outdoor metres) are this project's choice: the reference gives none."""
-    _check_fpfh(radius, normal_radius, min_neighbors)
+    _check_radii(radius, normal_radius, min_neighbors, "shot")
     pc, count = _frames(pc, count)
-    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc, "shot")
     perm = sort_along_x(pc, count)
-    nrm = ops.harris_normals(pc, count, perm, normal_radius, min_neighbors)[0] if normals is None else \
-        _supplied(normals, pc, "shot")
+    nrm = _normals_for(pc, count, perm, normals, normal_radius, min_neighbors, "shot")
     lrf, lrf_members = ops.shot_lrf(pc, count, perm, keypoints, kp_count, radius)
     hist, shot, kp_members = ops.shot_hist(pc, count, perm, nrm, keypoints, kp_count, lrf, radius)
-    desc = shot.to(torch.float32).transpose(1, 2).contiguous()
-    return (desc, kp_members, shot, hist, lrf, lrf_members) if want_f64 else (desc, kp_members)
+    return _channels_first(shot, kp_members, want_f64, hist, lrf, lrf_members)
 
 
 # ------------------------------------------------------------------------------------------------ spin images (DESIGN 8q)
 def _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure):
-    _check_fpfh(radius, normal_radius, min_neighbors)
+    _check_radii(radius, normal_radius, min_neighbors, "spin")
     if axis_radius is not None:
-        _check_fpfh(axis_radius, 1.0, 1)
+        _check_radii(axis_radius, 1.0, 1, "spin")
     if not 0.0 <= float(support_angle_cos) <= 1.0:
         raise ValueError("spin: support_angle_cos must be in [0, 1], got %r" % (support_angle_cos,))
     if structure not in ops.SPIN_STRUCTURES:
@@ -262,12 +271,11 @@ def spin_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2
     the cast of the f64 result.  One sort, no host synchronisation.  The radii (outdoor metres) are this project's choice."""
     _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure)
     pc, count = _frames(pc, count)
-    keypoints, kp_count = _keypoints(keypoints, kp_count, pc)
+    keypoints, kp_count = _keypoints(keypoints, kp_count, pc, "spin")
     perm = sort_along_x(pc, count)
     nrm = None
     if float(support_angle_cos) > 0.0:
-        nrm = ops.harris_normals(pc, count, perm, normal_radius, min_neighbors)[0] if normals is None else \
-            _supplied(normals, pc, "spin")
+        nrm = _normals_for(pc, count, perm, normals, normal_radius, min_neighbors, "spin")
     lrf_members = None
     if axes is None:
         lrf, lrf_members = ops.shot_lrf(pc, count, perm, keypoints, kp_count, radius if axis_radius is None else axis_radius)
@@ -278,8 +286,7 @@ def spin_descriptors(pc, keypoints, count=None, kp_count=None, radius: float = 2
     else:
         axes = axes.contiguous()
     hist, spin, kp_members = ops.spin_image(pc, count, perm, nrm, keypoints, kp_count, axes, radius, support_angle_cos, structure)
-    desc = spin.to(torch.float32).transpose(1, 2).contiguous()
-    return (desc, kp_members, spin, hist, axes, lrf_members) if want_f64 else (desc, kp_members)
+    return _channels_first(spin, kp_members, want_f64, hist, axes, lrf_members)
 
 
 # ------------------------------------------------------------------------------------------------ SIFT3D
@@ -533,58 +540,55 @@ class SiftDetector:
         return select_candidates(pc, count, self.last[0], self.last[1], self.num, self.ensure, self.seed, frame_ids)
 
 
-class FpfhDescriptor:
+class _Descriptor:
+    """A descriptor (dim, describe) with its parameters bundled, called where the learned descriptor is"""
+
+    def __init__(self, **params):
+        self.params = params
+        self.last = None
+
+    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
+        self.last = type(self).describe(pc, keypoints, count, kp_count, normals=normals, **self.params)
+        return self.last[0]
+
+
+class FpfhDescriptor(_Descriptor):
     """FPFH with its parameters bundled, called where the learned descriptor is: __call__(pc, keypoints, count, kp_count,
     normals) -> desc f32 [B,33,M]; .last holds (desc, kp_members) of the latest call.  normals f32 [B,3,N]: supplied ones (the
     cloud's sn[:, :3]) instead of estimated ones."""
 
-    dim = 33
+    dim, describe = 33, staticmethod(fpfh_descriptors)
 
     def __init__(self, radius: float = 2.0, normal_radius: float = 1.0, min_neighbors: int = 3):
-        _check_fpfh(radius, normal_radius, min_neighbors)
-        self.params = dict(radius=float(radius), normal_radius=float(normal_radius), min_neighbors=int(min_neighbors))
-        self.last = None
-
-    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
-        self.last = fpfh_descriptors(pc, keypoints, count, kp_count, normals=normals, **self.params)
-        return self.last[0]
+        _check_radii(radius, normal_radius, min_neighbors, "fpfh")
+        super().__init__(radius=float(radius), normal_radius=float(normal_radius), min_neighbors=int(min_neighbors))
 
 
-class ShotDescriptor:
+class ShotDescriptor(_Descriptor):
     """SHOT-352 with its parameters bundled, called where the learned descriptor is: __call__(pc, keypoints, count, kp_count,
     normals) -> desc f32 [B,352,M]; .last holds (desc, kp_members) of the latest call.  normals f32 [B,3,N]: supplied ones (the
     cloud's sn[:, :3]) instead of estimated ones."""
 
-    dim = 352
+    dim, describe = 352, staticmethod(shot_descriptors)
 
     def __init__(self, radius: float = 2.0, normal_radius: float = 1.0, min_neighbors: int = 3):
-        _check_fpfh(radius, normal_radius, min_neighbors)
-        self.params = dict(radius=float(radius), normal_radius=float(normal_radius), min_neighbors=int(min_neighbors))
-        self.last = None
-
-    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
-        self.last = shot_descriptors(pc, keypoints, count, kp_count, normals=normals, **self.params)
-        return self.last[0]
+        _check_radii(radius, normal_radius, min_neighbors, "shot")
+        super().__init__(radius=float(radius), normal_radius=float(normal_radius), min_neighbors=int(min_neighbors))
 
 
-class SpinDescriptor:
+class SpinDescriptor(_Descriptor):
     """Spin images with their parameters bundled, called where the learned descriptor is: __call__(pc, keypoints, count,
     kp_count, normals) -> desc f32 [B,153,M]; .last holds (desc, kp_members) of the latest call.  normals f32 [B,3,N]: supplied
     ones (the cloud's sn[:, :3]) instead of estimated ones, read only with a support angle."""
 
-    dim = 153
+    dim, describe = 153, staticmethod(spin_descriptors)
 
     def __init__(self, radius: float = 2.0, axis_radius=None, support_angle_cos: float = 0.0, normal_radius: float = 1.0,
                  min_neighbors: int = 3, structure: str = "rectangular"):
         _check_spin(radius, axis_radius, support_angle_cos, normal_radius, min_neighbors, structure)
-        self.params = dict(radius=float(radius), axis_radius=None if axis_radius is None else float(axis_radius),
-                           support_angle_cos=float(support_angle_cos), normal_radius=float(normal_radius),
-                           min_neighbors=int(min_neighbors), structure=structure)
-        self.last = None
-
-    def __call__(self, pc, keypoints, count=None, kp_count=None, normals=None) -> torch.Tensor:
-        self.last = spin_descriptors(pc, keypoints, count, kp_count, normals=normals, **self.params)
-        return self.last[0]
+        super().__init__(radius=float(radius), axis_radius=None if axis_radius is None else float(axis_radius),
+                         support_angle_cos=float(support_angle_cos), normal_radius=float(normal_radius),
+                         min_neighbors=int(min_neighbors), structure=structure)
 
 
 # ------------------------------------------------------------------------------------------------ host twins (numpy)
@@ -600,6 +604,26 @@ def _frames_np(pc, count):
     if c is not None and c.shape != (a.shape[0],):
         raise ValueError("count must be i32 [B]")
     return a, c
+
+
+def _normals_for_np(a, c, normals, radius, min_neighbors, num_threads, tag):
+    """_normals_for on numpy arrays: estimated by harris_normals_cpu, or the supplied f32 [B,3,N] cast to float64"""
+    if normals is None:
+        return harris_normals_cpu(a, c, radius, min_neighbors, num_threads)[0]
+    nrm = np.asarray(normals)
+    if nrm.dtype != np.float32 or nrm.shape != a.shape:
+        raise ValueError("%s: supplied normals must be f32 %s" % (tag, a.shape))
+    return np.ascontiguousarray(nrm, dtype=np.float64)
+
+
+def _keypoints_np(keypoints, kp_count, B, tag):
+    kp = np.ascontiguousarray(keypoints, dtype=np.float32)
+    if kp.ndim != 3 or kp.shape[:2] != (B, 3):
+        raise ValueError("%s: expected keypoints f32 [B,3,M], got %s" % (tag, kp.shape))
+    kc = None if kp_count is None else np.ascontiguousarray(kp_count, dtype=np.int32)
+    if kc is not None and kc.shape != (B,):
+        raise ValueError("%s: kp_count must be i32 [B]" % tag)
+    return kp, kc
 
 
 def iss_saliency_cpu(pc, count=None, salient_radius: float = 2.0, gamma_21: float = 0.975, gamma_32: float = 0.975,
@@ -641,13 +665,7 @@ def harris_response_cpu(pc, count=None, radius: float = 1.0, normals=None, respo
     _check_harris(radius, 0.0, response, min_neighbors)
     a, c = _frames_np(pc, count)
     B, _, N = a.shape
-    if normals is None:
-        nrm = harris_normals_cpu(a, c, radius, min_neighbors, num_threads)[0]
-    else:
-        nrm = np.asarray(normals)
-        if nrm.dtype != np.float32 or nrm.shape != a.shape:
-            raise ValueError("harris: supplied normals must be f32 %s" % (a.shape,))
-        nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    nrm = _normals_for_np(a, c, normals, radius, min_neighbors, num_threads, "harris")
     res, members = np.zeros((B, N), np.float64), np.zeros((B, N), np.int32)
     _lib.check(_lib.lib().usip_harris_response_f32_cpu(_p(a), _p(c), _p(nrm), B, N, float(radius),
                                                        ops.HARRIS_METHODS[response], _p(res), _p(members), int(num_threads)),
@@ -672,16 +690,10 @@ def harris_keypoints_cpu(pc, count=None, radius: float = 1.0, threshold: float =
 def fpfh_spfh_cpu(pc, count=None, radius: float = 2.0, normals=None, normal_radius: float = 1.0, min_neighbors: int = 3,
                   num_threads: int = 1):
     """-> (spfh i32 [B,N,33], members i32 [B,N], normals f64 [B,3,N])"""
-    _check_fpfh(radius, normal_radius, min_neighbors)
+    _check_radii(radius, normal_radius, min_neighbors, "fpfh")
     a, c = _frames_np(pc, count)
     B, _, N = a.shape
-    if normals is None:
-        nrm = harris_normals_cpu(a, c, normal_radius, min_neighbors, num_threads)[0]
-    else:
-        nrm = np.asarray(normals)
-        if nrm.dtype != np.float32 or nrm.shape != a.shape:
-            raise ValueError("fpfh: supplied normals must be f32 %s" % (a.shape,))
-        nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    nrm = _normals_for_np(a, c, normals, normal_radius, min_neighbors, num_threads, "fpfh")
     spfh, members = np.zeros((B, N, ops.FPFH_WIDTH), np.int32), np.zeros((B, N), np.int32)
     _lib.check(_lib.lib().usip_fpfh_spfh_f32_cpu(_p(a), _p(c), _p(nrm), B, N, float(radius), _p(spfh), _p(members),
                                                  int(num_threads)), "usip_fpfh_spfh_f32_cpu")
@@ -692,14 +704,11 @@ def fpfh_gather_cpu(pc, count, spfh, members, keypoints, kp_count, radius: float
     """-> (fpfh f64 [B,M,33], kp_members i32 [B,M])"""
     a, c = _frames_np(pc, count)
     B, _, N = a.shape
-    kp = np.ascontiguousarray(keypoints, dtype=np.float32)
-    if kp.ndim != 3 or kp.shape[:2] != (B, 3):
-        raise ValueError("fpfh: expected keypoints f32 [B,3,M], got %s" % (kp.shape,))
+    kp, kc = _keypoints_np(keypoints, kp_count, B, "fpfh")
     M = kp.shape[2]
-    kc = None if kp_count is None else np.ascontiguousarray(kp_count, dtype=np.int32)
     s, m = np.ascontiguousarray(spfh, dtype=np.int32), np.ascontiguousarray(members, dtype=np.int32)
-    if s.shape != (B, N, ops.FPFH_WIDTH) or m.shape != (B, N) or (kc is not None and kc.shape != (B,)):
-        raise ValueError("fpfh: expected spfh i32 [B,N,33], members i32 [B,N] and kp_count i32 [B]")
+    if s.shape != (B, N, ops.FPFH_WIDTH) or m.shape != (B, N):
+        raise ValueError("fpfh: expected spfh i32 [B,N,33] and members i32 [B,N]")
     fpfh, kp_members = np.zeros((B, max(M, 1), ops.FPFH_WIDTH), np.float64), np.zeros((B, max(M, 1)), np.int32)
     _lib.check(_lib.lib().usip_fpfh_gather_f32_cpu(_p(a), _p(c), _p(s), _p(m), _p(kp), _p(kc), B, N, M, float(radius),
                                                    _p(fpfh), _p(kp_members), int(num_threads)), "usip_fpfh_gather_f32_cpu")
@@ -711,25 +720,14 @@ def fpfh_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float
     """-> (desc f32 [B,33,M], kp_members i32 [B,M][, fpfh f64 [B,M,33]])"""
     spfh, members, _ = fpfh_spfh_cpu(pc, count, radius, normals, normal_radius, min_neighbors, num_threads)
     fpfh, kp_members = fpfh_gather_cpu(pc, count, spfh, members, keypoints, kp_count, radius, num_threads)
-    desc = np.ascontiguousarray(fpfh.astype(np.float32).transpose(0, 2, 1))
-    return (desc, kp_members, fpfh) if want_f64 else (desc, kp_members)
-
-
-def _keypoints_np(keypoints, kp_count, B):
-    kp = np.ascontiguousarray(keypoints, dtype=np.float32)
-    if kp.ndim != 3 or kp.shape[:2] != (B, 3):
-        raise ValueError("shot: expected keypoints f32 [B,3,M], got %s" % (kp.shape,))
-    kc = None if kp_count is None else np.ascontiguousarray(kp_count, dtype=np.int32)
-    if kc is not None and kc.shape != (B,):
-        raise ValueError("shot: kp_count must be i32 [B]")
-    return kp, kc
+    return _channels_first(fpfh, kp_members, want_f64)
 
 
 def shot_frames_cpu(pc, keypoints, count=None, kp_count=None, radius: float = 2.0, num_threads: int = 1):
     """-> (lrf f64 [B,M,9], lrf_members i32 [B,M])"""
     a, c = _frames_np(pc, count)
     B, _, N = a.shape
-    kp, kc = _keypoints_np(keypoints, kp_count, B)
+    kp, kc = _keypoints_np(keypoints, kp_count, B, "shot")
     M = kp.shape[2]
     lrf, members = np.zeros((B, max(M, 1), 9), np.float64), np.zeros((B, max(M, 1)), np.int32)
     _lib.check(_lib.lib().usip_shot_lrf_f32_cpu(_p(a), _p(c), _p(kp), _p(kc), B, N, M, float(radius), _p(lrf), _p(members),
@@ -741,7 +739,7 @@ def shot_hist_cpu(pc, count, normals, keypoints, kp_count, lrf, radius: float, n
     """normals f64 [B,3,N], lrf f64 [B,M,9] -> (hist i64 [B,M,352], shot f64 [B,M,352], kp_members i32 [B,M])"""
     a, c = _frames_np(pc, count)
     B, _, N = a.shape
-    kp, kc = _keypoints_np(keypoints, kp_count, B)
+    kp, kc = _keypoints_np(keypoints, kp_count, B, "shot")
     M = kp.shape[2]
     nrm, frames = np.ascontiguousarray(normals, dtype=np.float64), np.ascontiguousarray(lrf, dtype=np.float64)
     if nrm.shape != a.shape or frames.shape != (B, M, 9):
@@ -757,19 +755,12 @@ def shot_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float
                          normal_radius: float = 1.0, want_f64: bool = False, min_neighbors: int = 3, num_threads: int = 1):
     """-> (desc f32 [B,352,M], kp_members i32 [B,M][, shot f64 [B,M,352], hist i64 [B,M,352], lrf f64 [B,M,9], lrf_members i32
     [B,M]])"""
-    _check_fpfh(radius, normal_radius, min_neighbors)
+    _check_radii(radius, normal_radius, min_neighbors, "shot")
     a, c = _frames_np(pc, count)
-    if normals is None:
-        nrm = harris_normals_cpu(a, c, normal_radius, min_neighbors, num_threads)[0]
-    else:
-        nrm = np.asarray(normals)
-        if nrm.dtype != np.float32 or nrm.shape != a.shape:
-            raise ValueError("shot: supplied normals must be f32 %s" % (a.shape,))
-        nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+    nrm = _normals_for_np(a, c, normals, normal_radius, min_neighbors, num_threads, "shot")
     lrf, lrf_members = shot_frames_cpu(a, keypoints, c, kp_count, radius, num_threads)
     hist, shot, kp_members = shot_hist_cpu(a, c, nrm, keypoints, kp_count, lrf, radius, num_threads)
-    desc = np.ascontiguousarray(shot.astype(np.float32).transpose(0, 2, 1))
-    return (desc, kp_members, shot, hist, lrf, lrf_members) if want_f64 else (desc, kp_members)
+    return _channels_first(shot, kp_members, want_f64, hist, lrf, lrf_members)
 
 
 def shot_angle_cpu(y, x):
@@ -787,7 +778,7 @@ def spin_image_cpu(pc, count, normals, keypoints, kp_count, axes, radius: float,
     """normals f64 [B,3,N] or None, axes f64 [B,M,3] -> (hist i64 [B,M,153], spin f64 [B,M,153], kp_members i32 [B,M])"""
     a, c = _frames_np(pc, count)
     B, _, N = a.shape
-    kp, kc = _keypoints_np(keypoints, kp_count, B)
+    kp, kc = _keypoints_np(keypoints, kp_count, B, "spin")
     M = kp.shape[2]
     nrm = None if normals is None else np.ascontiguousarray(normals, dtype=np.float64)
     ax = np.ascontiguousarray(axes, dtype=np.float64)
@@ -812,13 +803,7 @@ def spin_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float
     a, c = _frames_np(pc, count)
     nrm = None
     if float(support_angle_cos) > 0.0:
-        if normals is None:
-            nrm = harris_normals_cpu(a, c, normal_radius, min_neighbors, num_threads)[0]
-        else:
-            nrm = np.asarray(normals)
-            if nrm.dtype != np.float32 or nrm.shape != a.shape:
-                raise ValueError("spin: supplied normals must be f32 %s" % (a.shape,))
-            nrm = np.ascontiguousarray(nrm, dtype=np.float64)
+        nrm = _normals_for_np(a, c, normals, normal_radius, min_neighbors, num_threads, "spin")
     lrf_members = None
     if axes is None:
         lrf, lrf_members = shot_frames_cpu(a, keypoints, c, kp_count, radius if axis_radius is None else axis_radius,
@@ -826,9 +811,7 @@ def spin_descriptors_cpu(pc, keypoints, count=None, kp_count=None, radius: float
         axes = np.ascontiguousarray(lrf[:, :, 6:9])
     hist, spin, kp_members = spin_image_cpu(a, c, nrm, keypoints, kp_count, axes, radius, support_angle_cos, structure,
                                             num_threads)
-    desc = np.ascontiguousarray(spin.astype(np.float32).transpose(0, 2, 1))
-    return (desc, kp_members, spin, hist, np.ascontiguousarray(axes, dtype=np.float64), lrf_members) if want_f64 else \
-        (desc, kp_members)
+    return _channels_first(spin, kp_members, want_f64, hist, np.ascontiguousarray(axes, dtype=np.float64), lrf_members)
 
 
 def sift_exp_cpu(x):

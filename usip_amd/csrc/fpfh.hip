@@ -13,23 +13,20 @@
 //                        (normals) + 33 * 256 * 4 (histograms) = 54 272 bytes.  Counts are integers: the walk's order cannot
 //                        move them.  spfh i32 [B][N][33] and members i32 [B][N] at ORIGINAL indices, every row written whole
 //                        by its lane.  A query without a normal walks nothing and gets zeros.
-//   fpfh_gather_kernel   grid = (ceil(M / 4), B), 256 lanes: one wave per keypoint.  The wave finds [lo, hi), the sorted
-//                        positions with |x - q_x| < r, by two binary searches (wave-uniform): a row before lo has fl(q_x - x)
-//                        >= r and a row from hi on has fl(x - q_x) >= r, so dx of sqdist has |dx| >= r and d2 >= fl(dx dx) >=
-//                        fl(r r) = r2 (float64 rounding is monotone): no member, and the result is the all-pairs answer.
-//                        Lane l tests rows lo + l + 64 k, ascending; a member's 33-int row and count are read and added to
-//                        33 float64 sums in registers (static indices); the lanes fold by the xor-butterfly 32 .. 1, lane
-//                        0 normalises and writes fpfh f64 [B][M][33] and kp_members i32 [B][M].
+//   fpfh_gather_kernel   one wave per keypoint over csrc/keypoint_walk.h (its window, its walk and its exactness argument): a
+//                        member's 33-int row and count are read and added to 33 float64 sums in registers (static indices);
+//                        the lanes fold by the xor-butterfly 32 .. 1, lane 0 normalises and writes fpfh f64 [B][M][33] and
+//                        kp_members i32 [B][M].
 // Slots beyond count[b] / kp_count[b] get zeros.
-#include "ascending_walk.h"
-#include "fpfh_math.h"
+#include "keypoint_walk.h"
 
 using namespace usip_fpfh;
 using usip_ascend::ascend;
 using usip_ascend::Frame;
 using usip_iss::bad_frames;
 using usip_iss::bad_radius;
-using usip_iss::live_points;
+using usip_keypoint::Keypoint;
+using usip_keypoint::Window;
 
 namespace {
 
@@ -114,36 +111,22 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(4))) void 
     const int32_t* __restrict__ kp_count, int N, int M, double r, double r2, double* __restrict__ fpfh,
     int32_t* __restrict__ kp_members)
 {
-    const int f = blockIdx.y, lane = threadIdx.x & (LANES - 1);
-    const int q = blockIdx.x * (TILE / LANES) + (threadIdx.x >> 6);    // the wave's keypoint
-    if (q >= M) return;                                                // wave-uniform
-    const Frame F(pc, count, perm, N, f);
-    const int32_t* rows = spfh + (long long)WIDTH * f * N;
-    const int32_t* mem = members + (long long)f * N;
+    const Frame F(pc, count, perm, N, blockIdx.y);
+    const Keypoint K(F, keypoints, kp_count, M);
+    if (!K.there) return;                                              // wave-uniform
+    const int32_t* rows = spfh + (long long)WIDTH * K.f * N;
+    const int32_t* mem = members + (long long)K.f * N;
     double acc[WIDTH];
 #pragma unroll
     for (int b = 0; b < WIDTH; ++b) acc[b] = 0.0;
     int32_t k = 0;
-    if (q < live_points(kp_count, f, M) && F.n > 0) {                  // wave-uniform (an empty frame has no row to read)
-        const float* kp = keypoints + 3LL * f * M;
-        const double qx = (double)kp[q], qy = (double)kp[M + q], qz = (double)kp[2LL * M + q];
-        const auto xs = [&](int s) { return F.xs(s); };
-        const int lo = first_within(F.n, qx, r, xs);
-        int hi = lo, end = F.n;                                        // the first position from lo on with x - q_x >= r
-        while (hi < end) {
-            const int mid = (hi + end) >> 1;
-            if (xs(mid) - qx >= r) end = mid; else hi = mid + 1;
+    usip_keypoint::walk(F, Window(F, K, r), K, [&](int j, float, float, float, double d2) {
+        const int32_t mj = mem[j];
+        if (gathers(d2, r2, mj)) {
+            add_row(acc, rows + (long long)WIDTH * j, mj, d2);
+            ++k;
         }
-        for (int s = lo + lane; s < hi; s += LANES) {
-            const int j = F.at(s);
-            const double d2 = usip_prep::sqdist(qx, qy, qz, F.x[j], F.y[j], F.z[j]);
-            const int32_t mj = mem[j];
-            if (gathers(d2, r2, mj)) {
-                add_row(acc, rows + (long long)WIDTH * j, mj, d2);
-                ++k;
-            }
-        }
-    }
+    });
 #pragma unroll 1                                                       // (unrolled, six steps' exchanges in flight spill)
     for (int off = LANES / 2; off >= 1; off >>= 1) {
 #pragma unroll
@@ -154,8 +137,8 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(4))) void 
         }
         k += __shfl_xor(k, off, LANES);
     }
-    if (lane != 0) return;
-    double* out = fpfh + (long long)WIDTH * ((long long)f * M + q);
+    if (K.lane != 0) return;
+    double* out = fpfh + WIDTH * K.slot(M);
     const auto put = [&](int h) {                                      // (a block leaves before the next is scaled)
 #pragma unroll
         for (int b = h * BINS; b < h * BINS + BINS; ++b) out[b] = acc[b];
@@ -167,7 +150,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(4))) void 
     put(1);
     normalise<2>(acc);
     put(2);
-    kp_members[(long long)f * M + q] = k;
+    kp_members[K.slot(M)] = k;
 }
 
 }  // namespace

@@ -2178,14 +2178,9 @@ def fpfh_gather(pc, count, perm, spfh, members, keypoints, kp_count, radius: flo
     SPFH rows of the cloud points within the radius of each keypoint, weighted by 1 / squared distance, each block of eleven
     scaled to the sum 100."""
     B, N = _need_frames(pc, count, perm, "fpfh")
-    _need(keypoints, "keypoints", torch.float32)
-    if keypoints.dim() != 3 or keypoints.shape[0] != B or keypoints.shape[1] != 3 or keypoints.device != pc.device \
-            or not 1 <= keypoints.shape[2] <= FPFH_MMAX:
-        raise RuntimeError("fpfh: expected keypoints f32 [B,3,M] on %s with M in 1..%d" % (pc.device, FPFH_MMAX))
-    M = keypoints.shape[2]
+    M = _need_keypoints(pc, keypoints, kp_count, "fpfh")
     _need_on(spfh, "spfh", torch.int32, (B, N, FPFH_WIDTH), pc.device)
     _need_on(members, "members", torch.int32, (B, N), pc.device)
-    _need_on(kp_count, "kp_count", torch.int32, (B,), pc.device)
     if spfh is None or members is None or not float(radius) > 0.0:
         raise RuntimeError("fpfh: spfh and members are required and radius must be positive")
     fpfh = torch.empty((B, M, FPFH_WIDTH), dtype=torch.float64, device=pc.device)
@@ -2209,6 +2204,13 @@ def _need_keypoints(pc, keypoints, kp_count, tag):
         raise RuntimeError("%s: expected keypoints f32 [B,3,M] on %s with M in 1..%d" % (tag, pc.device, FPFH_MMAX))
     _need_on(kp_count, "kp_count", torch.int32, (pc.shape[0],), pc.device)
     return keypoints.shape[2]
+
+
+def _histogram_rows(B, M, width, device):
+    """(hist i64, desc f64, both [B,M,width], kp_members i32 [B,M]) for a histogram kernel to fill"""
+    return (torch.empty((B, M, width), dtype=torch.int64, device=device),
+            torch.empty((B, M, width), dtype=torch.float64, device=device),
+            torch.empty((B, M), dtype=torch.int32, device=device))
 
 
 def shot_lrf(pc, count, perm, keypoints, kp_count, radius: float):
@@ -2238,9 +2240,7 @@ def shot_hist(pc, count, perm, normals, keypoints, kp_count, lrf, radius: float)
     _need_on(lrf, "lrf", torch.float64, (B, M, 9), pc.device)
     if normals is None or lrf is None or not float(radius) > 0.0:
         raise RuntimeError("shot: normals and lrf are required and radius must be positive")
-    hist = torch.empty((B, M, SHOT_WIDTH), dtype=torch.int64, device=pc.device)
-    shot = torch.empty((B, M, SHOT_WIDTH), dtype=torch.float64, device=pc.device)
-    kp_members = torch.empty((B, M), dtype=torch.int32, device=pc.device)
+    hist, shot, kp_members = _histogram_rows(B, M, SHOT_WIDTH, pc.device)
     with torch.cuda.device(pc.device), prof.kernel("shot_hist", 40.0 * B * N + (16.0 * SHOT_WIDTH + 88.0) * B * M, keyed=True):
         _lib.check(_lib.lib().usip_shot_hist_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _ptr(normals), _ptr(keypoints),
                                                  _opt_ptr(kp_count), _ptr(lrf), B, N, M, float(radius), _ptr(hist), _ptr(shot),
@@ -2269,9 +2269,7 @@ def spin_image(pc, count, perm, normals, keypoints, kp_count, axes, radius: floa
                            "required with a support angle")
     if structure not in SPIN_STRUCTURES:
         raise RuntimeError("spin: structure must be one of %s, got %r" % (sorted(SPIN_STRUCTURES), structure))
-    hist = torch.empty((B, M, SPIN_WIDTH), dtype=torch.int64, device=pc.device)
-    spin = torch.empty((B, M, SPIN_WIDTH), dtype=torch.float64, device=pc.device)
-    kp_members = torch.empty((B, M), dtype=torch.int32, device=pc.device)
+    hist, spin, kp_members = _histogram_rows(B, M, SPIN_WIDTH, pc.device)
     with torch.cuda.device(pc.device), prof.kernel("spin_image", (16.0 if s == 0.0 else 40.0) * B * N
                                                    + (16.0 * SPIN_WIDTH + 40.0) * B * M, keyed=True):
         _lib.check(_lib.lib().usip_spin_image_f32(_ptr(pc), _opt_ptr(count), _opt_ptr(perm), _opt_ptr(normals), _ptr(keypoints),
