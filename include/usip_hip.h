@@ -1661,6 +1661,27 @@ int usip_cgf_loss_backward_f32_cpu(const float* anc_desc, const float* pos_desc,
                                    const double* dist, const double* coef, const float* grad_loss, int B, int M, int C,
                                    float* d_anc, float* d_pos, int num_threads);
 
+/* ------------------------------------------------------------------ f-25  the indoor head's last line: unit columns
+ * out = x / (|x| + eps), the norm over the channels (models/networks.py:477), and its backward, one launch each.
+ * csrc/unit_math.h is the arithmetic.  x, out, grad, dx f32 [B][C][M]; norm f32 [B][M]; every buffer contiguous.
+ *
+ * usip_unit_columns_f32: per position (b, m): s = sum_c (double)x_c * (double)x_c in ascending c from 0; n = (float)sqrt(s),
+ * stored in norm; t = n + eps in float32; out_c = x_c / t in float32.
+ * usip_unit_columns_backward_f32: norm is the forward's; dot = sum_c (double)grad_c * (double)x_c in ascending c; t = n + eps in
+ * float32; in float64, dx_c = (float)(grad_c / t - (x_c * dot) / ((n * t) * t)), and (float)(grad_c / t) where n == 0 (torch's
+ * zero sub-gradient of the norm).
+ * NaN and Inf propagate with no special case, inside their own column.  One lane per position walks the channels, so no sum
+ * depends on the launch geometry; one-dimensional grid, with a loop beyond 65536 workgroups of 64.
+ * B * M == 0 returns USIP_OK and launches nothing (C == 0 with positions writes norm = 0).  USIP_EINVAL: a negative B, C or
+ * M, an eps that is negative or NaN, a NULL pointer. */
+int usip_unit_columns_f32(const float* x, int B, int C, int M, float eps, float* out, float* norm, void* stream);
+int usip_unit_columns_backward_f32(const float* grad, const float* x, const float* norm, int B, int C, int M, float eps, float* dx,
+                                   void* stream);
+/* HOST twins (every pointer on the host): the same arithmetic in the same order; num_threads splits the positions. */
+int usip_unit_columns_f32_cpu(const float* x, int B, int C, int M, float eps, float* out, float* norm, int num_threads);
+int usip_unit_columns_backward_f32_cpu(const float* grad, const float* x, const float* norm, int B, int C, int M, float eps,
+                                       float* dx, int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

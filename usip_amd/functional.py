@@ -1319,3 +1319,30 @@ def cgf_triplet(anc_kp, anc_desc, pos_kp, pos_desc, anc_sigma, radius: float, ga
         step = int(step.item())
     return _CgfTriplet.apply(anc_kp, anc_desc, pos_kp, pos_desc, anc_sigma, float(radius), float(gamma), float(sigma_max), draws,
                              int(seed), step, int(elem_base), int(num_threads))
+
+
+# --------------------------------------------------------------------------- the indoor head's unit normalisation (f-25)
+class _UnitColumns(torch.autograd.Function):
+    """x / (|x| + eps) over the channels of x [B,C,M] (models/networks.py:477) as one launch each way (csrc/unit_columns.hip)
+    instead of norm, add, divide and their backward chain.  Host tensors go to the host twin."""
+
+    @staticmethod
+    def forward(ctx, x, eps, num_threads):
+        x = x.contiguous()
+        out, norm = ops.unit_columns(x, eps) if x.is_cuda else ops.unit_columns_cpu(x, eps, num_threads)
+        ctx.save_for_backward(x, norm)
+        ctx.eps, ctx.num_threads = eps, num_threads
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, norm = ctx.saved_tensors
+        grad = grad.contiguous()
+        if x.is_cuda:
+            return ops.unit_columns_backward(grad, x, norm, ctx.eps), None, None
+        return ops.unit_columns_backward_cpu(grad, x, norm, ctx.eps, ctx.num_threads), None, None
+
+
+def unit_columns(x, eps: float = 1e-5, num_threads: int = 1):
+    """x f32 [B,C,M] -> x / (torch.norm(x, dim=1, keepdim=True) + eps), the norm taken in float64."""
+    return _UnitColumns.apply(x, float(eps), int(num_threads))

@@ -14,7 +14,7 @@ from . import functional as Fh
 from . import ops
 from torch.nn.modules.batchnorm import _BatchNorm
 
-from .layers import EquivariantLayer, GeneralKNNFusionModule, MyConv2d, PointNet, pooled_concat_layer
+from .layers import EquivariantLayer, GeneralKNNFusionModule, MyConv2d, PointNet, is_generic, pooled_concat_layer
 
 
 def _bn_kw(opt):
@@ -187,20 +187,13 @@ class RPN_Detector_KNN(RPN_Detector_Ball):
         return ops.knn_points(node, x, self.ball_k), "nn_idx"                              # :576-581 fused
 
 
-class DescriptorLiteOld(nn.Module):
-    """Descriptor head (SURVEY 8 f-1; models/networks.py:310-385): ball grouping around the detected
-    keypoints (radius opt.ball_radius, opt.ball_nsamples samples) -> conv1..3 -> max over K -> conv4 on
-    cat(features, max) -> conv5 (plain conv) -> max over K -> L2 normalisation.
-    forward(x Bx3xN, sn BxCsxN, keypoints Bx3xM) -> (descriptor BxCxM, x_features Bx(3+Cs)xMxK).
+class _DescriptorTrunk(nn.Module):
+    """conv1..conv5 around the keypoints' balls, shared by the two descriptor heads (models/networks.py:310-331 and :388-409
+    build the same five layers; :343-382 and :432-469 run the same lines)."""
 
-    The reference permutes the points with np.random.permutation on every call (networks.py:345-347)
-    because ball_query keeps the FIRST K points inside the ball; set `fixed_permutation` (int64 array or
-    tensor of length N) to make a call reproducible."""
-
-    def __init__(self, opt):
-        super().__init__()
+    def _build_trunk(self, opt):
         self.opt = opt
-        d = int(opt.descriptor_len)
+        d = int(opt.descriptor_len)                      # the indoor options declare it a float
         kw = dict(kernel_size=(1, 1), stride=1, padding=0, bias=True, activation=opt.activation,
                   normalization=opt.normalization, **_bn_kw(opt))
         self.conv1 = MyConv2d(3 + opt.surface_normal_len, d // 4, **kw)
@@ -210,11 +203,13 @@ class DescriptorLiteOld(nn.Module):
         self.conv5 = MyConv2d(d, d, kernel_size=(1, 1), stride=1, padding=0, bias=True,
                               activation=None, normalization=None)
         self.fixed_permutation = None
+        return d
 
-    def forward(self, x, sn, keypoints, is_train=False, epoch=None, perm=None):
-        """perm (optional, int64 [N], any device): the point permutation of networks.py:345-347; default: the
+    def _trunk(self, x, sn, keypoints, perm):
+        """-> (max over K of conv5's output BxCxM, x_features Bx(3+Cs)xMxK); sets last_indices.
+        perm (optional, int64 [N], any device): the point permutation of networks.py:345-347; default: the
         module's fixed_permutation (tests) or a fresh numpy permutation as in the reference."""
-        Fh.require_device(x, "DescriptorLiteOld")
+        Fh.require_device(x, type(self).__name__)
         import numpy as np
         N, K = x.shape[2], int(self.opt.ball_nsamples)
         if perm is None:
@@ -230,9 +225,80 @@ class DescriptorLiteOld(nn.Module):
         h = pooled_concat_layer(self.conv4, h, pooled, False)                                  # :375-377
         y = self.conv5(h)                                                                      # plain conv
         descriptor = Fh.group_max(y)                                                           # :379
-        descriptor = descriptor / (torch.norm(descriptor, dim=1, keepdim=True) + 1e-5)         # :380
         self.last_indices = dict(ball_idx=ball_idx32)
         return descriptor, x_features
+
+
+class DescriptorLiteOld(_DescriptorTrunk):
+    """Descriptor head (SURVEY 8 f-1; models/networks.py:310-385): ball grouping around the detected
+    keypoints (radius opt.ball_radius, opt.ball_nsamples samples) -> conv1..3 -> max over K -> conv4 on
+    cat(features, max) -> conv5 (plain conv) -> max over K -> L2 normalisation.
+    forward(x Bx3xN, sn BxCsxN, keypoints Bx3xM) -> (descriptor BxCxM, x_features Bx(3+Cs)xMxK).
+
+    The reference permutes the points with np.random.permutation on every call (networks.py:345-347)
+    because ball_query keeps the FIRST K points inside the ball; set `fixed_permutation` (int64 array or
+    tensor of length N) to make a call reproducible."""
+
+    def __init__(self, opt):
+        super().__init__()
+        self._build_trunk(opt)
+
+    def forward(self, x, sn, keypoints, is_train=False, epoch=None, perm=None):
+        descriptor, x_features = self._trunk(x, sn, keypoints, perm)
+        descriptor = descriptor / (torch.norm(descriptor, dim=1, keepdim=True) + 1e-5)         # :380
+        return descriptor, x_features
+
+
+class DescriptorLiteOldGlobal(_DescriptorTrunk):
+    """The indoor descriptor head (models/networks.py:388-479, what ModelDescriptorIndoor builds): the trunk
+    of DescriptorLiteOld, then the global context of PPFNet -- the max over the M keypoints of a scan, concatenated back
+    onto every keypoint's descriptor -- three EquivariantLayers fc1..fc3 and the unit normalisation.
+    forward(x Bx3xN, sn BxCsxN, keypoints Bx3xM) -> (descriptor BxCxM, x_features Bx(3+Cs)xMxK); state_dict keys as the
+    reference's (conv1..conv5, fc1..fc3).  The ball query is the one the reference's commented operations.ball_query_wrapper
+    states (models/operations.py:293-367): DescriptorLiteOld's.
+
+    The max over the keypoints is a pool over one neighbourhood of M samples per cloud, [B,C,1,M], and takes the pooling
+    kernel functional._group_path(M) names; fc1 takes descriptor and global feature apart (W.[d; g] = W_d.d + (W_g.g)[b],
+    layers.pooled_concat_layer) wherever that path is not "fallback", the literal concat elsewhere, in evaluation mode and
+    for a generic layer; in training mode both halves are centred on their batch means first (see forward).  The
+    normalisation is csrc/unit_columns.hip: one launch each way."""
+
+    def __init__(self, opt):
+        super().__init__()
+        d = self._build_trunk(opt)
+        kw = dict(activation=opt.activation, normalization=opt.normalization, **_bn_kw(opt))
+        self.fc1 = EquivariantLayer(2 * d, 2 * d, **kw)                                        # :412-420
+        self.fc2 = EquivariantLayer(2 * d, d, **kw)
+        self.fc3 = EquivariantLayer(d, d, activation=None, normalization=None)
+
+    def forward(self, x, sn, keypoints, is_train=False, epoch=None, perm=None):
+        descriptor, x_features = self._trunk(x, sn, keypoints, perm)
+        B, C, M = descriptor.shape
+        d4 = descriptor.view(B, C, 1, M)
+        g = Fh.group_max(d4)                                                                   # :472  [B,C,1]
+        if is_generic(self.fc1):                                                               # :473, :475 (no epoch)
+            h = self.fc1(torch.cat((descriptor, g.expand(B, C, M)), dim=1))
+        else:
+            bn = getattr(self.fc1, "norm", None)
+            centred = isinstance(bn, _BatchNorm) and bn.training and torch.is_grad_enabled()
+            if centred:
+                # fc1's input has a large common part -- the global half is one column per cloud -- and the layer's batch
+                # statistics are E[y^2] - E[y]^2 in float32.  BatchNorm cancels a constant per output channel, so both halves
+                # are centred on their batch means first (the same output; running_mean takes the constant back below)
+                dbar = descriptor.detach().mean(dim=(0, 2), keepdim=True)                      # [1,C,1]
+                gbar = g.detach().mean(dim=0, keepdim=True)                                    # [1,C,1]
+                d4, g = (descriptor - dbar).view(B, C, 1, M), g - gbar
+            h = pooled_concat_layer(self.fc1, d4, g, False)
+            if centred and bn.running_mean is not None:
+                with torch.no_grad():
+                    w = self.fc1.conv.weight.reshape(self.fc1.conv.weight.shape[0], 2 * C)
+                    bn.running_mean.add_(torch.mv(w, torch.cat((dbar, gbar), dim=1).reshape(2 * C)), alpha=float(bn.momentum))
+            if isinstance(h, Fh.LazyAct):                                                      # [B,2C,1,M] -> [B,2C,M]
+                h = Fh.LazyAct(h.y.view(B, -1, M), h.coef, h.relu, (B, h.shape[1], M))
+            else:
+                h = h.reshape(B, -1, M)
+        h = self.fc3(self.fc2(h, defer=True))
+        return Fh.unit_columns(h, 1e-5), x_features                                            # :477
 
 
 class DetectorOptions:
@@ -260,6 +326,27 @@ class DetectorOptions:
         self.ball_nsamples = 64
         self.triple_loss_gamma = 0.5
         self.sigma_max = 3.0
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class IndoorOptions(DetectorOptions):
+    """DetectorOptions with the values of the reference's indoor descriptor training (scenenn/options_descriptor.py):
+    5000 points, 512 keypoints, balls of radius 0.75 with 448 samples, 128 channels, CGF radius 0.075."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.input_pc_num = 5000
+        self.node_num = 512
+        self.ball_radius = 0.75
+        self.ball_nsamples = 448
+        self.descriptor_len = 128
+        self.CGF_radius = 0.075
+        self.triple_loss_gamma = 0.3
+        self.sigma_max = 0.5
+        self.surface_normal_len = 4
+        self.lr = 0.001
+        self.batch_size = 2
         for k, v in kw.items():
             setattr(self, k, v)
 

@@ -2861,3 +2861,83 @@ def cgf_loss_backward_cpu(anc_desc, pos_desc, sel, take_far, dist, coef, grad_lo
                                                          _ptr(coef), _ptr(grad_loss), B, M, C, _ptr(d_anc), _ptr(d_pos),
                                                          int(num_threads)), "usip_cgf_loss_backward_f32_cpu")
     return d_anc, d_pos
+
+
+# --------------------------------------------------------------------------- f-25: the indoor head's unit normalisation
+def _unit_shapes(x, host: bool, others=()):
+    """x f32 [B,C,M] (and same-shaped others) -> (B, C, M)"""
+    need = _need_host if host else _need
+    need(x, "x", torch.float32)
+    if x.dim() != 3:
+        raise RuntimeError("unit_columns: expected x f32 [B,C,M]")
+    for t, name in others:
+        need(t, name, torch.float32)
+        if t.shape != x.shape or t.device != x.device:
+            raise RuntimeError("unit_columns: %s must be f32 %s on %s" % (name, tuple(x.shape), x.device))
+    return tuple(int(v) for v in x.shape)
+
+
+def _unit_eps(eps) -> float:
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise RuntimeError("unit_columns: eps must be >= 0")
+    return eps
+
+
+def _unit_norm(norm, B: int, M: int, device, host: bool):
+    (_need_host if host else _need)(norm, "norm", torch.float32)
+    if tuple(norm.shape) != (B, M) or norm.device != device:
+        raise RuntimeError("unit_columns: norm must be f32 %s on %s" % ((B, M), device))
+
+
+def unit_columns(x, eps: float = 1e-5):
+    """f-25: x f32 [B,C,M] -> (x / (|x| + eps) f32 [B,C,M], |x| f32 [B,M]), the norm over the channels in float64."""
+    B, C, M = _unit_shapes(x, False)
+    eps = _unit_eps(eps)
+    out = torch.empty_like(x)
+    norm = torch.empty((B, M), dtype=torch.float32, device=x.device)
+    if x.numel() == 0:                               # no storage to point at: nothing to normalise, the norm of nothing is 0
+        return out, norm.zero_()
+    with torch.cuda.device(x.device), prof.kernel("unit_columns", 8.0 * B * C * M + 4.0 * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_unit_columns_f32(_ptr(x), B, C, M, eps, _ptr(out), _ptr(norm), _stream(x)),
+                   "usip_unit_columns_f32")
+    return out, norm
+
+
+def unit_columns_backward(grad, x, norm, eps: float = 1e-5):
+    """f-25: grad f32 [B,C,M] (the gradient of unit_columns' first output), x and norm as the forward had them -> dx f32 [B,C,M]"""
+    B, C, M = _unit_shapes(x, False, ((grad, "grad"),))
+    _unit_norm(norm, B, M, x.device, False)
+    eps = _unit_eps(eps)
+    dx = torch.empty_like(x)
+    if x.numel() == 0:
+        return dx
+    with torch.cuda.device(x.device), prof.kernel("unit_columns_backward", 12.0 * B * C * M + 4.0 * B * M, keyed=True):
+        _lib.check(_lib.lib().usip_unit_columns_backward_f32(_ptr(grad), _ptr(x), _ptr(norm), B, C, M, eps, _ptr(dx), _stream(x)),
+                   "usip_unit_columns_backward_f32")
+    return dx
+
+
+def unit_columns_cpu(x, eps: float = 1e-5, num_threads: int = 1):
+    """Host twin of unit_columns: HOST tensors."""
+    B, C, M = _unit_shapes(x, True)
+    eps = _unit_eps(eps)
+    out, norm = torch.zeros_like(x), torch.zeros((B, M), dtype=torch.float32)
+    if x.numel() == 0:
+        return out, norm
+    _lib.check(_lib.lib().usip_unit_columns_f32_cpu(_ptr(x), B, C, M, eps, _ptr(out), _ptr(norm), int(num_threads)),
+               "usip_unit_columns_f32_cpu")
+    return out, norm
+
+
+def unit_columns_backward_cpu(grad, x, norm, eps: float = 1e-5, num_threads: int = 1):
+    """Host twin of unit_columns_backward: HOST tensors."""
+    B, C, M = _unit_shapes(x, True, ((grad, "grad"),))
+    _unit_norm(norm, B, M, x.device, True)
+    eps = _unit_eps(eps)
+    dx = torch.zeros_like(x)
+    if x.numel() == 0:
+        return dx
+    _lib.check(_lib.lib().usip_unit_columns_backward_f32_cpu(_ptr(grad), _ptr(x), _ptr(norm), B, C, M, eps, _ptr(dx),
+                                                             int(num_threads)), "usip_unit_columns_backward_f32_cpu")
+    return dx

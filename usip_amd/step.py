@@ -662,6 +662,64 @@ class DescriptorStep(_GraphedStep):
         return loss
 
 
+class IndoorDescriptorStep(_GraphedStep):
+    """ModelDescriptorIndoor.optimize / test_model (models/keypoint_descriptor.py:425-489): siamese forward of the head with
+    the global context on cat(anchor, positive), the anchor keypoints moved into the positive's frame, the CGF triplet loss,
+    backward (+ all-reduce) (+ Adam).
+
+    batch: anc_pc, pos_pc [B,3,N]; anc_sn, pos_sn [B,Cs,N]; anc_kp, pos_kp [B,3,M]; anc_sigmas [B,M]; anc_R_pos [B,3,3],
+    anc_scale_pos [B,1], anc_shift_pos [B,3,1]; optional perm (int64 [N], DescriptorStep's) and draws (dict u1, u2 f32
+    [B,M,M], u3 f32 [B,M]: recorded uniforms, tests only -- such a step is not captured).  Without draws the loss's
+    counter-based generator reads a device step word that the loss increments in-stream, so a replayed graph draws anew.
+    The reference's random point dropout (:427-435) is not implemented: an opt.random_pc_dropout_lower_limit below 0.99
+    (the indoor default is 1) raises."""
+
+    def __init__(self, opt, device, with_optimizer: bool = False, graph: bool = False, seed: int = 0):
+        from .losses import DescCGFLoss
+        from .networks import DescriptorLiteOldGlobal
+        if getattr(opt, "random_pc_dropout_lower_limit", 1.0) < 0.99:
+            raise NotImplementedError("usip_amd: IndoorDescriptorStep does not implement random_pc_dropout_lower_limit < 0.99 "
+                                      "(models/keypoint_descriptor.py:427-435); the indoor options leave it at 1")
+        self.descriptor = DescriptorLiteOldGlobal(opt).to(torch.device(device))
+        self.triplet_criteria = DescCGFLoss(opt, seed=seed)
+        self._setup(self.descriptor, opt, device, with_optimizer, graph)
+
+    def _prepare(self, batch):
+        if "draws" in batch:
+            self._replay_this_call = False                    # a dict of recorded uniforms: plain launches
+        if "perm" in batch:
+            return batch
+        import numpy as np
+        perm = self.descriptor.fixed_permutation
+        if perm is None:
+            perm = np.random.permutation(batch["anc_pc"].shape[2])
+        return dict(batch, perm=torch.as_tensor(perm, dtype=torch.int64).to(self.device))
+
+    def forward_losses(self, batch: Dict[str, torch.Tensor], epoch: Optional[int] = None, train: bool = True):
+        """train=False: test_model -- the module in evaluation mode, the same loss, nothing to differentiate through BatchNorm."""
+        B = batch["anc_pc"].shape[0]
+        self.descriptor.train(train)
+        self.triplet_criteria.train(train)
+        desc, x_feat = self.descriptor(torch.cat((batch["anc_pc"], batch["pos_pc"]), 0),
+                                       torch.cat((batch["anc_sn"], batch["pos_sn"]), 0),
+                                       torch.cat((batch["anc_kp"], batch["pos_kp"]), 0), train, epoch,
+                                       perm=batch.get("perm"))                      # forward_siamese :413-423
+        anc, pos = torch.split(desc, B, dim=0)
+        anc_kp_t = Fh.rigid_transform(batch["anc_kp"], batch["anc_R_pos"], batch["anc_scale_pos"],
+                                      batch["anc_shift_pos"])                          # :448-450
+        triplet, active = self.triplet_criteria(anc_kp_t, anc, batch["pos_kp"], pos, batch["anc_sigmas"],
+                                                draws=batch.get("draws"))              # :456-459
+        loss = torch.mean(triplet)                                                     # :460-463
+        self.last = dict(descriptors=desc, x_features=x_feat, triplet=triplet, active=active,
+                         active_percentage=torch.mean(active), loss=loss)
+        return loss
+
+    def test_model(self, batch: Dict[str, torch.Tensor]):
+        """ModelDescriptorIndoor.test_model (:469-489) -> the loss; `last` as after a step."""
+        with torch.no_grad():
+            return self.forward_losses(self._prepare(batch), None, train=False)
+
+
 def batch_to_device(batch_np: Dict, device) -> Dict[str, torch.Tensor]:
     return {k: torch.as_tensor(v).to(device) for k, v in batch_np.items()}
 

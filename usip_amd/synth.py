@@ -72,6 +72,43 @@ def make_pair_batch(seed: int, pairs: int, n: int, m: int, cs: int, kind: str = 
     return {k: np.ascontiguousarray(np.stack(v), dtype=np.float32) for k, v in out.items()}
 
 
+def make_indoor_pair_batch(seed: int, pairs: int, n: int, m: int, cs: int, kind: str = "slab:1.5", jitter: float = 0.005
+                           ) -> Dict[str, np.ndarray]:
+    """One indoor descriptor batch (usip_amd.step.IndoorDescriptorStep): `pairs` (anchor, positive) pairs.  The positive is
+    the anchor cloud under a known rigid motion (a rotation of at most 0.5 rad about a random axis, a shift U(-0.2,0.2)^3)
+    with `jitter` of uniform noise per coordinate, its points shuffled; keypoints are a subset of the points -- the
+    positive's are the moved anchor keypoints' own points, shuffled, so most anchors have a match within a few jitters --
+    and the sigmas are U(0.05, 0.8).  anc_R_pos, anc_scale_pos (ones), anc_shift_pos take the anchor into the positive's frame."""
+    rng = np.random.default_rng(seed)
+    out = {k: [] for k in ("anc_pc", "anc_sn", "anc_kp", "anc_sigmas", "pos_pc", "pos_sn", "pos_kp", "anc_R_pos",
+                           "anc_scale_pos", "anc_shift_pos")}
+    for _ in range(pairs):
+        anc = make_cloud(rng, n, kind).astype(np.float64)
+        axis = rng.normal(0, 1, 3)
+        axis /= np.linalg.norm(axis)
+        ang = rng.uniform(0.1, 0.5)
+        Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + math.sin(ang) * Kx + (1 - math.cos(ang)) * (Kx @ Kx)
+        shift = rng.uniform(-0.2, 0.2, (3, 1))
+        moved = R @ anc + shift + rng.uniform(-jitter, jitter, (3, n))
+        order = rng.permutation(n)
+        sn = make_normals(rng, n, cs)
+        sn_pos = sn.copy()
+        sn_pos[:3] = (R @ sn[:3].astype(np.float64)).astype(np.float32)
+        pick = rng.permutation(n)[:m]
+        out["anc_pc"].append(anc)
+        out["pos_pc"].append(moved[:, order])
+        out["anc_sn"].append(sn)
+        out["pos_sn"].append(sn_pos[:, order])
+        out["anc_kp"].append(anc[:, pick])
+        out["pos_kp"].append(moved[:, pick[rng.permutation(m)]])
+        out["anc_sigmas"].append(rng.uniform(0.05, 0.8, m))
+        out["anc_R_pos"].append(R)
+        out["anc_scale_pos"].append(np.ones(1))
+        out["anc_shift_pos"].append(shift)
+    return {k: np.ascontiguousarray(np.stack(v), dtype=np.float32) for k, v in out.items()}
+
+
 def fill_parameters(named_shapes: Dict[str, tuple], head_std: float = 0.05
                     ) -> Dict[str, np.ndarray]:
     """Deterministic non-trivial values for every parameter / BN buffer of a detector:
