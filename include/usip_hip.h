@@ -981,6 +981,10 @@ int usip_desc_pairs_build_f32_cpu(const usip_desc_pairs_recipe* recipe, const us
                                   const usip_desc_pairs_bank* bank, const int32_t* scan_ids, int P, uint64_t seed,
                                   uint64_t step, long long pair_base, const usip_desc_pairs_out* out);
 
+/* ------------------------------------------------------------------ f-26  indoor descriptor batches (SceneNN pairs)
+ * usip_indoor_pairs_recipe, _bank, _draws, _out and the usip_indoor_pairs_* entries: in a header of their own. */
+#include "usip_hip_indoor_pairs.h"
+
 /* ------------------------------------------------------------------ f-9  indoor fragment registration (Redwood / 3DMatch)
  * Replaces the per-pair work of evaluation/matlab/eval_indoor/3dmatch/register2Fragments.m: k-nearest matching in both
  * directions and the union of the two lists, ransacfitRt on up to 10240 correspondences, the information matrix over

@@ -5,7 +5,8 @@ There is no fallback: if the library is missing or fails to load, every operator
 The interface is declared once, in include/usip_hip.h.  This module reads that file when it is imported (read_header):
 SIGNATURES (the argument and result types lib() installs on every entry point), STRUCTS (the ctypes classes of the
 header's structs) and ABI all come from it, so a new entry point or struct field needs its declaration and nothing here.
-A declaration the reader cannot map is an error at import, never a guess.
+A declaration the reader cannot map is an error at import, never a guess.  A header that usip_hip.h includes from its own
+directory (include/usip_hip_indoor_pairs.h) is read the same way into STRUCTS_INCLUDED and SIGNATURES_INCLUDED.
 """
 import ctypes
 import os
@@ -56,13 +57,14 @@ def _declaration(text, structs):
     return out
 
 
-def read_header(text):
+def read_header(text, known=None):
     """C header text -> (STRUCTS: name -> ctypes.Structure class, SIGNATURES: name -> (argtypes, restype)), from every
     `typedef struct ... { ... } name;` and every function declaration, in order.  Anything else but an enum and the
-    extern "C" braces raises, and so does a type that is not in the tables above: nothing is guessed."""
+    extern "C" braces raises, and so does a type that is not in the tables above: nothing is guessed.  known: the structs
+    of the header that includes this one, which its declarations may name; they are not returned again."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M).rstrip()
-    structs, signatures, pos = {}, {}, 0
+    structs, signatures, pos = dict(known or {}), {}, 0
     while pos < len(text):
         m = _DECL.match(text, pos)
         if m is None:
@@ -79,7 +81,7 @@ def read_header(text):
                 signatures[m.group("fn")] = ([t for _, t in params], _ctype(m.group("res"), structs))
             except ValueError as e:
                 raise ValueError("%s in %r" % (e, " ".join(m.group(0).split()))) from None
-    return structs, signatures
+    return {k: v for k, v in structs.items() if k not in (known or {})}, signatures
 
 
 # once per process; ABI = "abi=<n>" of usip_version(), bumped in the header with every incompatible change of it
@@ -87,6 +89,14 @@ with open(HEADER) as _f:
     _text = _f.read()
 ABI = int(re.search(r"^#define USIP_ABI (\d+)$", _text, re.M).group(1))
 STRUCTS, SIGNATURES = read_header(_text)
+# the headers usip_hip.h includes from its own directory (#include "usip_hip_indoor_pairs.h"), read the same way: a part of
+# the interface kept in a file of its own has its structs and signatures here, and lib() installs both
+STRUCTS_INCLUDED, SIGNATURES_INCLUDED = {}, {}
+for _name in re.findall(r'^#include "(\w+\.h)"$', _text, re.M):
+    with open(os.path.join(os.path.dirname(HEADER), _name)) as _f:
+        _st, _sg = read_header(_f.read(), known=dict(STRUCTS, **STRUCTS_INCLUDED))
+    STRUCTS_INCLUDED.update(_st)
+    SIGNATURES_INCLUDED.update(_sg)
 
 
 def lib():
@@ -112,7 +122,7 @@ def lib():
         if len(runtimes) > 1:
             raise RuntimeError("usip_amd: two HIP runtimes are loaded (%s); import torch before anything "
                                "that links libamdhip64" % ", ".join(runtimes))
-        for name, (args, res) in SIGNATURES.items():
+        for name, (args, res) in list(SIGNATURES.items()) + list(SIGNATURES_INCLUDED.items()):
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res

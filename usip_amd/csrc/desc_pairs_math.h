@@ -50,6 +50,12 @@ struct CloudView {
     }
     USIP_HD static int dst(int) { return 0; }
     USIP_HD static bool usable(long long n, int N) { return n >= N; }
+    USIP_HD static void move(int, int, double*) {}
+    USIP_HD static void move_sn(int, int, float*) {}
+    template <class Src>
+    USIP_HD static void node_xyz(const usip_pairs_recipe&, const Src&, int, int, int, int, double*) {}
+    USIP_HD static bool f32_array(int) { return true; }
+    USIP_HD static void post(int, const double*, float*, bool) {}
 };
 
 struct PosedBank {

@@ -138,10 +138,12 @@ USIP_HD void transform3(const double* T, float p[3], bool shift_scale)
 
 // A point (f32_array: the reference holds it in the scan's f32 array) or a node (float64 out of FPS): ENU -> cam,
 // augment (train) with jitter z[3] * sigma clipped, rounded as the reference rounds, then dst's transform.
+template <class Move>
 USIP_HD void finish_xyz(const usip_pairs_recipe& r, const double* T, int cloud, const float in[3], const double z[3],
-                        double sigma, double clp, bool f32_array, float out[3])
+                        double sigma, double clp, bool f32_array, float out[3], const Move& move)
 {
     double p[3] = {in[0], in[1], in[2]};
+    move(p);                                               // the float64 entry: a View's own frame (empty but for IndoorView)
     if (r.enu_to_cam) { const double y = p[1]; p[1] = -p[2]; p[2] = y; }
     if (r.train && f32_array && (int)T[T_NSTAGE] == 0) {
         for (int k = 0; k < 3; ++k) {
@@ -319,6 +321,11 @@ struct ExplicitDraws {
 //   scan(q, p, o0, n)     its scan's first bank row and row count
 //   dst(c)                1 where the cloud takes the table's transform
 //   usable(n, N)          false for a scan the entry points refuse on the host (min_rows)
+//   move(p, c, x)         float64 coordinates out of raw_xyz -> the cloud's own frame (empty but for the indoor builder's
+//   move_sn(p, c, s)      ICP move, csrc/indoor_pairs_math.h; the normals' counterpart, rounded to float32)
+//   node_xyz(...)         a node's float64 coordinates, preset to candidate ci's float32 ones (empty likewise)
+//   f32_array(c)          whether the reference holds the cloud's points in a float32 array when augment begins
+//   post(c, T, x, full)   after finish_xyz / finish_sn, on a point or node (full) or on sn[0:3]: a transform of the View's own
 struct CloudOut {
     float* pc[2];           // [P][3][N] per cloud of the pair
     float* sn[2];           // [P][Cs][N]
@@ -343,6 +350,12 @@ struct PairView {
     }
     USIP_HD static int dst(int c) { return c; }
     USIP_HD static bool usable(long long n, int) { return n >= 1; }
+    USIP_HD static void move(int, int, double*) {}
+    USIP_HD static void move_sn(int, int, float*) {}
+    template <class Src>
+    USIP_HD static void node_xyz(const usip_pairs_recipe&, const Src&, int, int, int, int, double*) {}
+    USIP_HD static bool f32_array(int) { return true; }
+    USIP_HD static void post(int, const double*, float*, bool) {}
 };
 
 // Slot j of cloud q: slot -> scan row through the keyed bijection (or the fix_idx layout), one row load, augment and
@@ -361,7 +374,9 @@ USIP_HD void cloud_point(const usip_pairs_recipe& r, const Src& src, const View&
         const long long crow = src.row(p, c, n, N, src.cand(p, c, N, j));
         float cx[3];
         raw_xyz(T, bank + (o0 + crow) * r.row_len, cx);
-        for (int k = 0; k < 3; ++k) cd[(long long)k * r.n_sub + j] = cx[k];
+        double cm[3] = {cx[0], cx[1], cx[2]};
+        v.move(p, c, cm);
+        for (int k = 0; k < 3; ++k) cd[(long long)k * r.n_sub + j] = (float)cm[k];
     }
     const long long row = src.row(p, c, n, N, j);
     const float* rp = bank + (o0 + row) * r.row_len;
@@ -374,9 +389,12 @@ USIP_HD void cloud_point(const usip_pairs_recipe& r, const Src& src, const View&
         src.jit_pc(p, c, N, j, zp);
         src.jit_sn(p, c, N, r.Cs, j, zs);
     }
+    v.move_sn(p, c, s);
     float o[3];
-    finish_xyz(r, T, v.dst(c), xyz, zp, r.pc_sigma, r.pc_clip, true, o);
+    finish_xyz(r, T, v.dst(c), xyz, zp, r.pc_sigma, r.pc_clip, v.f32_array(c), o, [&](double* x) { v.move(p, c, x); });
     finish_sn(r, T, v.dst(c), s, zs);
+    v.post(c, T, o, true);
+    if (r.Cs >= 3) v.post(c, T, s, false);
     float* pc = out.pc[c] + (long long)p * 3 * N;
     float* sn = out.sn[c] + (long long)p * r.Cs * N;
     for (int k = 0; k < 3; ++k) pc[(long long)k * N + j] = o[k];
@@ -396,7 +414,9 @@ USIP_HD void cloud_node(const usip_pairs_recipe& r, const Src& src, const View& 
     double z[4] = {0, 0, 0, 0};
     if (r.train) src.jit_node(p, c, M, m, z);
     float o[3];
-    finish_xyz(r, T, v.dst(c), xyz, z, r.node_sigma, r.node_clip, false, o);
+    finish_xyz(r, T, v.dst(c), xyz, z, r.node_sigma, r.node_clip, false, o,
+               [&](double* x) { v.node_xyz(r, src, q, p, c, ci, x); });
+    v.post(c, T, o, true);
     float* node = out.node[c] + (long long)p * 3 * M;
     for (int k = 0; k < 3; ++k) node[(long long)k * M + m] = o[k];
     if (out.node_slots) out.node_slots[(long long)q * M + m] = src.cand(p, c, r.N, ci);

@@ -322,7 +322,53 @@ def build_cpu(recipe: DescriptorPairRecipe, scans: Sequence[np.ndarray], poses, 
     return out, rows, nodes
 
 
-class DescriptorTrainer:
+class _FrozenDetectorTrainer:
+    """What DescriptorTrainer and indoor_pairs.IndoorDescriptorTrainer share: the frozen eval-mode detector that gives every
+    built batch its keypoints and sigmas, the descriptor step made under torch.manual_seed(seed), the point permutation
+    drawn ON THE DEVICE from the seed, and the checkpoint gate.  A trainer supplies _make_step and its own batches."""
+
+    def __init__(self, builder, detector_model: str, detector_state, opt, device=None, seed: int = 0, graph: bool = False,
+                 min_save_epoch: int = 0, with_optimizer: bool = True):
+        from . import inference
+        from .networks import build_detector
+        self.builder, self.opt = builder, opt
+        self.device = torch.device(device) if device is not None else builder.device
+        self.detector = build_detector(detector_model, opt).to(self.device)
+        inference.load_detector_state(self.detector, detector_state)
+        for p in self.detector.parameters():                  # freeze_model
+            p.requires_grad = False
+        self.detector.eval()
+        torch.manual_seed(int(seed))
+        self.st = self._make_step(opt, with_optimizer, graph, int(seed))
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+        self.best_loss, self.min_save_epoch = 1e6, int(min_save_epoch)
+        self.last_loss = self.last_active = None
+
+    def _keypoints(self, batch: Dict[str, torch.Tensor]):
+        """run_model_siamese on cat(anchor, positive), and the permutation: (P, keypoints [2P,3,M], sigmas [2P,M], perm)."""
+        from . import inference
+        P, N = batch["anc_pc"].shape[0], batch["anc_pc"].shape[2]
+        kp, sg = inference.run_model(self.detector, torch.cat((batch["anc_pc"], batch["pos_pc"]), 0),
+                                     torch.cat((batch["anc_sn"], batch["pos_sn"]), 0),
+                                     torch.cat((batch["anc_node"], batch["pos_node"]), 0))
+        return P, kp, sg, torch.randperm(N, generator=self._gen, device=self.device)
+
+    def _save_due(self, test_loss: float, epoch: int) -> bool:
+        return test_loss <= self.best_loss + 1e-5 and epoch >= self.min_save_epoch
+
+    def save_if_best(self, path: str, test_loss: float, epoch: int = 0) -> bool:
+        """The checkpoint (descriptor.state_dict(), the reference's keys) is written when the test loss is the best so far
+        and the epoch has reached min_save_epoch (the reference: half an lr_decay_step)."""
+        if test_loss <= self.best_loss:
+            self.best_loss = test_loss
+        if self._save_due(test_loss, epoch):
+            torch.save(self.st.descriptor.state_dict(), path)
+            return True
+        return False
+
+
+class DescriptorTrainer(_FrozenDetectorTrainer):
     """kitti/train_descriptor.py:69-212 on one device: a frozen detector gives the keypoints and sigmas of every built
     batch, DescriptorStep trains on them, a test pass gates the checkpoint.
 
@@ -334,33 +380,17 @@ class DescriptorTrainer:
 
     def __init__(self, builder: DescriptorPairBuilder, detector_model: str, detector_state, opt, device=None,
                  seed: int = 0, graph: bool = False, min_save_epoch: int = 0, with_optimizer: bool = True):
-        from . import inference
-        from .networks import build_detector
-        from .step import DescriptorStep
-        self.builder, self.opt = builder, opt
-        self.device = torch.device(device) if device is not None else builder.device
-        self.detector = build_detector(detector_model, opt).to(self.device)
-        inference.load_detector_state(self.detector, detector_state)
-        for p in self.detector.parameters():                  # freeze_model
-            p.requires_grad = False
-        self.detector.eval()
-        torch.manual_seed(int(seed))
-        self.st = DescriptorStep(opt, self.device, with_optimizer=with_optimizer, graph=graph)
-        self._gen = torch.Generator(device=self.device)
-        self._gen.manual_seed(int(seed))
+        super().__init__(builder, detector_model, detector_state, opt, device, seed, graph, min_save_epoch, with_optimizer)
         self.neg_fail_total = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.best_loss, self.min_save_epoch = 1e6, int(min_save_epoch)
-        self.last_loss = self.last_active = None
+
+    def _make_step(self, opt, with_optimizer, graph, seed):
+        from .step import DescriptorStep
+        return DescriptorStep(opt, self.device, with_optimizer=with_optimizer, graph=graph)
 
     def descriptor_batch(self, batch: Dict[str, torch.Tensor], out: Optional[Dict[str, torch.Tensor]] = None):
         """The builder's batch -> what DescriptorStep consumes; with `out` (DescriptorStep.static_batch) the keypoints,
         sigmas and permutation are written into it."""
-        from . import inference
-        P, N = batch["anc_pc"].shape[0], batch["anc_pc"].shape[2]
-        kp, sg = inference.run_model(self.detector, torch.cat((batch["anc_pc"], batch["pos_pc"]), 0),
-                                     torch.cat((batch["anc_sn"], batch["pos_sn"]), 0),
-                                     torch.cat((batch["anc_node"], batch["pos_node"]), 0))
-        perm = torch.randperm(N, generator=self._gen, device=self.device)
+        P, kp, sg, perm = self._keypoints(batch)
         d = dict(anc_pc=batch["anc_pc"], pos_pc=batch["pos_pc"], anc_sn=batch["anc_sn"], pos_sn=batch["pos_sn"],
                  anc_kp=kp[:P].contiguous(), pos_kp=kp[P:].contiguous(), anc_sigmas=sg[:P].contiguous(),
                  neg_idx=batch["neg_idx"], perm=perm)
@@ -402,13 +432,3 @@ class DescriptorTrainer:
         if count == 0:
             raise ValueError("DescriptorTrainer.test_pass: an empty schedule")
         return float(loss_sum) / count, float(active_sum) / count
-
-    def save_if_best(self, path: str, test_loss: float, epoch: int = 0) -> bool:
-        """train_descriptor.py:205-212: the checkpoint (descriptor.state_dict(), the reference's keys) is written when
-        the test loss is the best so far and the epoch has reached min_save_epoch (the reference: half an lr_decay_step)."""
-        if test_loss <= self.best_loss:
-            self.best_loss = test_loss
-        if test_loss <= self.best_loss + 1e-5 and epoch >= self.min_save_epoch:
-            torch.save(self.st.descriptor.state_dict(), path)
-            return True
-        return False

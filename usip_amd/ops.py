@@ -1722,6 +1722,125 @@ def desc_pairs_workspace_bytes(recipe: DescPairsRecipeC, P: int) -> int:
     return _workspace_query("usip_desc_pairs_workspace_bytes", recipe, P)
 
 
+# ------------------------------------------------------------------------------- f-26 indoor descriptor batches (SceneNN)
+# include/usip_hip_indoor_pairs.h, which usip_hip.h includes: _lib keeps an included header's structs apart
+IndoorPairsRecipeC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_recipe"]
+IndoorPairsBankC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_bank"]
+IndoorPairsDrawsC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_draws"]
+IndoorPairsOutC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_out"]
+
+INDOOR_PAIRS_KEYS = ("anc_pc", "anc_sn", "anc_node", "pos_pc", "pos_sn", "pos_node", "anc_R_pos", "anc_scale_pos",
+                     "anc_shift_pos")
+INDOOR_PAIRS_DRAWS = dict(rows=torch.int32, cand=torch.int32, first=torch.int32, params=torch.float64)
+
+
+def indoor_pairs_shapes(recipe: IndoorPairsRecipeC, P: int) -> dict:
+    """key -> shape of one batch of P pairs (all float32): what IndoorDescriptorStep.step documents."""
+    c = recipe.cloud
+    return dict(anc_pc=(P, 3, c.N), anc_sn=(P, c.Cs, c.N), anc_node=(P, 3, c.M), pos_pc=(P, 3, c.N),
+                pos_sn=(P, c.Cs, c.N), pos_node=(P, 3, c.M), anc_R_pos=(P, 3, 3), anc_scale_pos=(P, 1),
+                anc_shift_pos=(P, 3, 1))
+
+
+def indoor_pairs_out_struct(ptr, out: dict, rows, node_slots) -> IndoorPairsOutC:
+    """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
+    o = _clouds_out(IndoorPairsOutC(), ptr, out, ("anc", "pos"), (), rows, node_slots)
+    o.R, o.scale, o.shift = ptr(out["anc_R_pos"]), ptr(out["anc_scale_pos"]), ptr(out["anc_shift_pos"])
+    return o
+
+
+def indoor_pairs_draws_struct(ptr, draws: dict) -> IndoorPairsDrawsC:
+    d = IndoorPairsDrawsC()
+    for k in INDOOR_PAIRS_DRAWS:
+        if draws.get(k) is not None:
+            setattr(d.cloud, k, ptr(draws[k]))
+    return d
+
+
+def _indoor_pairs_check(recipe: IndoorPairsRecipeC, bank: dict, sample_ids, out: dict, rows, node_slots, workspace):
+    """Every tensor the launch touches on the bank's device, with its dtype and shape.  Returns (P, the bank struct)."""
+    import numpy as np
+    dev = bank["rows"].device
+    for k, dt in (("rows", torch.float32), ("offsets", torch.int64), ("pairs", torch.int32), ("icp", torch.float64),
+                  ("sample_mode", torch.int32)):
+        _need(bank[k], "bank " + k, dt)
+        if bank[k].device != dev:
+            raise RuntimeError("indoor_pairs: bank %s on %s, the rows on %s" % (k, bank[k].device, dev))
+    F, S = bank["offsets"].numel() - 1, bank["pairs"].shape[0]
+    host = bank["pairs_host"]
+    if tuple(bank["pairs"].shape) != (S, 2) or tuple(bank["icp"].shape) != (S, 12) or bank["sample_mode"].numel() != S or \
+            host.dtype != np.int32 or host.shape != (S, 2) or not host.flags.c_contiguous:
+        raise RuntimeError("indoor_pairs: pairs i32 (S, 2), icp f64 (S, 12), sample_mode i32 (S,) on the device and pairs "
+                           "as a C-contiguous int32 numpy array")
+    _need(sample_ids, "sample_ids", torch.int32)
+    P = sample_ids.numel()
+    if sample_ids.device != dev:
+        raise RuntimeError("indoor_pairs: sample_ids on %s, the bank on %s" % (sample_ids.device, dev))
+    for k, shape in indoor_pairs_shapes(recipe, P).items():
+        _need(out[k], k, torch.float32)
+        if tuple(out[k].shape) != shape or out[k].device != dev:
+            raise RuntimeError("indoor_pairs: %s must be f32 %s on %s" % (k, shape, dev))
+    _check_workspace_and_indices("indoor_pairs", recipe.cloud, P, dev, workspace, indoor_pairs_workspace_bytes(recipe, P),
+                                 rows, node_slots)
+    b = IndoorPairsBankC()
+    for k in ("rows", "offsets", "pairs", "icp", "sample_mode"):
+        setattr(b, k, bank[k].data_ptr())
+    b.pairs_host, b.num_frames, b.num_samples, b.min_rows = host.ctypes.data, F, S, int(bank["min_rows"])
+    return P, b
+
+
+def _indoor_pairs_bytes(recipe: IndoorPairsRecipeC, P: int) -> float:
+    c = recipe.cloud
+    return 2.0 * P * c.N * (32 + 4 * (3 + c.Cs))
+
+
+def indoor_pairs_build(recipe: IndoorPairsRecipeC, bank: dict, sample_ids: torch.Tensor, seed: int, step: int,
+                       pair_base: int, out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-26: P indoor descriptor pairs with Philox draws (usip_indoor_pairs_build_f32) into `out` (INDOOR_PAIRS_KEYS).
+    bank: rows, offsets, pairs, icp, sample_mode (device tensors), pairs_host (int32 numpy), min_rows."""
+    P, b = _indoor_pairs_check(recipe, bank, sample_ids, out, rows, node_slots, workspace)
+    o = indoor_pairs_out_struct(_data_ptr, out, rows, node_slots)
+    dev = bank["rows"].device
+    with torch.cuda.device(dev), prof.kernel("indoor_pairs_build", _indoor_pairs_bytes(recipe, P)):
+        _lib.check(_lib.lib().usip_indoor_pairs_build_f32(
+            ctypes.addressof(recipe), ctypes.addressof(b), _ptr(sample_ids), P, int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(step) & 0xFFFFFFFFFFFFFFFF, int(pair_base), ctypes.addressof(o), _ptr(workspace),
+            _stream(bank["rows"])), "usip_indoor_pairs_build_f32")
+    return out
+
+
+def indoor_pairs_apply(recipe: IndoorPairsRecipeC, draws: dict, bank: dict, sample_ids: torch.Tensor, out: dict,
+                       workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-26 with explicit draws (usip_indoor_pairs_apply_f32): INDOOR_PAIRS_DRAWS -> device tensors in f-5's layouts."""
+    P, b = _indoor_pairs_check(recipe, bank, sample_ids, out, rows, node_slots, workspace)
+    dev = bank["rows"].device
+    c = recipe.cloud
+    shapes = dict(rows=(P, 2, c.N), cand=(P, 2, c.n_sub), first=(P, 2), params=(P, 24))
+    for k, dt in INDOOR_PAIRS_DRAWS.items():
+        t = draws.get(k)
+        if t is None:
+            raise RuntimeError("indoor_pairs: draw %s is missing" % k)
+        _need(t, k, dt)
+        if t.device != dev or tuple(t.shape) != shapes[k]:
+            raise RuntimeError("indoor_pairs: draw %s must be %s on %s" % (k, shapes[k], dev))
+    d = indoor_pairs_draws_struct(_data_ptr, draws)
+    o = indoor_pairs_out_struct(_data_ptr, out, rows, node_slots)
+    with torch.cuda.device(dev), prof.kernel("indoor_pairs_apply", _indoor_pairs_bytes(recipe, P)):
+        _lib.check(_lib.lib().usip_indoor_pairs_apply_f32(
+            ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(sample_ids), P, ctypes.addressof(o),
+            _ptr(workspace), _stream(bank["rows"])), "usip_indoor_pairs_apply_f32")
+    return out
+
+
+def indoor_pairs_workspace_offset(recipe: IndoorPairsRecipeC, P: int, part: int) -> int:
+    """Byte offset of workspace part 0 tables, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud frame ids, 5 total."""
+    return _workspace_query("usip_indoor_pairs_workspace_offset", recipe, P, part)
+
+
+def indoor_pairs_workspace_bytes(recipe: IndoorPairsRecipeC, P: int) -> int:
+    return _workspace_query("usip_indoor_pairs_workspace_bytes", recipe, P)
+
+
 # ------------------------------------------------------------------------------------------------ f-6 evaluation
 def _opt_ptr(t):
     return _ptr(t) if t is not None else None

@@ -206,18 +206,26 @@ class _CloudBuilder:
     A builder supplies its library's workspace functions, _check (its refusals), _empty_batch and build."""
 
     _workspace_bytes = _workspace_offset = None              # ops functions of (recipe struct, P[, part])
+    _modes = ("train", "test")
 
     def __init__(self, bank, recipe, pairs: int, device=None, seed: int = 0, rank: int = 0, mode: str = "train"):
-        if mode not in ("train", "test"):
-            raise ValueError("%s: mode is 'train' or 'test'" % type(self).__name__)
+        if mode not in self._modes:
+            raise ValueError("%s: mode is %s" % (type(self).__name__, " or ".join(repr(m) for m in self._modes)))
         self.bank, self.recipe, self.pairs = bank, recipe, int(pairs)
         self.device = torch.device(device) if device is not None else bank.device
         self.seed, self.rank, self.mode = int(seed), int(rank), mode
-        self.c = recipe.c_struct(mode == "train")
+        self.c = self._c_struct()
         self._check()
         self._ws = [torch.empty(self._workspace_bytes(self.c, self.pairs), dtype=torch.uint8, device=self.device)
                     for _ in range(3)]
         self.last_rows = self.last_node_slots = None
+
+    def _c_struct(self):
+        return self.recipe.c_struct(self.mode == "train")
+
+    def _num_ids(self) -> int:
+        """What the ids of a call index: the bank's scans (the indoor builder: its samples)."""
+        return self.bank.num_scans
 
     def _ids(self, scan_ids) -> torch.Tensor:
         if isinstance(scan_ids, torch.Tensor) and scan_ids.is_cuda:
@@ -226,8 +234,8 @@ class _CloudBuilder:
             ids = scan_ids.to(torch.int32).contiguous()
         else:
             h = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
-            if h.size and (h.min() < 0 or h.max() >= self.bank.num_scans):
-                raise ValueError("PairBuilder: scan id out of range [0, %d)" % self.bank.num_scans)
+            if h.size and (h.min() < 0 or h.max() >= self._num_ids()):
+                raise ValueError("PairBuilder: scan id out of range [0, %d)" % self._num_ids())
             ids = torch.from_numpy(h.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
         if ids.numel() != self.pairs:
             raise ValueError("PairBuilder: %d scan ids for %d pairs" % (ids.numel(), self.pairs))
