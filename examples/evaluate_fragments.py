@@ -42,6 +42,17 @@ the random points that pad the count, which no two fragments share, so that run 
 angle and no normals, otherwise normals over 0.125 m or, with --fpfh-normals supplied, the files'; --spin-structure rectangular |
 radial): the `spin` of evaluate.m's descriptorName comment.
 
+--method tsf runs the reference's own pipeline (the `tsf` branch of evaluation/save_keypoints.py:262-351 behind its loaders,
+evaluation/redwood_loader.py and data/match3d_eval_loader.py) on the fragment files alone: --input-pc-num rows of every
+fragment, half of them FPS candidates, --node-num nodes (usip_amd.fragment_batch, built on the device in batches of
+--describe-batch), the eval-mode detector (--detector-model ball | som, --detector-ckpt F), sigma-ordered NMS over --nms-radius
+and the --top smallest sigmas, then the eval-mode descriptor (--descriptor-head global | plain, --descriptor-ckpt F; --dim is
+its length).  Without a checkpoint the module is a seeded, untrained one (a plumbing run) and the JSON line says so.  Fragment
+files with only x y z columns get normals and curvature on the device (9 neighbours, viewpoint at the origin).  No results file
+is read.  --write-keypoints DIR writes DIR/<scene>/<i>.bin, the float32 [count, 3] files eval_rep.m reads.
+--method results --descriptor-ckpt F describes the results files' keypoints by that checkpoint's descriptor instead of taking
+the files' descriptors.
+
 Prints ONE JSON line (what evaluate.m prints, per scene and as means, and the registrator) and writes <results>/<scene>.log as writeLog.m does;
 with --pair-files also the i-j.rt.txt of every pair, as clusterCallback.m does."""
 import argparse
@@ -108,8 +119,65 @@ def add_fpfh_fragment(ev, i, xyz, cloud, args):
     return ev.add_fragment_result(i, kp[0].t(), desc[0].t(), cloud)
 
 
+def make_networks(args):
+    """--method tsf, or --descriptor-ckpt: (detector or None, descriptor, what the JSON line says of them).  A module without a
+    checkpoint is seeded and untrained, as examples/train_descriptor_indoor.py's detector is."""
+    import torch
+    from usip_amd import inference
+    from usip_amd.networks import (DescriptorLiteOld, DescriptorLiteOldGlobal, IndoorDetectorOptions, IndoorOptions,
+                                   build_detector)
+    said, detector = {}, None
+    if args.method == "tsf":
+        torch.manual_seed(args.seed)
+        detector = build_detector(args.detector_model, IndoorDetectorOptions(input_pc_num=args.input_pc_num,
+                                                                             node_num=args.node_num)).to(args.device)
+        if args.detector_ckpt:
+            inference.load_detector_state(detector, torch.load(args.detector_ckpt, map_location="cpu"))
+        said["detector"] = dict(model=args.detector_model, checkpoint=args.detector_ckpt or "untrained (seeded)")
+    torch.manual_seed(args.seed + 1)
+    head = DescriptorLiteOldGlobal if args.descriptor_head == "global" else DescriptorLiteOld
+    descriptor = head(IndoorOptions(input_pc_num=args.input_pc_num, node_num=args.node_num,
+                                    descriptor_len=args.dim)).to(args.device)
+    if args.descriptor_ckpt:
+        inference.load_detector_state(descriptor, torch.load(args.descriptor_ckpt, map_location="cpu"))
+    said["descriptor"] = dict(head=args.descriptor_head, checkpoint=args.descriptor_ckpt or "untrained (seeded)")
+    return detector, descriptor, said
+
+
+def add_described_scene(ev, name, scenes, rows, args):
+    """--method tsf: every fragment of the scene through usip_amd.fragment_batch.FragmentDescriber in batches; with rows (the
+    results files' [xyz, descriptor]) their keypoints are described instead of the detector's."""
+    import torch
+    from usip_amd import fragment_batch as fb
+    from usip_amd.networks import IndoorDetectorOptions
+    bank = fb.FragmentScanBank.from_scene_dir(os.path.join(scenes, name), args.device)
+    recipe = fb.FragmentBatchRecipe.match3d(IndoorDetectorOptions(input_pc_num=args.input_pc_num, node_num=args.node_num))
+    detector, descriptor, said = make_networks(args)
+    describer = fb.FragmentDescriber(detector, descriptor, fb.FragmentBatchBuilder(bank, recipe, seed=args.seed),
+                                     nms_radius=args.nms_radius, top=ev.top)
+    for base in range(0, bank.num_scans, args.describe_batch):
+        ids = list(range(base, min(base + args.describe_batch, bank.num_scans)))
+        if rows is None:
+            out = describer.describe(ids)
+        else:
+            kp = np.zeros((len(ids), 3, ev.top), np.float32)
+            for b, i in enumerate(ids):                       # padded with the fragment's first keypoint, as the detector's are
+                x = np.asarray(rows[i][0], np.float32).T
+                kp[b] = x[:, :1]
+                kp[b, :, :x.shape[1]] = x
+            count = torch.tensor([len(rows[i][0]) for i in ids], dtype=torch.int32)
+            out = describer.describe_keypoints(ids, torch.from_numpy(kp), count)
+        ev.add_described(ids, out["kp"], out["desc"], out["count"], [bank.xyz(i) for i in ids])
+        if args.write_keypoints:
+            fb.write_keypoints_dir(os.path.join(args.write_keypoints, name), ids, out["kp"], out["count"])
+    return said
+
+
 def evaluate_scene(name, scenes, results, gt_root, args):
-    clouds = sorted(glob.glob(os.path.join(scenes, name, "*.npy")), key=lambda p: int(os.path.basename(p)[:-4]))
+    if args.method == "tsf":                                    # <i>.npy or cloud_bin_<i>.npy: usip_amd.fragment_batch reads them
+        clouds = glob.glob(os.path.join(scenes, name, "*.npy"))
+    else:
+        clouds = sorted(glob.glob(os.path.join(scenes, name, "*.npy")), key=lambda p: int(os.path.basename(p)[:-4]))
     if not clouds:
         raise SystemExit("no fragments under %s" % os.path.join(scenes, name))
     rows = None
@@ -122,7 +190,10 @@ def evaluate_scene(name, scenes, results, gt_root, args):
                               log_transform=args.log_transform, optimize=args.optimize,
                               optimize_args=dict(tau2=args.optimize_tau2, fill=args.optimize_fill,
                                                  transform=args.optimize_transform) if args.optimize else None)
-    for i, path in enumerate(clouds):
+    said = None
+    if args.method == "tsf" or args.descriptor_ckpt:
+        said = add_described_scene(ev, name, scenes, rows, args)
+    for i, path in enumerate(clouds if said is None else ()):
         if args.descriptor_method != "learned":
             add_fpfh_fragment(ev, i, rows[i][0] if rows is not None else None, np.load(path), args)
         else:
@@ -146,8 +217,11 @@ def evaluate_scene(name, scenes, results, gt_root, args):
     if args.optimize:
         pg.write_split(results, name, *out["split"])
         pg.write_refined(results, name, out["refined_entries"])
-    return {k: out[k] for k in ("pairs", "written", "recall", "precision", "inlier_num_mean", "inlier_ratio_mean", "good",
-                                "bad", "false_pos", "gt_num", "rs_num") + (LOOP_KEYS if args.optimize else ())}
+    scene = {k: out[k] for k in ("pairs", "written", "recall", "precision", "inlier_num_mean", "inlier_ratio_mean", "good",
+                                  "bad", "false_pos", "gt_num", "rs_num") + (LOOP_KEYS if args.optimize else ())}
+    if said is not None:
+        scene["networks"] = said
+    return scene
 
 
 def main():
@@ -176,7 +250,16 @@ def main():
     ap.add_argument("--pair-files", action="store_true")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--descriptor-method", choices=("learned", "fpfh", "shot", "spin"), default="learned")
-    ap.add_argument("--method", choices=("results", "iss", "harris", "sift", "random"), default="results")
+    ap.add_argument("--method", choices=("results", "iss", "harris", "sift", "random", "tsf"), default="results")
+    ap.add_argument("--detector-ckpt", metavar="F")
+    ap.add_argument("--detector-model", choices=("ball", "som"), default="ball")
+    ap.add_argument("--descriptor-ckpt", metavar="F")
+    ap.add_argument("--descriptor-head", choices=("global", "plain"), default="global")
+    ap.add_argument("--input-pc-num", type=int, default=10240)
+    ap.add_argument("--node-num", type=int, default=512)
+    ap.add_argument("--nms-radius", type=float, default=0.1)
+    ap.add_argument("--describe-batch", type=int, default=8)
+    ap.add_argument("--write-keypoints", metavar="DIR")
     ap.add_argument("--top", type=int, default=512)
     ap.add_argument("--scale", type=float, default=0.05)
     ap.add_argument("--fpfh-radius", type=float, default=0.25)
@@ -190,7 +273,21 @@ def main():
     ap.add_argument("--spin-structure", choices=("rectangular", "radial"), default="rectangular")
     ap.add_argument("--write-descriptors", metavar="DIR")
     args = ap.parse_args()
-    if args.method != "results" and args.descriptor_method == "learned":
+    if args.method == "tsf" and args.descriptor_method != "learned":
+        ap.error("--method tsf describes by the learned descriptor (--descriptor-ckpt), not --descriptor-method %s"
+                 % args.descriptor_method)
+    if args.detector_ckpt and args.method != "tsf":
+        ap.error("--detector-ckpt needs --method tsf")
+    if args.descriptor_ckpt and (args.method not in ("tsf", "results") or args.descriptor_method != "learned"):
+        ap.error("--descriptor-ckpt needs --method tsf or --method results, and --descriptor-method learned")
+    if args.write_keypoints and args.method != "tsf":
+        ap.error("--write-keypoints needs --method tsf")
+    for ckpt in (args.detector_ckpt, args.descriptor_ckpt):
+        if ckpt and not os.path.isfile(ckpt):
+            ap.error("no checkpoint at %s" % ckpt)
+    if args.describe_batch < 1 or args.input_pc_num < 2 or not 1 <= args.node_num <= args.input_pc_num // 2:
+        ap.error("--describe-batch >= 1, --input-pc-num >= 2 and 1 <= --node-num <= --input-pc-num / 2")
+    if args.method not in ("results", "tsf") and args.descriptor_method == "learned":
         ap.error("--method %s needs --descriptor-method fpfh, shot or spin (the results files hold the learned descriptors)"
                  % args.method)
     if args.log_transform == "refined" and args.refine != "icp":
@@ -206,7 +303,7 @@ def main():
         ap.error("give --make-synthetic DIR, or --scenes, --results and --gt")
     per_scene = {n: evaluate_scene(n, scenes, results, gt, args) for n in names}
     out = {"scenes": per_scene, "registration": args.registration}
-    if args.descriptor_method != "learned":
+    if args.descriptor_method != "learned" or args.method == "tsf":
         out.update(descriptor_method=args.descriptor_method, method=args.method)
     if args.refine != "none":
         out.update(refine=args.refine, log_transform=args.log_transform)

@@ -985,6 +985,10 @@ int usip_desc_pairs_build_f32_cpu(const usip_desc_pairs_recipe* recipe, const us
  * usip_indoor_pairs_recipe, _bank, _draws, _out and the usip_indoor_pairs_* entries: in a header of their own. */
 #include "usip_hip_indoor_pairs.h"
 
+/* ------------------------------------------------------------------ f-27  evaluation batches from indoor fragments
+ * usip_fragment_batch_bank, _draws, _out and the usip_fragment_batch_* entries: in a header of their own. */
+#include "usip_hip_fragment_batch.h"
+
 /* ------------------------------------------------------------------ f-9  indoor fragment registration (Redwood / 3DMatch)
  * Replaces the per-pair work of evaluation/matlab/eval_indoor/3dmatch/register2Fragments.m: k-nearest matching in both
  * directions and the union of the two lists, ransacfitRt on up to 10240 correspondences, the information matrix over

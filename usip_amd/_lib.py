@@ -6,7 +6,8 @@ The interface is declared once, in include/usip_hip.h.  This module reads that f
 SIGNATURES (the argument and result types lib() installs on every entry point), STRUCTS (the ctypes classes of the
 header's structs) and ABI all come from it, so a new entry point or struct field needs its declaration and nothing here.
 A declaration the reader cannot map is an error at import, never a guess.  A header that usip_hip.h includes from its own
-directory (include/usip_hip_indoor_pairs.h) is read the same way into STRUCTS_INCLUDED and SIGNATURES_INCLUDED.
+directory is read the same way into INCLUDED[its file name]; include/usip_hip_indoor_pairs.h's pair is also
+STRUCTS_INCLUDED and SIGNATURES_INCLUDED.
 """
 import ctypes
 import os
@@ -91,12 +92,15 @@ ABI = int(re.search(r"^#define USIP_ABI (\d+)$", _text, re.M).group(1))
 STRUCTS, SIGNATURES = read_header(_text)
 # the headers usip_hip.h includes from its own directory (#include "usip_hip_indoor_pairs.h"), read the same way: a part of
 # the interface kept in a file of its own has its structs and signatures here, and lib() installs both
-STRUCTS_INCLUDED, SIGNATURES_INCLUDED = {}, {}
+INCLUDED = {}                                  # header file name -> (its structs, its signatures), in the order of inclusion
 for _name in re.findall(r'^#include "(\w+\.h)"$', _text, re.M):
+    _known = dict(STRUCTS)
+    for _st, _ in INCLUDED.values():
+        _known.update(_st)
     with open(os.path.join(os.path.dirname(HEADER), _name)) as _f:
-        _st, _sg = read_header(_f.read(), known=dict(STRUCTS, **STRUCTS_INCLUDED))
-    STRUCTS_INCLUDED.update(_st)
-    SIGNATURES_INCLUDED.update(_sg)
+        INCLUDED[_name] = read_header(_f.read(), known=_known)
+# the first header that was split off keeps the names its users read it under
+STRUCTS_INCLUDED, SIGNATURES_INCLUDED = INCLUDED.get("usip_hip_indoor_pairs.h", ({}, {}))
 
 
 def lib():
@@ -122,7 +126,7 @@ def lib():
         if len(runtimes) > 1:
             raise RuntimeError("usip_amd: two HIP runtimes are loaded (%s); import torch before anything "
                                "that links libamdhip64" % ", ".join(runtimes))
-        for name, (args, res) in list(SIGNATURES.items()) + list(SIGNATURES_INCLUDED.items()):
+        for name, (args, res) in list(SIGNATURES.items()) + [s for _, sg in INCLUDED.values() for s in sg.items()]:
             fn = getattr(l, name)
             fn.argtypes = args
             fn.restype = res

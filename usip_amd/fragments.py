@@ -787,6 +787,17 @@ class FragmentEvaluator:
         count = torch.tensor(xyz.shape[0], dtype=torch.int32, device=self.device)
         return self._store(fragment_id, xyz.t(), desc.t(), count, cloud)
 
+    def add_described(self, fragment_ids, kp, desc, count, clouds):
+        """A batch described elsewhere (fragment_batch.FragmentDescriber): kp f32 [B,3,M'], desc f32 [B,D,M'], count i32 [B]
+        on the device, clouds: every fragment's full cloud.  Cached as add_fragment caches one; nothing is read back."""
+        ids = [int(i) for i in fragment_ids]
+        if kp.dim() != 3 or desc.dim() != 3 or kp.shape[0] != len(ids) or desc.shape[0] != len(ids) or kp.shape[1] != 3 or \
+                desc.shape[2] != kp.shape[2] or count.numel() != len(ids) or len(clouds) != len(ids):
+            raise ValueError("add_described: expected kp [B,3,M'], desc [B,D,M'], count [B] and B clouds for %d ids" % len(ids))
+        kp, desc = kp.to(self.device, torch.float32), desc.to(self.device, torch.float32)
+        count = torch.clamp(count.to(self.device, torch.int32).reshape(-1), max=kp.shape[2])
+        return [self._store(i, kp[b], desc[b], count[b], clouds[b]) for b, i in enumerate(ids)]
+
     def fragment_arrays(self, fragment_id):
         """(xyz [M',3], desc [M',D]) of a cached fragment on the host: what write_descriptors_bin takes."""
         kp, desc, count, _ = self.fragments[int(fragment_id)]

@@ -351,6 +351,20 @@ class IndoorOptions(DetectorOptions):
             setattr(self, k, v)
 
 
+class IndoorDetectorOptions(IndoorOptions):
+    """IndoorOptions with what the reference's indoor DETECTOR and its evaluation read (match3d/options_detector.py,
+    scenenn/options_detector.py): 10240 points, 512 nodes, 4 sn channels, node_knn_k_1 32."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.input_pc_num = 10240
+        self.node_num = 512
+        self.surface_normal_len = 4
+        self.node_knn_k_1 = 32
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 DETECTORS = {"som": RPN_Detector, "ball": RPN_Detector_Ball, "lite": RPN_DetectorLite, "knn": RPN_Detector_KNN}
 
 

@@ -1841,6 +1841,127 @@ def indoor_pairs_workspace_bytes(recipe: IndoorPairsRecipeC, P: int) -> int:
     return _workspace_query("usip_indoor_pairs_workspace_bytes", recipe, P)
 
 
+# ------------------------------------------------------------------------------- f-27 evaluation batches from fragments
+# include/usip_hip_fragment_batch.h; the recipe is f-5's PairsRecipeC
+_FRAGMENT_BATCH_STRUCTS = _lib.INCLUDED["usip_hip_fragment_batch.h"][0]
+FragmentBatchBankC = _FRAGMENT_BATCH_STRUCTS["usip_fragment_batch_bank"]
+FragmentBatchDrawsC = _FRAGMENT_BATCH_STRUCTS["usip_fragment_batch_draws"]
+FragmentBatchOutC = _FRAGMENT_BATCH_STRUCTS["usip_fragment_batch_out"]
+
+FRAGMENT_BATCH_KEYS = ("pc", "sn", "node")
+FRAGMENT_BATCH_DRAWS = ("rows", "cand", "first")
+
+
+def fragment_batch_clouds(B: int) -> int:
+    """The clouds every buffer of a call of B fragments holds: the cloud stage works in two halves."""
+    return 2 * ((int(B) + 1) // 2)
+
+
+def fragment_batch_shapes(recipe: PairsRecipeC, B: int) -> dict:
+    """key -> shape of the buffers of one call of B fragments (float32): B2 = fragment_batch_clouds(B) clouds each."""
+    B2 = fragment_batch_clouds(B)
+    return dict(pc=(B2, 3, recipe.N), sn=(B2, recipe.Cs, recipe.N), node=(B2, 3, recipe.M))
+
+
+def fragment_batch_out_struct(ptr, out: dict, rows, node_slots) -> FragmentBatchOutC:
+    """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
+    o = FragmentBatchOutC()
+    o.pc, o.sn, o.node = ptr(out["pc"]), ptr(out["sn"]), ptr(out["node"])
+    o.rows = ptr(rows) if rows is not None else None
+    o.node_slots = ptr(node_slots) if node_slots is not None else None
+    return o
+
+
+def _fragment_batch_check(recipe: PairsRecipeC, bank: dict, ids, out: dict, rows, node_slots, workspace):
+    """Every tensor the launch touches on the bank's device, with its dtype and shape.  Returns (B, the bank struct)."""
+    dev = bank["rows"].device
+    for k, dt in (("rows", torch.float32), ("offsets", torch.int64)):
+        _need(bank[k], "bank " + k, dt)
+        if bank[k].device != dev:
+            raise RuntimeError("fragment_batch: bank %s on %s, the rows on %s" % (k, bank[k].device, dev))
+    _need(ids, "ids", torch.int32)
+    B = ids.numel()
+    if ids.device != dev:
+        raise RuntimeError("fragment_batch: ids on %s, the bank on %s" % (ids.device, dev))
+    for k, shape in fragment_batch_shapes(recipe, B).items():
+        _need(out[k], k, torch.float32)
+        if tuple(out[k].shape) != shape or out[k].device != dev:
+            raise RuntimeError("fragment_batch: %s must be f32 %s on %s" % (k, shape, dev))
+    B2 = fragment_batch_clouds(B)
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < fragment_batch_workspace_bytes(recipe, B):
+        raise RuntimeError("fragment_batch: the workspace must hold usip_fragment_batch_workspace_bytes() bytes on %s" % dev)
+    for name, t, n in (("rows", rows, recipe.N), ("node_slots", node_slots, recipe.M)):
+        if t is not None:
+            _need(t, name, torch.int32)
+            if tuple(t.shape) != (B2, n) or t.device != dev:
+                raise RuntimeError("fragment_batch: %s must be i32 (%d, %d) on %s" % (name, B2, n, dev))
+    b = FragmentBatchBankC()
+    b.rows, b.offsets = bank["rows"].data_ptr(), bank["offsets"].data_ptr()
+    b.num_fragments, b.min_rows = bank["offsets"].numel() - 1, int(bank["min_rows"])
+    return B, b
+
+
+def _fragment_batch_bytes(recipe: PairsRecipeC, B: int) -> float:
+    return 1.0 * B * recipe.N * (32 + 4 * (3 + recipe.Cs))
+
+
+def _ids_host_ptr(ids_host, B: int):
+    import numpy as np
+    if ids_host is None:
+        return None
+    if ids_host.dtype != np.int32 or ids_host.size != B or not ids_host.flags.c_contiguous:
+        raise RuntimeError("fragment_batch: ids_host must be a C-contiguous int32 numpy array of the ids")
+    return ids_host.ctypes.data
+
+
+def fragment_batch_build(recipe: PairsRecipeC, bank: dict, ids: torch.Tensor, ids_host, seed: int, step: int, out: dict,
+                         workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-27: B evaluation fragments with Philox draws (usip_fragment_batch_build_f32) into `out` (FRAGMENT_BATCH_KEYS, each
+    holding fragment_batch_clouds(B) clouds).  bank: rows, offsets (device tensors), min_rows; ids_host: the ids as an
+    int32 numpy array (range-checked by the library) or None."""
+    B, b = _fragment_batch_check(recipe, bank, ids, out, rows, node_slots, workspace)
+    o = fragment_batch_out_struct(_data_ptr, out, rows, node_slots)
+    dev = bank["rows"].device
+    with torch.cuda.device(dev), prof.kernel("fragment_batch_build", _fragment_batch_bytes(recipe, B)):
+        _lib.check(_lib.lib().usip_fragment_batch_build_f32(
+            ctypes.addressof(recipe), ctypes.addressof(b), _ptr(ids), _ids_host_ptr(ids_host, B), B,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, ctypes.addressof(o), _ptr(workspace),
+            _stream(bank["rows"])), "usip_fragment_batch_build_f32")
+    return out
+
+
+def fragment_batch_apply(recipe: PairsRecipeC, draws: dict, bank: dict, ids: torch.Tensor, ids_host, out: dict,
+                         workspace: torch.Tensor, rows=None, node_slots=None):
+    """f-27 with explicit draws (usip_fragment_batch_apply_f32): rows i32 (B, N), cand i32 (B, n_sub), first i32 (B,)."""
+    B, b = _fragment_batch_check(recipe, bank, ids, out, rows, node_slots, workspace)
+    dev = bank["rows"].device
+    shapes = dict(rows=(B, recipe.N), cand=(B, recipe.n_sub), first=(B,))
+    d = FragmentBatchDrawsC()
+    for k in FRAGMENT_BATCH_DRAWS:
+        t = draws.get(k)
+        if t is None:
+            raise RuntimeError("fragment_batch: draw %s is missing" % k)
+        _need(t, k, torch.int32)
+        if t.device != dev or tuple(t.shape) != shapes[k]:
+            raise RuntimeError("fragment_batch: draw %s must be %s on %s" % (k, shapes[k], dev))
+        setattr(d, k, t.data_ptr())
+    o = fragment_batch_out_struct(_data_ptr, out, rows, node_slots)
+    with torch.cuda.device(dev), prof.kernel("fragment_batch_apply", _fragment_batch_bytes(recipe, B)):
+        _lib.check(_lib.lib().usip_fragment_batch_apply_f32(
+            ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(ids), _ids_host_ptr(ids_host, B), B,
+            ctypes.addressof(o), _ptr(workspace), _stream(bank["rows"])), "usip_fragment_batch_apply_f32")
+    return out
+
+
+def fragment_batch_workspace_offset(recipe: PairsRecipeC, B: int, part: int) -> int:
+    """Byte offset of workspace part 0 table, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud fragment ids, 5 total."""
+    return _workspace_query("usip_fragment_batch_workspace_offset", recipe, B, part)
+
+
+def fragment_batch_workspace_bytes(recipe: PairsRecipeC, B: int) -> int:
+    return _workspace_query("usip_fragment_batch_workspace_bytes", recipe, B)
+
+
 # ------------------------------------------------------------------------------------------------ f-6 evaluation
 def _opt_ptr(t):
     return _ptr(t) if t is not None else None
