@@ -16,7 +16,6 @@ stream, with no host synchronisation (csrc/desc_pairs.hip):
 Randomness is Philox4x64-10 keyed by the seed, with counter (element, stream, rank * P + p, step) and stream tags of its
 own (no draw is shared with usip_amd.pairs): a pair's clouds and its positive do not depend on the world size.
 """
-import ctypes
 import os
 from dataclasses import dataclass
 from typing import Dict, Iterable, Mapping, Optional, Sequence
@@ -24,8 +23,8 @@ from typing import Dict, Iterable, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
-from .pairs import ScanBank, _CloudBuilder, epoch_batches, epoch_order          # noqa: F401  (re-exported)
+from . import ops
+from .pairs import ScanBank, _CloudBuilder, _empty_batch, epoch_batches, epoch_order, host_twin   # noqa: F401  (re-exported)
 
 KEYS = ops.DESC_PAIRS_KEYS
 
@@ -214,8 +213,7 @@ def synthetic_sequences(num_seq: int = 2, scans: int = 40, rows: int = 20480, sp
 
 def empty_batch(c: ops.DescPairsRecipeC, pairs: int, device) -> Dict[str, torch.Tensor]:
     """Every build writes every float; neg_idx / neg_fail are written only when the recipe mines, so they start at 0."""
-    return {k: (torch.empty if dt == torch.float32 else torch.zeros)(shape, dtype=dt, device=device)
-            for k, (shape, dt) in ops.desc_pairs_shapes(c, pairs).items()}
+    return _empty_batch(ops.DESC_PAIRS, c, pairs, device)
 
 
 class DescriptorPairBuilder(_CloudBuilder):
@@ -231,13 +229,7 @@ class DescriptorPairBuilder(_CloudBuilder):
     prefetch(schedule): double-buffered, batch k+1 built on a side stream while the consumer runs batch k.
     build / apply use one workspace, each prefetch buffer one of its own."""
 
-    _workspace_bytes = staticmethod(ops.desc_pairs_workspace_bytes)
-    _workspace_offset = staticmethod(ops.desc_pairs_workspace_offset)
-
-    def __init__(self, bank: PosedScanBank, recipe: DescriptorPairRecipe, pairs: int, device=None, seed: int = 0,
-                 rank: int = 0, mode: str = "train"):
-        super().__init__(bank, recipe, pairs, device, seed, rank, mode)
-        self._bank = bank.c_dict()
+    spec = ops.DESC_PAIRS
 
     def _check(self):
         if self.bank.min_rows < self.recipe.N:
@@ -246,80 +238,19 @@ class DescriptorPairBuilder(_CloudBuilder):
         if self.recipe.mine and self.pairs < 2:
             raise ValueError("DescriptorPairBuilder: mining negatives needs at least 2 pairs per call")
 
-    def _empty_batch(self):
-        return empty_batch(self.c, self.pairs, self.device)
-
-    def _out(self, out, with_indices):
-        full = self._empty_batch() if out is None or any(k not in out for k in KEYS) else {}
-        if out is not None:
-            full.update({k: out[k] for k in KEYS if k in out})
-        return (full,) + self._index_out(with_indices)
-
-    def build(self, scan_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
-              _ws: int = 0) -> Dict[str, torch.Tensor]:
-        out, rows, nodes = self._out(out, with_indices)
-        ops.desc_pairs_build(self.c, self._bank, self._ids(scan_ids), self.seed, int(step), self.rank * self.pairs, out,
-                             self._ws[_ws], rows, nodes)
-        return out
-
-    def apply(self, scan_ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
-        out, rows, nodes = self._out(out, with_indices)
-        d = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=_DRAW_NP[k])).to(self.device)
-             for k, v in draws.items() if v is not None}
-        ops.desc_pairs_apply(self.c, d, self._bank, self._ids(scan_ids), out, self._ws[0], rows, nodes)
-        return out
-
-    def prefetch(self, schedule: Iterable, outs=None):
-        """schedule: iterable of (scan_ids, step).  The shared prefetch loop drives this builder (the same two
-        buffers, 'built' / 'consumed' events and side stream): the consumer's stream waits for 'built', the side stream
-        for 'consumed', the host never waits, and leaving the loop early (break, an exception, closing the generator)
-        makes the current stream wait for every build still in flight, so reusing `outs` or the memory afterwards is
-        ordered after the last write.  The two buffers allocated here live until the generator is gone, i.e. past that
-        wait, and go back to the current stream's pool.  A yielded batch is valid until the next iteration."""
-        if outs is None:
-            outs = [self._empty_batch() for _ in range(2)]
-        yield from super().prefetch(schedule, outs)
-
-
-_DRAW_NP = {k: (np.int32 if dt == torch.int32 else np.float64) for k, dt in ops.DESC_PAIRS_DRAWS.items()}
-
 
 def build_cpu(recipe: DescriptorPairRecipe, scans: Sequence[np.ndarray], poses, seq, scan_ids, pairs: int, seed: int = 0,
               step: int = 0, rank: int = 0, mode: str = "train", draws: Optional[Dict[str, np.ndarray]] = None):
     """The host twin (usip_desc_pairs_build_f32_cpu) on numpy scans and poses [S, 4, 4]: Philox draws, or `draws` (the
     layouts of include/usip_hip.h).  Returns (batch, rows [2,P,N], node_slots [2,P,M]).  The same refusals as the bank's."""
-    c = recipe.c_struct(mode == "train")
     scans = [np.asarray(s, dtype=np.float32) for s in scans]
-    lengths = [len(s) for s in scans]
-    seq_of, seq_start, _ = sequence_layout(seq, lengths, _names(scans), recipe.N)
-    rows_all = np.ascontiguousarray(np.concatenate(scans))
-    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    seq_of, seq_start, _ = sequence_layout(seq, [len(s) for s in scans], _names(scans), recipe.N)
     poses = np.ascontiguousarray(np.stack([load_pose(p) for p in poses]))
     if poses.shape[0] != len(scans):
         raise ValueError("build_cpu: %d poses for %d scans" % (poses.shape[0], len(scans)))
-    ids = np.ascontiguousarray(np.asarray(scan_ids, dtype=np.int32).reshape(-1))
-    P = int(pairs)
-    if ids.size != P:
-        raise ValueError("build_cpu: %d scan ids for %d pairs" % (ids.size, P))
-    np_dt = {torch.float32: np.float32, torch.int32: np.int32, torch.int64: np.int64}
-    out = {k: np.zeros(shape, dtype=np_dt[dt]) for k, (shape, dt) in ops.desc_pairs_shapes(c, P).items()}
-    rows = np.zeros((2, P, recipe.N), dtype=np.int32)
-    nodes = np.zeros((2, P, recipe.M), dtype=np.int32)
-    ptr = lambda a: a.ctypes.data   # noqa: E731
-    o = ops.desc_pairs_out_struct(ptr, out, rows, nodes)
-    b = ops.DescPairsBankC()
-    b.rows, b.offsets, b.poses, b.seq_of = ptr(rows_all), ptr(offsets), ptr(poses), ptr(seq_of)
-    b.seq_start = b.seq_start_host = ptr(seq_start)
-    b.num_scans, b.num_seq, b.min_rows = len(scans), len(seq_start) - 1, int(min(lengths))
-    d = None
-    if draws is not None:
-        keep = {k: np.ascontiguousarray(v, dtype=_DRAW_NP[k]) for k, v in draws.items() if v is not None}
-        d = ops.desc_pairs_draws_struct(ptr, keep, keep["tries"].shape[1] if "tries" in keep else 0)
-    _lib.check(_lib.lib().usip_desc_pairs_build_f32_cpu(
-        ctypes.addressof(c), ctypes.addressof(d) if d is not None else None, ctypes.addressof(b), ptr(ids), P,
-        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, rank * P, ctypes.addressof(o)),
-        "usip_desc_pairs_build_f32_cpu")
-    return out, rows, nodes
+    return host_twin(ops.DESC_PAIRS, lambda row_len: recipe.c_struct(mode == "train"), scans, "scan", scan_ids, pairs,
+                     bank=dict(poses=poses, seq_of=seq_of, seq_start=seq_start, seq_start_host=seq_start),
+                     counter=(seed, step, rank * int(pairs)), draws=draws)
 
 
 class _FrozenDetectorTrainer:

@@ -25,7 +25,6 @@ Two stated deviations from the reference:
      here every fragment keeps up to `top` of its own, whatever came before it.
 The script's noise_sigma robustness experiment is not here.
 """
-import ctypes
 import os
 import re
 from dataclasses import dataclass
@@ -34,9 +33,9 @@ from typing import Dict, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, inference, ops
+from . import inference, ops
 from .evaluation import select_keypoints_device
-from .pairs import ScanBank, _CloudBuilder
+from .pairs import ScanBank, _CloudBuilder, host_twin
 
 KEYS = ops.FRAGMENT_BATCH_KEYS
 _FILE = re.compile(r"(?:cloud_bin_)?(\d+)\.npy")
@@ -118,9 +117,6 @@ class FragmentScanBank(ScanBank):
     def xyz(self, i: int) -> torch.Tensor:
         return self.rows[int(self.offsets_host[i]):int(self.offsets_host[i + 1]), :3].contiguous()
 
-    def c_dict(self) -> dict:
-        return dict(rows=self.rows, offsets=self.offsets, min_rows=self.min_rows)
-
 
 @dataclass
 class FragmentBatchRecipe:
@@ -153,16 +149,12 @@ class FragmentBatchBuilder(_CloudBuilder):
         ops.fragment_batch_shapes(c, B) to write into.
     apply(ids, draws): the recorded draws of the reference (tests): rows [B,N], cand [B,n_sub], first [B]."""
 
+    spec = ops.FRAGMENT_BATCH
     _modes = ("eval",)
 
     def __init__(self, bank: FragmentScanBank, recipe: FragmentBatchRecipe, device=None, seed: int = 0):
         self._wsb = {}
         super().__init__(bank, recipe, 0, device, seed, 0, "eval")
-        self._bank = bank.c_dict()
-
-    @staticmethod
-    def _workspace_bytes(c, pairs):
-        return 0
 
     def _c_struct(self):
         return self.recipe.c_struct(self.bank.row_len)
@@ -173,55 +165,21 @@ class FragmentBatchBuilder(_CloudBuilder):
                              % (self.bank.row_len, self.recipe.Cs))
         ops.fragment_batch_workspace_bytes(self.c, 1)                # an invalid recipe is refused here
 
-    def _workspace(self, B: int) -> torch.Tensor:
+    def _workspace(self, B: int, which: int = 0) -> torch.Tensor:
+        """One workspace per number of clouds met."""
         B2 = ops.fragment_batch_clouds(B)
         if B2 not in self._wsb:
             self._wsb[B2] = torch.empty(ops.fragment_batch_workspace_bytes(self.c, B2), dtype=torch.uint8, device=self.device)
         return self._wsb[B2]
 
-    def _ids(self, ids):
-        """-> (i32 device tensor [B], the host's int32 copy or None for ids already on the device)."""
-        if isinstance(ids, torch.Tensor) and ids.is_cuda:
-            if ids.device != self.bank.device:
-                raise ValueError("FragmentBatchBuilder: ids on %s, the bank on %s" % (ids.device, self.bank.device))
-            return ids.to(torch.int32).reshape(-1).contiguous(), None
-        h = np.asarray(ids, dtype=np.int64).reshape(-1)
-        if h.size < 1:
-            raise ValueError("FragmentBatchBuilder: no ids")
-        if h.min() < 0 or h.max() >= self.bank.num_scans:
-            raise ValueError("FragmentBatchBuilder: fragment id out of range [0, %d)" % self.bank.num_scans)
-        h = np.ascontiguousarray(h, dtype=np.int32)
-        return torch.from_numpy(h).pin_memory().to(self.device, non_blocking=True), h
+    def _of_call(self, tensors: dict, B: int) -> dict:
+        return {k: t[:B] for k, t in tensors.items()}
 
-    def _out(self, B, out, with_indices):
-        shapes = ops.fragment_batch_shapes(self.c, B)
-        full = {k: (out[k] if out is not None and k in out else torch.empty(shapes[k], dtype=torch.float32, device=self.device))
-                for k in KEYS}
-        rows = nodes = None
-        if with_indices:
-            B2 = ops.fragment_batch_clouds(B)
-            rows = torch.empty((B2, self.recipe.N), dtype=torch.int32, device=self.device)
-            nodes = torch.empty((B2, self.recipe.M), dtype=torch.int32, device=self.device)
-        self.last_rows = rows[:B] if rows is not None else None
-        self.last_node_slots = nodes[:B] if nodes is not None else None
-        return full, rows, nodes
+    def _counter(self, step: int) -> tuple:
+        return (self.seed, int(step))
 
     def build(self, ids, step: int = 0, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False):
-        dev_ids, host_ids = self._ids(ids)
-        B = dev_ids.numel()
-        full, rows, nodes = self._out(B, out, with_indices)
-        ops.fragment_batch_build(self.c, self._bank, dev_ids, host_ids, self.seed, int(step), full, self._workspace(B), rows,
-                                 nodes)
-        return {k: full[k][:B] for k in KEYS}
-
-    def apply(self, ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
-        dev_ids, host_ids = self._ids(ids)
-        B = dev_ids.numel()
-        full, rows, nodes = self._out(B, out, with_indices)
-        d = {k: torch.from_numpy(np.ascontiguousarray(draws[k], dtype=np.int32)).to(self.device)
-             for k in ops.FRAGMENT_BATCH_DRAWS}
-        ops.fragment_batch_apply(self.c, d, self._bank, dev_ids, host_ids, full, self._workspace(B), rows, nodes)
-        return {k: full[k][:B] for k in KEYS}
+        return super().build(ids, step, out, with_indices)
 
     def prefetch(self, schedule, outs=None):
         raise NotImplementedError("FragmentBatchBuilder: evaluation batches are built in line")
@@ -235,42 +193,12 @@ def build_cpu(recipe: FragmentBatchRecipe, fragments: Sequence[np.ndarray], ids,
               draws: Optional[Dict[str, np.ndarray]] = None, num_threads: int = 1):
     """The host twin (usip_fragment_batch_build_f32_cpu) on numpy fragments [rows, row_len]: Philox draws, or `draws` (rows
     [B,N], cand [B,n_sub], first [B]).  Returns (batch of pc / sn / node, rows [B,N], node_slots [B,M])."""
-    fragments = [np.asarray(f, dtype=np.float32) for f in fragments]
-    if not fragments or any(f.ndim != 2 or f.shape[1] != fragments[0].shape[1] for f in fragments):
-        raise ValueError("build_cpu: fragments are [rows, row_len] arrays of one row length")
-    if any(f.shape[0] == 0 for f in fragments):
-        raise ValueError("build_cpu: an empty fragment")
-    c = recipe.c_struct(fragments[0].shape[1])
-    h = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+    h = np.asarray(ids, dtype=np.int64).reshape(-1)
     if h.size < 1 or h.min() < 0 or h.max() >= len(fragments):
         raise ValueError("build_cpu: fragment id out of range [0, %d)" % len(fragments))
-    h = h.astype(np.int32)
-    B = h.size
-    B2 = ops.fragment_batch_clouds(B)
-    rows_all = np.ascontiguousarray(np.concatenate(fragments))
-    offsets = np.concatenate([[0], np.cumsum([len(f) for f in fragments])]).astype(np.int64)
-    out = {k: np.zeros(shape, dtype=np.float32) for k, shape in ops.fragment_batch_shapes(c, B).items()}
-    rows = np.zeros((B2, recipe.N), dtype=np.int32)
-    nodes = np.zeros((B2, recipe.M), dtype=np.int32)
-    ptr = lambda a: a.ctypes.data   # noqa: E731
-    o = ops.fragment_batch_out_struct(ptr, out, rows, nodes)
-    b = ops.FragmentBatchBankC()
-    b.rows, b.offsets, b.num_fragments = ptr(rows_all), ptr(offsets), len(fragments)
-    b.min_rows = int(min(len(f) for f in fragments))
-    d = None
-    if draws is not None:
-        keep = {k: np.ascontiguousarray(draws[k], dtype=np.int32) for k in ops.FRAGMENT_BATCH_DRAWS}
-        want = dict(rows=(B, recipe.N), cand=(B, recipe.n_sub), first=(B,))
-        for k in keep:
-            if keep[k].shape != want[k]:
-                raise ValueError("build_cpu: draw %s must be %s" % (k, want[k]))
-        d = ops.FragmentBatchDrawsC()
-        d.rows, d.cand, d.first = ptr(keep["rows"]), ptr(keep["cand"]), ptr(keep["first"])
-    _lib.check(_lib.lib().usip_fragment_batch_build_f32_cpu(
-        ctypes.addressof(c), ctypes.addressof(d) if d is not None else None, ctypes.addressof(b), ptr(h), B,
-        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, ctypes.addressof(o), int(num_threads)),
-        "usip_fragment_batch_build_f32_cpu")
-    return {k: v[:B] for k, v in out.items()}, rows[:B], nodes[:B]
+    out, rows, nodes = host_twin(ops.FRAGMENT_BATCH, recipe.c_struct, fragments, "fragment", h, None, counter=(seed, step),
+                                 draws=draws, num_threads=num_threads)
+    return {k: v[:h.size] for k, v in out.items()}, rows[:h.size], nodes[:h.size]
 
 
 class FragmentDescriber:

@@ -19,7 +19,6 @@ The one stated deviation a user may choose: the reference adds the ICP TRANSLATI
 sn[:, 0:3] through the same homogeneous product as the points).  IndoorPairRecipe.icp_moves_normals = 1 (the default)
 reproduces that; 0 rotates the normals only.
 """
-import ctypes
 import os
 import pickle
 from dataclasses import dataclass
@@ -28,9 +27,10 @@ from typing import Dict, Iterable, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import ops
 from .desc_pairs import _FrozenDetectorTrainer
-from .pairs import ScanBank, _CloudBuilder, epoch_batches, epoch_order          # noqa: F401  (re-exported)
+from .pairs import ScanBank, _CloudBuilder, _empty_batch, bank_arrays, host_twin
+from .pairs import epoch_batches, epoch_order          # noqa: F401  (re-exported)
 
 KEYS = ops.INDOOR_PAIRS_KEYS
 MODES = {"train": 0, "val": 1, "test": 2, "bank": 3}
@@ -249,8 +249,7 @@ def synthetic_scenenn(root: str, frames: int = 6, rows: int = 6000, short_rows: 
 
 
 def empty_batch(c: ops.IndoorPairsRecipeC, pairs: int, device) -> Dict[str, torch.Tensor]:
-    return {k: torch.empty(shape, dtype=torch.float32, device=device)
-            for k, shape in ops.indoor_pairs_shapes(c, pairs).items()}
+    return _empty_batch(ops.INDOOR_PAIRS, c, pairs, device)
 
 
 class IndoorPairBuilder(_CloudBuilder):
@@ -262,15 +261,8 @@ class IndoorPairBuilder(_CloudBuilder):
     apply(sample_ids, draws, out=None): the recorded draws of the reference (tests).
     prefetch(schedule): double-buffered, batch k+1 built on a side stream while the consumer runs batch k."""
 
-    _workspace_bytes = staticmethod(ops.indoor_pairs_workspace_bytes)
-    _workspace_offset = staticmethod(ops.indoor_pairs_workspace_offset)
-
+    spec = ops.INDOOR_PAIRS
     _modes = tuple(MODES)
-
-    def __init__(self, bank: IndoorPairBank, recipe: IndoorPairRecipe, pairs: int, device=None, seed: int = 0,
-                 rank: int = 0, mode: str = "train"):
-        super().__init__(bank, recipe, pairs, device, seed, rank, mode)
-        self._bank = bank.c_dict()
 
     def _c_struct(self):
         return self.recipe.c_struct(self.mode, self.bank.row_len)
@@ -285,38 +277,6 @@ class IndoorPairBuilder(_CloudBuilder):
         if self.recipe.Cs < 3:
             raise ValueError("IndoorPairBuilder: the ICP move acts on sn[0:3]: surface_normal_len >= 3")
 
-    def _empty_batch(self):
-        return empty_batch(self.c, self.pairs, self.device)
-
-    def _out(self, out, with_indices):
-        full = self._empty_batch() if out is None or any(k not in out for k in KEYS) else {}
-        if out is not None:
-            full.update({k: out[k] for k in KEYS if k in out})
-        return (full,) + self._index_out(with_indices)
-
-    def build(self, sample_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
-              _ws: int = 0) -> Dict[str, torch.Tensor]:
-        out, rows, nodes = self._out(out, with_indices)
-        ops.indoor_pairs_build(self.c, self._bank, self._ids(sample_ids), self.seed, int(step), self.rank * self.pairs,
-                               out, self._ws[_ws], rows, nodes)
-        return out
-
-    def apply(self, sample_ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
-        out, rows, nodes = self._out(out, with_indices)
-        d = {k: torch.from_numpy(np.ascontiguousarray(draws[k], dtype=_DRAW_NP[k])).to(self.device) for k in _DRAW_NP}
-        ops.indoor_pairs_apply(self.c, d, self._bank, self._ids(sample_ids), out, self._ws[0], rows, nodes)
-        return out
-
-    def prefetch(self, schedule: Iterable, outs=None):
-        """schedule: iterable of (sample_ids, step), on the shared prefetch loop (usip_amd.pairs._CloudBuilder.prefetch):
-        the same two buffers, events and side stream, and the same safety when the loop is left early."""
-        if outs is None:
-            outs = [self._empty_batch() for _ in range(2)]
-        yield from super().prefetch(schedule, outs)
-
-
-_DRAW_NP = {k: (np.int32 if dt == torch.int32 else np.float64) for k, dt in ops.INDOOR_PAIRS_DRAWS.items()}
-
 
 def build_cpu(recipe: IndoorPairRecipe, frames: Sequence[np.ndarray], pairs, icp, sample_ids, num_pairs: int,
               seed: int = 0, step: int = 0, rank: int = 0, mode: str = "train", sample_mode=None,
@@ -324,41 +284,14 @@ def build_cpu(recipe: IndoorPairRecipe, frames: Sequence[np.ndarray], pairs, icp
     """The host twin (usip_indoor_pairs_build_f32_cpu) on numpy frames, pairs [S, 2] and icp [S, 4, 4]: Philox draws, or
     `draws` (f-5's layouts).  mode 'bank' reads sample_mode [S] (0 train, 1 val, 2 test).  Returns (batch, rows [2,P,N],
     node_slots [2,P,M]).  The same refusals as the bank's."""
-    frames = [np.asarray(f, dtype=np.float32) for f in frames]
-    if not frames or any(f.ndim != 2 or f.shape[1] != frames[0].shape[1] for f in frames):
-        raise ValueError("build_cpu: frames are [rows, row_len] arrays of one row length")
-    if any(f.shape[0] == 0 for f in frames):
-        raise ValueError("build_cpu: an empty frame")
-    c = recipe.c_struct(mode, frames[0].shape[1])
+    frames = bank_arrays(frames, "frame")
     pairs_h, icp_h = check_samples(pairs, icp, len(frames))
-    rows_all = np.ascontiguousarray(np.concatenate(frames))
-    offsets = np.concatenate([[0], np.cumsum([len(f) for f in frames])]).astype(np.int64)
-    ids = np.ascontiguousarray(np.asarray(sample_ids, dtype=np.int32).reshape(-1))
-    P = int(num_pairs)
-    if ids.size != P:
-        raise ValueError("build_cpu: %d sample ids for %d pairs" % (ids.size, P))
-    out = {k: np.zeros(shape, dtype=np.float32) for k, shape in ops.indoor_pairs_shapes(c, P).items()}
-    rows = np.zeros((2, P, recipe.N), dtype=np.int32)
-    nodes = np.zeros((2, P, recipe.M), dtype=np.int32)
-    ptr = lambda a: a.ctypes.data   # noqa: E731
-    o = ops.indoor_pairs_out_struct(ptr, out, rows, nodes)
-    modes = None if sample_mode is None else np.ascontiguousarray(sample_mode, dtype=np.int32)
+    modes = None if sample_mode is None else np.ascontiguousarray(sample_mode, dtype=np.int32).reshape(-1)
     if modes is not None and modes.size != pairs_h.shape[0]:
         raise ValueError("build_cpu: %d sample modes for %d samples" % (modes.size, pairs_h.shape[0]))
-    b = ops.IndoorPairsBankC()
-    b.rows, b.offsets, b.pairs, b.icp = ptr(rows_all), ptr(offsets), ptr(pairs_h), ptr(icp_h)
-    b.sample_mode = ptr(modes) if modes is not None else None
-    b.pairs_host, b.num_frames, b.num_samples = ptr(pairs_h), len(frames), pairs_h.shape[0]
-    b.min_rows = int(min(len(f) for f in frames))
-    d = None
-    if draws is not None:
-        keep = {k: np.ascontiguousarray(draws[k], dtype=_DRAW_NP[k]) for k in _DRAW_NP}
-        d = ops.indoor_pairs_draws_struct(ptr, keep)
-    _lib.check(_lib.lib().usip_indoor_pairs_build_f32_cpu(
-        ctypes.addressof(c), ctypes.addressof(d) if d is not None else None, ctypes.addressof(b), ptr(ids), P,
-        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, rank * P, ctypes.addressof(o), int(num_threads)),
-        "usip_indoor_pairs_build_f32_cpu")
-    return out, rows, nodes
+    return host_twin(ops.INDOOR_PAIRS, lambda row_len: recipe.c_struct(mode, row_len), frames, "frame", sample_ids,
+                     num_pairs, bank=dict(pairs=pairs_h, icp=icp_h, sample_mode=modes, pairs_host=pairs_h),
+                     counter=(seed, step, rank * int(num_pairs)), draws=draws, num_threads=num_threads)
 
 
 class IndoorDescriptorTrainer(_FrozenDetectorTrainer):

@@ -8,7 +8,8 @@ import ctypes
 import functools
 import math
 import os
-from typing import Optional
+import types
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -1483,123 +1484,271 @@ def index_max_cpu(data: torch.Tensor, index: torch.Tensor, K: int, num_threads: 
     return out
 
 
-# ------------------------------------------------------------------------------------------------ f-5 training pairs
-# The structs that go by address are the header's own (include/usip_hip.h), read by _lib: their fields are documented there.
-PairsRecipeC = _lib.STRUCTS["usip_pairs_recipe"]
-PairsDrawsC = _lib.STRUCTS["usip_pairs_draws"]
-PairsOutC = _lib.STRUCTS["usip_pairs_out"]
-
-PAIRS_KEYS = ("src_pc", "src_sn", "src_node", "dst_pc", "dst_sn", "dst_node", "R", "scale", "shift")
+# --------------------------------------------------------------- f-5, f-8, f-26, f-27: batches of clouds from a bank
+# Four builders (detector pairs, descriptor pairs, indoor pairs, evaluation fragments) over csrc/cloud_stage.h.  Each
+# states what is its own in one CloudBatchSpec; cloud_batch checks and launches any of them, the struct fillers serve it
+# and the host twins (usip_amd.pairs.host_twin) alike.  The structs that go by address are the header's own
+# (include/usip_hip.h and the headers it includes), read by _lib: their fields are documented there.
+class CloudBatchSpec(NamedTuple):
+    ids: str                 # what an id of a call names: "scan", "sample", "fragment"
+    tag: str                 # usip_<tag>_build_f32 / _apply_f32 / _build_f32_cpu / _workspace_bytes / _workspace_offset
+    out_c: type              # the header's out struct,
+    bank_c: Optional[type]   # bank struct (None: the bank goes as plain arguments)
+    draws_c: type            # and draws struct
+    bank: dict               # the bank's tensors -> dtype
+    bank_meta: Optional[Callable]   # (bank struct, bank dict): the bank's own refusals and counts
+    lead: Callable           # (ptr, bank dict, bank struct, ids, n, ids_host, on_device) -> the C call's leading arguments
+    keys: tuple              # the outputs, in the out struct's order
+    out_fields: tuple        # (output key, the out struct's field, index in it or None), in the struct's order
+    table: Callable          # (N, M, Cs, n) -> key -> (shape, dtype) of the outputs of a call of n ids (cached: read only)
+    draws: dict              # draw -> dtype
+    draw_fields: tuple       # (draw, whether its field is in the draws struct's nested f-5 `cloud`)
+    draw_shapes: Callable    # (cloud recipe, n) -> draw -> the header's layout (None: any extent)
+    required: tuple          # the draws that may not be absent
+    index_lead: Callable     # n -> the leading shape of rows [..., N] and node_slots [..., M]
+    clouds: float            # clouds per id (the traffic estimate)
 
 
 def _data_ptr(t):
     return t.data_ptr()
 
 
-def _clouds_out(o, ptr, out: dict, sides, rest, rows, node_slots):
-    """Fill an out struct of either builder: the two clouds' pc / sn / node, the fields `rest`, the optional indices.
-    ptr: tensor or array -> address (device tensors here, numpy arrays for the host twins)."""
-    for i, side in enumerate(sides):
-        o.pc[i], o.sn[i], o.node[i] = (ptr(out[side + "_" + k]) for k in ("pc", "sn", "node"))
-    for k in rest:
-        setattr(o, k, ptr(out[k]))
-    o.rows = ptr(rows) if rows is not None else None
-    o.node_slots = ptr(node_slots) if node_slots is not None else None
+def _out_fields(keys, sides=(), renamed=()) -> tuple:
+    """<sides[i]>_pc / _sn / _node are the out struct's pc[i] / sn[i] / node[i]; any other key is the field of its name,
+    or the one `renamed` gives it."""
+    cloud = {s + "_" + f: (f, i) for i, s in enumerate(sides) for f in ("pc", "sn", "node")}
+    return tuple((k,) + cloud.get(k, (dict(renamed).get(k, k), None)) for k in keys)
+
+
+def out_struct(spec: CloudBatchSpec, ptr, out: dict, rows, node_slots):
+    """ptr: tensor or array -> address (device tensors in cloud_batch, numpy arrays in the host twins)."""
+    o = spec.out_c()
+    for k, field, i in spec.out_fields:
+        if i is None:
+            setattr(o, field, ptr(out[k]))
+        else:
+            getattr(o, field)[i] = ptr(out[k])
+    o.rows = None if rows is None else ptr(rows)
+    o.node_slots = None if node_slots is None else ptr(node_slots)
     return o
 
 
-def _pairs_out(ptr, out: dict, rows, node_slots) -> PairsOutC:
-    return _clouds_out(PairsOutC(), ptr, out, ("src", "dst"), PAIRS_KEYS[6:], rows, node_slots)
+def bank_struct(spec: CloudBatchSpec, ptr, bank: dict):
+    """The bank struct of bank's tensors (or arrays), its counts and min_rows, after the bank's own refusals."""
+    if spec.bank_c is None:
+        return None
+    b = spec.bank_c()
+    for k in spec.bank:
+        setattr(b, k, None if bank[k] is None else ptr(bank[k]))
+    b.min_rows = int(bank["min_rows"])
+    spec.bank_meta(b, bank)
+    return b
 
 
-def _check_workspace_and_indices(tag: str, cloud: PairsRecipeC, P: int, device, workspace, need: int, rows, node_slots):
-    """What the two builders check alike: the workspace's size and the optional index outputs, all on `device`."""
-    if workspace.device != device or workspace.numel() * workspace.element_size() < need:
-        raise RuntimeError("%s: the workspace must hold usip_%s_workspace_bytes() bytes on %s" % (tag, tag, device))
-    for name, t, n in (("rows", rows, cloud.N), ("node_slots", node_slots, cloud.M)):
-        if t is not None:
-            _need(t, name, torch.int32)
-            if tuple(t.shape) != (2, P, n) or t.device != device:
-                raise RuntimeError("%s: %s must be i32 (2, %d, %d) on %s" % (tag, name, P, n, device))
+def _draw_fields(own=(), cloud=()) -> tuple:
+    return tuple((k, False) for k in own) + tuple((k, True) for k in cloud)
 
 
-def _workspace_query(symbol: str, recipe, P: int, part=None) -> int:
-    """usip_*_workspace_bytes, or with `part` usip_*_workspace_offset."""
-    args = (ctypes.addressof(recipe), int(P)) + (() if part is None else (int(part),))
-    n = int(getattr(_lib.lib(), symbol)(*args))
-    if n < 0:
+def draws_struct(spec: CloudBatchSpec, ptr, draws: dict):
+    d = spec.draws_c()
+    for k, nested in spec.draw_fields:
+        if draws.get(k) is not None:
+            setattr(d.cloud if nested else d, k, ptr(draws[k]))
+    if "tries" in spec.draws:                           # f-8 counts them: tries is i32 [P][T]
+        d.T = int(draws["tries"].shape[1])
+    return d
+
+
+def cloud_recipe(recipe):
+    """f-5's recipe: the struct itself, or the `cloud` a descriptor recipe nests."""
+    return recipe if type(recipe) is PairsRecipeC else recipe.cloud
+
+
+def check_draws(spec: CloudBatchSpec, c, n: int, draws: dict, error):
+    """Every present draw in the header's layout (the kernels and the host twin index it by that layout: a shorter array
+    would be read past its end); absent only where the builder allows it."""
+    want = spec.draw_shapes(c, n)
+    for k in spec.draws:
+        t = draws.get(k)
+        if t is None:
+            if k in spec.required:
+                raise error("%s: draw %s is missing" % (spec.tag, k))
+        elif len(t.shape) != len(want[k]) or any(w is not None and s != w for s, w in zip(t.shape, want[k])):
+            raise error("%s: draw %s must be %s %s, got %s" % (spec.tag, k, spec.draws[k], want[k], tuple(t.shape)))
+
+
+@functools.lru_cache(maxsize=None)
+def cloud_batch_entry(tag: str, what: str):
+    """(the library's usip_<tag>_<what>, its name)."""
+    symbol = "usip_%s_%s" % (tag, what)
+    return getattr(_lib.lib(), symbol), symbol
+
+
+def cloud_batch_workspace(spec: CloudBatchSpec, recipe, n: int, part=None) -> int:
+    """usip_<tag>_workspace_bytes, or with `part` usip_<tag>_workspace_offset."""
+    fn, symbol = cloud_batch_entry(spec.tag, "workspace_bytes" if part is None else "workspace_offset")
+    got = fn(ctypes.addressof(recipe), int(n)) if part is None else fn(ctypes.addressof(recipe), int(n), int(part))
+    if got < 0:
         raise RuntimeError("usip_amd: %s: invalid recipe%s (USIP_EINVAL)" % (symbol, "" if part is None else " or part"))
-    return n
+    return got
 
 
-def _pairs_check_out(recipe: PairsRecipeC, out: dict, P: int, device, scan_ids, rows, node_slots, workspace):
-    """Every tensor the launch touches on the bank's device, with its dtype and shape (a pointer to another device's
-    memory would be dereferenced by the kernels)."""
-    shapes = dict(src_pc=(P, 3, recipe.N), src_sn=(P, recipe.Cs, recipe.N), src_node=(P, 3, recipe.M), R=(P, 3, 3),
-                  scale=(P,), shift=(P, 3, 1))
-    for k in PAIRS_KEYS:
+def counter_args(counter) -> tuple:
+    """(seed, step[, pair_base]) as the entry points take them: the first two are uint64_t."""
+    return (int(counter[0]) & 0xFFFFFFFFFFFFFFFF, int(counter[1]) & 0xFFFFFFFFFFFFFFFF) + tuple(map(int, counter[2:]))
+
+
+def cloud_batch_table(spec: CloudBatchSpec, recipe, n: int) -> dict:
+    """key -> (shape, dtype) of the outputs of a call of n ids; recipe: the struct, or anything with its N, M and Cs."""
+    c = getattr(recipe, "cloud", recipe)
+    return spec.table(c.N, c.M, c.Cs, n)
+
+
+def cloud_batch(spec: CloudBatchSpec, recipe, bank: dict, ids: torch.Tensor, out: dict, workspace: torch.Tensor, rows=None,
+                node_slots=None, counter=None, draws=None, ids_host=None):
+    """One call of a builder into `out` (spec.keys -> tensors): usip_<tag>_build_f32 with Philox draws under counter =
+    (seed, step[, pair_base]), or with `draws` (spec.draws -> device tensors in the header's layouts)
+    usip_<tag>_apply_f32.  Every tensor the launch touches is held to the bank's device, its dtype and its shape (a
+    pointer to another device's memory, or past an array's end, would be dereferenced by the kernels); nothing is
+    enqueued before the last refusal."""
+    tag, c, dev = spec.tag, cloud_recipe(recipe), bank["rows"].device
+    for k, dt in spec.bank.items():
+        _need(bank[k], "bank " + k, dt)
+        if bank[k].device != dev:
+            raise RuntimeError("%s: bank %s on %s, the rows on %s" % (tag, k, bank[k].device, dev))
+    b = bank_struct(spec, _data_ptr, bank)
+    _need(ids, "ids", torch.int32)
+    n = ids.numel()
+    if ids.device != dev:
+        raise RuntimeError("%s: ids on %s, the bank on %s" % (tag, ids.device, dev))
+    if ids_host is not None and (ids_host.dtype != "int32" or ids_host.size != n or not ids_host.flags.c_contiguous):
+        raise RuntimeError("%s: ids_host must be a C-contiguous int32 numpy array of the ids" % tag)
+    for k, (shape, dt) in spec.table(c.N, c.M, c.Cs, n).items():
         t = out[k]
-        _need(t, k, torch.float32)
-        if tuple(t.shape) != shapes[k.replace("dst_", "src_")] or t.device != device:
-            raise RuntimeError("pairs: %s must be f32 %s on %s" % (k, shapes[k.replace("dst_", "src_")], device))
-    if scan_ids.device != device:
-        raise RuntimeError("pairs: scan_ids on %s, the bank on %s" % (scan_ids.device, device))
-    _check_workspace_and_indices("pairs", recipe, P, device, workspace, pairs_workspace_bytes(recipe, P), rows, node_slots)
+        _need(t, k, dt)
+        if t.shape != shape or t.device != dev:
+            raise RuntimeError("%s: %s must be %s %s on %s" % (tag, k, dt, shape, dev))
+    if workspace.device != dev or workspace.numel() * workspace.element_size() < cloud_batch_workspace(spec, recipe, n):
+        raise RuntimeError("%s: the workspace must hold usip_%s_workspace_bytes() bytes on %s" % (tag, tag, dev))
+    if rows is not None or node_slots is not None:
+        for name, t, last in (("rows", rows, c.N), ("node_slots", node_slots, c.M)):
+            if t is not None:
+                _need(t, name, torch.int32)
+                if tuple(t.shape) != spec.index_lead(n) + (last,) or t.device != dev:
+                    raise RuntimeError("%s: %s must be i32 %s on %s" % (tag, name, spec.index_lead(n) + (last,), dev))
+    kind, args = "build", [ctypes.addressof(recipe)]
+    if draws is not None:
+        for k, dt in spec.draws.items():
+            if draws.get(k) is not None:
+                _need(draws[k], "draw " + k, dt)
+                if draws[k].device != dev:
+                    raise RuntimeError("%s: draw %s on %s, the bank on %s" % (tag, k, draws[k].device, dev))
+        check_draws(spec, c, n, draws, RuntimeError)
+        d = draws_struct(spec, _data_ptr, draws)
+        kind, args = "apply", args + [ctypes.addressof(d)]
+    o = out_struct(spec, _data_ptr, out, rows, node_slots)
+    args += spec.lead(_data_ptr, bank, b, ids.data_ptr(), n, ids_host.ctypes.data if ids_host is not None else None, True)
+    args += counter_args(counter) if draws is None else ()
+    args += (ctypes.addressof(o), workspace.data_ptr(), _stream(bank["rows"]))
+    fn, symbol = cloud_batch_entry(tag, kind + "_f32")
+    with torch.cuda.device(dev), prof.kernel(symbol[5:-4], spec.clouds * n * c.N * (32 + 4 * (3 + c.Cs))):   # "<tag>_<kind>"
+        _lib.check(fn(*args), symbol)
+    return out
+
+
+def _cloud_table(N: int, M: int, Cs: int, n: int, a: str, b: str = None) -> dict:
+    """<a>pc, sn, node (and <b>pc, sn, node) of n clouds each, float32."""
+    pc, sn, node = ((n, 3, N), torch.float32), ((n, Cs, N), torch.float32), ((n, 3, M), torch.float32)
+    t = {a + "pc": pc, a + "sn": sn, a + "node": node}
+    if b is not None:
+        t.update({b + "pc": pc, b + "sn": sn, b + "node": node})
+    return t
+
+
+def _shapes(spec: CloudBatchSpec, recipe, n: int) -> dict:
+    return {k: shape for k, (shape, _) in cloud_batch_table(spec, recipe, n).items()}
+
+
+def _table(fn):
+    """A builder's table is asked for at every call, for a handful of shapes: kept per shape, handed out read-only."""
+    return functools.lru_cache(maxsize=64)(lambda N, M, Cs, n: types.MappingProxyType(fn(N, M, Cs, n)))
+
+
+def _f5_draw_shapes(c, n: int) -> dict:
+    """include/usip_hip.h, usip_pairs_draws: per pair p and cloud at [p][c]; params f64 [P][USIP_PAIRS_NPARAM]."""
+    return dict(rows=(n, 2, c.N), cand=(n, 2, c.n_sub), first=(n, 2), jit_pc=(n, 2, c.N, 3), jit_sn=(n, 2, c.N, c.Cs),
+                jit_node=(n, 2, c.M, 3), params=(n, 24))
+
+
+def _struct_lead(ptr, bank, b, ids, n, ids_host, on_device) -> tuple:
+    return (ctypes.addressof(b), ids, n)
+
+
+_F5_DRAWS = dict(rows=torch.int32, cand=torch.int32, first=torch.int32, jit_pc=torch.float64, jit_sn=torch.float64,
+                 jit_node=torch.float64, params=torch.float64)
+_ROWS = dict(rows=torch.float32, offsets=torch.int64)
+
+
+# ---- f-5 training pairs (include/usip_hip.h): the bank goes as plain arguments, the library refuses the draws it misses
+PairsRecipeC = _lib.STRUCTS["usip_pairs_recipe"]
+PairsDrawsC = _lib.STRUCTS["usip_pairs_draws"]
+PairsOutC = _lib.STRUCTS["usip_pairs_out"]
+
+PAIRS_KEYS = ("src_pc", "src_sn", "src_node", "dst_pc", "dst_sn", "dst_node", "R", "scale", "shift")
+PAIRS_DRAWS = _F5_DRAWS
+
+
+@_table
+def _pairs_table(N: int, M: int, Cs: int, P: int) -> dict:
+    f = torch.float32
+    return dict(_cloud_table(N, M, Cs, P, "src_", "dst_"), R=((P, 3, 3), f), scale=((P,), f), shift=((P, 3, 1), f))
+
+
+def pairs_shapes(recipe, P: int) -> dict:
+    """key -> shape of one batch of P pairs (all float32): what DetectorStep.step consumes."""
+    return _shapes(PAIRS, recipe, P)
+
+
+def _pairs_lead(ptr, bank, b, ids, n, ids_host, on_device) -> tuple:
+    """bank, offsets, num_scans, scan_ids, P, and for the device entries min_rows (the host twin reads the offsets)."""
+    return (ptr(bank["rows"]), ptr(bank["offsets"]), bank["offsets"].shape[0] - 1, ids, n) + \
+        ((int(bank["min_rows"]),) if on_device else ())
+
+
+PAIRS = CloudBatchSpec(
+    ids="scan", tag="pairs", out_c=PairsOutC, bank_c=None, draws_c=PairsDrawsC, bank=_ROWS, bank_meta=None, lead=_pairs_lead,
+    keys=PAIRS_KEYS, out_fields=_out_fields(PAIRS_KEYS, ("src", "dst")), table=_pairs_table, draws=PAIRS_DRAWS,
+    draw_fields=_draw_fields(own=PAIRS_DRAWS),
+    draw_shapes=_f5_draw_shapes, required=(), index_lead=lambda P: (2, P), clouds=2.0)
 
 
 def pairs_build(recipe: PairsRecipeC, bank: torch.Tensor, offsets: torch.Tensor, scan_ids: torch.Tensor, min_rows: int,
                 seed: int, step: int, pair_base: int, out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
     """f-5: P training pairs with Philox draws (usip_pairs_build_f32) into `out` (PAIRS_KEYS -> f32 tensors)."""
-    _need(bank, "bank", torch.float32)
-    _need(offsets, "offsets", torch.int64)
-    _need(scan_ids, "scan_ids", torch.int32)
-    P = scan_ids.numel()
-    _pairs_check_out(recipe, out, P, bank.device, scan_ids, rows, node_slots, workspace)
-    o = _pairs_out(_data_ptr, out, rows, node_slots)
-    with torch.cuda.device(bank.device), prof.kernel("pairs_build", 2.0 * P * recipe.N * (32 + 4 * (3 + recipe.Cs))):
-        _lib.check(_lib.lib().usip_pairs_build_f32(
-            ctypes.addressof(recipe), _ptr(bank), _ptr(offsets), offsets.numel() - 1, _ptr(scan_ids), P, int(min_rows),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, int(pair_base), ctypes.addressof(o),
-            _ptr(workspace), _stream(bank)), "usip_pairs_build_f32")
-    return out
+    return cloud_batch(PAIRS, recipe, dict(rows=bank, offsets=offsets, min_rows=min_rows), scan_ids, out, workspace, rows,
+                       node_slots, counter=(seed, step, pair_base))
 
 
 def pairs_apply(recipe: PairsRecipeC, draws: dict, bank: torch.Tensor, offsets: torch.Tensor, scan_ids: torch.Tensor,
                 min_rows: int, out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
     """f-5 with explicit draws (usip_pairs_apply_f32): draws = rows, cand, first (i32), jit_pc, jit_sn, jit_node,
     params (f64) device tensors in the layouts of include/usip_hip.h."""
-    _need(bank, "bank", torch.float32)
-    _need(offsets, "offsets", torch.int64)
-    _need(scan_ids, "scan_ids", torch.int32)
-    P = scan_ids.numel()
-    _pairs_check_out(recipe, out, P, bank.device, scan_ids, rows, node_slots, workspace)
-    d = PairsDrawsC()
-    for k in PairsDrawsC._fields_:
-        t = draws.get(k[0])
-        if t is not None:
-            _need(t, k[0], torch.int32 if k[0] in ("rows", "cand", "first") else torch.float64)
-            if t.device != bank.device:
-                raise RuntimeError("pairs: draw %s on %s, the bank on %s" % (k[0], t.device, bank.device))
-            setattr(d, k[0], t.data_ptr())
-    o = _pairs_out(_data_ptr, out, rows, node_slots)
-    with torch.cuda.device(bank.device), prof.kernel("pairs_apply", 2.0 * P * recipe.N * (32 + 4 * (3 + recipe.Cs))):
-        _lib.check(_lib.lib().usip_pairs_apply_f32(
-            ctypes.addressof(recipe), ctypes.addressof(d), _ptr(bank), _ptr(offsets), offsets.numel() - 1,
-            _ptr(scan_ids), P, int(min_rows), ctypes.addressof(o), _ptr(workspace), _stream(bank)), "usip_pairs_apply_f32")
-    return out
+    return cloud_batch(PAIRS, recipe, dict(rows=bank, offsets=offsets, min_rows=min_rows), scan_ids, out, workspace, rows,
+                       node_slots, draws=draws)
 
 
 def pairs_workspace_offset(recipe: PairsRecipeC, P: int, part: int) -> int:
     """Byte offset of workspace part 0 table, 1 candidates, 2 first indices, 3 FPS picks, 4 total (include/usip_hip.h)."""
-    return _workspace_query("usip_pairs_workspace_offset", recipe, P, part)
+    return cloud_batch_workspace(PAIRS, recipe, P, part)
 
 
 def pairs_workspace_bytes(recipe: PairsRecipeC, P: int) -> int:
-    return _workspace_query("usip_pairs_workspace_bytes", recipe, P)
+    return cloud_batch_workspace(PAIRS, recipe, P)
 
 
-# ------------------------------------------------------------------------------- f-8 descriptor batches from posed scans
-# the header's structs again (recipe.cloud is a PairsRecipeC, draws.cloud a PairsDrawsC: the reader nests the classes)
+# ---- f-8 descriptor batches from posed scans (recipe.cloud is a PairsRecipeC, draws.cloud a PairsDrawsC: the reader
+# nests the classes); the library counts tries, so they may not be absent.  params is f-8's own [P][24] table; the nested
+# cloud.params, which f-8 does not read, takes the same array so that no pointer of the struct stays NULL
 DescPairsRecipeC = _lib.STRUCTS["usip_desc_pairs_recipe"]
 DescPairsBankC = _lib.STRUCTS["usip_desc_pairs_bank"]
 DescPairsDrawsC = _lib.STRUCTS["usip_desc_pairs_draws"]
@@ -1607,123 +1756,71 @@ DescPairsOutC = _lib.STRUCTS["usip_desc_pairs_out"]
 
 DESC_PAIRS_KEYS = ("anc_pc", "anc_sn", "anc_node", "pos_pc", "pos_sn", "pos_node", "anc_pose", "pos_pose", "anc_seq",
                    "pos_id", "neg_idx", "neg_fail")
-DESC_PAIRS_DRAWS = dict(rows=torch.int32, cand=torch.int32, first=torch.int32, jit_pc=torch.float64,
-                        jit_sn=torch.float64, jit_node=torch.float64, params=torch.float64, tries=torch.int32,
-                        neg_pick=torch.int32)
+DESC_PAIRS_DRAWS = dict(_F5_DRAWS, tries=torch.int32, neg_pick=torch.int32)
+
+
+@_table
+def _desc_pairs_table(N: int, M: int, Cs: int, P: int) -> dict:
+    f, i32 = torch.float32, torch.int32
+    return dict(_cloud_table(N, M, Cs, P, "anc_", "pos_"), anc_pose=((P, 4, 4), f), pos_pose=((P, 4, 4), f),
+                anc_seq=((P,), i32), pos_id=((P,), i32), neg_idx=((P,), torch.int64), neg_fail=((1,), i32))
 
 
 def desc_pairs_shapes(recipe: DescPairsRecipeC, P: int) -> dict:
     """key -> (shape, dtype) of one batch of P pairs."""
-    c = recipe.cloud
-    f, i32 = torch.float32, torch.int32
-    return dict(anc_pc=((P, 3, c.N), f), anc_sn=((P, c.Cs, c.N), f), anc_node=((P, 3, c.M), f),
-                pos_pc=((P, 3, c.N), f), pos_sn=((P, c.Cs, c.N), f), pos_node=((P, 3, c.M), f),
-                anc_pose=((P, 4, 4), f), pos_pose=((P, 4, 4), f), anc_seq=((P,), i32), pos_id=((P,), i32),
-                neg_idx=((P,), torch.int64), neg_fail=((1,), i32))
+    return dict(cloud_batch_table(DESC_PAIRS, recipe, P))
 
 
-def desc_pairs_out_struct(ptr, out: dict, rows, node_slots) -> DescPairsOutC:
-    """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
-    return _clouds_out(DescPairsOutC(), ptr, out, ("anc", "pos"), DESC_PAIRS_KEYS[6:], rows, node_slots)
-
-
-def _desc_pairs_check(recipe: DescPairsRecipeC, bank: dict, scan_ids, out: dict, rows, node_slots, workspace):
-    """Every tensor the launch touches on the bank's device, with its dtype and shape (a pointer to another device's
-    memory would be dereferenced by the kernels).  Returns (P, the bank struct)."""
-    dev = bank["rows"].device
-    for k, dt in (("rows", torch.float32), ("offsets", torch.int64), ("poses", torch.float64), ("seq_of", torch.int32),
-                  ("seq_start", torch.int32)):
-        _need(bank[k], "bank " + k, dt)
-        if bank[k].device != dev:
-            raise RuntimeError("desc_pairs: bank %s on %s, the rows on %s" % (k, bank[k].device, dev))
-    import numpy as np
-    S, Q = bank["offsets"].numel() - 1, bank["seq_start"].numel() - 1
-    host = bank["seq_start_host"]
-    if tuple(bank["poses"].shape) != (S, 4, 4) or bank["seq_of"].numel() != S or host.dtype != np.int32 or \
+def _desc_pairs_bank(b: DescPairsBankC, bank: dict):
+    """bank: rows, offsets, poses, seq_of, seq_start (tensors), seq_start_host (int32 numpy), min_rows."""
+    S, Q, host = bank["offsets"].shape[0] - 1, bank["seq_start"].shape[0] - 1, bank["seq_start_host"]
+    if tuple(bank["poses"].shape) != (S, 4, 4) or tuple(bank["seq_of"].shape) != (S,) or host.dtype != "int32" or \
             host.size != Q + 1 or not host.flags.c_contiguous:
         raise RuntimeError("desc_pairs: poses f64 (S, 4, 4), seq_of i32 (S,), seq_start i32 (num_seq + 1,) on the "
                            "device and as a C-contiguous int32 numpy array")
-    _need(scan_ids, "scan_ids", torch.int32)
-    P = scan_ids.numel()
-    if scan_ids.device != dev:
-        raise RuntimeError("desc_pairs: scan_ids on %s, the bank on %s" % (scan_ids.device, dev))
-    for k, (shape, dt) in desc_pairs_shapes(recipe, P).items():
-        _need(out[k], k, dt)
-        if tuple(out[k].shape) != shape or out[k].device != dev:
-            raise RuntimeError("desc_pairs: %s must be %s %s on %s" % (k, dt, shape, dev))
-    _check_workspace_and_indices("desc_pairs", recipe.cloud, P, dev, workspace, desc_pairs_workspace_bytes(recipe, P), rows,
-                                 node_slots)
-    b = DescPairsBankC()
-    for k in ("rows", "offsets", "poses", "seq_of", "seq_start"):
-        setattr(b, k, bank[k].data_ptr())
-    b.seq_start_host, b.num_scans, b.num_seq, b.min_rows = host.ctypes.data, S, Q, int(bank["min_rows"])
-    return P, b
+    b.seq_start_host, b.num_scans, b.num_seq = host.ctypes.data, S, Q
 
 
-def _desc_pairs_bytes(recipe: DescPairsRecipeC, P: int) -> float:
-    c = recipe.cloud
-    return 2.0 * P * c.N * (32 + 4 * (3 + c.Cs))
+DESC_PAIRS = CloudBatchSpec(
+    ids="scan", tag="desc_pairs", out_c=DescPairsOutC, bank_c=DescPairsBankC, draws_c=DescPairsDrawsC,
+    bank=dict(_ROWS, poses=torch.float64, seq_of=torch.int32, seq_start=torch.int32), bank_meta=_desc_pairs_bank,
+    lead=_struct_lead, keys=DESC_PAIRS_KEYS, out_fields=_out_fields(DESC_PAIRS_KEYS, ("anc", "pos")),
+    table=_desc_pairs_table, draws=DESC_PAIRS_DRAWS, draw_fields=_draw_fields(own=("params", "tries", "neg_pick"), cloud=_F5_DRAWS),
+    draw_shapes=lambda c, P: dict(_f5_draw_shapes(c, P), tries=(P, None), neg_pick=(P,)),
+    required=("tries",), index_lead=lambda P: (2, P), clouds=2.0)
+
+
+def desc_pairs_out_struct(ptr, out: dict, rows, node_slots) -> DescPairsOutC:
+    return out_struct(DESC_PAIRS, ptr, out, rows, node_slots)
 
 
 def desc_pairs_build(recipe: DescPairsRecipeC, bank: dict, scan_ids: torch.Tensor, seed: int, step: int, pair_base: int,
                      out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
     """f-8: P descriptor pairs with Philox draws (usip_desc_pairs_build_f32) into `out` (DESC_PAIRS_KEYS -> tensors).
     bank: rows, offsets, poses, seq_of, seq_start (device tensors), seq_start_host (int32 numpy), min_rows."""
-    P, b = _desc_pairs_check(recipe, bank, scan_ids, out, rows, node_slots, workspace)
-    o = desc_pairs_out_struct(_data_ptr, out, rows, node_slots)
-    dev = bank["rows"].device
-    with torch.cuda.device(dev), prof.kernel("desc_pairs_build", _desc_pairs_bytes(recipe, P)):
-        _lib.check(_lib.lib().usip_desc_pairs_build_f32(
-            ctypes.addressof(recipe), ctypes.addressof(b), _ptr(scan_ids), P, int(seed) & 0xFFFFFFFFFFFFFFFF,
-            int(step) & 0xFFFFFFFFFFFFFFFF, int(pair_base), ctypes.addressof(o), _ptr(workspace),
-            _stream(bank["rows"])), "usip_desc_pairs_build_f32")
-    return out
-
-
-def desc_pairs_draws_struct(ptr, draws: dict, T: int) -> DescPairsDrawsC:
-    d = DescPairsDrawsC()
-    for k in DESC_PAIRS_DRAWS:
-        if draws.get(k) is not None:
-            setattr(d if k in ("params", "tries", "neg_pick") else d.cloud, k, ptr(draws[k]))
-    d.T = int(T)
-    return d
+    return cloud_batch(DESC_PAIRS, recipe, bank, scan_ids, out, workspace, rows, node_slots, counter=(seed, step, pair_base))
 
 
 def desc_pairs_apply(recipe: DescPairsRecipeC, draws: dict, bank: dict, scan_ids: torch.Tensor, out: dict,
                      workspace: torch.Tensor, rows=None, node_slots=None):
     """f-8 with explicit draws (usip_desc_pairs_apply_f32): DESC_PAIRS_DRAWS -> device tensors in the layouts of
     include/usip_hip.h; tries is i32 [P][T]."""
-    P, b = _desc_pairs_check(recipe, bank, scan_ids, out, rows, node_slots, workspace)
-    dev = bank["rows"].device
-    for k, dt in DESC_PAIRS_DRAWS.items():
-        t = draws.get(k)
-        if t is not None:
-            _need(t, k, dt)
-            if t.device != dev:
-                raise RuntimeError("desc_pairs: draw %s on %s, the bank on %s" % (k, t.device, dev))
-    tries = draws.get("tries")
-    if tries is None or tries.dim() != 2 or tries.shape[0] != P:
-        raise RuntimeError("desc_pairs: draw tries must be i32 (%d, T)" % P)
-    d = desc_pairs_draws_struct(_data_ptr, draws, tries.shape[1])
-    o = desc_pairs_out_struct(_data_ptr, out, rows, node_slots)
-    with torch.cuda.device(dev), prof.kernel("desc_pairs_apply", _desc_pairs_bytes(recipe, P)):
-        _lib.check(_lib.lib().usip_desc_pairs_apply_f32(
-            ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(scan_ids), P, ctypes.addressof(o),
-            _ptr(workspace), _stream(bank["rows"])), "usip_desc_pairs_apply_f32")
-    return out
+    return cloud_batch(DESC_PAIRS, recipe, bank, scan_ids, out, workspace, rows, node_slots, draws=draws)
 
 
 def desc_pairs_workspace_offset(recipe: DescPairsRecipeC, P: int, part: int) -> int:
     """Byte offset of workspace part 0 tables, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud scan ids, 5 total."""
-    return _workspace_query("usip_desc_pairs_workspace_offset", recipe, P, part)
+    return cloud_batch_workspace(DESC_PAIRS, recipe, P, part)
 
 
 def desc_pairs_workspace_bytes(recipe: DescPairsRecipeC, P: int) -> int:
-    return _workspace_query("usip_desc_pairs_workspace_bytes", recipe, P)
+    return cloud_batch_workspace(DESC_PAIRS, recipe, P)
 
 
-# ------------------------------------------------------------------------------- f-26 indoor descriptor batches (SceneNN)
-# include/usip_hip_indoor_pairs.h, which usip_hip.h includes: _lib keeps an included header's structs apart
+# ---- f-26 indoor descriptor batches (SceneNN): include/usip_hip_indoor_pairs.h, which usip_hip.h includes (_lib keeps
+# an included header's structs apart).  The draws struct is f-5's whole: rows, cand, first and params are read and may
+# not be absent (INDOOR_PAIRS_DRAWS); the three jitters are not read, may be absent, and are declared so that every
+# pointer of the nested struct has a draw that fills it
 IndoorPairsRecipeC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_recipe"]
 IndoorPairsBankC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_bank"]
 IndoorPairsDrawsC = _lib.STRUCTS_INCLUDED["usip_indoor_pairs_draws"]
@@ -1734,115 +1831,69 @@ INDOOR_PAIRS_KEYS = ("anc_pc", "anc_sn", "anc_node", "pos_pc", "pos_sn", "pos_no
 INDOOR_PAIRS_DRAWS = dict(rows=torch.int32, cand=torch.int32, first=torch.int32, params=torch.float64)
 
 
+@_table
+def _indoor_pairs_table(N: int, M: int, Cs: int, P: int) -> dict:
+    f = torch.float32
+    return dict(_cloud_table(N, M, Cs, P, "anc_", "pos_"), anc_R_pos=((P, 3, 3), f), anc_scale_pos=((P, 1), f),
+                anc_shift_pos=((P, 3, 1), f))
+
+
 def indoor_pairs_shapes(recipe: IndoorPairsRecipeC, P: int) -> dict:
     """key -> shape of one batch of P pairs (all float32): what IndoorDescriptorStep.step documents."""
-    c = recipe.cloud
-    return dict(anc_pc=(P, 3, c.N), anc_sn=(P, c.Cs, c.N), anc_node=(P, 3, c.M), pos_pc=(P, 3, c.N),
-                pos_sn=(P, c.Cs, c.N), pos_node=(P, 3, c.M), anc_R_pos=(P, 3, 3), anc_scale_pos=(P, 1),
-                anc_shift_pos=(P, 3, 1))
+    return _shapes(INDOOR_PAIRS, recipe, P)
+
+
+def _indoor_pairs_bank(b: IndoorPairsBankC, bank: dict):
+    """bank: rows, offsets, pairs, icp, sample_mode (tensors; the host twin: sample_mode or None), pairs_host (int32
+    numpy), min_rows."""
+    S, host, modes = bank["pairs"].shape[0], bank["pairs_host"], bank["sample_mode"]
+    if tuple(bank["pairs"].shape) != (S, 2) or tuple(bank["icp"].shape) != (S, 12) or host.dtype != "int32" or \
+            (modes is not None and tuple(modes.shape) != (S,)) or host.shape != (S, 2) or not host.flags.c_contiguous:
+        raise RuntimeError("indoor_pairs: pairs i32 (S, 2), icp f64 (S, 12), sample_mode i32 (S,) on the device and pairs "
+                           "as a C-contiguous int32 numpy array")
+    b.pairs_host, b.num_frames, b.num_samples = host.ctypes.data, bank["offsets"].shape[0] - 1, S
+
+
+INDOOR_PAIRS = CloudBatchSpec(
+    ids="sample", tag="indoor_pairs", out_c=IndoorPairsOutC, bank_c=IndoorPairsBankC, draws_c=IndoorPairsDrawsC,
+    bank=dict(_ROWS, pairs=torch.int32, icp=torch.float64, sample_mode=torch.int32), bank_meta=_indoor_pairs_bank,
+    lead=_struct_lead, keys=INDOOR_PAIRS_KEYS,
+    out_fields=_out_fields(INDOOR_PAIRS_KEYS, ("anc", "pos"),
+                           dict(anc_R_pos="R", anc_scale_pos="scale", anc_shift_pos="shift")),
+    table=_indoor_pairs_table, draws=_F5_DRAWS, draw_fields=_draw_fields(cloud=_F5_DRAWS),
+    draw_shapes=_f5_draw_shapes, required=tuple(INDOOR_PAIRS_DRAWS),
+    index_lead=lambda P: (2, P), clouds=2.0)
 
 
 def indoor_pairs_out_struct(ptr, out: dict, rows, node_slots) -> IndoorPairsOutC:
-    """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
-    o = _clouds_out(IndoorPairsOutC(), ptr, out, ("anc", "pos"), (), rows, node_slots)
-    o.R, o.scale, o.shift = ptr(out["anc_R_pos"]), ptr(out["anc_scale_pos"]), ptr(out["anc_shift_pos"])
-    return o
-
-
-def indoor_pairs_draws_struct(ptr, draws: dict) -> IndoorPairsDrawsC:
-    d = IndoorPairsDrawsC()
-    for k in INDOOR_PAIRS_DRAWS:
-        if draws.get(k) is not None:
-            setattr(d.cloud, k, ptr(draws[k]))
-    return d
-
-
-def _indoor_pairs_check(recipe: IndoorPairsRecipeC, bank: dict, sample_ids, out: dict, rows, node_slots, workspace):
-    """Every tensor the launch touches on the bank's device, with its dtype and shape.  Returns (P, the bank struct)."""
-    import numpy as np
-    dev = bank["rows"].device
-    for k, dt in (("rows", torch.float32), ("offsets", torch.int64), ("pairs", torch.int32), ("icp", torch.float64),
-                  ("sample_mode", torch.int32)):
-        _need(bank[k], "bank " + k, dt)
-        if bank[k].device != dev:
-            raise RuntimeError("indoor_pairs: bank %s on %s, the rows on %s" % (k, bank[k].device, dev))
-    F, S = bank["offsets"].numel() - 1, bank["pairs"].shape[0]
-    host = bank["pairs_host"]
-    if tuple(bank["pairs"].shape) != (S, 2) or tuple(bank["icp"].shape) != (S, 12) or bank["sample_mode"].numel() != S or \
-            host.dtype != np.int32 or host.shape != (S, 2) or not host.flags.c_contiguous:
-        raise RuntimeError("indoor_pairs: pairs i32 (S, 2), icp f64 (S, 12), sample_mode i32 (S,) on the device and pairs "
-                           "as a C-contiguous int32 numpy array")
-    _need(sample_ids, "sample_ids", torch.int32)
-    P = sample_ids.numel()
-    if sample_ids.device != dev:
-        raise RuntimeError("indoor_pairs: sample_ids on %s, the bank on %s" % (sample_ids.device, dev))
-    for k, shape in indoor_pairs_shapes(recipe, P).items():
-        _need(out[k], k, torch.float32)
-        if tuple(out[k].shape) != shape or out[k].device != dev:
-            raise RuntimeError("indoor_pairs: %s must be f32 %s on %s" % (k, shape, dev))
-    _check_workspace_and_indices("indoor_pairs", recipe.cloud, P, dev, workspace, indoor_pairs_workspace_bytes(recipe, P),
-                                 rows, node_slots)
-    b = IndoorPairsBankC()
-    for k in ("rows", "offsets", "pairs", "icp", "sample_mode"):
-        setattr(b, k, bank[k].data_ptr())
-    b.pairs_host, b.num_frames, b.num_samples, b.min_rows = host.ctypes.data, F, S, int(bank["min_rows"])
-    return P, b
-
-
-def _indoor_pairs_bytes(recipe: IndoorPairsRecipeC, P: int) -> float:
-    c = recipe.cloud
-    return 2.0 * P * c.N * (32 + 4 * (3 + c.Cs))
+    return out_struct(INDOOR_PAIRS, ptr, out, rows, node_slots)
 
 
 def indoor_pairs_build(recipe: IndoorPairsRecipeC, bank: dict, sample_ids: torch.Tensor, seed: int, step: int,
                        pair_base: int, out: dict, workspace: torch.Tensor, rows=None, node_slots=None):
     """f-26: P indoor descriptor pairs with Philox draws (usip_indoor_pairs_build_f32) into `out` (INDOOR_PAIRS_KEYS).
     bank: rows, offsets, pairs, icp, sample_mode (device tensors), pairs_host (int32 numpy), min_rows."""
-    P, b = _indoor_pairs_check(recipe, bank, sample_ids, out, rows, node_slots, workspace)
-    o = indoor_pairs_out_struct(_data_ptr, out, rows, node_slots)
-    dev = bank["rows"].device
-    with torch.cuda.device(dev), prof.kernel("indoor_pairs_build", _indoor_pairs_bytes(recipe, P)):
-        _lib.check(_lib.lib().usip_indoor_pairs_build_f32(
-            ctypes.addressof(recipe), ctypes.addressof(b), _ptr(sample_ids), P, int(seed) & 0xFFFFFFFFFFFFFFFF,
-            int(step) & 0xFFFFFFFFFFFFFFFF, int(pair_base), ctypes.addressof(o), _ptr(workspace),
-            _stream(bank["rows"])), "usip_indoor_pairs_build_f32")
-    return out
+    return cloud_batch(INDOOR_PAIRS, recipe, bank, sample_ids, out, workspace, rows, node_slots,
+                       counter=(seed, step, pair_base))
 
 
 def indoor_pairs_apply(recipe: IndoorPairsRecipeC, draws: dict, bank: dict, sample_ids: torch.Tensor, out: dict,
                        workspace: torch.Tensor, rows=None, node_slots=None):
     """f-26 with explicit draws (usip_indoor_pairs_apply_f32): INDOOR_PAIRS_DRAWS -> device tensors in f-5's layouts."""
-    P, b = _indoor_pairs_check(recipe, bank, sample_ids, out, rows, node_slots, workspace)
-    dev = bank["rows"].device
-    c = recipe.cloud
-    shapes = dict(rows=(P, 2, c.N), cand=(P, 2, c.n_sub), first=(P, 2), params=(P, 24))
-    for k, dt in INDOOR_PAIRS_DRAWS.items():
-        t = draws.get(k)
-        if t is None:
-            raise RuntimeError("indoor_pairs: draw %s is missing" % k)
-        _need(t, k, dt)
-        if t.device != dev or tuple(t.shape) != shapes[k]:
-            raise RuntimeError("indoor_pairs: draw %s must be %s on %s" % (k, shapes[k], dev))
-    d = indoor_pairs_draws_struct(_data_ptr, draws)
-    o = indoor_pairs_out_struct(_data_ptr, out, rows, node_slots)
-    with torch.cuda.device(dev), prof.kernel("indoor_pairs_apply", _indoor_pairs_bytes(recipe, P)):
-        _lib.check(_lib.lib().usip_indoor_pairs_apply_f32(
-            ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(sample_ids), P, ctypes.addressof(o),
-            _ptr(workspace), _stream(bank["rows"])), "usip_indoor_pairs_apply_f32")
-    return out
+    return cloud_batch(INDOOR_PAIRS, recipe, bank, sample_ids, out, workspace, rows, node_slots, draws=draws)
 
 
 def indoor_pairs_workspace_offset(recipe: IndoorPairsRecipeC, P: int, part: int) -> int:
     """Byte offset of workspace part 0 tables, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud frame ids, 5 total."""
-    return _workspace_query("usip_indoor_pairs_workspace_offset", recipe, P, part)
+    return cloud_batch_workspace(INDOOR_PAIRS, recipe, P, part)
 
 
 def indoor_pairs_workspace_bytes(recipe: IndoorPairsRecipeC, P: int) -> int:
-    return _workspace_query("usip_indoor_pairs_workspace_bytes", recipe, P)
+    return cloud_batch_workspace(INDOOR_PAIRS, recipe, P)
 
 
-# ------------------------------------------------------------------------------- f-27 evaluation batches from fragments
-# include/usip_hip_fragment_batch.h; the recipe is f-5's PairsRecipeC
+# ---- f-27 evaluation batches from fragments: include/usip_hip_fragment_batch.h; the recipe is f-5's PairsRecipeC, one
+# cloud per id, no pair_base, and the ids' host copy (range-checked by the library) rides along
 _FRAGMENT_BATCH_STRUCTS = _lib.INCLUDED["usip_hip_fragment_batch.h"][0]
 FragmentBatchBankC = _FRAGMENT_BATCH_STRUCTS["usip_fragment_batch_bank"]
 FragmentBatchDrawsC = _FRAGMENT_BATCH_STRUCTS["usip_fragment_batch_draws"]
@@ -1857,61 +1908,35 @@ def fragment_batch_clouds(B: int) -> int:
     return 2 * ((int(B) + 1) // 2)
 
 
+@_table
+def _fragment_batch_table(N: int, M: int, Cs: int, B: int) -> dict:
+    return _cloud_table(N, M, Cs, fragment_batch_clouds(B), "")
+
+
 def fragment_batch_shapes(recipe: PairsRecipeC, B: int) -> dict:
     """key -> shape of the buffers of one call of B fragments (float32): B2 = fragment_batch_clouds(B) clouds each."""
-    B2 = fragment_batch_clouds(B)
-    return dict(pc=(B2, 3, recipe.N), sn=(B2, recipe.Cs, recipe.N), node=(B2, 3, recipe.M))
+    return _shapes(FRAGMENT_BATCH, recipe, B)
+
+
+def _fragment_batch_bank(b: FragmentBatchBankC, bank: dict):
+    b.num_fragments = bank["offsets"].shape[0] - 1
+
+
+def _fragment_batch_lead(ptr, bank, b, ids, B, ids_host, on_device) -> tuple:
+    return (ctypes.addressof(b), ids) + ((ids_host,) if on_device else ()) + (B,)
+
+
+FRAGMENT_BATCH = CloudBatchSpec(
+    ids="fragment", tag="fragment_batch", out_c=FragmentBatchOutC, bank_c=FragmentBatchBankC,
+    draws_c=FragmentBatchDrawsC, bank=_ROWS, bank_meta=_fragment_batch_bank, lead=_fragment_batch_lead,
+    keys=FRAGMENT_BATCH_KEYS, out_fields=_out_fields(FRAGMENT_BATCH_KEYS), table=_fragment_batch_table,
+    draws=dict.fromkeys(FRAGMENT_BATCH_DRAWS, torch.int32), draw_fields=_draw_fields(own=FRAGMENT_BATCH_DRAWS),
+    draw_shapes=lambda c, B: dict(rows=(B, c.N), cand=(B, c.n_sub), first=(B,)), required=FRAGMENT_BATCH_DRAWS,
+    index_lead=lambda B: (fragment_batch_clouds(B),), clouds=1.0)
 
 
 def fragment_batch_out_struct(ptr, out: dict, rows, node_slots) -> FragmentBatchOutC:
-    """ptr: tensor or array -> address (device tensors here, numpy arrays for the host twin)."""
-    o = FragmentBatchOutC()
-    o.pc, o.sn, o.node = ptr(out["pc"]), ptr(out["sn"]), ptr(out["node"])
-    o.rows = ptr(rows) if rows is not None else None
-    o.node_slots = ptr(node_slots) if node_slots is not None else None
-    return o
-
-
-def _fragment_batch_check(recipe: PairsRecipeC, bank: dict, ids, out: dict, rows, node_slots, workspace):
-    """Every tensor the launch touches on the bank's device, with its dtype and shape.  Returns (B, the bank struct)."""
-    dev = bank["rows"].device
-    for k, dt in (("rows", torch.float32), ("offsets", torch.int64)):
-        _need(bank[k], "bank " + k, dt)
-        if bank[k].device != dev:
-            raise RuntimeError("fragment_batch: bank %s on %s, the rows on %s" % (k, bank[k].device, dev))
-    _need(ids, "ids", torch.int32)
-    B = ids.numel()
-    if ids.device != dev:
-        raise RuntimeError("fragment_batch: ids on %s, the bank on %s" % (ids.device, dev))
-    for k, shape in fragment_batch_shapes(recipe, B).items():
-        _need(out[k], k, torch.float32)
-        if tuple(out[k].shape) != shape or out[k].device != dev:
-            raise RuntimeError("fragment_batch: %s must be f32 %s on %s" % (k, shape, dev))
-    B2 = fragment_batch_clouds(B)
-    if workspace.device != dev or workspace.numel() * workspace.element_size() < fragment_batch_workspace_bytes(recipe, B):
-        raise RuntimeError("fragment_batch: the workspace must hold usip_fragment_batch_workspace_bytes() bytes on %s" % dev)
-    for name, t, n in (("rows", rows, recipe.N), ("node_slots", node_slots, recipe.M)):
-        if t is not None:
-            _need(t, name, torch.int32)
-            if tuple(t.shape) != (B2, n) or t.device != dev:
-                raise RuntimeError("fragment_batch: %s must be i32 (%d, %d) on %s" % (name, B2, n, dev))
-    b = FragmentBatchBankC()
-    b.rows, b.offsets = bank["rows"].data_ptr(), bank["offsets"].data_ptr()
-    b.num_fragments, b.min_rows = bank["offsets"].numel() - 1, int(bank["min_rows"])
-    return B, b
-
-
-def _fragment_batch_bytes(recipe: PairsRecipeC, B: int) -> float:
-    return 1.0 * B * recipe.N * (32 + 4 * (3 + recipe.Cs))
-
-
-def _ids_host_ptr(ids_host, B: int):
-    import numpy as np
-    if ids_host is None:
-        return None
-    if ids_host.dtype != np.int32 or ids_host.size != B or not ids_host.flags.c_contiguous:
-        raise RuntimeError("fragment_batch: ids_host must be a C-contiguous int32 numpy array of the ids")
-    return ids_host.ctypes.data
+    return out_struct(FRAGMENT_BATCH, ptr, out, rows, node_slots)
 
 
 def fragment_batch_build(recipe: PairsRecipeC, bank: dict, ids: torch.Tensor, ids_host, seed: int, step: int, out: dict,
@@ -1919,47 +1944,23 @@ def fragment_batch_build(recipe: PairsRecipeC, bank: dict, ids: torch.Tensor, id
     """f-27: B evaluation fragments with Philox draws (usip_fragment_batch_build_f32) into `out` (FRAGMENT_BATCH_KEYS, each
     holding fragment_batch_clouds(B) clouds).  bank: rows, offsets (device tensors), min_rows; ids_host: the ids as an
     int32 numpy array (range-checked by the library) or None."""
-    B, b = _fragment_batch_check(recipe, bank, ids, out, rows, node_slots, workspace)
-    o = fragment_batch_out_struct(_data_ptr, out, rows, node_slots)
-    dev = bank["rows"].device
-    with torch.cuda.device(dev), prof.kernel("fragment_batch_build", _fragment_batch_bytes(recipe, B)):
-        _lib.check(_lib.lib().usip_fragment_batch_build_f32(
-            ctypes.addressof(recipe), ctypes.addressof(b), _ptr(ids), _ids_host_ptr(ids_host, B), B,
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, ctypes.addressof(o), _ptr(workspace),
-            _stream(bank["rows"])), "usip_fragment_batch_build_f32")
-    return out
+    return cloud_batch(FRAGMENT_BATCH, recipe, bank, ids, out, workspace, rows, node_slots, counter=(seed, step),
+                       ids_host=ids_host)
 
 
 def fragment_batch_apply(recipe: PairsRecipeC, draws: dict, bank: dict, ids: torch.Tensor, ids_host, out: dict,
                          workspace: torch.Tensor, rows=None, node_slots=None):
     """f-27 with explicit draws (usip_fragment_batch_apply_f32): rows i32 (B, N), cand i32 (B, n_sub), first i32 (B,)."""
-    B, b = _fragment_batch_check(recipe, bank, ids, out, rows, node_slots, workspace)
-    dev = bank["rows"].device
-    shapes = dict(rows=(B, recipe.N), cand=(B, recipe.n_sub), first=(B,))
-    d = FragmentBatchDrawsC()
-    for k in FRAGMENT_BATCH_DRAWS:
-        t = draws.get(k)
-        if t is None:
-            raise RuntimeError("fragment_batch: draw %s is missing" % k)
-        _need(t, k, torch.int32)
-        if t.device != dev or tuple(t.shape) != shapes[k]:
-            raise RuntimeError("fragment_batch: draw %s must be %s on %s" % (k, shapes[k], dev))
-        setattr(d, k, t.data_ptr())
-    o = fragment_batch_out_struct(_data_ptr, out, rows, node_slots)
-    with torch.cuda.device(dev), prof.kernel("fragment_batch_apply", _fragment_batch_bytes(recipe, B)):
-        _lib.check(_lib.lib().usip_fragment_batch_apply_f32(
-            ctypes.addressof(recipe), ctypes.addressof(d), ctypes.addressof(b), _ptr(ids), _ids_host_ptr(ids_host, B), B,
-            ctypes.addressof(o), _ptr(workspace), _stream(bank["rows"])), "usip_fragment_batch_apply_f32")
-    return out
+    return cloud_batch(FRAGMENT_BATCH, recipe, bank, ids, out, workspace, rows, node_slots, draws=draws, ids_host=ids_host)
 
 
 def fragment_batch_workspace_offset(recipe: PairsRecipeC, B: int, part: int) -> int:
     """Byte offset of workspace part 0 table, 1 candidates, 2 first indices, 3 FPS picks, 4 cloud fragment ids, 5 total."""
-    return _workspace_query("usip_fragment_batch_workspace_offset", recipe, B, part)
+    return cloud_batch_workspace(FRAGMENT_BATCH, recipe, B, part)
 
 
 def fragment_batch_workspace_bytes(recipe: PairsRecipeC, B: int) -> int:
-    return _workspace_query("usip_fragment_batch_workspace_bytes", recipe, B)
+    return cloud_batch_workspace(FRAGMENT_BATCH, recipe, B)
 
 
 # ------------------------------------------------------------------------------------------------ f-6 evaluation

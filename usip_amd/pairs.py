@@ -178,6 +178,10 @@ class ScanBank:
         self.min_rows = int(self.lengths.min())
         return self
 
+    def c_dict(self) -> dict:
+        """What ops.cloud_batch takes as `bank`."""
+        return dict(rows=self.rows, offsets=self.offsets, min_rows=self.min_rows)
+
 
 def epoch_order(num_scans: int, seed: int, epoch: int) -> np.ndarray:
     """DataLoader(shuffle=True) order of one epoch: a permutation of the scans, a function of (seed, epoch) only."""
@@ -193,19 +197,28 @@ def epoch_batches(num_scans: int, pairs: int, seed: int, epoch: int, rank: int =
         yield order[k * g + rank * pairs:k * g + (rank + 1) * pairs]
 
 
+def _empty_batch(spec: ops.CloudBatchSpec, c, n: int, device, skip=()) -> Dict[str, torch.Tensor]:
+    """Buffers of a call of n ids, bar the keys in `skip`.  Every build writes every float; an integer output may be left
+    untouched (f-8's neg_idx / neg_fail when the recipe does not mine), so those start at 0."""
+    return {k: (torch.empty if dt == torch.float32 else torch.zeros)(shape, dtype=dt, device=device)
+            for k, (shape, dt) in ops.cloud_batch_table(spec, c, n).items() if k not in skip}
+
+
 def empty_batch(recipe: PairRecipe, pairs: int, device) -> Dict[str, torch.Tensor]:
-    P, N, M, Cs = pairs, recipe.N, recipe.M, recipe.Cs
-    shapes = dict(src_pc=(P, 3, N), src_sn=(P, Cs, N), src_node=(P, 3, M), dst_pc=(P, 3, N), dst_sn=(P, Cs, N),
-                  dst_node=(P, 3, M), R=(P, 3, 3), scale=(P,), shift=(P, 3, 1))
-    return {k: torch.empty(shapes[k], dtype=torch.float32, device=device) for k in KEYS}
+    return _empty_batch(ops.PAIRS, recipe, pairs, device)
+
+
+_NP = {torch.float32: np.float32, torch.float64: np.float64, torch.int32: np.int32, torch.int64: np.int64}
 
 
 class _CloudBuilder:
-    """What PairBuilder and desc_pairs.DescriptorPairBuilder share: the bookkeeping, the upload of the scan ids, the
-    optional index outputs, three workspaces ([0]: build / apply, [1], [2]: the two prefetch buffers) and prefetch.
-    A builder supplies its library's workspace functions, _check (its refusals), _empty_batch and build."""
+    """What the four builders share (PairBuilder, desc_pairs.DescriptorPairBuilder, indoor_pairs.IndoorPairBuilder,
+    fragment_batch.FragmentBatchBuilder): the bookkeeping, the upload of the ids, completing `out`, the optional index
+    outputs, build and apply, three workspaces ([0]: build / apply, [1], [2]: the two prefetch buffers) and prefetch.
+    A builder supplies its declaration `spec` (ops.CloudBatchSpec) and _check (its refusals).  pairs = 0: any number of
+    ids per call (the fragment builder, which keeps its own workspaces)."""
 
-    _workspace_bytes = _workspace_offset = None              # ops functions of (recipe struct, P[, part])
+    spec = None
     _modes = ("train", "test")
 
     def __init__(self, bank, recipe, pairs: int, device=None, seed: int = 0, rank: int = 0, mode: str = "train"):
@@ -216,8 +229,9 @@ class _CloudBuilder:
         self.seed, self.rank, self.mode = int(seed), int(rank), mode
         self.c = self._c_struct()
         self._check()
-        self._ws = [torch.empty(self._workspace_bytes(self.c, self.pairs), dtype=torch.uint8, device=self.device)
-                    for _ in range(3)]
+        self._bank, self._keys = bank.c_dict(), frozenset(self.spec.keys)
+        self._ws = [torch.empty(ops.cloud_batch_workspace(self.spec, self.c, self.pairs), dtype=torch.uint8,
+                                device=self.device) for _ in range(3 if self.pairs else 0)]
         self.last_rows = self.last_node_slots = None
 
     def _c_struct(self):
@@ -227,34 +241,88 @@ class _CloudBuilder:
         """What the ids of a call index: the bank's scans (the indoor builder: its samples)."""
         return self.bank.num_scans
 
-    def _ids(self, scan_ids) -> torch.Tensor:
-        if isinstance(scan_ids, torch.Tensor) and scan_ids.is_cuda:
-            if scan_ids.device != self.bank.device:
-                raise ValueError("PairBuilder: scan ids on %s, the bank on %s" % (scan_ids.device, self.bank.device))
-            ids = scan_ids.to(torch.int32).contiguous()
+    def _ids(self, ids, with_host: bool = False):
+        """-> the ids as an i32 device tensor; with_host: (that, their int32 host copy, or None for ids already on the
+        device)."""
+        name, what, host = type(self).__name__, self.spec.ids, None
+        if isinstance(ids, torch.Tensor) and ids.is_cuda:
+            if ids.device != self.bank.device:
+                raise ValueError("%s: %s ids on %s, the bank on %s" % (name, what, ids.device, self.bank.device))
+            dev = ids.to(torch.int32).contiguous()
+            dev = dev if dev.dim() == 1 else dev.reshape(-1)
         else:
-            h = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
+            h = np.asarray(ids, dtype=np.int64).reshape(-1)
             if h.size and (h.min() < 0 or h.max() >= self._num_ids()):
-                raise ValueError("PairBuilder: scan id out of range [0, %d)" % self._num_ids())
-            ids = torch.from_numpy(h.astype(np.int32)).pin_memory().to(self.device, non_blocking=True)
-        if ids.numel() != self.pairs:
-            raise ValueError("PairBuilder: %d scan ids for %d pairs" % (ids.numel(), self.pairs))
-        return ids
+                raise ValueError("%s: %s id out of range [0, %d)" % (name, what, self._num_ids()))
+            host = np.ascontiguousarray(h, dtype=np.int32)
+            dev = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+        n = dev.numel()
+        if self.pairs and n != self.pairs:
+            raise ValueError("%s: %d %s ids for %d pairs" % (name, n, what, self.pairs))
+        if n < 1:
+            raise ValueError("%s: no ids" % name)
+        return (dev, host) if with_host else dev
 
-    def _index_out(self, with_indices):
-        rows = nodes = None
+    def _empty_batch(self, n: Optional[int] = None):
+        return _empty_batch(self.spec, self.c, self.pairs if n is None else n, self.device)
+
+    def _out(self, n: int, out, with_indices):
+        """(the builder's keys: those `out` holds, fresh buffers for the rest; rows, node_slots).  Every key given:
+        nothing is allocated, and an `out` of exactly the keys is used as it is."""
+        keys = self.spec.keys
+        if out is None or out.keys() != self._keys:
+            given = {} if out is None else {k: out[k] for k in keys if k in out}
+            fresh = _empty_batch(self.spec, self.c, n, self.device, skip=given)
+            out = {k: given[k] if k in given else fresh[k] for k in keys}
+        return (out,) + self._index_out(n, with_indices)
+
+    def _index_out(self, n: int, with_indices):
+        self.last_rows = self.last_node_slots = rows = nodes = None
         if with_indices:
-            rows = torch.empty((2, self.pairs, self.recipe.N), dtype=torch.int32, device=self.device)
-            nodes = torch.empty((2, self.pairs, self.recipe.M), dtype=torch.int32, device=self.device)
-        self.last_rows, self.last_node_slots = rows, nodes
+            lead = self.spec.index_lead(n)
+            rows = torch.empty(lead + (self.recipe.N,), dtype=torch.int32, device=self.device)
+            nodes = torch.empty(lead + (self.recipe.M,), dtype=torch.int32, device=self.device)
+            self.last_rows, self.last_node_slots = self._of_call(dict(rows=rows, nodes=nodes), n).values()
         return rows, nodes
+
+    def _of_call(self, tensors: dict, n: int) -> dict:
+        """What a call of n ids hands back of the buffers it filled (the fragment builder: their first n clouds)."""
+        return tensors
+
+    def _workspace(self, n: int, which: int = 0) -> torch.Tensor:
+        return self._ws[which]
+
+    def _counter(self, step: int) -> tuple:
+        return (self.seed, int(step), self.rank * self.pairs)
+
+    def _run(self, ids, out, with_indices, which, counter=None, draws=None):
+        ids, host = self._ids(ids, with_host=True)
+        n = ids.numel()
+        out, rows, nodes = self._out(n, out, with_indices)
+        ops.cloud_batch(self.spec, self.c, self._bank, ids, out, self._workspace(n, which), rows, nodes, counter, draws,
+                        host)
+        return self._of_call(out, n)
+
+    def build(self, ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
+              _ws: int = 0) -> Dict[str, torch.Tensor]:
+        """Philox draws under (seed, step); `out` may hold any of the builder's KEYS, which are then written in place."""
+        return self._run(ids, out, with_indices, _ws, counter=self._counter(step))
+
+    def apply(self, ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
+        """The recorded draws of the reference (tests), as arrays in the header's layouts: held to them before any is
+        uploaded."""
+        h = {k: np.ascontiguousarray(draws[k], dtype=_NP[dt]) for k, dt in self.spec.draws.items()
+             if draws.get(k) is not None}
+        ops.check_draws(self.spec, ops.cloud_recipe(self.c), ids.numel() if isinstance(ids, torch.Tensor) else np.size(ids),
+                        h, ValueError)
+        return self._run(ids, out, with_indices, 0, draws={k: torch.from_numpy(a).to(self.device) for k, a in h.items()})
 
     def workspace_candidates(self, which: int = 0):
         """The un-augmented FPS candidates [2P, 3, n_sub] and first indices [2P] in workspace `which` (0: the last build
         or apply), at the offsets the library reports (usip_pairs_workspace_offset, usip_desc_pairs_workspace_offset)."""
         P, ns = self.pairs, self.recipe.n_sub
         ws = self._ws[which]
-        o_c, o_f = self._workspace_offset(self.c, P, 1), self._workspace_offset(self.c, P, 2)
+        o_c, o_f = (ops.cloud_batch_workspace(self.spec, self.c, P, part) for part in (1, 2))
         cand = ws[o_c:o_c + 2 * P * 3 * ns * 4].view(torch.float32).view(2 * P, 3, ns)
         first = ws[o_f:o_f + 2 * P * 4].view(torch.int32)
         return cand, first
@@ -323,61 +391,65 @@ class PairBuilder(_CloudBuilder):
     a live prefetch; two builds on two different streams at once are the caller's to order."""
 
     epoch_order = staticmethod(epoch_order)
-    _workspace_bytes = staticmethod(ops.pairs_workspace_bytes)
-    _workspace_offset = staticmethod(ops.pairs_workspace_offset)
+    spec = ops.PAIRS
 
     def _check(self):
         if self.recipe.require_full and self.bank.min_rows < self.recipe.N:
             raise ValueError("PairBuilder: this recipe needs scans of at least N = %d rows; the bank's shortest has %d"
                              % (self.recipe.N, self.bank.min_rows))
 
-    def _empty_batch(self):
-        return empty_batch(self.recipe, self.pairs, self.device)
 
-    def _out(self, out, with_indices):
-        return (out if out is not None else self._empty_batch(),) + self._index_out(with_indices)
+def bank_arrays(arrays: Sequence, what: str):
+    """The bank's arrays as float32 [rows, row_len]: one row length, none empty (`what` one of them is called)."""
+    arrays = [np.asarray(a, dtype=np.float32) for a in arrays]
+    if not arrays or any(a.ndim != 2 or a.shape[1] != arrays[0].shape[1] for a in arrays):
+        raise ValueError("build_cpu: %ss are [rows, row_len] arrays of one row length" % what)
+    if any(a.shape[0] == 0 for a in arrays):
+        raise ValueError("build_cpu: an empty %s" % what)
+    return arrays
 
-    def build(self, scan_ids, step: int, out: Optional[Dict[str, torch.Tensor]] = None, with_indices: bool = False,
-              _ws: int = 0) -> Dict[str, torch.Tensor]:
-        out, rows, nodes = self._out(out, with_indices)
-        ops.pairs_build(self.c, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, self.seed,
-                        int(step), self.rank * self.pairs, out, self._ws[_ws], rows, nodes)
-        return out
 
-    def apply(self, scan_ids, draws: Dict[str, np.ndarray], out=None, with_indices: bool = True):
-        out, rows, nodes = self._out(out, with_indices)
-        d = {k: torch.from_numpy(np.ascontiguousarray(v)).to(self.device) for k, v in draws.items() if v is not None}
-        ops.pairs_apply(self.c, d, self.bank.rows, self.bank.offsets, self._ids(scan_ids), self.bank.min_rows, out,
-                        self._ws[0], rows, nodes)
-        return out
+def host_twin(spec: ops.CloudBatchSpec, c_struct, arrays: Sequence[np.ndarray], what: str, ids, count: Optional[int],
+              bank: Optional[dict] = None, counter: tuple = (0, 0), draws: Optional[Dict[str, np.ndarray]] = None,
+              num_threads: Optional[int] = None):
+    """What the four build_cpu share, and the call of usip_<tag>_build_f32_cpu.  arrays: the bank's [rows, row_len] arrays
+    (`what` one of them is called); c_struct: row_len -> the recipe struct; count: the ids a call must have (None: any);
+    bank: what the bank struct holds beside rows, offsets and min_rows; counter: (seed, step[, pair_base]); draws: arrays
+    in the header's layouts, or None for Philox draws.  Returns (outputs, rows, node_slots) as numpy arrays."""
+    arrays = bank_arrays(arrays, what)
+    recipe = c_struct(arrays[0].shape[1])
+    c = ops.cloud_recipe(recipe)
+    lengths = [len(a) for a in arrays]
+    bank = dict(bank or {}, rows=np.ascontiguousarray(np.concatenate(arrays)), min_rows=min(lengths),
+                offsets=np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64))
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+    n = ids.size
+    if count is not None and n != int(count):
+        raise ValueError("build_cpu: %d %s ids for %d pairs" % (n, spec.ids, count))
+    out = {k: np.zeros(shape, dtype=_NP[dt]) for k, (shape, dt) in ops.cloud_batch_table(spec, recipe, n).items()}
+    rows = np.zeros(spec.index_lead(n) + (c.N,), dtype=np.int32)
+    nodes = np.zeros(spec.index_lead(n) + (c.M,), dtype=np.int32)
+    ptr = lambda a: a.ctypes.data   # noqa: E731
+    d = None
+    if draws is not None:
+        draws = {k: np.ascontiguousarray(draws[k], dtype=_NP[dt]) for k, dt in spec.draws.items()
+                 if draws.get(k) is not None}
+        ops.check_draws(spec, c, n, draws, ValueError)
+        d = ops.draws_struct(spec, ptr, draws)
+    b = ops.bank_struct(spec, ptr, bank)
+    o = ops.out_struct(spec, ptr, out, rows, nodes)
+    symbol = "usip_%s_build_f32_cpu" % spec.tag
+    args = (ctypes.addressof(recipe), ctypes.addressof(d) if d is not None else None)
+    args += spec.lead(ptr, bank, b, ptr(ids), n, None, False) + ops.counter_args(counter) + (ctypes.addressof(o),)
+    _lib.check(getattr(_lib.lib(), symbol)(*args, *(() if num_threads is None else (int(num_threads),))), symbol)
+    return out, rows, nodes
 
 
 def build_cpu(recipe: PairRecipe, scans: Sequence[np.ndarray], scan_ids, pairs: int, seed: int = 0, step: int = 0,
               rank: int = 0, mode: str = "train", draws: Optional[Dict[str, np.ndarray]] = None):
     """The host twin (usip_pairs_build_f32_cpu) on numpy scans: Philox draws, or `draws` (the layouts of
     include/usip_hip.h).  Returns (batch, rows [2,P,N], node_slots [2,P,M])."""
-    c = recipe.c_struct(mode == "train")
-    bank = np.ascontiguousarray(np.concatenate([np.asarray(s, dtype=np.float32) for s in scans]))
-    offsets = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
-    ids = np.ascontiguousarray(np.asarray(scan_ids, dtype=np.int32))
-    P, N, M, Cs = pairs, recipe.N, recipe.M, recipe.Cs
-    out = {k: np.zeros(s, dtype=np.float32) for k, s in dict(
-        src_pc=(P, 3, N), src_sn=(P, Cs, N), src_node=(P, 3, M), dst_pc=(P, 3, N), dst_sn=(P, Cs, N), dst_node=(P, 3, M),
-        R=(P, 3, 3), scale=(P,), shift=(P, 3, 1)).items()}
-    rows = np.zeros((2, P, N), dtype=np.int32)
-    nodes = np.zeros((2, P, M), dtype=np.int32)
-    o = ops._pairs_out(lambda a: a.ctypes.data, out, rows, nodes)
-    keep = []
-    d = None
-    if draws is not None:
-        d = ops.PairsDrawsC()
-        for k, _ in ops.PairsDrawsC._fields_:
-            if draws.get(k) is not None:
-                a = np.ascontiguousarray(draws[k], dtype=np.int32 if k in ("rows", "cand", "first") else np.float64)
-                keep.append(a)
-                setattr(d, k, a.ctypes.data)
-    _lib.check(_lib.lib().usip_pairs_build_f32_cpu(
-        ctypes.addressof(c), ctypes.addressof(d) if d is not None else None, bank.ctypes.data, offsets.ctypes.data,
-        len(scans), ids.ctypes.data, P, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF, rank * P,
-        ctypes.addressof(o)), "usip_pairs_build_f32_cpu")
-    return out, rows, nodes
+    return host_twin(ops.PAIRS, lambda row_len: recipe.c_struct(mode == "train"), scans, "scan", scan_ids, pairs,
+                     counter=(seed, step, rank * int(pairs)), draws=draws)
+
+
