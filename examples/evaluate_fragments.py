@@ -19,6 +19,8 @@ Registration on the mutual nearest descriptors, at most 1024 keypoints per fragm
 point-to-point ICP (pcregrigid's InlierRatio 0.3; --refine-iterations N, default 20; --refine-tolerance T R, default 0.01 m
 0.009 rad), the share of moved points within 0.05 m recomputed and the log gated by `> 0.15` instead of `> 0.23`.  The log
 holds the unrefined estimate, as the reference's does; --log-transform refined writes the refined pose instead.
+--refine-metric plane refines under pcregrigid's 'pointToPlane' metric instead (default point): the downsampled fragments
+get their 9-nearest normals, and every kept point is drawn towards the plane through its nearest point.
 
 --optimize (needs --refine icp) adds split_txt_compute_G.m and the robust pose-graph optimisation behind it: the dense
 information matrix of every pair under its refined pose, the log's pairs as a pose graph, the loop closures the graph does
@@ -187,6 +189,7 @@ def evaluate_scene(name, scenes, results, gt_root, args):
     ev = fr.FragmentEvaluator(None, None, None, args.device, top=top, k=args.k, max_trials=args.trials, seed=args.seed,
                               batch_pairs=args.batch_pairs, registrator=args.registration, refine=args.refine == "icp",
                               refine_args=dict(max_iterations=args.refine_iterations, tolerance=tuple(args.refine_tolerance)),
+                              refine_metric={"point": "point_to_point", "plane": "point_to_plane"}[args.refine_metric],
                               log_transform=args.log_transform, optimize=args.optimize,
                               optimize_args=dict(tau2=args.optimize_tau2, fill=args.optimize_fill,
                                                  transform=args.optimize_transform) if args.optimize else None)
@@ -238,6 +241,7 @@ def main():
     ap.add_argument("--trials", type=int, default=fr.MAX_TRIALS)
     ap.add_argument("--registration", choices=("ransac", "fgr"), default="ransac")
     ap.add_argument("--refine", choices=("none", "icp"), default="none")
+    ap.add_argument("--refine-metric", choices=("point", "plane"), default="point")
     ap.add_argument("--log-transform", choices=("estimate", "refined"), default="estimate")
     ap.add_argument("--refine-tolerance", type=float, nargs=2, metavar=("T", "R"), default=list(fr.REFINE_TOLERANCE))
     ap.add_argument("--refine-iterations", type=int, default=fr.REFINE_ITERATIONS)
@@ -294,6 +298,8 @@ def main():
         ap.error("--log-transform refined needs --refine icp")
     if args.optimize and args.refine != "icp":
         ap.error("--optimize needs --refine icp")
+    if args.refine_metric != "point" and args.refine != "icp":
+        ap.error("--refine-metric plane needs --refine icp")
     if args.make_synthetic:
         scenes, results, gt = make_synthetic(args.make_synthetic, args.fragments, args.points, args.dim, args.seed)
         names = ["synthetic"]
@@ -307,6 +313,8 @@ def main():
         out.update(descriptor_method=args.descriptor_method, method=args.method)
     if args.refine != "none":
         out.update(refine=args.refine, log_transform=args.log_transform)
+    if args.refine_metric != "point":
+        out.update(refine_metric=args.refine_metric)
     for k in ("recall", "precision", "inlier_num_mean", "inlier_ratio_mean"):          # evaluate.m's last line: means
         out[k] = float(np.mean([s[k] for s in per_scene.values()]))
     for k in ("pairs", "written"):

@@ -1690,6 +1690,52 @@ int usip_unit_columns_f32_cpu(const float* x, int B, int C, int M, float eps, fl
 int usip_unit_columns_backward_f32_cpu(const float* grad, const float* x, const float* norm, int B, int C, int M, float eps,
                                        float* dx, int num_threads);
 
+/* ------------------------------------------------------------------ f-28  trimmed ICP under the point-to-plane metric
+ * pcregrigid's 'Metric' option 'pointToPlane' for the refinement of f-13: every kept row of B is drawn towards the PLANE
+ * through its nearest row of A instead of towards that row, so a cloud may slide along a wall while it is still off it.
+ * pcregrigid is a MATLAB built-in; the definition is this project's own (the linearised point-to-plane fit of Chen and
+ * Medioni 1992 as Low 2004 states it, one Gauss-Newton step per iteration).  f-13's conventions apply word for word: float32
+ * inputs, float64 arithmetic, never contracted, sums in a fixed order, no floating-point atomics, no launch synchronises the
+ * host, every index read from memory is clamped before use.  csrc/icp_plane_math.h is the arithmetic.
+ *
+ * The bank is f-13's with row_len >= 6: x y z, then the row's unit normal nx ny nz in float32 (f-7's scan normals of the
+ * DOWNSAMPLED rows: fragments.RefineBank(normals=True)); row_len < 6 is USIP_EINVAL.  Only the normals of A are read.
+ *
+ * usip_icp_refine_plane_f32 is f-13's loop with another step 3.  Steps 1, 2 and 5, the final pass, mask, order2, Lmax,
+ * cut_d2 / cut_i, visits, stage_ms, the workspace and the limits are f-13's: the trim stays on the POINT distance d2, rmse
+ * stays the root mean kept d2.  Step 3 under the current pose (R, t), for every kept row i of B in f-13's lane-strided order
+ * (lane l of 256 adds its kept rows among l, l + 256, ... in ascending i, then f-6's binary tree, each of the 27 columns alone):
+ *    q = R b_i + t by f-9's xform (the bits the search used); a, n = the position and normal of row idx[i] of A, widened;
+ *    c = (q1 n2 - q2 n1, q2 n0 - q0 n2, q0 n1 - q1 n0);  J = (c0, c1, c2, n0, n1, n2);
+ *    r = ((q0 - a0) n0 + (q1 - a1) n1) + (q2 - a2) n2;
+ *    27 sums: the 21 entries H_jk += J_j J_k (j <= k, row-major), then the six g_j += J_j r.
+ * H x = -g is solved by a Cholesky factorisation written as f-12's solve6 is, for a full upper triangle: the factor column by
+ * column, inner sums subtracted in ascending k, then the forward and the backward substitution.  The new pose is f-12's
+ * apply_step: R <- D R, t <- D t + x3..5 with D = Rz(x2) Ry(x1) Rx(x0) from f-12's sine and cosine.
+ * A solve FAILS on a pivot that is not finite and positive, a component of x that is not finite, or |x0..2| > pi.  A failed
+ * solve ends the pair exactly as f-13's rule 4 does: the last pose stays, converged = 0, iterations = k - 1, and the final
+ * pass still runs.  There is no damping and no fallback to the other metric: a fragment whose normals are all zero (fewer
+ * rows than the normals need), all parallel (one wall) or all in one plane (two walls) fails its first solve and keeps Rt0.
+ * Negating any of the normals changes no bit of any output: J and r change sign together, and every sum is of their products.
+ *
+ * fit_sums f64 [P][max_iterations][27], optional (NULL): the 27 sums of every fit that ran -- the one whose solve failed
+ * included -- fit k at [k - 1], zeros elsewhere; what cut_d2 / cut_i are for the trim. */
+int usip_icp_refine_plane_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                              const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt0,
+                              const uint8_t* mask, const int32_t* order2, int P, int Lmax, double inlier_ratio,
+                              int max_iterations, double tol_t, double tol_c, double align_radius, void* workspace,
+                              long long workspace_bytes, double* Rt, int32_t* iterations, uint8_t* converged, double* rmse,
+                              int32_t* hits, double* ratio, double* cut_d2, int32_t* cut_i, unsigned long long* visits,
+                              double* stage_ms, double* fit_sums, void* stream);
+/* HOST twin (every pointer on the host), as usip_icp_refine_f32_cpu is f-13's. */
+int usip_icp_refine_plane_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                                  const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt0,
+                                  const uint8_t* mask, const int32_t* order2, int P, int Lmax, double inlier_ratio,
+                                  int max_iterations, double tol_t, double tol_c, double align_radius, double* Rt,
+                                  int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
+                                  double* cut_d2, int32_t* cut_i, int32_t* idx_out, double* d2_out, double* fit_sums,
+                                  int num_threads);
+
 #ifdef __cplusplus
 }
 #endif

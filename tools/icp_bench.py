@@ -9,8 +9,13 @@ it, in the same run: the full-cloud overlap walk of the same pairs, and the libr
 search is the loop over all rows) on `--threads` threads, timed on `--host-pairs` of the refined pairs and scaled to them.
 One JSON line; --out writes it to a file as well.
 
+--metric plane times the same stages under the point-to-plane metric (f-28): the bank is built with normals (the downsampling
+stage then includes them), the loop runs icp_fit_plane_kernel, and -- in the same process, after it, on the same bank and
+estimates -- the point-to-point loop runs once more, so that "beside_point_to_point" holds the other fit's stage times and
+iterations per pair next to this one's.
+
     python tools/icp_bench.py [--fragments 57] [--points 100000] [--keypoints 512] [--batch-pairs 32] [--threads 16]
-                              [--host-pairs 8] [--out profiles/f13_icp_bench.json]"""
+                              [--host-pairs 8] [--metric point|plane] [--out profiles/f13_icp_bench.json]"""
 import argparse
 import json
 import os
@@ -44,8 +49,11 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--host-pairs", type=int, default=8)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--metric", choices=("point", "plane"), default="point")
     ap.add_argument("--out")
     a = ap.parse_args()
+    metric = {"point": "point_to_point", "plane": "point_to_plane"}[a.metric]
+    plane = a.metric == "plane"
     F, M = a.fragments, a.keypoints
     span, step = 5.0, 1.0
     marks = int(round(M * (span + (F - 1) * step) / span))
@@ -57,9 +65,9 @@ def main():
     pairs = [(i, j) for i in range(F) for j in range(i + 1, F)]
     f1h, f2h = np.array([p[0] for p in pairs], np.int32), np.array([p[1] for p in pairs], np.int32)
     bank = fr.FragmentBank(sc["clouds"], "cuda:0")
-    fr.RefineBank(sc["clouds"][:2], "cuda:0")                              # warm-up
+    fr.RefineBank(sc["clouds"][:2], "cuda:0", normals=plane)               # warm-up
     torch.cuda.synchronize()
-    fine, ev_down = timed(lambda: fr.RefineBank(sc["clouds"], "cuda:0"))
+    fine, ev_down = timed(lambda: fr.RefineBank(sc["clouds"], "cuda:0", normals=plane))
     dkp, dde, dcnt = [torch.from_numpy(t).cuda() for t in (kp, de, cnt)]
     f1d, f2d = torch.from_numpy(f1h).cuda(), torch.from_numpy(f2h).cuda()
     ir, it, tt, tc, ar = fr._refine_args(fr.REFINE_INLIER_RATIO, fr.REFINE_ITERATIONS, fr.REFINE_TOLERANCE, fr.REFINE_RADIUS)
@@ -68,7 +76,7 @@ def main():
     stage = np.zeros(4)
     outs = []
 
-    def run_all(limit=None, measure=True):
+    def run_all(limit=None, measure=True, metric=metric, stage=stage, outs=outs):
         for base in range(0, len(pairs) if limit is None else limit, a.batch_pairs):
             sl = slice(base, min(base + a.batch_pairs, len(pairs)))
             i1, i2 = f1d[sl].long(), f2d[sl].long()
@@ -90,7 +98,7 @@ def main():
                                                      stable=True).to(torch.int32))
             events["keys_sort"].append(ev)
             o = ops.icp_refine(fine.rows, fine.offsets, fine.perm, g1, g2, Rt, fine.lmax, mask, order2, ir, it, tt, tc, ar,
-                               want_visits=True, want_stage_ms=measure)
+                               want_visits=True, want_stage_ms=measure, metric=metric)
             if measure:
                 stage[:] += o["stage_ms"]
                 outs.append((mask, o["iterations"], o["converged"], o["visits"], o["ratio"], ratio, reg.inlier_ratio, Rt, o["Rt"]))
@@ -104,6 +112,18 @@ def main():
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     ms = {k: sum(s.elapsed_time(e) for s, e in v) for k, v in events.items()}
+    beside = None
+    if plane:                                                              # the other fit, same process, same bank and estimates
+        stage_pt, outs_pt = np.zeros(4), []
+        run_all(a.batch_pairs, False, "point_to_point")
+        torch.cuda.synchronize()
+        run_all(None, True, "point_to_point", stage_pt, outs_pt)
+        torch.cuda.synchronize()
+        m_pt, it_pt, conv_pt = [torch.cat([o[k] for o in outs_pt]).cpu().numpy() for k in range(3)]
+        beside = {"device_stage_ms": {"nearest": round(stage_pt[0], 2), "trim": round(stage_pt[1], 2), "fit": round(stage_pt[2], 2),
+                                      "final_pass": round(stage_pt[3], 2)},
+                  "iterations_mean": round(float(it_pt[m_pt != 0].mean()), 2) if (m_pt != 0).any() else 0,
+                  "pairs_converged": int(conv_pt[m_pt != 0].sum())}
     mask, iters, conv, visits, ratio_ref, ratio_full, inl, Rt0, Rt1 = [torch.cat([o[k] for o in outs]).cpu().numpy() for k in range(9)]
     refined = mask != 0
     lengths = np.asarray(fine.lengths, np.float64)
@@ -118,12 +138,12 @@ def main():
     host_ms = 0.0
     if len(pick):
         t0 = time.perf_counter()
-        h = fr.icp_refine_cpu(host_bank, f1h[pick], f2h[pick], Rt0[pick], None, num_threads=a.threads)
+        h = fr.icp_refine_cpu(host_bank, f1h[pick], f2h[pick], Rt0[pick], None, num_threads=a.threads, metric=metric)
         host_ms = (time.perf_counter() - t0) * 1e3
         assert np.array_equal(h.iterations, iters[pick]) and np.array_equal(h.Rt.view(np.uint64), Rt1[pick].view(np.uint64))
     device_ms = float(stage.sum())
     host_scaled = host_ms * int(refined.sum()) / max(len(pick), 1)
-    res = {"what": "icp_bench",
+    res = {"what": "icp_bench", "metric": metric,
            "shape": {"fragments": F, "pairs": len(pairs), "points_per_fragment": a.points, "keypoints": M,
                      "batch_pairs": a.batch_pairs, "leaf": fr.REFINE_LEAF, "rows_per_downsampled_fragment_mean":
                      round(float(lengths.mean()), 1), "rows_per_downsampled_fragment_max": int(lengths.max())},
@@ -142,6 +162,8 @@ def main():
            "gates": {"first_gate": int(((ratio_full[:, 0] > fr.GATE_ALIGNED) & (inl > fr.GATE_INLIER_RATIO)).sum()),
                      "refined_gate": int(((ratio_ref[:, 0] > fr.GATE_REFINED) & (inl > fr.GATE_INLIER_RATIO)).sum())},
            "device": torch.cuda.get_device_name(0), "host": platform.processor() or platform.machine()}
+    if beside is not None:
+        res["beside_point_to_point"] = beside
     line = json.dumps(res)
     print(line)
     if a.out:

@@ -17,10 +17,10 @@
 //   icp_fit_kernel       one workgroup per pair: two lane-strided passes over the kept rows (centroids, then B[10]), the
 //                        tree; every lane solves (8 Jacobi sweeps) and lane 0 advances the pose, the histories, the state.
 //   icp_final_kernel     one workgroup per pair: the hits within the radius, the root mean kept d2.
+// Under the point-to-plane metric the same sequence launches csrc/icp_plane.hip's icp_fit_plane_kernel in
+// icp_fit_kernel's place; csrc/icp_state.h is what the two files share.
 #include <vector>
-#include "common.h"
-#include "bank.h"
-#include "icp_math.h"
+#include "icp_state.h"
 #include "tile_walk.h"
 
 using namespace usip_reg;
@@ -39,17 +39,6 @@ constexpr int WAVES = usip_walk::WALK_WAVES;
 struct SortedBank : Bank {
     const int32_t* perm1;
 };
-
-struct Pairs {
-    const int32_t* frag1;
-    const int32_t* frag2;
-    int Lmax;
-};
-
-__device__ __forceinline__ Range range_of(const Bank& bank, const int32_t* frag, int p, int lmax)
-{
-    return bank.range(frag[p], lmax);
-}
 
 // Exclusive scan of one flag per lane over the workgroup; the caller puts a barrier between two calls.
 __device__ __forceinline__ int block_scan(bool flag, int* wave_tot, int* total)
@@ -288,27 +277,7 @@ __global__ __launch_bounds__(LANES) void icp_fit_kernel(Bank bank, Pairs pr, con
     for (int k = 0; k < 10; ++k) B[k] = part[0][k];
     double Rn[12];
     transform_from(B, ca, cb, Rn);                                     // every lane: the same instructions on the same values
-    if (l != 0) return;
-    double* Rt = Rt_all + (long long)p * 12;
-    double* h = hist_all + (long long)p * 6;
-    if (!finite12(Rn)) {                                               // the last finite pose stays
-        state[p] = STOPPED;
-        return;
-    }
-    double old[12], dt, dc;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) old[k] = Rt[k];
-    pose_delta(Rn, old, &dt, &dc);
-#pragma unroll
-    for (int k = 0; k < 12; ++k) Rt[k] = Rn[k];
-    push(h, dt);
-    push(h + 3, dc);
-    const int k = iterations[p] + 1;
-    iterations[p] = k;
-    if (recent_mean(h, k) <= tol_t && recent_mean(h + 3, k) <= tol_c) {
-        converged[p] = 1;
-        state[p] = STOPPED;
-    }
+    if (l == 0) advance(finite12(Rn), Rn, p, tol_t, tol_c, state, Rt_all, hist_all, iterations, converged);
 }
 
 __global__ __launch_bounds__(LANES) void icp_final_kernel(Bank bank, Pairs pr, const int32_t* __restrict__ state,
@@ -390,16 +359,17 @@ extern "C" int usip_icp_nearest_f32(const float* rows, int row_len, const int64_
     return USIP_OK;
 }
 
-extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags,
-                                   long long total_rows, const int32_t* perm1, const int32_t* frag1, const int32_t* frag2,
-                                   const double* Rt0, const uint8_t* mask, const int32_t* order2, int P, int Lmax,
-                                   double inlier_ratio, int max_iterations, double tol_t, double tol_c, double align_radius,
-                                   void* workspace, long long workspace_bytes, double* Rt, int32_t* iterations,
-                                   uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
-                                   double* cut_d2, int32_t* cut_i_out, unsigned long long* visits, double* stage_ms,
-                                   void* stream)
+// Both entries of the loop: everything but the fit's launch is one sequence, whatever the metric.  fit_sums: the plane
+// metric's optional record.
+static int refine_loop(bool plane, const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                       const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt0,
+                       const uint8_t* mask, const int32_t* order2, int P, int Lmax, double inlier_ratio, int max_iterations,
+                       double tol_t, double tol_c, double align_radius, void* workspace, long long workspace_bytes, double* Rt,
+                       int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits, double* ratio, double* cut_d2,
+                       int32_t* cut_i_out, unsigned long long* visits, double* stage_ms, double* fit_sums, void* stream)
 {
-    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1)) return USIP_EINVAL;
+    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1) || (plane && row_len < 6))
+        return USIP_EINVAL;
     if (!(inlier_ratio > 0.0 && inlier_ratio <= 1.0) || max_iterations < 0 || max_iterations > MAX_ITERATIONS ||
         !(tol_t >= 0.0) || !(tol_c >= 0.0) || !(align_radius > 0.0))
         return USIP_EINVAL;
@@ -423,6 +393,8 @@ extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t
     const int slots = max_iterations + 1;
     if (e == hipSuccess && cut_d2) e = hipMemsetAsync(cut_d2, 0, (size_t)P * slots * sizeof(double), st);
     if (e == hipSuccess && cut_d2) e = hipMemsetAsync(cut_i_out, 0, (size_t)P * slots * sizeof(int32_t), st);
+    if (e == hipSuccess && fit_sums && max_iterations > 0)
+        e = hipMemsetAsync(fit_sums, 0, (size_t)P * max_iterations * PLANE_SUMS * sizeof(double), st);
     if (e != hipSuccess) return (int)e;
     const SortedBank bank{{rows, offsets, row_len, num_frags, total_rows}, perm1};
     const Pairs pr{frag1, frag2, Lmax};
@@ -456,7 +428,11 @@ extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t
                     (const unsigned long long*)d2bits, cut_bits, cut_i, cut_d2, cut_i_out, round, slots);
         USIP_LAUNCH_CHECK();
         mark();
-        if (!final_pass) {
+        if (!final_pass && plane) {
+            const int rc = launch_fit_plane(bank, pr, P, idx, d2bits, cut_bits, cut_i, tol_t, tol_c, state, Rt, hist,
+                                            iterations, converged, fit_sums, max_iterations, st);
+            if (rc != USIP_OK) return rc;
+        } else if (!final_pass) {
             USIP_LAUNCH(icp_fit_kernel, dim3(P), dim3(LANES), 0, st, bank, pr, (const int32_t*)idx,
                         (const unsigned long long*)d2bits, (const unsigned long long*)cut_bits, (const int32_t*)cut_i,
                         inlier_ratio, tol_t, tol_c, state, Rt, hist, iterations, converged);
@@ -478,4 +454,32 @@ extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t
         if (marks.err != hipSuccess) return (int)marks.err;
     }
     return USIP_OK;
+}
+
+extern "C" int usip_icp_refine_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags,
+                                   long long total_rows, const int32_t* perm1, const int32_t* frag1, const int32_t* frag2,
+                                   const double* Rt0, const uint8_t* mask, const int32_t* order2, int P, int Lmax,
+                                   double inlier_ratio, int max_iterations, double tol_t, double tol_c, double align_radius,
+                                   void* workspace, long long workspace_bytes, double* Rt, int32_t* iterations,
+                                   uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
+                                   double* cut_d2, int32_t* cut_i_out, unsigned long long* visits, double* stage_ms,
+                                   void* stream)
+{
+    return refine_loop(false, rows, row_len, offsets, num_frags, total_rows, perm1, frag1, frag2, Rt0, mask, order2, P, Lmax,
+                       inlier_ratio, max_iterations, tol_t, tol_c, align_radius, workspace, workspace_bytes, Rt, iterations,
+                       converged, rmse, hits, ratio, cut_d2, cut_i_out, visits, stage_ms, nullptr, stream);
+}
+
+extern "C" int usip_icp_refine_plane_f32(const float* rows, int row_len, const int64_t* offsets, int num_frags,
+                                         long long total_rows, const int32_t* perm1, const int32_t* frag1,
+                                         const int32_t* frag2, const double* Rt0, const uint8_t* mask, const int32_t* order2,
+                                         int P, int Lmax, double inlier_ratio, int max_iterations, double tol_t, double tol_c,
+                                         double align_radius, void* workspace, long long workspace_bytes, double* Rt,
+                                         int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits, double* ratio,
+                                         double* cut_d2, int32_t* cut_i_out, unsigned long long* visits, double* stage_ms,
+                                         double* fit_sums, void* stream)
+{
+    return refine_loop(true, rows, row_len, offsets, num_frags, total_rows, perm1, frag1, frag2, Rt0, mask, order2, P, Lmax,
+                       inlier_ratio, max_iterations, tol_t, tol_c, align_radius, workspace, workspace_bytes, Rt, iterations,
+                       converged, rmse, hits, ratio, cut_d2, cut_i_out, visits, stage_ms, fit_sums, stream);
 }

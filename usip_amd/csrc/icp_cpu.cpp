@@ -2,7 +2,8 @@
 // (csrc/icp_math.h) on host pointers.  The nearest-neighbour search is the plain loop over ALL rows of fragment 1 in
 // ascending row order -- which is what proves the device's walk; the trim is a sort of (bit pattern, row); every sum is
 // taken in the device's order (LANES strided partial sums, then the binary tree).  num_threads splits the pairs.  Never
-// reached from the device entry points.
+// reached from the device entry points.  The point-to-plane metric (csrc/icp_plane_math.h) is the same loop
+// with another fit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -10,6 +11,7 @@
 #include "bank.h"
 #include "host_split.h"
 #include "icp_math.h"
+#include "icp_plane_math.h"
 #include "../../include/usip_hip.h"
 
 using namespace usip_reg;
@@ -66,7 +68,7 @@ void cut_of(const double* d2, int n2, int m, std::vector<std::pair<unsigned long
 
 struct Scratch {
     std::vector<std::pair<unsigned long long, int>> key;
-    std::vector<double> part;
+    std::vector<double> part, lanes;
     Scratch() : part((size_t)LANES * 10) {}
     double (*parts())[10] { return reinterpret_cast<double (*)[10]>(part.data()); }
 };
@@ -108,6 +110,36 @@ void fit_of(const Bank& bank, const Pair& pr, const int32_t* idx, const double* 
     transform_from(B, ca, cb, Rn);
 }
 
+// the fit under the plane metric (f-28): the lanes' 27 partial sums, the tree in the device's rounds of nine columns, the
+// solve and the step.  S: the 27 sums.  false: the solve failed.
+bool fit_plane_of(const Bank& bank, const Pair& pr, const double* Rt, const int32_t* idx, const double* d2,
+                  unsigned long long cut, int icut, Scratch& sc, double S[PLANE_SUMS], double Rn[12])
+{
+    double (*part)[10] = sc.parts();
+    const int row_len = bank.row_len;
+    sc.lanes.assign((size_t)LANES * PLANE_SUMS, 0.0);
+    for (int l = 0; l < LANES; ++l) {
+        double* s = sc.lanes.data() + (size_t)l * PLANE_SUMS;
+        for (int i = l; i < pr.n2; i += LANES)
+            if (kept(bits_of(d2[i]), i, cut, icut)) {
+                const float* a = pr.rows1 + (long long)clamp_index(idx[i], pr.n1) * row_len;
+                const float* b = pr.rows2 + (long long)i * row_len;
+                const double b0 = (double)b[0], b1 = (double)b[1], b2 = (double)b[2];
+                plane_terms(s, xform(Rt, 0, b0, b1, b2), xform(Rt, 1, b0, b1, b2), xform(Rt, 2, b0, b1, b2), a);
+            }
+    }
+    for (int base = 0; base < PLANE_SUMS; base += 9) {
+        for (int l = 0; l < LANES; ++l)
+            for (int k = 0; k < 9; ++k) part[l][k] = sc.lanes[(size_t)l * PLANE_SUMS + base + k];
+        tree_sum<9>(part);
+        for (int k = 0; k < 9; ++k) S[base + k] = part[0][k];
+    }
+    double x[6];
+    const bool ok = plane_solve(S, x);
+    if (ok) plane_step(Rt, x, Rn);                                     // (a failed solve's x may hold anything)
+    return ok;
+}
+
 }  // namespace
 
 extern "C" int usip_icp_nearest_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
@@ -133,15 +165,16 @@ extern "C" int usip_icp_nearest_f32_cpu(const float* rows, int row_len, const in
     return USIP_OK;
 }
 
-extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
-                                       long long total_rows, const int32_t* perm1, const int32_t* frag1,
-                                       const int32_t* frag2, const double* Rt0, const uint8_t* mask, const int32_t* order2,
-                                       int P, int Lmax, double inlier_ratio, int max_iterations, double tol_t, double tol_c,
-                                       double align_radius, double* Rt_out, int32_t* iterations, uint8_t* converged,
-                                       double* rmse, int32_t* hits, double* ratio, double* cut_d2, int32_t* cut_i_out,
-                                       int32_t* idx_out, double* d2_out, int num_threads)
+// Both entries of the loop; only the fit differs with the metric.  fit_sums: the plane metric's optional record.
+static int refine_loop(bool plane, const float* rows, int row_len, const int64_t* offsets, int num_frags, long long total_rows,
+                       const int32_t* perm1, const int32_t* frag1, const int32_t* frag2, const double* Rt0,
+                       const uint8_t* mask, const int32_t* order2, int P, int Lmax, double inlier_ratio, int max_iterations,
+                       double tol_t, double tol_c, double align_radius, double* Rt_out, int32_t* iterations,
+                       uint8_t* converged, double* rmse, int32_t* hits, double* ratio, double* cut_d2, int32_t* cut_i_out,
+                       int32_t* idx_out, double* d2_out, double* fit_sums, int num_threads)
 {
-    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1)) return USIP_EINVAL;
+    if (!(bank_ok(rows, row_len, offsets, num_frags, total_rows, P, Lmax) && perm1) || (plane && row_len < 6))
+        return USIP_EINVAL;
     if (!(inlier_ratio > 0.0 && inlier_ratio <= 1.0) || max_iterations < 0 || max_iterations > MAX_ITERATIONS ||
         !(tol_t >= 0.0) || !(tol_c >= 0.0) || !(align_radius > 0.0))
         return USIP_EINVAL;
@@ -154,6 +187,7 @@ extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int
         std::memset(cut_d2, 0, sizeof(double) * (size_t)P * (size_t)slots);
         std::memset(cut_i_out, 0, sizeof(int32_t) * (size_t)P * (size_t)slots);
     }
+    if (fit_sums && max_iterations > 0) std::memset(fit_sums, 0, sizeof(double) * (size_t)P * (size_t)max_iterations * PLANE_SUMS);
     const Bank bank{rows, offsets, row_len, num_frags, total_rows};
     const double r2hi = radius_sq_hi(align_radius);
     if (idx_out) std::memset(idx_out, 0, sizeof(int32_t) * (size_t)P * (size_t)Lmax);
@@ -187,8 +221,17 @@ extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int
                     cut_i_out[(long long)p * slots + k - 1] = icut;
                 }
                 double Rn[12], dt, dc;
-                fit_of(bank, pr, idx.data(), d2.data(), cut, icut, m, sc, Rn);
-                if (!finite12(Rn)) break;
+                bool ok;
+                if (plane) {
+                    double S[PLANE_SUMS];
+                    ok = fit_plane_of(bank, pr, Rt, idx.data(), d2.data(), cut, icut, sc, S, Rn);
+                    if (fit_sums)
+                        std::memcpy(fit_sums + ((long long)p * max_iterations + k - 1) * PLANE_SUMS, S, sizeof(S));
+                } else {
+                    fit_of(bank, pr, idx.data(), d2.data(), cut, icut, m, sc, Rn);
+                    ok = finite12(Rn);
+                }
+                if (!ok) break;
                 pose_delta(Rn, Rt, &dt, &dc);
                 for (int e = 0; e < 12; ++e) Rt[e] = Rn[e];
                 push(h, dt);
@@ -224,4 +267,31 @@ extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int
         }
     });
     return USIP_OK;
+}
+
+extern "C" int usip_icp_refine_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
+                                       long long total_rows, const int32_t* perm1, const int32_t* frag1,
+                                       const int32_t* frag2, const double* Rt0, const uint8_t* mask, const int32_t* order2,
+                                       int P, int Lmax, double inlier_ratio, int max_iterations, double tol_t, double tol_c,
+                                       double align_radius, double* Rt_out, int32_t* iterations, uint8_t* converged,
+                                       double* rmse, int32_t* hits, double* ratio, double* cut_d2, int32_t* cut_i_out,
+                                       int32_t* idx_out, double* d2_out, int num_threads)
+{
+    return refine_loop(false, rows, row_len, offsets, num_frags, total_rows, perm1, frag1, frag2, Rt0, mask, order2, P, Lmax,
+                       inlier_ratio, max_iterations, tol_t, tol_c, align_radius, Rt_out, iterations, converged, rmse, hits,
+                       ratio, cut_d2, cut_i_out, idx_out, d2_out, nullptr, num_threads);
+}
+
+extern "C" int usip_icp_refine_plane_f32_cpu(const float* rows, int row_len, const int64_t* offsets, int num_frags,
+                                             long long total_rows, const int32_t* perm1, const int32_t* frag1,
+                                             const int32_t* frag2, const double* Rt0, const uint8_t* mask,
+                                             const int32_t* order2, int P, int Lmax, double inlier_ratio, int max_iterations,
+                                             double tol_t, double tol_c, double align_radius, double* Rt_out,
+                                             int32_t* iterations, uint8_t* converged, double* rmse, int32_t* hits,
+                                             double* ratio, double* cut_d2, int32_t* cut_i_out, int32_t* idx_out,
+                                             double* d2_out, double* fit_sums, int num_threads)
+{
+    return refine_loop(true, rows, row_len, offsets, num_frags, total_rows, perm1, frag1, frag2, Rt0, mask, order2, P, Lmax,
+                       inlier_ratio, max_iterations, tol_t, tol_c, align_radius, Rt_out, iterations, converged, rmse, hits,
+                       ratio, cut_d2, cut_i_out, idx_out, d2_out, fit_sums, num_threads);
 }

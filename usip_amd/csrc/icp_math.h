@@ -18,6 +18,7 @@ namespace usip_icp {
 constexpr int LANES = 256;              // lanes of every workgroup; the strided sums' width (= usip_reg::REFIT_LANES)
 constexpr int TILE = 256;               // fragment-1 rows per LDS tile of the walk
 constexpr int MAX_ITERATIONS = 64;
+constexpr int PLANE_SUMS = 27;          // f-28's fit (csrc/icp_plane_math.h): H_00 H_01 .. H_05 H_11 .. H_55, then g_0 .. g_5
 constexpr int RUNNING = 0, STOPPED = 1, NOT_REFINED = 2;               // a pair's state between the launches
 static_assert(LANES == usip_reg::REFIT_LANES, "the fit's sums go through registration_math.h's tree");
 

@@ -12,7 +12,8 @@ mrEvaluateRegistrationMy.m).
   overlap_ratio            ratioAligned: the share of each full fragment with a point of the other closer than 0.2 m
   RefineBank / icp_refine  writeLogReconputeAlign.m: both fragments voxel-averaged at 0.04 m, the estimate refined by trimmed
                            point-to-point ICP (pcregrigid's InlierRatio 0.3), the share of moved points within 0.05 m and
-                           the second gate, `> 0.15` (csrc/icp.hip)
+                           the second gate, `> 0.15` (csrc/icp.hip); metric "point_to_plane", on a bank built
+                           with normals, is pcregrigid's 'pointToPlane' (csrc/icp_plane_math.h)
   optimize                 split_txt_compute_G.m and the robust pose-graph optimisation behind it: the dense information of
                            every pair under its refined pose, the loop closures the graph does not support pruned, recall
                            and precision after pruning (usip_amd/posegraph.py, csrc/posegraph.hip)
@@ -51,6 +52,7 @@ GATE_ALIGNED, GATE_INLIER_RATIO = 0.23, 0.025                                # w
 GATE_REFINED, REFINE_LEAF, REFINE_RADIUS, REFINE_INLIER_RATIO = 0.15, 0.04, 0.05, 0.3      # writeLogReconputeAlign.m
 REFINE_ITERATIONS, REFINE_TOLERANCE = 20, (0.01, 0.009)                      # pcregrigid's documented defaults
 IcpResult = namedtuple("IcpResult", "Rt iterations converged rmse hits ratio")
+REFINE_METRICS, NORMALS_K = ops.ICP_METRICS, 9                                # f-28: pcregrigid's 'Metric'; f-7's neighbours
 REFINE_KEYS = ("refined_Rt", "refine_iterations", "refine_converged", "refined_ratio_aligned", "refined_hits", "gate_refined")
 
 
@@ -179,13 +181,31 @@ class RefineBank(FragmentBank):
     """The fragments' clouds voxel-averaged at `leaf` (pcdownsample 'gridAverage', f-7's kernels; positions only: a zero
     reflectance column and zero normals go in), in ONE float32 device buffer [rows, 3] with offsets and the x-order of every
     fragment, as FragmentBank holds the full clouds.  Built once per scene: every fragment's cell count is read from the
-    device here, nothing is read after."""
+    device here, nothing is read after.
 
-    def __init__(self, clouds: Sequence, device, leaf: float = REFINE_LEAF):
-        self.leaf = float(leaf)
+    normals=True (what the point-to-plane metric reads, f-28): the buffer is [rows, 6], the voxel-averaged positions and
+    their unit normals -- per fragment f-7's 9 nearest neighbours (ops.scan_knn on the bank's own x-order) and ops.scan_normals
+    of the DOWNSAMPLED rows, turned towards the fragment frame's origin, its float32 rounding.  A fragment of fewer than 10
+    downsampled rows is below scan_knn's limit and gets zero normals: a pair that takes it as fragment 1 fails its first
+    plane fit and keeps the pose it came with."""
+
+    def __init__(self, clouds: Sequence, device, leaf: float = REFINE_LEAF, normals: bool = False):
+        self.leaf, self.normals = float(leaf), bool(normals)
         if not self.leaf > 0.0:
             raise ValueError("RefineBank: leaf must be positive")
         FragmentBank.__init__(self, [self._downsample(_rows3(c, torch.device(device))) for c in clouds], device)
+        if self.normals:
+            self.rows = torch.cat((self.rows, self._normals()), 1).contiguous()
+
+    def _normals(self):
+        out = self.rows.new_zeros((self.rows.shape[0], 3))
+        for lo, n in zip(self.offsets_host.tolist(), self.lengths):
+            if n < NORMALS_K + 1:
+                continue
+            xyzi = torch.cat((self.rows[lo:lo + n], self.rows.new_zeros((n, 1))), 1).contiguous()
+            idx = ops.scan_knn(xyzi, self.perm[lo:lo + n].contiguous(), NORMALS_K)
+            out[lo:lo + n] = ops.scan_normals(xyzi, idx, (0.0, 0.0, 0.0))[1][:, :3]
+        return out
 
     def _downsample(self, xyz):
         n = xyz.shape[0]
@@ -210,20 +230,25 @@ def _refine_args(inlier_ratio, max_iterations, tolerance, align_radius):
 
 def icp_refine(bank: RefineBank, frag1, frag2, Rt, mask=None, inlier_ratio: float = REFINE_INLIER_RATIO,
                max_iterations: int = REFINE_ITERATIONS, tolerance=REFINE_TOLERANCE,
-               align_radius: float = REFINE_RADIUS, want_cuts: bool = False) -> IcpResult:
+               align_radius: float = REFINE_RADIUS, want_cuts: bool = False, metric: str = "point_to_point",
+               want_sums: bool = False) -> IcpResult:
     """writeLogReconputeAlign.m's refinement for a batch of pairs, on the device: frag1, frag2 i32 [P] into the bank, Rt f64
     [P,3,4] the estimate (fragment 2 into fragment 1), mask bool or u8 [P] (pairs with 0 are not refined: Rt stays, the rest
     is 0).  tolerance = (translation, rotation in radians) on the mean change of the last three iterations, pcregrigid's.
     -> IcpResult(Rt, iterations, converged, rmse, hits, ratio f64 [P,2] = hits over either fragment's downsampled length).
     Fragment 2's rows are sorted along their moved x here, by the keys the library computes.  No host synchronisation.
-    want_cuts: -> (IcpResult, cut_d2 f64, cut_i i32 [P,max_iterations+1]), the trim's cut of every pass, the final pass last."""
+    want_cuts: -> (IcpResult, cut_d2 f64, cut_i i32 [P,max_iterations+1]), the trim's cut of every pass, the final pass last.
+    metric "point_to_plane" (f-28; the bank built with normals=True, otherwise ValueError): every kept row is drawn towards
+    the plane through its nearest row instead of towards the row; the trim, the stopping rule, the final pass and the
+    fields are the same.  want_sums (that metric only): the tuple ends with fit_sums f64 [P,max_iterations,27]."""
     ir, it, tt, tc, ar = _refine_args(inlier_ratio, max_iterations, tolerance, align_radius)
     Rt = Rt.contiguous()
     m = None if mask is None else mask.to(torch.uint8).contiguous()
     o = ops.icp_refine(bank.rows, bank.offsets, bank.perm, frag1, frag2, Rt, bank.lmax, m, moved_x_order(bank, frag2, Rt),
-                       ir, it, tt, tc, ar, want_cuts=want_cuts)
+                       ir, it, tt, tc, ar, want_cuts=want_cuts, metric=metric, want_sums=want_sums)
     res = IcpResult(o["Rt"], o["iterations"], o["converged"], o["rmse"], o["hits"], o["ratio"])
-    return (res, o["cut_d2"], o["cut_i"]) if want_cuts else res
+    extra = ((o["cut_d2"], o["cut_i"]) if want_cuts else ()) + ((o["fit_sums"],) if want_sums else ())
+    return (res,) + extra if extra else res
 
 
 def _refined(out, res: IcpResult):
@@ -366,19 +391,27 @@ def overlap_ratio_cpu(bank: HostBank, frag1, frag2, Rt, radius: float = OVERLAP_
     return ratio, hits
 
 
-def refine_bank_cpu(clouds: Sequence, leaf: float = REFINE_LEAF) -> HostBank:
-    """RefineBank on the host: every cloud through the grid average's host twin -> HostBank of the downsampled rows [rows, 3]."""
+def refine_bank_cpu(clouds: Sequence, leaf: float = REFINE_LEAF, normals: bool = False) -> HostBank:
+    """RefineBank on the host: every cloud through the grid average's host twin -> HostBank of the downsampled rows [rows, 3];
+    normals=True: [rows, 6], with the normals of prepare.knn_cpu / normals_cpu on the downsampled rows (zeros below 10 rows)."""
     parts = []
     for c in clouds:
         a = np.ascontiguousarray(np.asarray(c)[:, :3], dtype=np.float32)
-        if a.shape[0] == 0:
-            parts.append(a)
-            continue
-        xyzi = np.ascontiguousarray(np.concatenate((a, np.zeros((a.shape[0], 1), np.float32)), 1))
-        parts.append(np.ascontiguousarray(prepare.grid_cpu(xyzi, np.zeros((a.shape[0], 4)), float(leaf))[0][:, :3]))
+        if a.shape[0]:
+            xyzi = np.ascontiguousarray(np.concatenate((a, np.zeros((a.shape[0], 1), np.float32)), 1))
+            a = np.ascontiguousarray(prepare.grid_cpu(xyzi, np.zeros((a.shape[0], 4)), float(leaf))[0][:, :3])
+        parts.append(a)
     if not parts:
         raise ValueError("refine_bank_cpu: no fragments")
-    return host_bank(parts)
+    bank = host_bank(parts)
+    if not normals:
+        return bank
+    nrm = np.zeros((bank.rows.shape[0], 3), np.float32)
+    for lo, a in zip(bank.offsets.tolist(), parts):
+        if a.shape[0] >= NORMALS_K + 1:
+            xyzi = np.ascontiguousarray(np.concatenate((a, np.zeros((a.shape[0], 1), np.float32)), 1))
+            nrm[lo:lo + a.shape[0]] = prepare.normals_cpu(xyzi, None, NORMALS_K, (0.0, 0.0, 0.0))[2][:, :3]
+    return bank._replace(rows=np.ascontiguousarray(np.concatenate((bank.rows, nrm), 1)))
 
 
 def _icp_host(bank: HostBank, frag1, frag2, Rt, mask, order2):
@@ -417,9 +450,19 @@ def icp_nearest_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, order2=None, nu
 
 def icp_refine_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, inlier_ratio: float = REFINE_INLIER_RATIO,
                    max_iterations: int = REFINE_ITERATIONS, tolerance=REFINE_TOLERANCE, align_radius: float = REFINE_RADIUS,
-                   num_threads: int = 1, want_neighbours: bool = False, order2="moved_x", want_cuts: bool = False):
+                   num_threads: int = 1, want_neighbours: bool = False, order2="moved_x", want_cuts: bool = False,
+                   metric: str = "point_to_point", want_sums: bool = False):
     """icp_refine on numpy arrays over the host twin -> IcpResult; with want_neighbours also the final pass's (idx, d2); with
-    want_cuts also (cut_d2 f64, cut_i i32) [P,max_iterations+1]: the trim's cut (d2*, i*) of every pass, the final pass last."""
+    want_cuts also (cut_d2 f64, cut_i i32) [P,max_iterations+1]: the trim's cut (d2*, i*) of every pass, the final pass last;
+    with want_sums (metric "point_to_plane" only) also fit_sums f64 [P,max_iterations,27]."""
+    if metric not in REFINE_METRICS:
+        raise ValueError("icp: metric must be one of %s (got %r)" % (", ".join(REFINE_METRICS), metric))
+    plane = metric == "point_to_plane"
+    if want_sums and not plane:
+        raise ValueError("icp: want_sums is the point_to_plane metric's")
+    if plane and np.shape(bank.rows)[1] < 6:
+        raise ValueError("icp: the point_to_plane metric needs a bank with normals, rows f32 [total,>=6] (got row_len %d)"
+                         % np.shape(bank.rows)[1])
     ir, it, tt, tc, ar = _refine_args(inlier_ratio, max_iterations, tolerance, align_radius)
     if isinstance(order2, str):
         order2 = moved_x_order_cpu(bank, frag2, Rt)
@@ -429,10 +472,12 @@ def icp_refine_cpu(bank: HostBank, frag1, frag2, Rt, mask=None, inlier_ratio: fl
                     np.zeros((P, 2)))
     idx, d2 = (np.zeros((P, L), np.int32), np.zeros((P, L))) if want_neighbours else (None, None)
     cd, ci = (np.zeros((P, it + 1)), np.zeros((P, it + 1), np.int32)) if want_cuts else (None, None)
-    _lib.check(_lib.lib().usip_icp_refine_f32_cpu(
+    sums = np.zeros((P, it, 27)) if want_sums else None
+    name = "usip_icp_refine_plane_f32_cpu" if plane else "usip_icp_refine_f32_cpu"
+    _lib.check(getattr(_lib.lib(), name)(
         *args, ir, it, tt, tc, ar, _p(out.Rt), _p(out.iterations), _p(out.converged), _p(out.rmse), _p(out.hits),
-        _p(out.ratio), _p(cd), _p(ci), _p(idx), _p(d2), int(num_threads)), "usip_icp_refine_f32_cpu")
-    extra = ((idx, d2) if want_neighbours else ()) + ((cd, ci) if want_cuts else ())
+        _p(out.ratio), _p(cd), _p(ci), _p(idx), _p(d2), *((_p(sums),) if plane else ()), int(num_threads)), name)
+    extra = ((idx, d2) if want_neighbours else ()) + ((cd, ci) if want_cuts else ()) + ((sums,) if want_sums else ())
     return (out,) + extra if extra else out
 
 
@@ -466,12 +511,14 @@ def _host(nt: int) -> _Backend:
 
 
 def _register_pairs(be, name, kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k, threshold, max_trials, radius,
-                    seed, registrator, refine, refine_args, dense_radius):
+                    seed, registrator, refine, refine_args, dense_radius, refine_metric):
     """register_pairs over the backend `be` (_DEVICE, or _host(num_threads))."""
     if registrator not in ("ransac", "fgr"):
         raise ValueError("registrator must be 'ransac' or 'fgr' (got %r)" % (registrator,))
     if dense_radius is not None and refine is None:
         raise ValueError("%s: dense_radius needs refine" % name)
+    if refine_metric not in REFINE_METRICS:
+        raise ValueError("%s: refine_metric must be one of %s (got %r)" % (name, ", ".join(REFINE_METRICS), refine_metric))
     k = 1 if registrator == "fgr" else k
     nn12, _ = be.match(desc1, desc2, n1, n2, k)
     nn21, _ = be.match(desc2, desc1, n2, n1, k)
@@ -493,7 +540,7 @@ def _register_pairs(be, name, kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2
                gate=(ratio[:, 0] > GATE_ALIGNED) & (reg.inlier_ratio > GATE_INLIER_RATIO), frag1=frag1, frag2=frag2)
     if refine is not None:
         mask = (out["valid"] != 0) & (out["inlier_ratio"] > GATE_INLIER_RATIO)
-        _refined(out, be.refine(refine, frag1, frag2, out["Rt"], mask, **(refine_args or {})))
+        _refined(out, be.refine(refine, frag1, frag2, out["Rt"], mask, metric=refine_metric, **(refine_args or {})))
         if dense_radius is not None:
             out["dense_information"], out["dense_count"] = be.dense(refine, frag1, frag2, out["refined_Rt"], mask, dense_radius)
     return out
@@ -502,7 +549,8 @@ def _register_pairs(be, name, kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2
 def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                    threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
                    seed: int = 0, registrator: str = "ransac", refine: Optional[RefineBank] = None,
-                   refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None) -> Dict[str, torch.Tensor]:
+                   refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None,
+                   refine_metric: str = "point_to_point") -> Dict[str, torch.Tensor]:
     """register2Fragments.m for a batch of pairs, on the device: kp f32 [P,3,M], desc f32 [P,D,M], n i32 [P] of either
     fragment; frag1, frag2 i32 [P] into the bank; pair_ids i64 [P] key the draws.  No host synchronisation.
 
@@ -516,21 +564,25 @@ def register_pairs(kp1, desc1, n1, kp2, desc2, n2, bank: FragmentBank, frag1, fr
     icp_refine(refine, frag1, frag2, Rt, mask = valid & inlier_ratio > 0.025, **refine_args) and the keys refined_Rt,
     refine_iterations, refine_converged, refined_ratio_aligned, refined_hits and gate_refined = refined ratio(1) > 0.15 &
     inlier_ratio > 0.025.  A pair outside the mask fails that gate whatever ICP would find.  Every other key is unchanged.
+    refine_metric "point_to_plane" (f-28) refines under the plane metric instead, on a bank that carries normals
+    (RefineBank(..., normals=True)); the keys are the same under either metric.
 
     dense_radius (with refine): split_txt_compute_G.m's computeInformation 'point' under refined_Rt, over the same mask:
     the keys dense_information f64 [P,6,6] and dense_count i32 [P] (posegraph.dense_information)."""
     return _register_pairs(_DEVICE, "register_pairs", kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2, pair_ids, k,
-                           threshold, max_trials, radius, seed, registrator, refine, refine_args, dense_radius)
+                           threshold, max_trials, radius, seed, registrator, refine, refine_args, dense_radius, refine_metric)
 
 
 def register_pairs_cpu(kp1, desc1, n1, kp2, desc2, n2, bank: HostBank, frag1, frag2, pair_ids, k: int = K_MATCH,
                        threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS, radius: float = OVERLAP_RADIUS,
                        seed: int = 0, num_threads: int = 1, registrator: str = "ransac", refine: Optional[HostBank] = None,
-                       refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None) -> Dict[str, np.ndarray]:
+                       refine_args: Optional[Dict] = None, dense_radius: Optional[float] = None,
+                       refine_metric: str = "point_to_point") -> Dict[str, np.ndarray]:
     """register_pairs assembled from the host twins, on numpy arrays; refine: the HostBank of the downsampled fragments
-    (refine_bank_cpu, or RefineBank.host())."""
+    (refine_bank_cpu, or RefineBank.host(); with normals for refine_metric "point_to_plane")."""
     return _register_pairs(_host(int(num_threads)), "register_pairs_cpu", kp1, desc1, n1, kp2, desc2, n2, bank, frag1, frag2,
-                           pair_ids, k, threshold, max_trials, radius, seed, registrator, refine, refine_args, dense_radius)
+                           pair_ids, k, threshold, max_trials, radius, seed, registrator, refine, refine_args, dense_radius,
+                           refine_metric)
 
 
 # ------------------------------------------------------------------------------------------------ the score
@@ -718,13 +770,20 @@ class FragmentEvaluator:
     prune, iterations1, iterations2 (include/usip_hip.h f-14), fill ("gt": a missing odometry pair comes from gt.log and
     gt.info, the default when evaluate() is given them; "estimate": from the pair's ungated estimate; None), transform
     ("edge" or "graph": what the refined log's entries hold), radius.  summarize() then also returns loop_recall,
-    loop_precision, loops_in, loops_kept, and per pair dense_information, dense_count, loop_weight, loop_kept, loop_Rt."""
+    loop_precision, loops_in, loops_kept, and per pair dense_information, dense_count, loop_weight, loop_kept, loop_Rt.
+
+    refine_metric "point_to_plane" (with refine): the refinement runs under the plane metric (f-28) and refine_bank() builds
+    the downsampled fragments' normals; the second gate, the refined log and the graph read the same keys as before."""
 
     def __init__(self, detector, descriptor, opt, device, nms_radius: float = 0.1, top: int = 512, k: int = K_MATCH,
                  inlier_threshold: float = INLIER_THRESHOLD, max_trials: int = MAX_TRIALS,
                  overlap_radius: float = OVERLAP_RADIUS, seed: int = 0, batch_pairs: int = 32, registrator: str = "ransac",
                  refine: bool = False, refine_leaf: float = REFINE_LEAF, refine_args: Optional[Dict] = None,
-                 log_transform: str = "estimate", optimize: bool = False, optimize_args: Optional[Dict] = None):
+                 log_transform: str = "estimate", optimize: bool = False, optimize_args: Optional[Dict] = None,
+                 refine_metric: str = "point_to_point"):
+        if refine_metric not in REFINE_METRICS:
+            raise ValueError("refine_metric must be one of %s (got %r)" % (", ".join(REFINE_METRICS), refine_metric))
+        self.refine_metric = refine_metric
         if log_transform not in ("estimate", "refined"):
             raise ValueError("log_transform must be 'estimate' or 'refined' (got %r)" % (log_transform,))
         if log_transform == "refined" and not refine:
@@ -815,7 +874,8 @@ class FragmentEvaluator:
     def refine_bank(self) -> Optional[RefineBank]:
         """The downsampled fragments beside bank(), when refine is on; built once (it reads every fragment's row count)."""
         if self.refine and self._refine_bank is None:
-            self._refine_bank = RefineBank([self.fragments[i][3] for i in self.ids()], self.device, self.refine_leaf)
+            self._refine_bank = RefineBank([self.fragments[i][3] for i in self.ids()], self.device, self.refine_leaf,
+                                           normals=self.refine_metric == "point_to_plane")
         return self._refine_bank
 
     def all_pairs(self):
@@ -849,7 +909,7 @@ class FragmentEvaluator:
             a, b = f1.long(), f2.long()
             parts.append(register_pairs(kp[a], desc[a], cnt[a].contiguous(), kp[b], desc[b], cnt[b].contiguous(), bank, f1,
                                         f2, ids, self.k, self.inlier_threshold, self.max_trials, self.overlap_radius,
-                                        self.seed, self.registrator, fine, self.refine_args, dense))
+                                        self.seed, self.registrator, fine, self.refine_args, dense, self.refine_metric))
         if not parts:
             return {}
         out = {key: torch.cat([p[key] for p in parts]) for key in parts[0]}

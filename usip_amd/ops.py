@@ -2693,6 +2693,7 @@ def fgr_optimize(kp1, kp2, mutual, mutual_count, norm, rows, row_count, threshol
 
 # ------------------------------------------------------------------------------------------------ f-13 trimmed ICP refinement
 ICP_MAX_ITERATIONS = 64
+ICP_METRICS = ("point_to_point", "point_to_plane")
 ICP_TOL_C = 2.0 * 2.0 ** 0.5 * math.sin(0.5 * 0.009)     # |R - R'|_F of rotations 0.009 rad apart: pcregrigid's default, chordal
 
 
@@ -2744,13 +2745,24 @@ def icp_workspace_bytes(P: int, Lmax: int) -> int:
 
 def icp_refine(rows, offsets, perm1, frag1, frag2, Rt0, Lmax: int, mask=None, order2=None, inlier_ratio: float = 0.3,
                max_iterations: int = 20, tol_t: float = 0.01, tol_c: float = ICP_TOL_C, align_radius: float = 0.05,
-               want_visits: bool = False, workspace=None, want_stage_ms: bool = False, want_cuts: bool = False):
+               want_visits: bool = False, workspace=None, want_stage_ms: bool = False, want_cuts: bool = False,
+               metric: str = "point_to_point", want_sums: bool = False):
     """f-13: trimmed point-to-point ICP from Rt0 f64 [P,3,4] on the bank of icp_nearest -> dict(Rt f64 [P,3,4], iterations
     i32 [P], converged u8 [P], rmse f64 [P], hits i32 [P], ratio f64 [P,2]; visits i64 [P] with want_visits; cut_d2 f64 and
     cut_i i32 [P,max_iterations+1] with want_cuts: the trim's cut (d2*, i*) of every pass, the final pass last).  tol_c bounds
     the Frobenius norm of the change of R (include/usip_hip.h f-13).  No host synchronisation -- unless want_stage_ms asks for
-    the measurement stage_ms (host f64 [4]: nearest, trim, fit, the final pass), which waits for the launches."""
+    the measurement stage_ms (host f64 [4]: nearest, trim, fit, the final pass), which waits for the launches.
+    metric "point_to_plane" (f-28): the same loop with the plane fit, on a bank whose rows carry their unit normals in
+    columns 3..5 (a narrower bank: ValueError); want_sums then adds fit_sums f64 [P,max_iterations,27], every fit's sums."""
+    if metric not in ICP_METRICS:
+        raise ValueError("icp: metric must be one of %s (got %r)" % (", ".join(ICP_METRICS), metric))
+    plane = metric == "point_to_plane"
+    if want_sums and not plane:
+        raise ValueError("icp: want_sums is the point_to_plane metric's")
     P = _need_icp(rows, offsets, perm1, frag1, frag2, Rt0, mask, order2)
+    if plane and rows.shape[1] < 6:
+        raise ValueError("icp: the point_to_plane metric needs a bank with normals, rows f32 [total,>=6] (got row_len %d)"
+                         % rows.shape[1])
     Lmax = int(Lmax) if order2 is None else order2.shape[1]
     if not 1 <= Lmax <= 1 << 24:
         raise RuntimeError("icp: Lmax must be in 1..2^24 (got %d)" % Lmax)
@@ -2775,13 +2787,18 @@ def icp_refine(rows, offsets, perm1, frag1, frag2, Rt0, Lmax: int, mask=None, or
     stage_ms = (ctypes.c_double * 4)() if want_stage_ms else None
     cut_d2 = torch.empty((P, int(max_iterations) + 1), dtype=torch.float64, device=dev) if want_cuts else None
     cut_i = torch.empty((P, int(max_iterations) + 1), dtype=torch.int32, device=dev) if want_cuts else None
+    fit_sums = torch.empty((P, int(max_iterations), 27), dtype=torch.float64, device=dev) if want_sums else None
+    name = "usip_icp_refine_plane_f32" if plane else "usip_icp_refine_f32"
     with torch.cuda.device(dev), prof.kernel("icp_refine", 28.0 * P * Lmax * (int(max_iterations) + 1)):
-        _lib.check(_lib.lib().usip_icp_refine_f32(
+        _lib.check(getattr(_lib.lib(), name)(
             *_bank_args(rows, offsets), _ptr(perm1), _ptr(frag1), _ptr(frag2), _ptr(Rt0), _opt_ptr(mask), _opt_ptr(order2), P,
             Lmax, float(inlier_ratio), int(max_iterations), float(tol_t), float(tol_c), float(align_radius),
             _ptr(workspace), workspace.numel(), _ptr(out["Rt"]),
             _ptr(out["iterations"]), _ptr(out["converged"]), _ptr(out["rmse"]), _ptr(out["hits"]), _ptr(out["ratio"]),
-            _opt_ptr(cut_d2), _opt_ptr(cut_i), _opt_ptr(visits), ctypes.addressof(stage_ms) if want_stage_ms else None, _stream(rows)), "usip_icp_refine_f32")
+            _opt_ptr(cut_d2), _opt_ptr(cut_i), _opt_ptr(visits), ctypes.addressof(stage_ms) if want_stage_ms else None,
+            *((_opt_ptr(fit_sums),) if plane else ()), _stream(rows)), name)
+    if want_sums:
+        out["fit_sums"] = fit_sums
     if want_visits:
         out["visits"] = visits
     if want_stage_ms:
